@@ -7,6 +7,8 @@ on the ~100k-triangle scene (configs[2]).  A *step* is one frame = one trace+acc
 (RayTracing.shader:256), counted by the kernel itself.
 
     python bench.py --gpus 1 --steps 16 --warmup 1
+    python bench.py --gpus 1 --steps 16 --warmup 1 --full            (+ roofline counting pass, single-frame latencies, CPU baseline)
+    python bench.py --gpus 1 --steps 16 --warmup 1 --dump-outputs DIR (+ resultTexture and ray count of the timed steps as DIR/*.npy)
     python bench.py --gpus N --steps K --warmup W        (starts the N ranks itself, as a child process, and relays their one line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
@@ -72,9 +74,15 @@ def parse():
                     help="N>1: interleaved 8-row bands (balanced, default) or N contiguous strips")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--rng", choices=["pcg", "philox"], default="pcg", help="pcg = the reference's stream (parity mode, headline); philox = the counter-based latency mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the (untimed) counting pass")
-    ap.add_argument("--no-latency", action="store_true", help="skip the (untimed) single-frame latency measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed extras: the counting pass (roofline), the single-frame latency "
+                         "measurements and the CPU baseline; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left for the caller (resultTexture after the K steps, and the ray count) "
+                         "as DIR/<name>.npy, so that two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the (untimed) counting pass")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the (untimed) single-frame latency measurements")
     ap.add_argument("--as-rank-of", type=int, default=0, metavar="N",
                     help="diagnostic on one GPU: render only what rank 0 of N ranks would (bands 0, N, 2N, ...): the compute side of the N-GPU "
                          "strong-scaling run without the gather; the printed value is this rank's own rate, not a job rate")
@@ -198,6 +206,27 @@ def cpu_baseline(rtx, buffers):
     return out
 
 
+DUMP_LIMIT_BYTES = 60_000_000        # all dumped arrays together stay below 64 MB
+
+
+def dump_outputs(out_dir, accum, rays):
+    """--dump-outputs: resultTexture [rows, W, 4] as accum.npy (float32) and the traced ray count as rays.npy (float64).  An image too
+    large for the budget (4K) is written as a fixed sample instead: accum_sample.npy [n, 4] at the pixels (row-major index) that
+    accum_sample_index.npy holds, drawn with a fixed seed so that every run and every build samples the same pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    np.save(os.path.join(out_dir, "rays.npy"), np.array([rays], dtype=np.float64))
+    if accum.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "accum.npy"), accum)
+        return
+    pixels = accum.reshape(-1, accum.shape[-1])
+    n = DUMP_LIMIT_BYTES // (pixels.shape[1] * 4 + 8)
+    index = np.sort(np.random.default_rng(0).choice(pixels.shape[0], n, replace=False))
+    np.save(os.path.join(out_dir, "accum_sample.npy"), pixels[index])
+    np.save(os.path.join(out_dir, "accum_sample_index.npy"), index.astype(np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -314,7 +343,12 @@ def main():
         raise SystemExit(f"the {args.backend} process group has {job['world_seen']} ranks, WORLD_SIZE says {world}")
     kernel_ms_rank0 = st["totalKernelMs"]
     busy = job["per_rank"]["kernel_ms"]
+    # ---- --dump-outputs: what the timed path left for its caller, read back before any extra of --full renders again
+    if args.dump_outputs and rank == 0:
+        accum = image.cpu().numpy() if dist is not None else tr.read_accum()
+        dump_outputs(args.dump_outputs, accum, total_rays)
 
+    # ---- the untimed extras below (roofline, latency, CPU baseline) run with --full only: the headline figure does not need them
     # ---- roofline (rank 0's strip): counting build of the same kernel over the same K frames, untimed
     roofline = None
     kernel_names = ({1: "k_stream<false,true,{H}>"} if args.rng == "philox" else
@@ -327,7 +361,7 @@ def main():
         kernel_name = "k_trace<false,false,false,6>"                      # spheres only: the six-waves-per-SIMD instantiation
     elif len(tris) == 0 and kernel_name.startswith("k_stream"):
         kernel_name = f"k_stream<false,{'true' if args.rng == 'philox' else 'false'},false,false>"    # ... and k_stream's, without traversal code
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         tr.reset_accum()
         tr.render_counting(0, args.steps)
         sc = tr.stats()
@@ -477,7 +511,7 @@ def main():
 
     # ---- latency of one rt_render_frame, camera fixed and camera moved before every frame (untimed extras, rank 0, N = 1)
     latency = None
-    if world == 1 and not args.no_latency and not sim and not force_dist:
+    if args.full and world == 1 and not args.no_latency and not sim and not force_dist:
         tr.reset_accum()
         tr.render_frame(0)
         t0 = time.perf_counter()
@@ -514,7 +548,7 @@ def main():
                            "device every frame; queued = the K frames of the timed region submitted one by one with rt_submit_frame, then rt_wait "
                            "(wall time per frame; queued_vs_batched = its rate against the timed rt_render(0, K))"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(rtx, buffers)
 
     if dist is not None:

@@ -19,15 +19,15 @@ profiles2)
   tools/profile.sh r04c_config2_philox --config 2 --rng philox > $O/prof_r04c_config2_philox.log 2>&1
   echo profiles done ;;
 bench)
-  timeout -k 10 300 python bench.py > $O/bench_r04_config3.json 2> $O/bench_r04_config3.err
-  timeout -k 10 300 python bench.py --rng philox > $O/bench_r04_config3_philox.json 2> $O/bench_r04_config3_philox.err
-  timeout -k 10 300 python bench.py --config 5 > $O/bench_r04_config5.json 2> $O/bench_r04_config5.err
-  timeout -k 10 300 python bench.py --config 5 --rng philox --no-cpu-baseline > $O/bench_r04_config5_philox.json 2> $O/bench_r04_config5_philox.err
-  timeout -k 10 300 python bench.py --config 4 > $O/bench_r04_config4.json 2> $O/bench_r04_config4.err
-  timeout -k 10 300 python bench.py --config 2 > $O/bench_r04_config2.json 2> $O/bench_r04_config2.err
-  timeout -k 10 300 python bench.py --config 2 --rng philox --no-cpu-baseline > $O/bench_r04_config2_philox.json 2> $O/bench_r04_config2_philox.err
-  for n in 2 4 8; do timeout -k 10 200 python bench.py --steps 20 --no-cpu-baseline --no-latency --as-rank-of $n > $O/bench_r04_rank0of$n.json 2>> $O/bench_r04_rank.err; done
-  RTX_BENCH_DEVICE=0 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --backend gloo --steps 8 --no-cpu-baseline 2> $O/bench_r04_gloo2.err | tail -1 > $O/bench_r04_gloo2_one_gpu.json
+  timeout -k 10 300 python bench.py --full > $O/bench_r04_config3.json 2> $O/bench_r04_config3.err
+  timeout -k 10 300 python bench.py --full --rng philox > $O/bench_r04_config3_philox.json 2> $O/bench_r04_config3_philox.err
+  timeout -k 10 300 python bench.py --full --config 5 > $O/bench_r04_config5.json 2> $O/bench_r04_config5.err
+  timeout -k 10 300 python bench.py --full --config 5 --rng philox --no-cpu-baseline > $O/bench_r04_config5_philox.json 2> $O/bench_r04_config5_philox.err
+  timeout -k 10 300 python bench.py --full --config 4 > $O/bench_r04_config4.json 2> $O/bench_r04_config4.err
+  timeout -k 10 300 python bench.py --full --config 2 > $O/bench_r04_config2.json 2> $O/bench_r04_config2.err
+  timeout -k 10 300 python bench.py --full --config 2 --rng philox --no-cpu-baseline > $O/bench_r04_config2_philox.json 2> $O/bench_r04_config2_philox.err
+  for n in 2 4 8; do timeout -k 10 200 python bench.py --full --steps 20 --no-cpu-baseline --no-latency --as-rank-of $n > $O/bench_r04_rank0of$n.json 2>> $O/bench_r04_rank.err; done
+  RTX_BENCH_DEVICE=0 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --backend gloo --steps 8 --no-cpu-baseline 2> $O/bench_r04_gloo2.err | tail -1 > $O/bench_r04_gloo2_one_gpu.json
   python tools/bench_bvh_build.py > $O/bench_bvh_build_r04.json 2> $O/bvh.err
   python tools/bench_geometry.py > $O/bench_geometry_r04.json 2>> $O/bvh.err
   python tools/bsum.py $O/bench_r04_config*.json $O/bench_r04_rank0of*.json $O/bench_r04_gloo2_one_gpu.json ;;

@@ -5,7 +5,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-ARGS=${BENCH_ARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-roofline}
+ARGS=${BENCH_ARGS:---full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline}
 cd /tmp && export TMPDIR=/tmp
 i=0
 for pass in "$@"; do

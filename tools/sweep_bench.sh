@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/sweep_$TAG.jsonl
 for v in "$@"; do
   args=""
   for kv in $v; do args="$args --opt $kv"; done
-  line=$(python3 "$R/bench.py" --config $CFG --steps ${STEPS:-16} --warmup 1 --no-cpu-baseline ${EXTRA:-} $args 2>/dev/null | tail -1)
+  line=$(python3 "$R/bench.py" --full --config $CFG --steps ${STEPS:-16} --warmup 1 --no-cpu-baseline ${EXTRA:-} $args 2>/dev/null | tail -1)
   echo "{\"variant\": \"$v\", \"config\": $CFG, \"result\": $line}" >> "$OUT"
   echo "$line" | python3 -c "
 import sys, json

@@ -2,7 +2,7 @@
 # Option sweep of the Philox mode on the GPU box (one box, back to back): tools/sweep_philox.sh > gpurun_out/sweep_philox.txt
 set -eo pipefail
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; cd "$R"
-run() { printf "%-60s " "$*"; timeout -k 10 200 python bench.py --rng philox --no-cpu-baseline --no-roofline "$@" 2>/dev/null | python -c "
+run() { printf "%-60s " "$*"; timeout -k 10 200 python bench.py --full --rng philox --no-cpu-baseline --no-roofline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d.get('latency_ms_single_frame'))"; }
 run
