@@ -156,7 +156,7 @@ typedef struct rt_stats {
     double   lastDisplayMs;             /* HIP-event time of the last linear -> sRGB8 display kernel     */
     int32_t  lastFramesPerLaunch;       /* frames traced per k_trace launch in the last rt_render (1 = frame by frame) */
     int32_t  autoKernel;                /* kernel the automatic choice picked for single-frame launches (-1 = not decided yet / not automatic) */
-    int32_t  lastKernel;                /* kernel that ran the last launch: 0 k_trace, 1 k_stream, 4 flat twin */
+    int32_t  lastKernel;                /* kernel that ran the last launch: 0 k_trace, 1 k_stream, 2 k_stream with a per-frame camera table, 4 flat twin */
     int32_t  lastFramesInterleaved;     /* k_stream: frames interleaved in a wave by the last launch (1, 4 or 16)        */
     double   lastBvhBuildMs;            /* last BVH build: HIP-event time of the device builder (sort + PLOC + collapse + records), */
                                         /* or host wall time of the binned-SAH builder                                   */
@@ -297,6 +297,16 @@ int rt_render_counting(rt_ctx* ctx, int first_frame, int n_frames);
  * passing chunks) on the GPU — a validation/baseline path, not the fast path.                          */
 int rt_render_frame_flat(rt_ctx* ctx, int frame_index);
 
+/* Per-frame cameras (the reference reads the camera again on every OnRenderImage, RayTracingManager.cs:104,126-133, and keeps
+ * accumulating).  The CAMERA FIELDS of rt_params are viewParams, camLocalToWorld and worldSpaceCameraPos; every other field is a
+ * setting.  params holds n_frames entries: entry f is the uniforms of frame first_frame + f.  The result (resultTexture, the last
+ * frame, numRenderedFrames and the context's params afterwards = params[n_frames - 1]) is bit for bit that of
+ *     for f: rt_set_params(ctx, &params[f]); rt_render_frame(ctx, first_frame + f);
+ * but the frames share launches: frames that differ in camera are traced by one k_stream launch with a camera table.  Every entry
+ * must have the same settings (else -2, and nothing is rendered or changed); when they differ from the context's, the call first
+ * acts as rt_set_params(&params[0]).  Byte-identical entries take rt_render's path.                                            */
+int rt_render_params(rt_ctx* ctx, int first_frame, int n_frames, const rt_params* params);
+
 /* Queued submission for a host that renders frame by frame, as the reference does (one trace blit + one accumulate blit per
  * OnRenderImage, RayTracingManager.cs:74-91).  rt_submit_frame returns at once; a worker thread of the library traces what has queued
  * up while the previous launch ran — consecutive frame indices share ONE launch (frame-interleaved work items, one launch tail: the
@@ -306,6 +316,11 @@ int rt_render_frame_flat(rt_ctx* ctx, int frame_index);
  * the next call that waits.  Option "queue_depth": most frames per launch (default 64).                                        */
 int rt_submit_frame(rt_ctx* ctx, int frame_index);
 int rt_wait(rt_ctx* ctx);
+/* rt_submit_frame with the frame's own uniforms (*params is copied).  A frame whose params differ from those in effect at the tail of
+ * the queue only in the camera fields (see rt_render_params) is queued without waiting and may share a launch with its neighbours; a
+ * change of settings waits for the queue, applies the new params as rt_set_params does, then queues the frame.  Errors as for
+ * rt_submit_frame.  rt_submit_frame queues a frame with the params in effect at the tail of the queue.                       */
+int rt_submit_frame_params(rt_ctx* ctx, int frame_index, const rt_params* params);
 
 /* Zero the accumulation target and the frame counter (RayTracingManager.Start, :43-46).                */
 int rt_reset_accum(rt_ctx* ctx);
@@ -364,6 +379,9 @@ int rt_multi_set_mesh_transforms(rt_multi* m, const rt_mesh_transform* transform
 int rt_multi_set_option      (rt_multi* m, const char* name, int value);
 int rt_multi_reset_accum     (rt_multi* m);
 int rt_multi_render          (rt_multi* m, int first_frame, int n_frames);
+/* rt_render_params on every context (its bands, frame f with params[f]), then the one gather.  Same settings rule as rt_render_params
+ * (-2 and nothing changed when the entries differ outside the camera fields; new settings act as rt_multi_set_params(&params[0])).  */
+int rt_multi_render_params   (rt_multi* m, int first_frame, int n_frames, const rt_params* params);
 /* the assembled resultTexture: height*width*4 floats, row 0 = bottom */
 int rt_multi_read_accum      (rt_multi* m, float* rgba, size_t n_floats);
 /* the assembled image through the display step (rt_read_display's twin: linear -> sRGB8 on the first device; height*width pixels) */

@@ -66,6 +66,7 @@ SYMBOLS = [
     "rt_multi_upload_spheres", "rt_multi_upload_triangles", "rt_multi_upload_meshinfo", "rt_multi_set_option", "rt_multi_reset_accum",
     "rt_multi_render", "rt_multi_read_accum", "rt_multi_get_stats", "rt_multi_get_info",
     "rt_multi_upload_local_meshes", "rt_multi_set_mesh_transforms", "rt_multi_read_display", "rt_multi_write_accum",
+    "rt_render_params", "rt_submit_frame_params", "rt_multi_render_params",
 ]
 
 _lib = None
@@ -107,6 +108,9 @@ def load_library() -> ctypes.CDLL:
     lib.rt_reset_accum.argtypes = [c_void_p]
     lib.rt_submit_frame.argtypes = [c_void_p, c_int]
     lib.rt_wait.argtypes = [c_void_p]
+    lib.rt_render_params.argtypes = [c_void_p, c_int, c_int, c_void_p]
+    lib.rt_submit_frame_params.argtypes = [c_void_p, c_int, c_void_p]
+    lib.rt_multi_render_params.argtypes = [c_void_p, c_int, c_int, c_void_p]
     lib.rt_read_accum.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     lib.rt_read_last_frame.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     lib.rt_copy_accum_to_device.argtypes = [c_void_p, c_void_p, c_size_t]
@@ -152,6 +156,12 @@ def load_library() -> ctypes.CDLL:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
     _lib = lib
     return lib
+
+
+def _params_run(params):
+    """a C-contiguous array of PARAMS records (one per frame) and its length"""
+    p = np.ascontiguousarray(params, dtype=PARAMS).reshape(-1)
+    return p, int(p.shape[0])
 
 
 def _as_buffer(arr, dtype):
@@ -247,6 +257,13 @@ class Tracer:
     def render(self, first_frame: int, n_frames: int):
         self._check(self._lib.rt_render(self._ctx, first_frame, n_frames), "rt_render")
 
+    def render_params(self, first_frame: int, params):
+        """rt_render_params: frame first_frame + f with the uniforms params[f] (a PARAMS array; all entries share the settings)."""
+        p, n = _params_run(params)
+        self._check(self._lib.rt_render_params(self._ctx, int(first_frame), n, p.ctypes.data_as(c_void_p)), "rt_render_params")
+        if n:
+            self._params = p[-1].copy()
+
     def render_counting(self, first_frame: int, n_frames: int):
         self._check(self._lib.rt_render_counting(self._ctx, first_frame, n_frames), "rt_render_counting")
 
@@ -271,6 +288,12 @@ class Tracer:
     def submit_frame(self, frame_index: int):
         """Queue one frame (returns at once); wait() or any other call makes sure it is in resultTexture."""
         self._check(self._lib.rt_submit_frame(self._ctx, int(frame_index)), "rt_submit_frame")
+
+    def submit_frame_params(self, frame_index: int, params):
+        """rt_submit_frame_params: queue one frame with its own uniforms (a camera move does not wait for the queue)."""
+        p = np.ascontiguousarray(params, dtype=PARAMS).reshape(())
+        self._check(self._lib.rt_submit_frame_params(self._ctx, int(frame_index), p.ctypes.data_as(c_void_p)), "rt_submit_frame_params")
+        self._params = p.copy()
 
     def wait(self):
         self._check(self._lib.rt_wait(self._ctx), "rt_wait")
@@ -386,6 +409,13 @@ class MultiTracer:
 
     def render(self, first_frame: int, n_frames: int):
         self._check(self._lib.rt_multi_render(self._m, first_frame, n_frames), "rt_multi_render")
+
+    def render_params(self, first_frame: int, params):
+        """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""
+        p, n = _params_run(params)
+        self._check(self._lib.rt_multi_render_params(self._m, int(first_frame), n, p.ctypes.data_as(c_void_p)), "rt_multi_render_params")
+        if n:
+            self._shape = (int(p[0]["height"]), int(p[0]["width"]))
 
     def read_accum(self) -> np.ndarray:
         H, W = self._shape

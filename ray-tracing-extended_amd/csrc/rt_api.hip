@@ -21,7 +21,10 @@
 
 #include "rt_kernels.hpp"
 #include "rt_stream.hpp"
-namespace rtk { const void* stream_kernel(bool counting, bool philox, bool compact, bool triangles); }   // rt_stream_kernels.hip
+namespace rtk {
+const void* stream_kernel(bool counting, bool philox, bool compact, bool triangles);        // rt_stream_kernels.hip
+const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
+}
 #include "rt_geom.hpp"
 #include "rt_bvh_gpu.hpp"
 #include "rt_primary.hpp"
@@ -155,13 +158,16 @@ struct rt_ctx {
     unsigned long long scene_version = 0;           // bumped whenever the tree or its boxes change (build, refit, re-padding)
     int opt_primary_lists = 1;                      // 1: camera rays of a static camera start from their pixel's candidate leaves (k_stream); 0: always from the root
     DevBuf<float> d_park;              // k_stream, Philox mode: parked sub-stream sums
+    std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
     rt_stats stats{};
 
     // ---- queued submission (rt_submit_frame / rt_wait): frames handed in one by one — the reference's OnRenderImage pattern,
     // RayTracingManager.cs:74-91 — are traced by a worker thread in launches of whatever has queued up while the previous launch ran
     std::thread q_thread; bool q_started = false;
     std::mutex q_mu; std::condition_variable q_cv, q_idle;
-    std::deque<int> q_frames; bool q_busy = false, q_stop = false;
+    struct QItem { int frame; rt_params p; };   // a queued frame and its uniforms (rt_submit_frame: the params in effect at the tail of the queue)
+    std::deque<QItem> q_frames; bool q_busy = false, q_stop = false;
+    rt_params q_tail{};                         // the params of the last queued frame (the context's params once the queue has run)
     int q_rc = 0; std::string q_err;
     int opt_queue_depth = 64;       // most frames the worker puts into one launch
     int opt_queue_linger_us = 200;  // after the first frame of an idle queue arrives the worker waits this long for more (a host that submits a burst
@@ -619,6 +625,38 @@ int ensure_targets(rt_ctx* c)
 
 enum class Variant { Fast, Counting, Flat };
 
+// The camera fields of rt_params (viewParams, camLocalToWorld, worldSpaceCameraPos: what UpdateCameraParams sets, plus _WorldSpaceCameraPos)
+// are one contiguous range; every other field is a setting.
+constexpr size_t kCamBegin = offsetof(rt_params, viewParams), kCamEnd = offsetof(rt_params, worldSpaceLightPos0);
+static_assert(offsetof(rt_params, camLocalToWorld) == kCamBegin + 12 && offsetof(rt_params, worldSpaceCameraPos) == kCamBegin + 76
+              && kCamEnd == kCamBegin + 88, "the camera fields of rt_params are contiguous");
+bool same_settings(const rt_params& a, const rt_params& b)
+{
+    return std::memcmp(&a, &b, kCamBegin) == 0 && std::memcmp((const char*)&a + kCamEnd, (const char*)&b + kCamEnd, sizeof(rt_params) - kCamEnd) == 0;
+}
+// p (same settings as c->params) becomes the context's params, as rt_set_params(p) would make it
+void use_camera(rt_ctx* c, const rt_params& p)
+{
+    if (std::memcmp(&c->params, &p, sizeof p) != 0) c->tile_order_stale = true;
+    c->params = p;
+}
+
+// the per-launch figures of rt_stats summed over the launches of one call
+void add_launch_stats(rt_stats& sum, const rt_stats& s)
+{
+    sum.rays += s.rays; sum.sphereTests += s.sphereTests; sum.nodeVisits += s.nodeVisits; sum.triTests += s.triTests; sum.hits += s.hits;
+    for (int k = 0; k < 5; ++k) { sum.phaseLanes[k] += s.phaseLanes[k]; sum.phaseExecs[k] += s.phaseExecs[k]; }
+    for (int k = 0; k < rtk::kNumRegions; ++k) sum.regionExecs[k] += s.regionExecs[k];
+    sum.lastKernelMs += s.lastKernelMs;
+}
+void set_launch_stats(rt_stats& st, const rt_stats& sum)
+{
+    st.rays = sum.rays; st.sphereTests = sum.sphereTests; st.nodeVisits = sum.nodeVisits; st.triTests = sum.triTests; st.hits = sum.hits;
+    for (int k = 0; k < 5; ++k) { st.phaseLanes[k] = sum.phaseLanes[k]; st.phaseExecs[k] = sum.phaseExecs[k]; }
+    for (int k = 0; k < rtk::kNumRegions; ++k) st.regionExecs[k] = sum.regionExecs[k];
+    st.lastKernelMs = sum.lastKernelMs;
+}
+
 // f(std::bool_constant<a>, std::bool_constant<b>, std::bool_constant<c>) for run-time a, b, c
 template <class Fn> const void* dispatch3(bool a, bool b, bool c3, Fn f)
 {
@@ -630,8 +668,33 @@ template <class Fn> const void* dispatch3(bool a, bool b, bool c3, Fn f)
 }
 
 // One kernel choice for all n_frames (kernel: 0 k_trace, 1 k_stream).
-int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int kernel)
+// cams: frame first_frame + f has the uniforms cams[f] (rt_render_params; all with the settings of c->params); null = c->params for all.
+int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int kernel, const rt_params* cams = nullptr)
 {
+    if (n_frames <= 0) cams = nullptr;
+    if (cams) {
+        // Per-frame cameras.  A k_stream launch of several frames becomes a k_cam_stream launch with a camera table (one record per frame);
+        // every other launch — one frame, k_trace, the counting build, the flat twin — goes frame by frame with the frame's camera in
+        // c->params.  Both give the bits of the per-frame loop rt_set_params + rt_render_frame.
+        const bool philox_ = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
+        const bool table = n_frames > 1 && var == Variant::Fast && (kernel == 1 || philox_) && c->params.numRaysPerPixel >= 1
+                           && (c->opt_tile_sync || philox_) && c->params.width <= 65535 && c->params.height <= 65535;     // (= stream_sync below)
+        if (!table) {
+            rt_stats sum{};
+            for (int f = 0; f < n_frames; ++f) {
+                use_camera(c, cams[f]);
+                const int r = launch_frames_k(c, first_frame + f, 1, var, kernel);
+                if (r) return r;
+                add_launch_stats(sum, c->stats);
+            }
+            set_launch_stats(c->stats, sum);
+            return 0;
+        }
+        // the box padding (build, re-pad or geometry pass below, from c->params) for the camera that reaches farthest
+        int far = 0;
+        for (int f = 1; f < n_frames; ++f) if (camera_magnitude(cams[f]) > camera_magnitude(cams[far])) far = f;
+        use_camera(c, cams[far]);
+    }
     c->frames_traced += (uint64_t)std::max(n_frames, 0);
     if (!c) return -1;
     if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
@@ -647,6 +710,7 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
             if (om > c->bvh.magnitude) { int r = repad_boxes(c, 2.0f * om); if (r) return r; }     // widen the box padding, keep the tree
         }
     }
+    if (cams) use_camera(c, cams[n_frames - 1]);      // (from here on only the settings of c->params are read; the context ends with the last frame's)
     { int r = ensure_targets(c); if (r) return r; }
     if (c->target_pixels == 0 || n_frames == 0) return 0;
 
@@ -691,7 +755,9 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     const bool stream_spill = stream && F.stack_cap > stream_stack;
     if (stream_spill) F.stack_cap = stream_stack;
     F.full_sort = c->opt_full_sort;
-    F.fixed_origin = camera_origin_is_fixed(c->params) ? 1 : 0;
+    bool fixed_origin = camera_origin_is_fixed(c->params);
+    if (cams) for (int f = 0; f < n_frames; ++f) fixed_origin = fixed_origin && camera_origin_is_fixed(cams[f]);      // (wave-uniform: all frames or none)
+    F.fixed_origin = fixed_origin ? 1 : 0;
     F.out_frame = c->d_frame.p; F.accum = c->d_accum.p;
     F.tile_counter = c->d_tile_counter; F.counters = c->d_counters;
 
@@ -702,7 +768,8 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     const bool counting = var == Variant::Counting;
     const bool compact = c->opt_compact_nodes != 0;            // k_trace / k_stream; the flat twin reads neither
     const void* fn = var == Variant::Flat ? (const void*)rtk::k_trace<false, true>
-                   : stream ? rtk::stream_kernel(counting, philox, compact, c->n_nodes > 0)       // instantiated in rt_stream_kernels.hip
+                   : stream ? (cams ? rtk::cam_stream_kernel(philox, compact, c->n_nodes > 0)
+                                    : rtk::stream_kernel(counting, philox, compact, c->n_nodes > 0))     // instantiated in rt_stream_kernels.hip
                    : c->n_nodes == 0      // spheres only: the instantiation compiled for six waves per SIMD
                             ? dispatch3(counting, false, false, [](auto C, auto, auto) { return (const void*)rtk::k_trace<decltype(C)::value, false, false, 6>; })
                             : dispatch3(counting, false, compact, [](auto C, auto, auto H) { return (const void*)rtk::k_trace<decltype(C)::value, false, decltype(H)::value>; });
@@ -715,6 +782,7 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     // Philox mode: S = 16 / 4 / 1 sample lanes per pixel (the estimator's sub-streams, include/rt.h RT_RNG_PHILOX)
     const int sample_lanes_log2 = !philox ? 0 : c->params.numRaysPerPixel >= 16 ? 4 : c->params.numRaysPerPixel >= 4 ? 2 : 0;
     const bool stream_sync = stream && (c->opt_tile_sync || philox);       // k_stream taking whole work items (the Philox instantiation always does)
+    if (cams && !stream_sync) return fail(c, -7, "per-frame cameras: no k_cam_stream launch for this target");
     const size_t frames_in_queue = ((stream_sync && c->opt_frame_batch != 1) ? (size_t)std::max(1, std::min(n_frames, 64)) : 1) << sample_lanes_log2;
     const int want = (int)std::min<size_t>(((size_t)ntiles * frames_in_queue + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock, (size_t)1 << 20);
     if (c->opt_blocks_per_cu > 0) per_cu = std::min(per_cu, c->opt_blocks_per_cu);
@@ -774,7 +842,7 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
         const unsigned long long geo[6] = { c->scene_version, (unsigned long long)c->target_row0, (unsigned long long)c->target_rows,
                                             (unsigned long long)c->target_row_stride, (unsigned long long)c->target_w, (unsigned long long)c->target_h };
         key.append((const char*)geo, sizeof geo);
-        const bool eligible = stream && c->opt_primary_lists && c->n_nodes > 0 && F.fixed_origin && c->target_pixels > 0 && c->bvh.maxStack <= 160;
+        const bool eligible = stream && !cams && c->opt_primary_lists && c->n_nodes > 0 && F.fixed_origin && c->target_pixels > 0 && c->bvh.maxStack <= 160;
         if (eligible) {                 // (the build takes well under a millisecond at 1080p: a camera that moves every frame pays it every frame and still gains)
             if (key != c->primary_key) {
                 RT_HIP(c, c->d_primary.ensure(c->target_pixels)); RT_HIP(c, c->d_focus.ensure(c->target_pixels)); RT_HIP(c, c->d_primary_counts.ensure(4));
@@ -800,6 +868,19 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
             }
             F.primary = c->d_primary.p; F.focus = c->d_focus.p;
         }
+    }
+    // ---- per-frame cameras: the launch's camera table (a launch of frames i .. i + nb - 1 reads its records from entry i)
+    if (cams) {
+        c->h_cams.resize((size_t)n_frames);
+        for (int f = 0; f < n_frames; ++f) {
+            const rt_params& q = cams[f];
+            rtk::CamRecord& rec = c->h_cams[f];
+            rec.view = make_float4(q.viewParams[0], q.viewParams[1], q.viewParams[2], 0.f);
+            rec.m0 = f4(q.camLocalToWorld); rec.m1 = f4(q.camLocalToWorld + 4); rec.m2 = f4(q.camLocalToWorld + 8);
+            rec.pos = make_float4(q.worldSpaceCameraPos[0], q.worldSpaceCameraPos[1], q.worldSpaceCameraPos[2], 0.f);
+        }
+        RT_HIP(c, c->d_cams.ensure((size_t)n_frames));
+        RT_HIP(c, hipMemcpyAsync(c->d_cams.p, c->h_cams.data(), (size_t)n_frames * sizeof(rtk::CamRecord), hipMemcpyHostToDevice, c->stream));
     }
     RT_HIP(c, hipMemsetAsync(c->d_counters, 0, rtk::kNumCounters * sizeof(unsigned long long), c->stream));
     RT_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -827,7 +908,8 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
         F.out_frame = nb > 1 ? c->d_batch.p : c->d_frame.p;
         RT_HIP(c, hipMemsetAsync(c->d_tile_counter, 0, sizeof(unsigned int), c->stream));
         {
-            void* args[3] = { (void*)&S, (void*)&F, (void*)&A };    // k_trace takes (S, F) only
+            const rtk::CamRecord* cam_tab = cams ? c->d_cams.p + i : nullptr;
+            void* args[4] = { (void*)&S, (void*)&F, (void*)&A, (void*)&cam_tab };    // k_trace takes (S, F) only, k_stream (S, F, A)
             RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
         }
         RT_HIP(c, hipGetLastError());
@@ -840,7 +922,7 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
         i += nb;
     }
     c->stats.lastFramesPerLaunch = batch;
-    c->stats.lastKernel = var == Variant::Flat ? 4 : stream ? 1 : 0;
+    c->stats.lastKernel = var == Variant::Flat ? 4 : stream ? (cams ? 2 : 1) : 0;
     c->stats.lastFramesInterleaved = stream ? (philox ? 1 : A.n16 ? 16 : A.n4 ? 4 : 1) : 1;
     c->stats.lastSampleLanes = philox ? 1 << sample_lanes_log2 : 1;
     RT_HIP(c, hipEventRecord(c->ev1, c->stream));
@@ -882,14 +964,14 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
 // workload, -5 % on the 1M-triangle one, -13 % on spheres only).  So the first frames after a scene / camera change are
 // used as the measurement: one frame records the tile costs, one is timed with k_trace, one with k_stream (all three are
 // ordinary frames of the render — nothing is traced twice); the faster kernel takes the rest.
-int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var)
+int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var, const rt_params* cams = nullptr)
 {
     if (!c) return -1;
     const bool eligible = c->opt_kernel < 0 && var != Variant::Flat && c->have_params
                           && c->params.numRaysPerPixel >= 1 && c->params.rngMode != RT_RNG_PHILOX;   // (Philox: always k_stream)
     if (!eligible) {
         const int kernel = c->opt_kernel < 0 ? 0 : c->opt_kernel;
-        return launch_frames_k(c, first_frame, n_frames, var, kernel);
+        return launch_frames_k(c, first_frame, n_frames, var, kernel, cams);
     }
     // (with the costliest-first order switched off, or a single tile, there is no order to wait for)
     auto order_ready = [&]() { return c->tile_order_valid || !c->lpt_active; };
@@ -898,7 +980,7 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var)
     // triangle workloads: +13 % / +10 % over its own 8x8 x 1 items, which is what the single-frame timing compares)
     auto decided = [&](int frames) { return (c->stats.numBvhNodes > 0 && frames >= 4 && c->opt_tile_sync) ? 1 : c->auto_choice; };
     if (c->auto_choice >= 0 && !c->scene_dirty && order_ready())
-        return launch_frames_k(c, first_frame, n_frames, var, decided(n_frames));
+        return launch_frames_k(c, first_frame, n_frames, var, decided(n_frames), cams);
 
     if (n_frames == 0) {            // scene / geometry update only (rt_multi's build on its first context)
         const bool was_dirty = c->scene_dirty;
@@ -907,13 +989,7 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var)
         return r;
     }
     rt_stats sum{}; bool any = false;
-    auto add = [&]() {
-        const rt_stats& s = c->stats;
-        sum.rays += s.rays; sum.sphereTests += s.sphereTests; sum.nodeVisits += s.nodeVisits; sum.triTests += s.triTests; sum.hits += s.hits;
-        for (int k = 0; k < 5; ++k) { sum.phaseLanes[k] += s.phaseLanes[k]; sum.phaseExecs[k] += s.phaseExecs[k]; }
-        for (int k = 0; k < rtk::kNumRegions; ++k) sum.regionExecs[k] += s.regionExecs[k];
-        sum.lastKernelMs += s.lastKernelMs; any = true;
-    };
+    auto add = [&]() { add_launch_stats(sum, c->stats); any = true; };
     int done = 0;
     while (done < n_frames) {
         int kernel, count = 1;
@@ -922,7 +998,7 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var)
         else if (c->auto_ms[0] < 0) kernel = 0;
         else kernel = 1;
         const bool probing = c->auto_choice < 0 && !c->scene_dirty && order_ready();
-        int r = launch_frames_k(c, first_frame + done, count, var, kernel);
+        int r = launch_frames_k(c, first_frame + done, count, var, kernel, cams ? cams + done : nullptr);
         if (r) return r;
         add();
         if (c->target_pixels == 0) { done += count; continue; }
@@ -937,13 +1013,7 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var)
         }
         done += count;
     }
-    if (any) {
-        c->stats.rays = sum.rays; c->stats.sphereTests = sum.sphereTests; c->stats.nodeVisits = sum.nodeVisits;
-        c->stats.triTests = sum.triTests; c->stats.hits = sum.hits;
-        for (int k = 0; k < 5; ++k) { c->stats.phaseLanes[k] = sum.phaseLanes[k]; c->stats.phaseExecs[k] = sum.phaseExecs[k]; }
-        for (int k = 0; k < rtk::kNumRegions; ++k) c->stats.regionExecs[k] = sum.regionExecs[k];
-        c->stats.lastKernelMs = sum.lastKernelMs;
-    }
+    if (any) set_launch_stats(c->stats, sum);
     c->stats.autoKernel = c->auto_choice;
     return 0;
 }
@@ -963,22 +1033,36 @@ int read_target(rt_ctx* c, bool accum, float* dst, size_t n_floats, bool to_devi
     return 0;
 }
 
+// Frames first .. first + n - 1 with the uniforms params[f] (all with the settings of c->params).  One camera for all: today's path
+// (candidate lists, cached focus points, k_stream) — a static camera pays nothing for the per-frame form.  Otherwise k_cam_stream's
+// camera table (launch_frames_k).  The context ends with params[n - 1].
+int launch_run(rt_ctx* c, int first, int n, const rt_params* params)
+{
+    bool one_camera = true;
+    for (int f = 1; f < n && one_camera; ++f) one_camera = std::memcmp(&params[f], &params[0], sizeof(rt_params)) == 0;
+    if (one_camera) { use_camera(c, params[0]); return launch_frames(c, first, n, Variant::Fast); }
+    return launch_frames(c, first, n, Variant::Fast, params);
+}
+
 // ---- queued submission ----------------------------------------------------------------------------------------------------------
 void queue_worker(rt_ctx* c)
 {
     std::unique_lock<std::mutex> lk(c->q_mu);
+    std::vector<rt_params> run;
     for (;;) {
         c->q_cv.wait(lk, [&] { return c->q_stop || !c->q_frames.empty(); });
         if (c->q_frames.empty()) break;                 // (stop is honoured once the queue has drained)
         if (c->opt_queue_linger_us > 0 && !c->q_stop)
             c->q_cv.wait_for(lk, std::chrono::microseconds(c->opt_queue_linger_us), [&] { return c->q_stop || (int)c->q_frames.size() >= c->opt_queue_depth; });
         // the longest run of consecutive frame indices at the head of the queue: one launch (rt_render(first, n))
-        const int first = c->q_frames.front(); int n = 0;
-        while (!c->q_frames.empty() && c->q_frames.front() == first + n && n < c->opt_queue_depth) { c->q_frames.pop_front(); ++n; }
+        // (its frames share the settings — a change of settings settles the queue before it is queued — and may differ in camera)
+        const int first = c->q_frames.front().frame; int n = 0;
+        run.clear();
+        while (!c->q_frames.empty() && c->q_frames.front().frame == first + n && n < c->opt_queue_depth) { run.push_back(c->q_frames.front().p); c->q_frames.pop_front(); ++n; }
         c->q_busy = true;
         const bool failed = c->q_rc != 0;
         lk.unlock();
-        const int r = failed ? 0 : launch_frames(c, first, n, Variant::Fast);      // after a failure the rest of the queue is dropped
+        const int r = failed ? 0 : launch_run(c, first, n, run.data());      // after a failure the rest of the queue is dropped
         lk.lock();
         if (r && !c->q_rc) { c->q_rc = r; c->q_err = c->err; }
         if (!failed && !r) c->stats.queuedLaunches++;
@@ -999,6 +1083,17 @@ int settle(rt_ctx* c)
     return r;
 }
 #define RT_SETTLE(c) do { const int qr_ = settle(c); if (qr_) return qr_; } while (0)
+
+// (with c->q_mu held) queue frame `frame` with the uniforms p; the worker starts with the first frame
+void queue_push(rt_ctx* c, int frame, const rt_params& p)
+{
+    if (!c->q_started) { c->q_thread = std::thread(queue_worker, c); c->q_started = true; }
+    c->q_frames.push_back(rt_ctx::QItem{ frame, p });
+    c->q_tail = p;
+}
+// (with c->q_mu held) the params the next queued frame follows: the last queued frame's, or the context's once the queue has run
+// (the worker only changes c->params while it is busy)
+const rt_params& queue_tail(const rt_ctx* c) { return (c->q_frames.empty() && !c->q_busy) ? c->params : c->q_tail; }
 
 } // namespace
 
@@ -1254,6 +1349,19 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames) { if (!c) return -1; RT_
 int rt_render_counting(rt_ctx* c, int first_frame, int n_frames) { if (!c) return -1; RT_SETTLE(c); return launch_frames(c, first_frame, n_frames, Variant::Counting); }
 int rt_render_frame_flat(rt_ctx* c, int frame_index) { if (!c) return -1; RT_SETTLE(c); return launch_frames(c, frame_index, 1, Variant::Flat); }
 
+int rt_render_params(rt_ctx* c, int first_frame, int n_frames, const rt_params* params)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (n_frames < 0) return fail(c, -2, "n_frames < 0");
+    if (n_frames == 0) return 0;
+    if (!params) return fail(c, -2, "null params");
+    for (int f = 1; f < n_frames; ++f)
+        if (!same_settings(params[f], params[0])) return fail(c, -2, "rt_render_params: entry %d differs from entry 0 outside the camera fields", f);
+    if (!c->have_params || !same_settings(c->params, params[0])) { const int r = rt_set_params(c, &params[0]); if (r) return r; }
+    return launch_run(c, first_frame, n_frames, params);
+}
+
 // Queued submission.  rt_submit_frame returns at once; a worker thread of the library traces the queued frames in launches of whatever
 // has queued up while the previous launch ran (consecutive frame indices share a launch: frame-interleaved work items, one launch tail)
 // and accumulates them in submission order — the image equals rt_render's over the same frames, bit for bit.
@@ -1264,8 +1372,25 @@ int rt_submit_frame(rt_ctx* c, int frame_index)
     {
         std::lock_guard<std::mutex> lk(c->q_mu);
         if (c->q_rc) return c->q_rc;                    // a queued launch failed: rt_wait (or any other call) reports it
-        if (!c->q_started) { c->q_thread = std::thread(queue_worker, c); c->q_started = true; }
-        c->q_frames.push_back(frame_index);
+        queue_push(c, frame_index, queue_tail(c));
+    }
+    c->q_cv.notify_one();
+    return 0;
+}
+int rt_submit_frame_params(rt_ctx* c, int frame_index, const rt_params* p)
+{
+    if (!c) return -1;
+    if (!p) { RT_SETTLE(c); return fail(c, -2, "null params"); }
+    bool new_settings;
+    {
+        std::lock_guard<std::mutex> lk(c->q_mu);
+        if (c->q_rc) return c->q_rc;
+        new_settings = !c->have_params || !same_settings(queue_tail(c), *p);
+    }
+    if (new_settings) { const int r = rt_set_params(c, p); if (r) return r; }      // settles the queue first; a moved camera does not wait
+    {
+        std::lock_guard<std::mutex> lk(c->q_mu);
+        queue_push(c, frame_index, *p);
     }
     c->q_cv.notify_one();
     return 0;
@@ -1519,9 +1644,12 @@ int rt_multi_set_option(rt_multi* m, const char* name, int value)
 }
 int rt_multi_reset_accum(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_accum", [&](rt_ctx* c) { return rt_reset_accum(c); }) : -1; }
 
-int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
+} // extern "C"
+
+namespace {
+// rt_multi_render (params null) and rt_multi_render_params (frame f with params[f] on every context)
+int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
 {
-    if (!m) return -1;
     if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
     const int N = (int)m->ctx.size();
     bool stale = m->scene_dirty;
@@ -1551,11 +1679,12 @@ int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
     std::vector<int> rc(N, 0);
     {
         std::vector<std::thread> th;
-        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = rt_render(m->ctx[i], first_frame, n_frames); });
-        rc[0] = rt_render(m->ctx[0], first_frame, n_frames);
+        auto render = [&](int i) { return params ? rt_render_params(m->ctx[i], first_frame, n_frames, params) : rt_render(m->ctx[i], first_frame, n_frames); };
+        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = render(i); });
+        rc[0] = render(0);
         for (std::thread& t : th) t.join();
     }
-    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "rt_render on context %d: %s", i, rt_last_error(m->ctx[i]));
+    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "%s on context %d: %s", params ? "rt_render_params" : "rt_render", i, rt_last_error(m->ctx[i]));
     // ---- the one gather: strips -> first device, rows to their places
     rt_ctx* root = m->ctx[0];
     const int W = m->width, H = m->height;
@@ -1592,6 +1721,27 @@ int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
     M_HIP(m, hipStreamSynchronize(root->stream));
     m->lastGatherMs = now_ms() - tg0;           // host wall time from the first copy's submission to the assembled image (the copies run on N - 1 streams)
     return 0;
+}
+} // namespace
+
+extern "C" {
+
+int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
+{
+    if (!m) return -1;
+    return multi_render(m, first_frame, n_frames, nullptr);
+}
+
+int rt_multi_render_params(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
+{
+    if (!m) return -1;
+    if (n_frames < 0) return mfail(m, -2, "n_frames < 0");
+    if (n_frames == 0) return 0;
+    if (!params) return mfail(m, -2, "null params");
+    for (int f = 1; f < n_frames; ++f)
+        if (!same_settings(params[f], params[0])) return mfail(m, -2, "rt_multi_render_params: entry %d differs from entry 0 outside the camera fields", f);
+    if (!m->have_params || !same_settings(m->ctx[0]->params, params[0])) { const int r = rt_multi_set_params(m, &params[0]); if (r) return r; }
+    return multi_render(m, first_frame, n_frames, params);
 }
 
 // The display step for the assembled image (rt_read_display's twin): linear -> sRGB8 on the first device.

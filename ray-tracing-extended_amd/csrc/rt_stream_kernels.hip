@@ -30,4 +30,16 @@ const void* stream_kernel(bool counting, bool philox, bool compact, bool triangl
     }
 }
 
+// ... and of k_cam_stream<philox, compact nodes, triangles>, the twin with a per-frame camera table (non-counting only)
+const void* cam_stream_kernel(bool philox, bool compact, bool triangles)
+{
+    if (!triangles) return philox ? (const void*)k_cam_stream<true, false, false> : (const void*)k_cam_stream<false, false, false>;
+    switch ((philox ? 2 : 0) | (compact ? 1 : 0)) {
+    case 0: return (const void*)k_cam_stream<false, false, true>;
+    case 1: return (const void*)k_cam_stream<false, true, true>;
+    case 2: return (const void*)k_cam_stream<true, false, true>;
+    default: return (const void*)k_cam_stream<true, true, true>;
+    }
+}
+
 } // namespace rtk

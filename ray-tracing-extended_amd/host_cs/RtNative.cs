@@ -173,10 +173,12 @@ namespace RtMi355x
         // ---- rendering
         [DllImport(Lib)] public static extern int rt_render_frame(IntPtr ctx, int frameIndex);
         [DllImport(Lib)] public static extern int rt_render(IntPtr ctx, int firstFrame, int nFrames);
+        [DllImport(Lib)] public static extern int rt_render_params(IntPtr ctx, int firstFrame, int nFrames, [In] RtParams[] p);   // p: nFrames entries
         [DllImport(Lib)] public static extern int rt_render_counting(IntPtr ctx, int firstFrame, int nFrames);
         [DllImport(Lib)] public static extern int rt_render_frame_flat(IntPtr ctx, int frameIndex);
         [DllImport(Lib)] public static extern int rt_reset_accum(IntPtr ctx);
         [DllImport(Lib)] public static extern int rt_submit_frame(IntPtr ctx, int frameIndex);
+        [DllImport(Lib)] public static extern int rt_submit_frame_params(IntPtr ctx, int frameIndex, ref RtParams p);
         [DllImport(Lib)] public static extern int rt_wait(IntPtr ctx);
         // ---- read-back / restore
         [DllImport(Lib)] public static extern int rt_read_accum(IntPtr ctx, IntPtr rgba, UIntPtr nFloats);
@@ -202,6 +204,7 @@ namespace RtMi355x
         [DllImport(Lib, CharSet = CharSet.Ansi)] public static extern int rt_multi_set_option(IntPtr multi, string name, int value);
         [DllImport(Lib)] public static extern int rt_multi_reset_accum(IntPtr multi);
         [DllImport(Lib)] public static extern int rt_multi_render(IntPtr multi, int firstFrame, int nFrames);
+        [DllImport(Lib)] public static extern int rt_multi_render_params(IntPtr multi, int firstFrame, int nFrames, [In] RtParams[] p);
         [DllImport(Lib)] public static extern int rt_multi_read_accum(IntPtr multi, IntPtr rgba, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_multi_get_stats(IntPtr multi, out RtStats stats, out double gatherMs);
         [DllImport(Lib)] public static extern int rt_multi_get_info(IntPtr multi, out RtMultiInfo info);
