@@ -184,6 +184,14 @@ int fail(rt_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
+// d = v on the device: ensure, then an asynchronous copy on the context's stream (v must live until the stream is synchronised)
+template <class T> hipError_t upload(rt_ctx* c, DevBuf<T>& d, const std::vector<T>& v)
+{
+    hipError_t e = d.ensure(v.size());
+    if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
+    return e;
+}
+
 inline double now_ms()
 {
     timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -280,18 +288,75 @@ int device_build(rt_ctx* c, uint32_t nt, float origin_magnitude)
     RT_HIP(c, rtgb::internal_area(c->stream, reinterpret_cast<const rtbvh::Node4*>(c->d_nodes.p), (uint32_t)c->n_nodes, c->bvh_ws, c->area_at_build));
     float ms = 0.f;
     RT_HIP(c, hipEventElapsedTime(&ms, c->evg0, c->evg1));
-    c->stats.lastBvhBuildMs = ms; c->stats.bvhBuiltOnDevice = 1; c->stats.bvhBuilds++; c->scene_version++;
+    c->stats.lastBvhBuildMs = ms; c->stats.bvhBuiltOnDevice = 1; c->stats.bvhBuilds++;
     return 0;
 }
 
-// Re-layout of the uploaded buffers + BVH build.  Edge vectors and their cross product are the operands of
-// RayTriangle (RayTracing.shader:152-154) evaluated once here with the same float operations.
+// BVH over n triangles (triangle i's corners at positions + i * stride floats), built by the host's binned-SAH builder; then on the
+// device the nodes, d_order (BVH order -> uploaded triangle: through live_map for world-space uploads, the identity for local ones),
+// the f16 nodes, the tracer's triangle records and the internal area.  Needs d_raw_tris, d_tri_chunk and d_tri_rank uploaded.
+int host_build(rt_ctx* c, const float* positions, int stride, uint32_t n, const uint32_t* live_map, float G)
+{
+    const double t0 = now_ms();
+    rtbvh::build(positions, stride, n, G, bvh_tuning(c), c->bvh);
+    c->stats.lastBvhBuildMs = now_ms() - t0; c->stats.bvhBuilds++;
+    c->n_nodes = c->bvh.nodes.size();
+    RT_HIP(c, c->d_nodes.ensure(c->bvh.nodes.size() * 8));
+    if (!c->bvh.nodes.empty())
+        RT_HIP(c, hipMemcpyAsync(c->d_nodes.p, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(rtbvh::Node4), hipMemcpyHostToDevice, c->stream));
+    std::vector<uint32_t> order_raw(live_map ? n : 0);      // (n > 0 means a tree: internal_area below synchronises before it dies)
+    for (size_t i = 0; i < order_raw.size(); ++i) order_raw[i] = live_map[c->bvh.order[i]];
+    RT_HIP(c, upload(c, c->d_order, live_map ? order_raw : c->bvh.order));
+    { int r = compact_nodes(c); if (r) return r; }
+    // the records: edge vectors and their cross product are the operands of RayTriangle (RayTracing.shader:152-154), evaluated once
+    RT_HIP(c, c->d_tri_geo.ensure(3 * (size_t)n)); RT_HIP(c, c->d_tri_nrm.ensure(3 * (size_t)n));
+    if (n) {
+        hipLaunchKernelGGL(rtg::k_relayout, dim3((n + 255) / 256), dim3(256), 0, c->stream,
+                           c->d_raw_tris.p, c->d_order.p, c->d_tri_chunk.p, c->d_tri_rank.p, c->d_tri_geo.p, c->d_tri_nrm.p, n);
+        RT_HIP(c, hipGetLastError());
+    }
+    RT_HIP(c, rtgb::internal_area(c->stream, reinterpret_cast<const rtbvh::Node4*>(c->d_nodes.p), (uint32_t)c->n_nodes, c->bvh_ws, c->area_at_build));
+    return 0;
+}
+
+int upload_spheres_and_materials(rt_ctx* c)
+{
+    const size_t ns = c->h_spheres.size();
+    std::vector<float4> sg(ns), sm(4 * ns);
+    for (size_t i = 0; i < ns; ++i) {
+        const rt_sphere& s = c->h_spheres[i];
+        sg[i] = make_float4(s.position[0], s.position[1], s.position[2], s.radius);
+        pack_material(s.material, &sm[4 * i]);
+    }
+    RT_HIP(c, upload(c, c->d_sph_geom, sg)); RT_HIP(c, upload(c, c->d_sph_mat, sm));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    c->stats.numSpheres = (int)ns;
+    return 0;
+}
+
+// The end of a build: the scene's figures and the counts the launches read.  A new scene starts without a tile order; a rebuild of
+// meshes that moved keeps the last one as a predictor, re-measured by the next launch.
+void finish_build(rt_ctx* c, bool rebuild = false)
+{
+    const size_t nt = c->geom_local ? c->h_local_tris.size() : c->h_tris.size(), nm = c->geom_local ? c->h_lchunks.size() : c->h_mesh.size();
+    c->stats.numSpheres = (int)c->h_spheres.size(); c->stats.numTriangles = (int)nt; c->stats.numMeshChunks = (int)nm;
+    c->stats.numBvhNodes = (int)c->n_nodes; c->stats.bvhMaxStack = c->bvh.maxStack; c->stats.bvhInternalArea = c->area_at_build;
+    c->n_spheres = c->h_spheres.size(); c->n_tris = nt; c->n_chunks = nm; c->sphere_mag = sphere_magnitude(c);
+    c->scene_dirty = false; c->xf_dirty = false; c->scene_version++;
+    if (rebuild) c->tile_order_stale = true;
+    else c->tile_order_valid = false;
+}
+
+// Re-layout of the uploaded buffers + BVH build.
 int build_scene(rt_ctx* c)
 {
-    const size_t ns = c->h_spheres.size(), nt = c->h_tris.size(), nm = c->h_mesh.size();
+    const size_t nt = c->h_tris.size(), nm = c->h_mesh.size();
     if (nt > (1u << 28)) return fail(c, -3, "too many triangles (%zu)", nt);
-    // triangle -> chunk map; every triangle the shader can reach belongs to exactly the chunk ranges given
-    std::vector<uint32_t> chunk_of(nt, 0xFFFFFFFFu);
+    // triangle -> chunk map; every triangle the shader can reach belongs to exactly the chunk ranges given.  Equal-distance hits: the
+    // reference keeps the triangle its loops reach first — chunks in AllMeshInfo order, triangles in order inside the chunk
+    // (CalculateRayCollision :276-293).  That visiting rank, not the buffer index, is the tie-break key.
+    std::vector<uint32_t> chunk_of(nt, 0xFFFFFFFFu), visit_rank(nt, 0xFFFFFFFFu);
+    uint32_t rank = 0;
     for (size_t m = 0; m < nm; ++m) {
         const rt_meshinfo& mi = c->h_mesh[m];
         if ((uint64_t)mi.firstTriangleIndex + mi.numTriangles > nt)
@@ -302,26 +367,14 @@ int build_scene(rt_ctx* c)
             if (slot != 0xFFFFFFFFu)
                 return fail(c, -5, "triangle %u is referenced by chunks %u and %zu (overlapping chunk ranges are not supported)",
                             mi.firstTriangleIndex + i, slot, m);
-            slot = (uint32_t)m;
+            slot = (uint32_t)m; visit_rank[mi.firstTriangleIndex + i] = rank++;
         }
-    }
-    // equal-distance hits: the reference keeps the triangle its loops reach first — chunks in AllMeshInfo order, triangles in
-    // order inside the chunk (CalculateRayCollision :276-293).  That visiting rank, not the buffer index, is the tie-break key.
-    std::vector<uint32_t> visit_rank(nt, 0xFFFFFFFFu);
-    {
-        uint32_t r = 0;
-        for (size_t m = 0; m < nm; ++m)
-            for (uint32_t i = 0; i < c->h_mesh[m].numTriangles; ++i) visit_rank[c->h_mesh[m].firstTriangleIndex + i] = r++;
     }
     // triangles outside every chunk are never visited by the shader: leave them out of the hierarchy
     std::vector<uint32_t> live; live.reserve(nt);
     for (size_t t = 0; t < nt; ++t) if (chunk_of[t] != 0xFFFFFFFFu) live.push_back((uint32_t)t);
-    std::vector<float4> sg(ns), sm(4 * ns), cm(4 * nm), cb(2 * nm);
-    for (size_t i = 0; i < ns; ++i) {
-        const rt_sphere& s = c->h_spheres[i];
-        sg[i] = make_float4(s.position[0], s.position[1], s.position[2], s.radius);
-        pack_material(s.material, &sm[4 * i]);
-    }
+    { int r = upload_spheres_and_materials(c); if (r) return r; }
+    std::vector<float4> cm(4 * nm), cb(2 * nm);
     std::vector<uint32_t> range(2 * nm);
     for (size_t m = 0; m < nm; ++m) {
         const rt_meshinfo& mi = c->h_mesh[m];
@@ -330,14 +383,10 @@ int build_scene(rt_ctx* c)
         cb[2 * m + 1] = make_float4(mi.boundsMax[0], mi.boundsMax[1], mi.boundsMax[2], 0.f);
         range[2 * m] = mi.firstTriangleIndex; range[2 * m + 1] = mi.numTriangles;
     }
-#define RT_UP(buf, vec, T)                                                                                  \
-    RT_HIP(c, buf.ensure(vec.size()));                                                                      \
-    if (!vec.empty()) RT_HIP(c, hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    RT_UP(c->d_sph_geom, sg, float4) RT_UP(c->d_sph_mat, sm, float4)
-    RT_UP(c->d_chunk_mat, cm, float4) RT_UP(c->d_chunk_box, cb, float4)
-    RT_UP(c->d_raw_range, range, uint32_t)
+    RT_HIP(c, upload(c, c->d_chunk_mat, cm)); RT_HIP(c, upload(c, c->d_chunk_box, cb)); RT_HIP(c, upload(c, c->d_raw_range, range));
     RT_HIP(c, c->d_raw_tris.ensure(nt * 18));
     if (nt) RT_HIP(c, hipMemcpyAsync(c->d_raw_tris.p, c->h_tris.data(), nt * sizeof(rt_triangle), hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, upload(c, c->d_tri_chunk, chunk_of)); RT_HIP(c, upload(c, c->d_tri_rank, visit_rank));     // (what k_relayout reads)
     // headroom: the boxes are padded for ray origins up to twice as far out as the camera and the spheres are now (the term is
     // 2e-6 * G), so a camera that drifts away from the geometry widens the padding (repad_boxes) once per doubling, not per frame
     const float origin_mag = 2.0f * std::max(camera_magnitude(c->params), sphere_magnitude(c));
@@ -347,72 +396,42 @@ int build_scene(rt_ctx* c)
     // RayTracedMesh.cs:36-84 — and a 50-600 ms host build per frame would dwarf the trace: those builds go to the device (2.5-5.4 ms)
     const bool moving = c->opt_device_bvh == -1 && c->frames_at_world_build != ~0ull && c->frames_traced - c->frames_at_world_build <= 16;
     c->frames_at_world_build = c->frames_traced;
+    int r;
     if ((c->opt_device_bvh == 1 || moving) && nt > 0) {
         // the device builder takes every uploaded triangle; one that belongs to no chunk gets NaN records (k_relayout) and can never be hit
-        RT_UP(c->d_tri_chunk, chunk_of, uint32_t) RT_UP(c->d_tri_rank, visit_rank, uint32_t)
-        { int r = device_build(c, (uint32_t)nt, origin_mag); if (r) return r; }
+        r = device_build(c, (uint32_t)nt, origin_mag);
     } else {
         std::vector<float> pos(9 * live.size());
         for (size_t i = 0; i < live.size(); ++i) std::memcpy(&pos[9 * i], c->h_tris[live[i]].posA, 36);
-        const double t0 = now_ms();
-        rtbvh::build(pos.data(), 9, (uint32_t)live.size(), origin_mag, bvh_tuning(c), c->bvh);
-        c->stats.lastBvhBuildMs = now_ms() - t0; c->stats.bvhBuilds++;
-        c->n_nodes = c->bvh.nodes.size();
+        r = host_build(c, pos.data(), 9, (uint32_t)live.size(), live.data(), origin_mag);
         if (live.empty()) c->bvh.magnitude = origin_mag;        // no tree: only the trigger of repad_boxes looks at it
-        const size_t nl = live.size();
-        std::vector<float4> geo(3 * nl), nrm(3 * nl);
-        for (size_t i = 0; i < nl; ++i) {
-            const uint32_t orig = live[c->bvh.order[i]];
-            const rt_triangle& t = c->h_tris[orig];
-            const float ex = t.posB[0] - t.posA[0], ey = t.posB[1] - t.posA[1], ez = t.posB[2] - t.posA[2];
-            const float fx = t.posC[0] - t.posA[0], fy = t.posC[1] - t.posA[1], fz = t.posC[2] - t.posA[2];
-            const float nx = ey * fz - ez * fy, ny = ez * fx - ex * fz, nz = ex * fy - ey * fx;
-            geo[3 * i + 0] = make_float4(t.posA[0], t.posA[1], t.posA[2], ex);
-            geo[3 * i + 1] = make_float4(ey, ez, fx, fy);
-            geo[3 * i + 2] = make_float4(fz, nx, ny, nz);
-            nrm[3 * i + 0] = make_float4(t.normalA[0], t.normalA[1], t.normalA[2], u2f(chunk_of[orig]));
-            nrm[3 * i + 1] = make_float4(t.normalB[0], t.normalB[1], t.normalB[2], u2f(visit_rank[orig]));
-            nrm[3 * i + 2] = make_float4(t.normalC[0], t.normalC[1], t.normalC[2], 0.f);
-        }
-        RT_UP(c->d_tri_geo, geo, float4) RT_UP(c->d_tri_nrm, nrm, float4)
-        // BVH order -> uploaded triangle, on the device: what a later widening of the box padding (repad_boxes) refits from
-        std::vector<uint32_t> order_raw(nl);
-        for (size_t i = 0; i < nl; ++i) order_raw[i] = live[c->bvh.order[i]];
-        RT_UP(c->d_order, order_raw, uint32_t)
-        RT_HIP(c, c->d_nodes.ensure(c->bvh.nodes.size() * 8));
-        if (!c->bvh.nodes.empty())
-            RT_HIP(c, hipMemcpyAsync(c->d_nodes.p, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(rtbvh::Node4),
-                                     hipMemcpyHostToDevice, c->stream));
-        { int r = compact_nodes(c); if (r) return r; }
-        RT_HIP(c, hipStreamSynchronize(c->stream));     // host staging vectors die here
-        RT_HIP(c, rtgb::internal_area(c->stream, reinterpret_cast<const rtbvh::Node4*>(c->d_nodes.p), (uint32_t)c->n_nodes, c->bvh_ws, c->area_at_build));
     }
-#undef RT_UP
+    if (r) return r;
     RT_HIP(c, hipStreamSynchronize(c->stream));     // host staging vectors die here
-
-    c->stats.numSpheres = (int)ns; c->stats.numTriangles = (int)nt; c->stats.numMeshChunks = (int)nm;
-    c->stats.numBvhNodes = (int)c->n_nodes; c->stats.bvhMaxStack = c->bvh.maxStack; c->stats.bvhInternalArea = c->area_at_build;
-    c->n_spheres = ns; c->n_tris = nt; c->n_chunks = nm; c->sphere_mag = sphere_magnitude(c);
-    c->scene_dirty = false; c->tile_order_valid = false; c->scene_version++;
+    finish_build(c);
     return 0;
 }
 
+// Bottom-up refit of the tree's boxes from the world-space triangles in d_raw_tris (k_refit_level writes the padded leaf boxes a build
+// for magnitude G would), then the f16 form of the nodes.
+int refit_tree(rt_ctx* c, float G)
+{
+    for (int L = (int)c->bvh.levelStart.size() - 2; L >= 0; --L) {
+        const uint32_t n0 = c->bvh.levelStart[L], n1 = c->bvh.levelStart[L + 1];
+        if (n1 > n0)
+            hipLaunchKernelGGL(rtg::k_refit_level, dim3(((n1 - n0) * 4 + 255) / 256), dim3(256), 0, c->stream,
+                               reinterpret_cast<rtbvh::Node4*>(c->d_nodes.p), n0, n1, c->d_raw_tris.p, c->d_order.p, G);
+    }
+    RT_HIP(c, hipGetLastError());
+    return compact_nodes(c);
+}
+
 // World-space uploads: a ray origin (camera, defocus disc, sphere surface) has moved beyond the magnitude G the boxes were padded
-// for (pad = 3e-5 |coord| + 2e-6 G, bvh.cpp pad_box).  The tree stays: its boxes are refitted bottom-up from the uploaded triangles
-// with the new G (k_refit_level writes the same padded leaf boxes a build would) and the f16 form is derived again — a few small
-// launches instead of a host rebuild and a re-upload of every record.
+// for (pad = 3e-5 |coord| + 2e-6 G, bvh.cpp pad_box).  The tree stays: its boxes are refitted with the new G — a few small launches
+// instead of a host rebuild and a re-upload of every record.
 int repad_boxes(rt_ctx* c, float G)
 {
-    if (c->n_nodes && c->bvh.levelStart.size() >= 2) {
-        for (int L = (int)c->bvh.levelStart.size() - 2; L >= 0; --L) {
-            const uint32_t n0 = c->bvh.levelStart[L], n1 = c->bvh.levelStart[L + 1];
-            if (n1 > n0)
-                hipLaunchKernelGGL(rtg::k_refit_level, dim3(((n1 - n0) * 4 + 255) / 256), dim3(256), 0, c->stream,
-                                   reinterpret_cast<rtbvh::Node4*>(c->d_nodes.p), n0, n1, c->d_raw_tris.p, c->d_order.p, G);
-        }
-        RT_HIP(c, hipGetLastError());
-        { int r = compact_nodes(c); if (r) return r; }
-    }
+    if (c->n_nodes && c->bvh.levelStart.size() >= 2) { int r = refit_tree(c, G); if (r) return r; }
     c->bvh.magnitude = G;
     c->stats.bvhRepads++; c->scene_version++;
     return 0;
@@ -432,25 +451,6 @@ float local_scene_magnitude(const rt_ctx* c)
     return G;
 }
 
-int upload_spheres_and_materials(rt_ctx* c)
-{
-    const size_t ns = c->h_spheres.size();
-    std::vector<float4> sg(ns), sm(4 * ns);
-    for (size_t i = 0; i < ns; ++i) {
-        const rt_sphere& s = c->h_spheres[i];
-        sg[i] = make_float4(s.position[0], s.position[1], s.position[2], s.radius);
-        pack_material(s.material, &sm[4 * i]);
-    }
-    RT_HIP(c, c->d_sph_geom.ensure(ns)); RT_HIP(c, c->d_sph_mat.ensure(4 * ns));
-    if (ns) {
-        RT_HIP(c, hipMemcpyAsync(c->d_sph_geom.p, sg.data(), ns * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        RT_HIP(c, hipMemcpyAsync(c->d_sph_mat.p, sm.data(), 4 * ns * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    }
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    c->stats.numSpheres = (int)ns;
-    return 0;
-}
-
 // transform + chunk bounds (+ re-layout and refit when the BVH topology already exists)
 int run_geometry_kernels(rt_ctx* c, bool have_bvh)
 {
@@ -461,8 +461,7 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh)
         xf[m] = { t.position[0], t.position[1], t.position[2], t.rotation[0], t.rotation[1], t.rotation[2], t.rotation[3],
                   t.lossyScale[0], t.lossyScale[1], t.lossyScale[2] };
     }
-    RT_HIP(c, c->d_xf.ensure(xf.size()));
-    if (!xf.empty()) RT_HIP(c, hipMemcpyAsync(c->d_xf.p, xf.data(), xf.size() * sizeof(rtg::MeshXf), hipMemcpyHostToDevice, c->stream));
+    RT_HIP(c, upload(c, c->d_xf, xf));
     RT_HIP(c, hipEventRecord(c->evg0, c->stream));
     if (nt) {
         hipLaunchKernelGGL(rtg::k_transform, dim3((nt + 255) / 256), dim3(256), 0, c->stream,
@@ -475,13 +474,7 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh)
                            c->d_raw_tris.p, c->d_order.p, c->d_tri_chunk.p, c->d_tri_rank.p, c->d_tri_geo.p, c->d_tri_nrm.p, nt);
         const float G = std::max(c->bvh.magnitude, local_scene_magnitude(c));
         c->bvh.magnitude = G;
-        for (int L = (int)c->bvh.levelStart.size() - 2; L >= 0; --L) {
-            const uint32_t n0 = c->bvh.levelStart[L], n1 = c->bvh.levelStart[L + 1];
-            if (n1 > n0)
-                hipLaunchKernelGGL(rtg::k_refit_level, dim3(((n1 - n0) * 4 + 255) / 256), dim3(256), 0, c->stream,
-                                   reinterpret_cast<rtbvh::Node4*>(c->d_nodes.p), n0, n1, c->d_raw_tris.p, c->d_order.p, G);
-        }
-        { int r = compact_nodes(c); if (r) return r; }
+        { int r = refit_tree(c, G); if (r) return r; }
     }
     RT_HIP(c, hipGetLastError());
     // a refit keeps the topology: meshes that moved apart leave boxes that overlap more and more.  The refitted tree's internal area is
@@ -499,8 +492,8 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh)
         c->stats.refitAreaRatio = area / c->area_at_build;
         if (area > c->area_at_build * (float)c->opt_rebuild_percent / 100.0f) {
             int r = device_build(c, nt, local_scene_magnitude(c)); if (r) return r;
-            c->stats.numBvhNodes = (int)c->n_nodes; c->stats.bvhMaxStack = c->bvh.maxStack;
-            c->stats.bvhRebuilds++; c->tile_order_stale = true;
+            c->stats.bvhRebuilds++;
+            finish_build(c, true);
         }
     }
     return 0;
@@ -523,46 +516,41 @@ int build_scene_local(rt_ctx* c)
         range[2 * m] = ch.firstTriangleIndex; range[2 * m + 1] = ch.numTriangles;
         pack_material(ch.material, &cm[4 * m]);
     }
-#define RT_UP(buf, vec, T)                                                                                  \
-    RT_HIP(c, buf.ensure(vec.size()));                                                                      \
-    if (!vec.empty()) RT_HIP(c, hipMemcpyAsync(buf.p, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    RT_UP(c->d_tri_mesh, tri_mesh, uint32_t) RT_UP(c->d_tri_chunk, tri_chunk, uint32_t) RT_UP(c->d_tri_rank, tri_rank, uint32_t)
-    RT_UP(c->d_raw_range, range, uint32_t) RT_UP(c->d_chunk_mat, cm, float4)
-#undef RT_UP
-    RT_HIP(c, c->d_local_tris.ensure(nt * 18)); RT_HIP(c, c->d_raw_tris.ensure(nt * 18));
-    RT_HIP(c, c->d_chunk_box.ensure(2 * nm)); RT_HIP(c, c->d_tri_geo.ensure(3 * nt)); RT_HIP(c, c->d_tri_nrm.ensure(3 * nt));
+    RT_HIP(c, upload(c, c->d_tri_mesh, tri_mesh)); RT_HIP(c, upload(c, c->d_tri_chunk, tri_chunk)); RT_HIP(c, upload(c, c->d_tri_rank, tri_rank));
+    RT_HIP(c, upload(c, c->d_raw_range, range)); RT_HIP(c, upload(c, c->d_chunk_mat, cm));
+    RT_HIP(c, c->d_local_tris.ensure(nt * 18)); RT_HIP(c, c->d_raw_tris.ensure(nt * 18)); RT_HIP(c, c->d_chunk_box.ensure(2 * nm));
     if (nt) RT_HIP(c, hipMemcpyAsync(c->d_local_tris.p, c->h_local_tris.data(), nt * sizeof(rt_triangle), hipMemcpyHostToDevice, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    { int r = run_geometry_kernels(c, false); if (r) return r; }
+    int r = run_geometry_kernels(c, false);
+    if (r) return r;
     c->stats.bvhBuiltOnDevice = 0;
     if (c->opt_device_bvh != 0 && nt > 0) {
         // topology on the device from the world triangles the transform kernel just wrote: nothing goes back to the host
-        { int r = device_build(c, (uint32_t)nt, local_scene_magnitude(c)); if (r) return r; }
+        r = device_build(c, (uint32_t)nt, local_scene_magnitude(c));
     } else {
         // world positions (device) -> host, for the one-off topology build
         std::vector<rt_triangle> world(nt);
         if (nt) RT_HIP(c, hipMemcpy(world.data(), c->d_raw_tris.p, nt * sizeof(rt_triangle), hipMemcpyDeviceToHost));
-        const double t0 = now_ms();
-        rtbvh::build(nt ? world[0].posA : nullptr, 18, (uint32_t)nt, local_scene_magnitude(c), bvh_tuning(c), c->bvh);
-        c->stats.lastBvhBuildMs = now_ms() - t0; c->stats.bvhBuilds++;
-        c->n_nodes = c->bvh.nodes.size();
-        RT_HIP(c, c->d_nodes.ensure(c->bvh.nodes.size() * 8)); RT_HIP(c, c->d_order.ensure(nt));
-        if (!c->bvh.nodes.empty()) {
-            RT_HIP(c, hipMemcpyAsync(c->d_nodes.p, c->bvh.nodes.data(), c->bvh.nodes.size() * sizeof(rtbvh::Node4), hipMemcpyHostToDevice, c->stream));
-            RT_HIP(c, hipMemcpyAsync(c->d_order.p, c->bvh.order.data(), nt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            { int r = compact_nodes(c); if (r) return r; }
-            hipLaunchKernelGGL(rtg::k_relayout, dim3(((uint32_t)nt + 255) / 256), dim3(256), 0, c->stream,
-                               c->d_raw_tris.p, c->d_order.p, c->d_tri_chunk.p, c->d_tri_rank.p, c->d_tri_geo.p, c->d_tri_nrm.p, (uint32_t)nt);
-            RT_HIP(c, hipGetLastError());
-        }
-        RT_HIP(c, rtgb::internal_area(c->stream, reinterpret_cast<const rtbvh::Node4*>(c->d_nodes.p), (uint32_t)c->n_nodes, c->bvh_ws, c->area_at_build));
+        r = host_build(c, nt ? world[0].posA : nullptr, 18, (uint32_t)nt, nullptr, local_scene_magnitude(c));
     }
+    if (r) return r;
     RT_HIP(c, hipStreamSynchronize(c->stream));
-    c->stats.numTriangles = (int)nt; c->stats.numMeshChunks = (int)nm;
-    c->stats.numBvhNodes = (int)c->n_nodes; c->stats.bvhMaxStack = c->bvh.maxStack; c->stats.bvhInternalArea = c->area_at_build;
-    c->n_spheres = c->h_spheres.size(); c->n_tris = nt; c->n_chunks = nm; c->sphere_mag = sphere_magnitude(c);
-    c->scene_dirty = false; c->xf_dirty = false; c->tile_order_valid = false; c->scene_version++;
+    finish_build(c);
     return 0;
+}
+
+// Make the device's scene current for c->params: build what was uploaded, move the meshes, or widen the box padding when a ray origin
+// has moved beyond it
+int prepare_scene(rt_ctx* c)
+{
+    if (c->geom_local) {
+        if (c->scene_dirty) return build_scene_local(c);
+        if (c->xf_dirty || local_scene_magnitude(c) > c->bvh.magnitude) { int r = run_geometry_kernels(c, true); if (r) return r; c->xf_dirty = false; }
+        return 0;
+    }
+    if (c->scene_dirty) return build_scene(c);
+    const float om = std::max(camera_magnitude(c->params), c->sphere_mag);
+    return om > c->bvh.magnitude ? repad_boxes(c, 2.0f * om) : 0;     // widen the box padding, keep the tree
 }
 
 // Give `dst` the scene `src` has built (world-space uploads): every device buffer is copied device to device — over xGMI when the
@@ -634,6 +622,12 @@ bool same_settings(const rt_params& a, const rt_params& b)
 {
     return std::memcmp(&a, &b, kCamBegin) == 0 && std::memcmp((const char*)&a + kCamEnd, (const char*)&b + kCamEnd, sizeof(rt_params) - kCamEnd) == 0;
 }
+// the first entry of params[0 .. n - 1] whose settings differ from entry 0's, 0 if none does (rt_render_params, rt_multi_render_params)
+int other_settings(const rt_params* params, int n)
+{
+    for (int f = 1; f < n; ++f) if (!same_settings(params[f], params[0])) return f;
+    return 0;
+}
 // p (same settings as c->params) becomes the context's params, as rt_set_params(p) would make it
 void use_camera(rt_ctx* c, const rt_params& p)
 {
@@ -667,54 +661,18 @@ template <class Fn> const void* dispatch3(bool a, bool b, bool c3, Fn f)
     return a ? lvl2(std::true_type{}) : lvl2(std::false_type{});
 }
 
-// One kernel choice for all n_frames (kernel: 0 k_trace, 1 k_stream).
-// cams: frame first_frame + f has the uniforms cams[f] (rt_render_params; all with the settings of c->params); null = c->params for all.
-int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int kernel, const rt_params* cams = nullptr)
-{
-    if (n_frames <= 0) cams = nullptr;
-    if (cams) {
-        // Per-frame cameras.  A k_stream launch of several frames becomes a k_cam_stream launch with a camera table (one record per frame);
-        // every other launch — one frame, k_trace, the counting build, the flat twin — goes frame by frame with the frame's camera in
-        // c->params.  Both give the bits of the per-frame loop rt_set_params + rt_render_frame.
-        const bool philox_ = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
-        const bool table = n_frames > 1 && var == Variant::Fast && (kernel == 1 || philox_) && c->params.numRaysPerPixel >= 1
-                           && (c->opt_tile_sync || philox_) && c->params.width <= 65535 && c->params.height <= 65535;     // (= stream_sync below)
-        if (!table) {
-            rt_stats sum{};
-            for (int f = 0; f < n_frames; ++f) {
-                use_camera(c, cams[f]);
-                const int r = launch_frames_k(c, first_frame + f, 1, var, kernel);
-                if (r) return r;
-                add_launch_stats(sum, c->stats);
-            }
-            set_launch_stats(c->stats, sum);
-            return 0;
-        }
-        // the box padding (build, re-pad or geometry pass below, from c->params) for the camera that reaches farthest
-        int far = 0;
-        for (int f = 1; f < n_frames; ++f) if (camera_magnitude(cams[f]) > camera_magnitude(cams[far])) far = f;
-        use_camera(c, cams[far]);
-    }
-    c->frames_traced += (uint64_t)std::max(n_frames, 0);
-    if (!c) return -1;
-    if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
-    if (n_frames < 0) return fail(c, -2, "n_frames < 0");
-    RT_HIP(c, hipSetDevice(c->device));
-    if (c->geom_local) {
-        if (c->scene_dirty) { int r = build_scene_local(c); if (r) return r; }
-        else if (c->xf_dirty || local_scene_magnitude(c) > c->bvh.magnitude) { int r = run_geometry_kernels(c, true); if (r) return r; c->xf_dirty = false; }
-    } else {
-        if (c->scene_dirty) { int r = build_scene(c); if (r) return r; }
-        else {
-            const float om = std::max(camera_magnitude(c->params), c->sphere_mag);
-            if (om > c->bvh.magnitude) { int r = repad_boxes(c, 2.0f * om); if (r) return r; }     // widen the box padding, keep the tree
-        }
-    }
-    if (cams) use_camera(c, cams[n_frames - 1]);      // (from here on only the settings of c->params are read; the context ends with the last frame's)
-    { int r = ensure_targets(c); if (r) return r; }
-    if (c->target_pixels == 0 || n_frames == 0) return 0;
+// What a launch_frames_k call launches, and with which arguments
+struct LaunchPlan {
+    rtk::DeviceScene S{}; rtk::FrameArgs F{}; rtk::StreamArgs A{};
+    const void* fn = nullptr; size_t lds = 0;
+    int grid = 1, batch = 1, ntiles = 0, sample_lanes_log2 = 0;
+    bool philox = false, stream = false, tile_kernel = false, stream_sync = false, cam_table = false, record_costs = false;
+};
 
-    rtk::DeviceScene S{};
+// Kernel choice, traversal stack and LDS, grid, frames per launch, spill buffers (kernel: 0 k_trace, 1 k_stream)
+int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n_frames, LaunchPlan& P)
+{
+    rtk::DeviceScene& S = P.S; rtk::FrameArgs& F = P.F; rtk::StreamArgs& A = P.A;
     S.sph_geom = c->d_sph_geom.p; S.sph_mat = c->d_sph_mat.p; S.nodes = c->d_nodes.p; S.nodes_h = c->d_nodes_h.p;
     S.tri_geo = c->d_tri_geo.p; S.tri_nrm = c->d_tri_nrm.p; S.chunk_mat = c->d_chunk_mat.p; S.chunk_box = c->d_chunk_box.p;
     S.raw_tris = c->d_raw_tris.p; S.raw_chunk_range = c->d_raw_range.p;
@@ -725,7 +683,6 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     S.nt = (int)c->n_tris;
     S.nm = (int)c->n_chunks;
 
-    rtk::FrameArgs F{};
     F.p = c->params;
     F.row0 = c->target_row0; F.nrows = c->target_rows; F.row_stride = c->target_row_stride;
     F.tile_w_log2 = 3;
@@ -737,16 +694,16 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     }
     // the counter-based mode is k_stream's Philox instantiation whatever kernel was asked for (its estimator spreads a pixel's samples
     // over the lanes of a wave); NumRaysPerPixel < 1 draws nothing in either mode and goes to k_trace
-    const bool philox = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
+    const bool philox = P.philox = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
     if (philox && var == Variant::Flat) return fail(c, -2, "the flat validation kernel implements the PCG stream only");
     if (philox) kernel = 1;
     if (philox && (c->target_w > 65535 || c->target_rows > 65535)) return fail(c, -7, "the Philox mode addresses at most 65535 x 65535 pixels per context");
     if (philox && (c->params.numRaysPerPixel > 65000 || c->params.maxBounceCount > 32000))
         return fail(c, -7, "the Philox mode takes at most 65000 rays per pixel per frame and 32000 bounces (sample and bounce share one signed 32-bit register)");
-    const bool stream = kernel == 1 && var != Variant::Flat && c->params.numRaysPerPixel >= 1        // PCG or Philox instantiation
-                        && c->target_w <= 65535 && c->target_rows <= 65535;                          // (16-bit pixel coordinates in k_stream's item tables)
+    const bool stream = P.stream = kernel == 1 && var != Variant::Flat && c->params.numRaysPerPixel >= 1   // PCG or Philox instantiation
+                                   && c->target_w <= 65535 && c->target_rows <= 65535;                     // (16-bit pixel coordinates in k_stream's item tables)
     F.stack_cap = std::max(1, c->bvh.maxStack) + (stream ? 3 : 0);    // the branch-free push writes up to 3 slots past the top
-    const bool tile_kernel = !stream && var != Variant::Flat;   // k_trace, PCG or Philox
+    const bool tile_kernel = P.tile_kernel = !stream && var != Variant::Flat;   // k_trace, PCG or Philox
     if (tile_kernel && c->opt_lds_stack > 0) F.stack_cap = std::min(F.stack_cap, c->opt_lds_stack);
     if (tile_kernel) F.stack_cap = std::min(F.stack_cap, 64);        // a very deep tree spills past 64 entries instead of overflowing the LDS
     // k_stream: at most opt_stream_stack entries per lane in LDS (30 = five workgroups per CU); a deeper worst case spills
@@ -761,13 +718,14 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     F.out_frame = c->d_frame.p; F.accum = c->d_accum.p;
     F.tile_counter = c->d_tile_counter; F.counters = c->d_counters;
 
-    const size_t lds = var == Variant::Flat ? 0
-                              : (size_t)F.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock
-                                + (stream ? (size_t)rtk::kGroupMax * sizeof(uint2) * rtk::kWavesPerBlock : 0);     // k_stream: + the groups' item tables
+    const size_t lds = P.lds = var == Variant::Flat ? 0
+                                       : (size_t)F.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock
+                                         + (stream ? (size_t)rtk::kGroupMax * sizeof(uint2) * rtk::kWavesPerBlock : 0);     // k_stream: + the groups' item tables
     if (lds > 160 * 1024) return fail(c, -7, "BVH needs a %d-entry traversal stack: exceeds the 160 KiB LDS", F.stack_cap);
     const bool counting = var == Variant::Counting;
     const bool compact = c->opt_compact_nodes != 0;            // k_trace / k_stream; the flat twin reads neither
-    const void* fn = var == Variant::Flat ? (const void*)rtk::k_trace<false, true>
+    P.cam_table = cams != nullptr;
+    const void* fn = P.fn = var == Variant::Flat ? (const void*)rtk::k_trace<false, true>
                    : stream ? (cams ? rtk::cam_stream_kernel(philox, compact, c->n_nodes > 0)
                                     : rtk::stream_kernel(counting, philox, compact, c->n_nodes > 0))     // instantiated in rt_stream_kernels.hip
                    : c->n_nodes == 0      // spheres only: the instantiation compiled for six waves per SIMD
@@ -777,21 +735,20 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     int per_cu = 0;
     RT_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, rtk::kBlock, lds));
     if (per_cu < 1) return fail(c, -7, "kernel does not fit a CU (LDS %zu B)", lds);
-    const int ntiles = F.tiles_x * F.tiles_y;
+    P.ntiles = F.tiles_x * F.tiles_y;
     // work items of a multi-frame launch = tiles x frames: a thin strip (one rank of eight: 4,080 tiles) still fills every resident wave
     // Philox mode: S = 16 / 4 / 1 sample lanes per pixel (the estimator's sub-streams, include/rt.h RT_RNG_PHILOX)
-    const int sample_lanes_log2 = !philox ? 0 : c->params.numRaysPerPixel >= 16 ? 4 : c->params.numRaysPerPixel >= 4 ? 2 : 0;
-    const bool stream_sync = stream && (c->opt_tile_sync || philox);       // k_stream taking whole work items (the Philox instantiation always does)
+    P.sample_lanes_log2 = !philox ? 0 : c->params.numRaysPerPixel >= 16 ? 4 : c->params.numRaysPerPixel >= 4 ? 2 : 0;
+    const bool stream_sync = P.stream_sync = stream && (c->opt_tile_sync || philox);       // k_stream taking whole work items (the Philox instantiation always does)
     if (cams && !stream_sync) return fail(c, -7, "per-frame cameras: no k_cam_stream launch for this target");
-    const size_t frames_in_queue = ((stream_sync && c->opt_frame_batch != 1) ? (size_t)std::max(1, std::min(n_frames, 64)) : 1) << sample_lanes_log2;
-    const int want = (int)std::min<size_t>(((size_t)ntiles * frames_in_queue + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock, (size_t)1 << 20);
+    const size_t frames_in_queue = ((stream_sync && c->opt_frame_batch != 1) ? (size_t)std::max(1, std::min(n_frames, 64)) : 1) << P.sample_lanes_log2;
+    const int want = (int)std::min<size_t>(((size_t)P.ntiles * frames_in_queue + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock, (size_t)1 << 20);
     if (c->opt_blocks_per_cu > 0) per_cu = std::min(per_cu, c->opt_blocks_per_cu);
-    const int grid = std::max(1, std::min(want, per_cu * c->n_cu));
-    rtk::StreamArgs A{};
+    const int grid = P.grid = std::max(1, std::min(want, per_cu * c->n_cu));
     A.shade_threshold = std::max(1, std::min(64, c->opt_shade_threshold));
-    A.total_pixels = (unsigned int)ntiles * 64u;
+    A.total_pixels = (unsigned int)P.ntiles * 64u;
     A.tile_sync = stream_sync ? 1 : 0;
-    A.sample_lanes_log2 = sample_lanes_log2;
+    A.sample_lanes_log2 = P.sample_lanes_log2;
     A.tiles_per_fetch = std::max(1, std::min(rtk::kGroupMax, c->opt_tiles_per_fetch));
     A.guide_div = 1;
     A.node_min = std::max(1, std::min(64, c->opt_node_min));
@@ -808,92 +765,106 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
         RT_HIP(c, c->d_gstack.ensure((size_t)(c->bvh.maxStack - F.stack_cap) * gstack_stride));
         F.gstack = c->d_gstack.p; F.gstack_stride = gstack_stride;
     }
-
     // k_trace can trace several frames per launch (work items = (frame, tile)): the persistent waves then balance over
     // frames as well — what matters when a rank's strip has about as many tiles as the chip has wave slots.
-    int batch = 1;
-    const bool stream_tiles = stream_sync;                       // k_stream taking whole tiles: same (frame, tile) items as k_trace
-    if ((tile_kernel || stream_tiles) && n_frames > 1 && c->opt_frame_batch != 1) {
+    // k_stream taking whole tiles (stream_sync) has the same (frame, tile) items as k_trace
+    if ((tile_kernel || stream_sync) && n_frames > 1 && c->opt_frame_batch != 1) {
         const size_t budget = (size_t)4 << 30;                                  // <= 4 GiB of per-frame outputs (16 frames at 3840x2160)
         const size_t per_frame = c->target_pixels * sizeof(float4);
-        batch = (int)std::min<size_t>((size_t)n_frames, std::max<size_t>(1, budget / per_frame));
+        int batch = (int)std::min<size_t>((size_t)n_frames, std::max<size_t>(1, budget / per_frame));
         if (c->opt_frame_batch > 1) batch = std::min(batch, c->opt_frame_batch);
-        batch = std::min(batch, 256);
+        P.batch = batch = std::min(batch, 256);
         if (batch > 1) RT_HIP(c, c->d_batch.ensure((size_t)batch * c->target_pixels));
     }
-    // LPT scheduling of the persistent waves: a launch records every tile's cost; the next ones hand tiles out costliest
-    // first, so the end of a launch is filled with cheap tiles instead of waiting for a few expensive ones.
-    const bool lpt = (tile_kernel || stream_sync) && c->opt_tile_lpt && ntiles > 1;
+    return 0;
+}
+
+// LPT scheduling of the persistent waves: a launch records every tile's cost; the next ones hand tiles out costliest
+// first, so the end of a launch is filled with cheap tiles instead of waiting for a few expensive ones.
+int plan_tile_order(rt_ctx* c, LaunchPlan& P)
+{
+    const int ntiles = P.ntiles;
+    const bool lpt = (P.tile_kernel || P.stream_sync) && c->opt_tile_lpt && ntiles > 1;
     c->lpt_active = lpt;
-    bool record_costs = false;
-    if (lpt) {
-        if (c->tile_order_n != ntiles) { c->tile_order_valid = false; c->tile_order_n = ntiles; }
-        RT_HIP(c, c->d_tile_cost.ensure(ntiles)); RT_HIP(c, c->d_tile_order.ensure(ntiles));
-        if (!c->tile_order_valid || c->tile_order_stale) {
-            record_costs = true;
-            RT_HIP(c, hipMemsetAsync(c->d_tile_cost.p, 0, (size_t)ntiles * sizeof(uint32_t), c->stream));
-        }
-        F.tile_order = c->tile_order_valid ? c->d_tile_order.p : nullptr;
-        F.tile_cost = record_costs ? c->d_tile_cost.p : nullptr;
+    if (!lpt) return 0;
+    if (c->tile_order_n != ntiles) { c->tile_order_valid = false; c->tile_order_n = ntiles; }
+    RT_HIP(c, c->d_tile_cost.ensure(ntiles)); RT_HIP(c, c->d_tile_order.ensure(ntiles));
+    if (!c->tile_order_valid || c->tile_order_stale) {
+        P.record_costs = true;
+        RT_HIP(c, hipMemsetAsync(c->d_tile_cost.p, 0, (size_t)ntiles * sizeof(uint32_t), c->stream));
     }
-    // ---- camera rays' candidate lists: every pixel's camera rays start from <= 4 leaves found once per camera / scene (rt_primary.hpp)
-    {
-        std::string key((const char*)&c->params, sizeof c->params);
-        const unsigned long long geo[6] = { c->scene_version, (unsigned long long)c->target_row0, (unsigned long long)c->target_rows,
-                                            (unsigned long long)c->target_row_stride, (unsigned long long)c->target_w, (unsigned long long)c->target_h };
-        key.append((const char*)geo, sizeof geo);
-        const bool eligible = stream && !cams && c->opt_primary_lists && c->n_nodes > 0 && F.fixed_origin && c->target_pixels > 0 && c->bvh.maxStack <= 160;
-        if (eligible) {                 // (the build takes well under a millisecond at 1080p: a camera that moves every frame pays it every frame and still gains)
-            if (key != c->primary_key) {
-                RT_HIP(c, c->d_primary.ensure(c->target_pixels)); RT_HIP(c, c->d_focus.ensure(c->target_pixels)); RT_HIP(c, c->d_primary_counts.ensure(4));
-                RT_HIP(c, hipMemsetAsync(c->d_primary_counts.p, 0, 4 * sizeof(unsigned int), c->stream));
-                rtp::PrimaryArgs PA{};
-                PA.p = c->params; PA.row0 = c->target_row0; PA.nrows = c->target_rows; PA.row_stride = c->target_row_stride;
-                PA.lists = c->d_primary.p; PA.focus = c->d_focus.p; PA.counts = c->d_primary_counts.p;
-                const int tiles = ((c->target_w + 7) / 8) * ((c->target_rows + 7) / 8);
-                PA.stack_cap = std::max(1, c->bvh.maxStack);                       // (the whole worst case in LDS: at most 160 entries x 64 lanes x 4 B = 40 KB per wave)
-                const size_t plds = (size_t)PA.stack_cap * 64 * sizeof(uint32_t);
-                RT_HIP(c, hipEventRecord(c->evg0, c->stream));
-                hipLaunchKernelGGL(rtp::k_primary_lists, dim3(tiles), dim3(64), plds, c->stream, S, PA);
-                RT_HIP(c, hipGetLastError());
-                RT_HIP(c, hipEventRecord(c->evg1, c->stream));
-                unsigned int h[4];
-                RT_HIP(c, hipMemcpyAsync(h, c->d_primary_counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-                RT_HIP(c, hipStreamSynchronize(c->stream));
-                float ms = 0.f;
-                RT_HIP(c, hipEventElapsedTime(&ms, c->evg0, c->evg1));
-                for (int k = 0; k < 4; ++k) c->stats.primaryLists[k] = h[k];
-                c->stats.lastPrimaryListsMs = ms; c->stats.primaryListBuilds++;
-                c->primary_key = key;
-            }
-            F.primary = c->d_primary.p; F.focus = c->d_focus.p;
-        }
+    P.F.tile_order = c->tile_order_valid ? c->d_tile_order.p : nullptr;
+    P.F.tile_cost = P.record_costs ? c->d_tile_cost.p : nullptr;
+    return 0;
+}
+
+// Camera rays' candidate lists: every pixel's camera rays start from <= 4 leaves found once per camera / scene (rt_primary.hpp)
+int ensure_primary_lists(rt_ctx* c, LaunchPlan& P)
+{
+    const bool eligible = P.stream && !P.cam_table && c->opt_primary_lists && c->n_nodes > 0 && P.F.fixed_origin && c->target_pixels > 0
+                          && c->bvh.maxStack <= 160;
+    if (!eligible) return 0;
+    std::string key((const char*)&c->params, sizeof c->params);
+    const unsigned long long geo[6] = { c->scene_version, (unsigned long long)c->target_row0, (unsigned long long)c->target_rows,
+                                        (unsigned long long)c->target_row_stride, (unsigned long long)c->target_w, (unsigned long long)c->target_h };
+    key.append((const char*)geo, sizeof geo);
+    if (key != c->primary_key) {     // (the build takes well under a millisecond at 1080p: a camera that moves every frame pays it every frame and still gains)
+        RT_HIP(c, c->d_primary.ensure(c->target_pixels)); RT_HIP(c, c->d_focus.ensure(c->target_pixels)); RT_HIP(c, c->d_primary_counts.ensure(4));
+        RT_HIP(c, hipMemsetAsync(c->d_primary_counts.p, 0, 4 * sizeof(unsigned int), c->stream));
+        rtp::PrimaryArgs PA{};
+        PA.p = c->params; PA.row0 = c->target_row0; PA.nrows = c->target_rows; PA.row_stride = c->target_row_stride;
+        PA.lists = c->d_primary.p; PA.focus = c->d_focus.p; PA.counts = c->d_primary_counts.p;
+        const int tiles = ((c->target_w + 7) / 8) * ((c->target_rows + 7) / 8);
+        PA.stack_cap = std::max(1, c->bvh.maxStack);                       // (the whole worst case in LDS: at most 160 entries x 64 lanes x 4 B = 40 KB per wave)
+        const size_t plds = (size_t)PA.stack_cap * 64 * sizeof(uint32_t);
+        RT_HIP(c, hipEventRecord(c->evg0, c->stream));
+        hipLaunchKernelGGL(rtp::k_primary_lists, dim3(tiles), dim3(64), plds, c->stream, P.S, PA);
+        RT_HIP(c, hipGetLastError());
+        RT_HIP(c, hipEventRecord(c->evg1, c->stream));
+        unsigned int h[4];
+        RT_HIP(c, hipMemcpyAsync(h, c->d_primary_counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&ms, c->evg0, c->evg1));
+        for (int k = 0; k < 4; ++k) c->stats.primaryLists[k] = h[k];
+        c->stats.lastPrimaryListsMs = ms; c->stats.primaryListBuilds++;
+        c->primary_key = key;
     }
-    // ---- per-frame cameras: the launch's camera table (a launch of frames i .. i + nb - 1 reads its records from entry i)
-    if (cams) {
-        c->h_cams.resize((size_t)n_frames);
-        for (int f = 0; f < n_frames; ++f) {
-            const rt_params& q = cams[f];
-            rtk::CamRecord& rec = c->h_cams[f];
-            rec.view = make_float4(q.viewParams[0], q.viewParams[1], q.viewParams[2], 0.f);
-            rec.m0 = f4(q.camLocalToWorld); rec.m1 = f4(q.camLocalToWorld + 4); rec.m2 = f4(q.camLocalToWorld + 8);
-            rec.pos = make_float4(q.worldSpaceCameraPos[0], q.worldSpaceCameraPos[1], q.worldSpaceCameraPos[2], 0.f);
-        }
-        RT_HIP(c, c->d_cams.ensure((size_t)n_frames));
-        RT_HIP(c, hipMemcpyAsync(c->d_cams.p, c->h_cams.data(), (size_t)n_frames * sizeof(rtk::CamRecord), hipMemcpyHostToDevice, c->stream));
+    P.F.primary = c->d_primary.p; P.F.focus = c->d_focus.p;
+    return 0;
+}
+
+// Per-frame cameras: the launch's camera table (a launch of frames i .. i + nb - 1 reads its records from entry i)
+int upload_camera_table(rt_ctx* c, const rt_params* cams, int n_frames)
+{
+    c->h_cams.resize((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        const rt_params& q = cams[f];
+        rtk::CamRecord& rec = c->h_cams[f];
+        rec.view = make_float4(q.viewParams[0], q.viewParams[1], q.viewParams[2], 0.f);
+        rec.m0 = f4(q.camLocalToWorld); rec.m1 = f4(q.camLocalToWorld + 4); rec.m2 = f4(q.camLocalToWorld + 8);
+        rec.pos = make_float4(q.worldSpaceCameraPos[0], q.worldSpaceCameraPos[1], q.worldSpaceCameraPos[2], 0.f);
     }
+    RT_HIP(c, upload(c, c->d_cams, c->h_cams));
+    return 0;
+}
+
+// The trace launches of frames first_frame .. first_frame + n_frames - 1, P.batch frames per launch, each batch accumulated
+int run_launches(rt_ctx* c, LaunchPlan& P, int first_frame, int n_frames)
+{
+    rtk::FrameArgs& F = P.F; rtk::StreamArgs& A = P.A;
     RT_HIP(c, hipMemsetAsync(c->d_counters, 0, rtk::kNumCounters * sizeof(unsigned long long), c->stream));
     RT_HIP(c, hipEventRecord(c->ev0, c->stream));
     for (int i = 0; i < n_frames; ) {
-        int nb = batch > 1 ? std::min(batch, n_frames - i) : 1;
+        int nb = P.batch > 1 ? std::min(P.batch, n_frames - i) : 1;
         // k_stream, frame-interleaved sub-tiles: a wave = (4x4 or 2x2 pixels) x (4 or 16 frames); launches take whole frame
         // groups, the remainder of the render goes out as 8x8 x 1 items
         A.n16 = A.n4 = 0; A.n1 = nb;
-        if (stream_tiles) {
+        if (P.stream_sync) {
             // as many groups of 16 frames as fit, then groups of 4, the rest one by one — all in this one launch
             int rem = nb;
-            if (!philox && c->opt_stream_tile >= 4) { A.n16 = rem / 16; rem -= A.n16 * 16; }      // (Philox: sample lanes, not frames, fill a wave)
-            if (!philox && c->opt_stream_tile >= 2) { A.n4 = rem / 4; rem -= A.n4 * 4; }
+            if (!P.philox && c->opt_stream_tile >= 4) { A.n16 = rem / 16; rem -= A.n16 * 16; }      // (Philox: sample lanes, not frames, fill a wave)
+            if (!P.philox && c->opt_stream_tile >= 2) { A.n4 = rem / 4; rem -= A.n4 * 4; }
             A.n1 = rem;
             // groups shrink towards the end of the launch (k_stream: guided self-scheduling): up to tiles_per_fetch items per fetch
             // while more than guide x (waves of the launch) x that many items are left
@@ -901,16 +872,16 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
             // (Philox: the units of a group are small — a few samples — and handed out dynamically, so big groups balance by themselves and
             // only the launch's last round of groups needs to shrink: a single 1080p frame 19.2 -> 17.5 ms with guide 1; PCG units are whole
             // pixels and need the finer tail: 19.9 -> 47.9 ms with it)
-            A.guide_div = std::max(1, grid * rtk::kWavesPerBlock * (philox ? std::max(1, c->opt_fetch_guide_philox) : std::max(1, c->opt_fetch_guide)));
+            A.guide_div = std::max(1, P.grid * rtk::kWavesPerBlock * (P.philox ? std::max(1, c->opt_fetch_guide_philox) : std::max(1, c->opt_fetch_guide)));
         }
         F.frame = first_frame + i;
         F.frames_in_launch = nb; F.frame_stride = (unsigned int)c->target_pixels;
         F.out_frame = nb > 1 ? c->d_batch.p : c->d_frame.p;
         RT_HIP(c, hipMemsetAsync(c->d_tile_counter, 0, sizeof(unsigned int), c->stream));
         {
-            const rtk::CamRecord* cam_tab = cams ? c->d_cams.p + i : nullptr;
-            void* args[4] = { (void*)&S, (void*)&F, (void*)&A, (void*)&cam_tab };    // k_trace takes (S, F) only, k_stream (S, F, A)
-            RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
+            const rtk::CamRecord* cam_tab = P.cam_table ? c->d_cams.p + i : nullptr;
+            void* args[4] = { (void*)&P.S, (void*)&F, (void*)&A, (void*)&cam_tab };    // k_trace takes (S, F) only, k_stream (S, F, A)
+            RT_HIP(c, hipLaunchKernel(P.fn, dim3(P.grid), dim3(rtk::kBlock), args, P.lds, c->stream));
         }
         RT_HIP(c, hipGetLastError());
         if (nb > 1) {
@@ -921,42 +892,87 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
         }
         i += nb;
     }
-    c->stats.lastFramesPerLaunch = batch;
-    c->stats.lastKernel = var == Variant::Flat ? 4 : stream ? (cams ? 2 : 1) : 0;
-    c->stats.lastFramesInterleaved = stream ? (philox ? 1 : A.n16 ? 16 : A.n4 ? 4 : 1) : 1;
-    c->stats.lastSampleLanes = philox ? 1 << sample_lanes_log2 : 1;
+    return 0;
+}
+
+// After the launches: the kernel time, the tile order for the next launches and the counters
+int finish_launch(rt_ctx* c, const LaunchPlan& P, Variant var, int n_frames)
+{
+    c->stats.lastFramesPerLaunch = P.batch;
+    c->stats.lastKernel = var == Variant::Flat ? 4 : P.stream ? (P.cam_table ? 2 : 1) : 0;
+    c->stats.lastFramesInterleaved = P.stream ? (P.philox ? 1 : P.A.n16 ? 16 : P.A.n4 ? 4 : 1) : 1;
+    c->stats.lastSampleLanes = P.philox ? 1 << P.sample_lanes_log2 : 1;
     RT_HIP(c, hipEventRecord(c->ev1, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
     RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     c->stats.lastKernelMs = ms; c->stats.totalKernelMs += ms;
-    if (record_costs) {
+    if (P.record_costs) {
         // costliest tiles first for the next launches: counting sort on the device, no host round trip
+        const uint32_t ntiles = (uint32_t)P.ntiles;
         RT_HIP(c, c->d_tile_hist.ensure(rtg::kCostBuckets));
         RT_HIP(c, hipMemsetAsync(c->d_tile_hist.p, 0, rtg::kCostBuckets * sizeof(uint32_t), c->stream));
-        hipLaunchKernelGGL(rtg::k_tile_hist, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost.p, (uint32_t)ntiles, c->d_tile_hist.p);
+        hipLaunchKernelGGL(rtg::k_tile_hist, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost.p, ntiles, c->d_tile_hist.p);
         hipLaunchKernelGGL(rtg::k_tile_scan, dim3(1), dim3(1024), 0, c->stream, c->d_tile_hist.p);
-        hipLaunchKernelGGL(rtg::k_tile_scatter, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost.p, (uint32_t)ntiles,
+        hipLaunchKernelGGL(rtg::k_tile_scatter, dim3((ntiles + 255) / 256), dim3(256), 0, c->stream, c->d_tile_cost.p, ntiles,
                            c->d_tile_hist.p, c->d_tile_order.p);
         RT_HIP(c, hipGetLastError());
         c->tile_order_valid = true; c->tile_order_stale = false;
     }
     c->stats.numRenderedFrames += n_frames;
-    {
-        unsigned long long h[rtk::kNumCounters];
-        RT_HIP(c, hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-        c->stats.rays = h[0];                        // counted by every variant
-        if (var == Variant::Counting) {
-            c->stats.sphereTests = h[1]; c->stats.nodeVisits = h[2]; c->stats.triTests = h[3]; c->stats.hits = h[4];
-            for (int k = 0; k < 5; ++k) { c->stats.phaseLanes[k] = h[5 + k]; c->stats.phaseExecs[k] = h[10 + k]; }
-            for (int k = 0; k < rtk::kNumRegions; ++k) c->stats.regionExecs[k] = h[15 + k];
-        } else {
-            c->stats.sphereTests = c->stats.nodeVisits = c->stats.triTests = c->stats.hits = 0;
-            for (int k = 0; k < 5; ++k) c->stats.phaseLanes[k] = c->stats.phaseExecs[k] = 0;
-            for (int k = 0; k < rtk::kNumRegions; ++k) c->stats.regionExecs[k] = 0;
-        }
-    }
+    unsigned long long h[rtk::kNumCounters];
+    RT_HIP(c, hipMemcpy(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    c->stats.rays = h[0];                        // counted by every variant
+    const bool counting = var == Variant::Counting;
+    c->stats.sphereTests = counting ? h[1] : 0; c->stats.nodeVisits = counting ? h[2] : 0; c->stats.triTests = counting ? h[3] : 0; c->stats.hits = counting ? h[4] : 0;
+    for (int k = 0; k < 5; ++k) { c->stats.phaseLanes[k] = counting ? h[5 + k] : 0; c->stats.phaseExecs[k] = counting ? h[10 + k] : 0; }
+    for (int k = 0; k < rtk::kNumRegions; ++k) c->stats.regionExecs[k] = counting ? h[15 + k] : 0;
     return 0;
+}
+
+// One kernel choice for all n_frames (kernel: 0 k_trace, 1 k_stream).
+// cams: frame first_frame + f has the uniforms cams[f] (rt_render_params; all with the settings of c->params); null = c->params for all.
+int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int kernel, const rt_params* cams = nullptr)
+{
+    if (!c) return -1;
+    if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
+    if (n_frames < 0) return fail(c, -2, "n_frames < 0");
+    if (n_frames == 0) cams = nullptr;
+    // Per-frame cameras.  A k_stream launch of several frames becomes a k_cam_stream launch with a camera table (one record per frame);
+    // every other launch — one frame, k_trace, the counting build, the flat twin — goes frame by frame with the frame's camera in
+    // c->params.  Both give the bits of the per-frame loop rt_set_params + rt_render_frame.
+    const bool philox = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
+    const bool table = n_frames > 1 && var == Variant::Fast && (kernel == 1 || philox) && c->params.numRaysPerPixel >= 1
+                       && (c->opt_tile_sync || philox) && c->params.width <= 65535 && c->params.height <= 65535;     // (= stream_sync of plan_launch)
+    if (cams && !table) {
+        rt_stats sum{};
+        for (int f = 0; f < n_frames; ++f) {
+            use_camera(c, cams[f]);
+            const int r = launch_frames_k(c, first_frame + f, 1, var, kernel);
+            if (r) return r;
+            add_launch_stats(sum, c->stats);
+        }
+        set_launch_stats(c->stats, sum);
+        return 0;
+    }
+    if (cams) {     // the box padding (prepare_scene, from c->params) for the camera that reaches farthest
+        int far = 0;
+        for (int f = 1; f < n_frames; ++f) if (camera_magnitude(cams[f]) > camera_magnitude(cams[far])) far = f;
+        use_camera(c, cams[far]);
+    }
+    c->frames_traced += (uint64_t)n_frames;     // (before the build: the moving-scene window of build_scene counts this launch)
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = prepare_scene(c); if (r) return r; }
+    if (cams) use_camera(c, cams[n_frames - 1]);      // (from here on only the settings of c->params are read; the context ends with the last frame's)
+    { int r = ensure_targets(c); if (r) return r; }
+    if (c->target_pixels == 0 || n_frames == 0) return 0;
+    LaunchPlan P;
+    int r = plan_launch(c, var, kernel, cams, n_frames, P);
+    if (!r) r = plan_tile_order(c, P);
+    if (!r) r = ensure_primary_lists(c, P);
+    if (!r && cams) r = upload_camera_table(c, cams, n_frames);
+    if (!r) r = run_launches(c, P, first_frame, n_frames);
+    return r ? r : finish_launch(c, P, var, n_frames);
 }
 
 // Kernel choice "auto" (option kernel = -1, the default): k_trace and k_stream (resumable traversal, stragglers deferred)
@@ -1265,8 +1281,7 @@ int rt_read_world_geometry(rt_ctx* c, rt_triangle* tris_out, int n_tris, rt_mesh
     if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
     if (n_tris != (int)c->h_local_tris.size() || n_chunks != (int)c->h_lchunks.size()) return fail(c, -2, "size mismatch");
     RT_HIP(c, hipSetDevice(c->device));
-    if (c->scene_dirty) { int r = build_scene_local(c); if (r) return r; }
-    else if (c->xf_dirty) { int r = run_geometry_kernels(c, true); if (r) return r; c->xf_dirty = false; }
+    { int r = prepare_scene(c); if (r) return r; }     // (a pass for a wider padding refits node boxes only: the world triangles and chunk boxes stay)
     if (n_tris) RT_HIP(c, hipMemcpy(tris_out, c->d_raw_tris.p, (size_t)n_tris * sizeof(rt_triangle), hipMemcpyDeviceToHost));
     std::vector<float4> box(2 * (size_t)n_chunks);
     if (n_chunks) RT_HIP(c, hipMemcpy(box.data(), c->d_chunk_box.p, box.size() * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1356,8 +1371,7 @@ int rt_render_params(rt_ctx* c, int first_frame, int n_frames, const rt_params* 
     if (n_frames < 0) return fail(c, -2, "n_frames < 0");
     if (n_frames == 0) return 0;
     if (!params) return fail(c, -2, "null params");
-    for (int f = 1; f < n_frames; ++f)
-        if (!same_settings(params[f], params[0])) return fail(c, -2, "rt_render_params: entry %d differs from entry 0 outside the camera fields", f);
+    if (const int f = other_settings(params, n_frames)) return fail(c, -2, "rt_render_params: entry %d differs from entry 0 outside the camera fields", f);
     if (!c->have_params || !same_settings(c->params, params[0])) { const int r = rt_set_params(c, &params[0]); if (r) return r; }
     return launch_run(c, first_frame, n_frames, params);
 }
@@ -1738,8 +1752,7 @@ int rt_multi_render_params(rt_multi* m, int first_frame, int n_frames, const rt_
     if (n_frames < 0) return mfail(m, -2, "n_frames < 0");
     if (n_frames == 0) return 0;
     if (!params) return mfail(m, -2, "null params");
-    for (int f = 1; f < n_frames; ++f)
-        if (!same_settings(params[f], params[0])) return mfail(m, -2, "rt_multi_render_params: entry %d differs from entry 0 outside the camera fields", f);
+    if (const int f = other_settings(params, n_frames)) return mfail(m, -2, "rt_multi_render_params: entry %d differs from entry 0 outside the camera fields", f);
     if (!m->have_params || !same_settings(m->ctx[0]->params, params[0])) { const int r = rt_multi_set_params(m, &params[0]); if (r) return r; }
     return multi_render(m, first_frame, n_frames, params);
 }
@@ -1809,10 +1822,9 @@ int rt_multi_get_stats(rt_multi* m, rt_stats* out, double* gather_ms)
     rt_stats sum = m->ctx[0]->stats;
     for (size_t i = 1; i < m->ctx.size(); ++i) {
         const rt_stats& s = m->ctx[i]->stats;
-        sum.rays += s.rays; sum.sphereTests += s.sphereTests; sum.nodeVisits += s.nodeVisits; sum.triTests += s.triTests; sum.hits += s.hits;
-        for (int k = 0; k < 5; ++k) { sum.phaseLanes[k] += s.phaseLanes[k]; sum.phaseExecs[k] += s.phaseExecs[k]; }
-        for (int k = 0; k < rtk::kNumRegions; ++k) sum.regionExecs[k] += s.regionExecs[k];
-        sum.lastKernelMs = std::max(sum.lastKernelMs, s.lastKernelMs); sum.totalKernelMs = std::max(sum.totalKernelMs, s.totalKernelMs);
+        const double last_ms = std::max(sum.lastKernelMs, s.lastKernelMs);      // (kernel times: the slowest context's)
+        add_launch_stats(sum, s);
+        sum.lastKernelMs = last_ms; sum.totalKernelMs = std::max(sum.totalKernelMs, s.totalKernelMs);
     }
     *out = sum;
     if (gather_ms) *gather_ms = m->lastGatherMs;
