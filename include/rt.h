@@ -190,7 +190,10 @@ rt_ctx*     rt_create(int device);
 void        rt_destroy(rt_ctx* ctx);
 const char* rt_last_error(const rt_ctx* ctx);
 
-/* Optional: run on a caller-owned hipStream_t (pass as void*).  NULL restores the context's own stream. */
+/* Optional: run on a caller-owned hipStream_t (pass as void*).  NULL restores the context's own stream.  The switch is ordered: work the
+ * context enqueued on the outgoing stream completes before anything it enqueues on the incoming one (an event recorded on the outgoing
+ * stream, waited for by the incoming one), so a device query left running on a caller's stream is never overtaken by the context's next
+ * upload, geometry pass or render.                                                                                                   */
 int rt_set_stream(rt_ctx* ctx, void* hip_stream);
 
 /* Uniform upload.  Replaces SetShaderParams + UpdateCameraParams (RayTracingManager.cs:111-133).
@@ -350,6 +353,58 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * Either destination may be NULL.  Tests check that every f16 box contains its f32 box.                                 */
 int rt_read_bvh(rt_ctx* ctx, void* nodes_f32, void* nodes_f16, size_t n_nodes);
 
+/* ---- ray queries: what a caller-supplied ray hits -------------------------------------------------------------------
+ * The reference answers "what does this ray hit?" only inside its shader: CalculateRayCollision (RayTracing.shader:256-297) over
+ * every sphere, then every chunk whose RayBoundingBox passes (:276-294), strict '<' throughout.  These calls run that function for
+ * rays the caller makes (picking, autofocus, line of sight) against the scene the next frame would trace, through the library's
+ * BVH; the answer is the reference's bit for bit in every field of rt_hit.
+ *
+ *   closest hit   hits[i] = CalculateRayCollision(origin, direction) when its dst < tMax, else a miss.  The context's
+ *                 intersectMode applies (RT_INTERSECT_FLAT_CHUNKS when rt_set_params was never called: a query needs no params).
+ *   occlusion     occluded[i] = 1 exactly when the closest-hit query with the same ray hits: an any-hit traversal that stops at the
+ *                 first sphere or triangle with dst < tMax (in FLAT_CHUNKS mode, one whose chunk's box test passes).
+ *   scene         the queue is settled first; then the scene is made current as for a frame (pending uploads, moved meshes).  The box
+ *                 padding is widened, as for a camera, when the largest finite |origin coordinate| of the rays that are traced exceeds
+ *                 what the boxes were padded for (rt_stats.bvhRepads; local uploads: one geometry pass).  Nothing else changes: no
+ *                 accumulation state, frame counter or work counter moves (only bvhBuilds / bvhRebuilds / bvhRepads, when the query
+ *                 triggered that build or re-padding).  The widened padding outlives the query, as a camera's does: boxes padded for
+ *                 origins far out prune less, so later frames trace slower until the next build (a new upload).
+ *   arguments     n == 0 returns 0; a null context -1; n < 0, a null buffer with n > 0, or a device pointer of another device
+ *                 (device entries: also one not 16-byte aligned) -2 with a message in rt_last_error.                              */
+typedef struct rt_ray {                 /* 32 B */
+    float   origin[3];
+    float   tMax;                       /* only hits with dst < tMax count; +inf = unbounded; <= 0 or NaN = a miss, nothing is traced */
+    float   direction[3];               /* not normalised by the library: dst is in units of |direction|, as in the shader             */
+    int32_t _reserved;
+} rt_ray;
+
+enum { RT_HIT_NONE = 0, RT_HIT_SPHERE = 1, RT_HIT_TRIANGLE = 2 };
+
+typedef struct rt_hit {                 /* 64 B; a miss: dst = +inf, hitPoint = normal = 0, kind = RT_HIT_NONE, indices -1, u = v = 0 */
+    float   dst;                        /* CalculateRayCollision's closest.dst (:256-297)                                               */
+    float   hitPoint[3];                /* origin + direction * dst (RaySphere :141, RayTriangle :170)                                  */
+    float   normal[3];                  /* the shading normal Trace uses: sphere normalize(hitPoint - centre) (:142), triangle the       */
+                                        /* normalised interpolation of the vertex normals (:171)                                        */
+    int32_t kind;                       /* RT_HIT_*                                                                                      */
+    int32_t primitive;                  /* sphere: index in the uploaded sphere buffer; triangle: index in the world triangle buffer     */
+                                        /* (rt_upload_triangles order; local uploads: rt_read_world_geometry order); else -1             */
+    int32_t chunk;                      /* triangle: its rt_meshinfo index (the chunk whose material shades it); else -1                 */
+    int32_t mesh;                       /* triangle of an rt_upload_local_meshes scene: its mesh index; else -1                          */
+    float   u, v;                       /* triangle: RayTriangle's u, v (:163-165; w = 1 - u - v); else 0                                */
+    int32_t _reserved[3];
+} rt_hit;
+
+/* Host memory; return when the results are in hits / occluded.  The rays go through device buffers of the context in slices of at
+ * most 4M rays, so the memory used does not grow with n.                                                                        */
+int rt_trace_rays (rt_ctx* ctx, const rt_ray* rays, int n, rt_hit* hits);
+int rt_occluded   (rt_ctx* ctx, const rt_ray* rays, int n, uint8_t* occluded);
+/* Device memory of the context's GPU (rays: n rt_ray, hits: n rt_hit, occluded: n bytes; rays and hits 16-byte aligned), ordered on
+ * the context's stream (rt_set_stream; switching the stream away afterwards keeps the order: the next stream waits for the query).  The call returns once the query is enqueued, with one exception to the asynchrony: the
+ * box padding needs the largest |origin coordinate| of the batch, so a small reduction kernel runs first and the call waits for
+ * its 4-byte result (a stream synchronisation) before it enqueues the query.                                                     */
+int rt_trace_rays_device(rt_ctx* ctx, const void* rays, int n, void* hits);
+int rt_occluded_device  (rt_ctx* ctx, const void* rays, int n, void* occluded);
+
 /* ---- several GPUs of one node behind one handle ---------------------------------------------------------------------
  * The reference renders on one GPU; its path shards into independent pixels (seed = global pixel index + Frame * 719393,
  * RayTracing.shader:360-362; Accumulate.shader is per pixel), so the frame tiles across devices by rows.  An rt_multi owns one
@@ -404,10 +459,14 @@ typedef struct rt_multi_info {
                                         /* (copies go GPU to GPU over xGMI), 0: the runtime stages them; [0] = 1            */
 } rt_multi_info;
 int rt_multi_get_info        (rt_multi* m, rt_multi_info* out);
+/* Ray queries behind the handle (host memory): the batch is cut into one contiguous slice per context, the slices are traced
+ * concurrently against each context's copy of the scene and gathered in order — bitwise the single-context result.              */
+int rt_multi_trace_rays      (rt_multi* m, const rt_ray* rays, int n, rt_hit* hits);
+int rt_multi_occluded        (rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" */
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,12 @@ MULTI_INFO = np.dtype([("numContexts", "<i4"), ("bvhBuilds", "<i4"), ("lastSetup
                        ("device", "<i4", 16), ("peerAccess", "<i4", 16)])
 LOCAL_CHUNK = np.dtype([("firstTriangleIndex", "<u4"), ("numTriangles", "<u4"), ("meshIndex", "<u4"), ("_reserved", "<u4"),
                         ("material", MATERIAL)])
+# ray queries (rt_trace_rays / rt_occluded): a caller's ray and what it hits
+RAY = np.dtype([("origin", "<f4", 3), ("tMax", "<f4"), ("direction", "<f4", 3), ("_reserved", "<i4")])
+HIT = np.dtype([("dst", "<f4"), ("hitPoint", "<f4", 3), ("normal", "<f4", 3), ("kind", "<i4"), ("primitive", "<i4"), ("chunk", "<i4"),
+                ("mesh", "<i4"), ("u", "<f4"), ("v", "<f4"), ("_reserved", "<i4", 3)])
+RT_HIT_NONE, RT_HIT_SPHERE, RT_HIT_TRIANGLE = 0, 1, 2
+assert RAY.itemsize == 32 and HIT.itemsize == 64
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 RT_INTERSECT_FLAT_CHUNKS = 0
@@ -67,6 +73,7 @@ SYMBOLS = [
     "rt_multi_render", "rt_multi_read_accum", "rt_multi_get_stats", "rt_multi_get_info",
     "rt_multi_upload_local_meshes", "rt_multi_set_mesh_transforms", "rt_multi_read_display", "rt_multi_write_accum",
     "rt_render_params", "rt_submit_frame_params", "rt_multi_render_params",
+    "rt_trace_rays", "rt_occluded", "rt_trace_rays_device", "rt_occluded_device", "rt_multi_trace_rays", "rt_multi_occluded",
 ]
 
 _lib = None
@@ -142,6 +149,8 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_set_mesh_transforms.argtypes = [c_void_p, c_void_p, c_int]
     lib.rt_multi_read_display.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.rt_multi_write_accum.argtypes = [c_void_p, POINTER(c_float), c_size_t, c_int]
+    for n in ("rt_trace_rays", "rt_occluded", "rt_trace_rays_device", "rt_occluded_device", "rt_multi_trace_rays", "rt_multi_occluded"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -150,7 +159,8 @@ def load_library() -> ctypes.CDLL:
         f.restype = c_int
     for name, dt in (("rt_material", MATERIAL), ("rt_sphere", SPHERE), ("rt_triangle", TRIANGLE),
                      ("rt_meshinfo", MESHINFO), ("rt_params", PARAMS), ("rt_stats", STATS),
-                     ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO)):
+                     ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO),
+                     ("rt_ray", RAY), ("rt_hit", HIT)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -164,9 +174,32 @@ def _params_run(params):
     return p, int(p.shape[0])
 
 
+def _ray_array(rays) -> np.ndarray:
+    """a C-contiguous RAY array from a RAY array or a float32 (n, 8) array (origin, tMax, direction, -)"""
+    a = np.asarray(rays)
+    if a.dtype == RAY:
+        return np.ascontiguousarray(a.reshape(-1))
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"rays: a RAY array or float32 (n, 8), not {a.dtype} {a.shape}")
+    return a.view(RAY).reshape(-1)
+
+
+def _query_host(call, handle, rays, any_hit: bool, check, what):
+    r = _ray_array(rays)
+    out = np.zeros(r.shape[0], np.uint8) if any_hit else np.zeros(r.shape[0], HIT)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
 def _as_buffer(arr, dtype):
     a = np.ascontiguousarray(arr, dtype=dtype)
     return a, a.ctypes.data_as(c_void_p), int(a.shape[0]) if a.ndim else 0
+
+
+def _is_tensor(x) -> bool:
+    t = type(x)
+    return t.__module__.startswith("torch") and t.__name__ == "Tensor" and getattr(x, "is_cuda", False)
 
 
 class Tracer:
@@ -249,6 +282,52 @@ class Tracer:
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.rt_set_stream(self._ctx, c_void_p(stream_ptr)), "rt_set_stream")
+        self._stream = stream_ptr
+
+    # -- ray queries
+    def trace_rays(self, rays):
+        """rt_trace_rays: the closest hit of every ray.  rays: a RAY array or float32 (n, 8) -> a HIT array.  A float32 CUDA tensor
+        (n, 8) on the context's device takes the device entry instead and returns a float32 (n, 16) tensor (the HIT records)."""
+        if _is_tensor(rays):
+            return self._query_device(rays, False)
+        return _query_host(self._lib.rt_trace_rays, self._ctx, rays, False, self._check, "rt_trace_rays")
+
+    def occluded(self, rays):
+        """rt_occluded: 1 where the closest-hit query of the ray would hit.  rays as for trace_rays -> uint8 (n,) (array or tensor)."""
+        if _is_tensor(rays):
+            return self._query_device(rays, True)
+        return _query_host(self._lib.rt_occluded, self._ctx, rays, True, self._check, "rt_occluded")
+
+    def _query_device(self, rays, any_hit: bool):
+        """The device entries on torch tensors, ordered with torch's current stream both ways: the context runs the call on that stream
+        (rt_set_stream: the stream first waits for what the context enqueued before) and goes back to its own stream (or the one set_stream
+        gave it) afterwards, which then waits for the query (rt_set_stream's switch is ordered) — so torch's later work on the stream sees
+        the results, and the context's next upload, geometry pass or render cannot overtake the query.  torch's legacy default stream has no handle the
+        library can take (NULL means the context's own stream), so there the call is fenced: torch's stream is synchronised before it and
+        the device after it.  (torch ships its own HIP runtime: import torch before the library is loaded, so that both use that one.)"""
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays: a float32 (n, 8) tensor, not {rays.dtype} {tuple(rays.shape)}")
+        rays = rays.contiguous()
+        n = int(rays.shape[0])
+        out = torch.empty((n,), dtype=torch.uint8, device=rays.device) if any_hit else torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+        stream = torch.cuda.current_stream(rays.device)
+        handle = int(stream.cuda_stream)
+        call = self._lib.rt_occluded_device if any_hit else self._lib.rt_trace_rays_device
+        what = "rt_occluded_device" if any_hit else "rt_trace_rays_device"
+        if handle == 0:
+            stream.synchronize()
+            rc = call(self._ctx, c_void_p(rays.data_ptr()), n, c_void_p(out.data_ptr()))
+            torch.cuda.synchronize(rays.device)
+            self._check(rc, what)
+            return out
+        self._check(self._lib.rt_set_stream(self._ctx, c_void_p(handle)), "rt_set_stream")
+        try:
+            rc = call(self._ctx, c_void_p(rays.data_ptr()), n, c_void_p(out.data_ptr()))
+        finally:
+            self._lib.rt_set_stream(self._ctx, c_void_p(getattr(self, "_stream", None) or None))
+        self._check(rc, what)
+        return out
 
     # -- rendering
     def render_frame(self, frame: int):
@@ -409,6 +488,14 @@ class MultiTracer:
 
     def render(self, first_frame: int, n_frames: int):
         self._check(self._lib.rt_multi_render(self._m, first_frame, n_frames), "rt_multi_render")
+
+    def trace_rays(self, rays) -> np.ndarray:
+        """rt_multi_trace_rays: Tracer.trace_rays over the contexts (host arrays), one contiguous slice of the batch each."""
+        return _query_host(self._lib.rt_multi_trace_rays, self._m, rays, False, self._check, "rt_multi_trace_rays")
+
+    def occluded(self, rays) -> np.ndarray:
+        """rt_multi_occluded: Tracer.occluded over the contexts (host arrays)."""
+        return _query_host(self._lib.rt_multi_occluded, self._m, rays, True, self._check, "rt_multi_occluded")
 
     def render_params(self, first_frame: int, params):
         """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <condition_variable>
 #include <deque>
@@ -28,6 +29,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_geom.hpp"
 #include "rt_bvh_gpu.hpp"
 #include "rt_primary.hpp"
+#include "rt_query.hpp"
 
 namespace {
 
@@ -84,6 +86,7 @@ struct rt_ctx {
     DevBuf<uint32_t> d_tri_mesh, d_tri_chunk, d_tri_rank, d_order;
     DevBuf<rtg::MeshXf> d_xf;
     hipEvent_t evg0 = nullptr, evg1 = nullptr;
+    hipEvent_t ev_switch = nullptr;        // rt_set_stream: the work enqueued on the outgoing stream, waited for by the incoming one
 
     DevBuf<float4> d_sph_geom, d_sph_mat, d_nodes, d_nodes_h, d_tri_geo, d_tri_nrm, d_chunk_mat, d_chunk_box;
     DevBuf<float>  d_raw_tris;
@@ -159,6 +162,8 @@ struct rt_ctx {
     int opt_primary_lists = 1;                      // 1: camera rays of a static camera start from their pixel's candidate leaves (k_stream); 0: always from the root
     DevBuf<float> d_park;              // k_stream, Philox mode: parked sub-stream sums
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
+    DevBuf<float4> d_q_rays, d_q_hits; DevBuf<uint8_t> d_q_occ;            // ray queries: staging of the host entries (one slice)
+    DevBuf<unsigned int> d_q_bound;                                         // ... the device entries' origin bound
     rt_stats stats{};
 
     // ---- queued submission (rt_submit_frame / rt_wait): frames handed in one by one — the reference's OnRenderImage pattern,
@@ -451,8 +456,9 @@ float local_scene_magnitude(const rt_ctx* c)
     return G;
 }
 
-// transform + chunk bounds (+ re-layout and refit when the BVH topology already exists)
-int run_geometry_kernels(rt_ctx* c, bool have_bvh)
+// transform + chunk bounds (+ re-layout and refit when the BVH topology already exists).  min_G: ray origins beyond the scene's own
+// (a ray query's) that the padding must cover as well
+int run_geometry_kernels(rt_ctx* c, bool have_bvh, float min_G = 0.f)
 {
     const uint32_t nt = (uint32_t)c->h_local_tris.size(), nm = (uint32_t)c->h_lchunks.size();
     std::vector<rtg::MeshXf> xf(c->n_meshes);
@@ -472,7 +478,7 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh)
     if (have_bvh && nt) {
         hipLaunchKernelGGL(rtg::k_relayout, dim3((nt + 255) / 256), dim3(256), 0, c->stream,
                            c->d_raw_tris.p, c->d_order.p, c->d_tri_chunk.p, c->d_tri_rank.p, c->d_tri_geo.p, c->d_tri_nrm.p, nt);
-        const float G = std::max(c->bvh.magnitude, local_scene_magnitude(c));
+        const float G = std::max(std::max(c->bvh.magnitude, local_scene_magnitude(c)), min_G);
         c->bvh.magnitude = G;
         { int r = refit_tree(c, G); if (r) return r; }
     }
@@ -491,7 +497,7 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh)
         const float area = c->area_after_refit;
         c->stats.refitAreaRatio = area / c->area_at_build;
         if (area > c->area_at_build * (float)c->opt_rebuild_percent / 100.0f) {
-            int r = device_build(c, nt, local_scene_magnitude(c)); if (r) return r;
+            int r = device_build(c, nt, std::max(local_scene_magnitude(c), min_G)); if (r) return r;
             c->stats.bvhRebuilds++;
             finish_build(c, true);
         }
@@ -551,6 +557,15 @@ int prepare_scene(rt_ctx* c)
     if (c->scene_dirty) return build_scene(c);
     const float om = std::max(camera_magnitude(c->params), c->sphere_mag);
     return om > c->bvh.magnitude ? repad_boxes(c, 2.0f * om) : 0;     // widen the box padding, keep the tree
+}
+
+// After prepare_scene: ray origins of a query reach |coordinate| G.  The rule prepare_scene applies to the camera: world-space uploads
+// widen the padding to twice G, local ones run the geometry pass with G.  (Twice a finite G above FLT_MAX / 2 is FLT_MAX, not +inf: a pad
+// of +inf would turn the empty child slots' (+inf, -inf) boxes into NaN ones; FLT_MAX still bounds every finite origin.)
+int cover_origins(rt_ctx* c, float G)
+{
+    if (!(G > c->bvh.magnitude)) return 0;
+    return c->geom_local ? run_geometry_kernels(c, true, G) : repad_boxes(c, std::min(2.0f * G, FLT_MAX));
 }
 
 // Give `dst` the scene `src` has built (world-space uploads): every device buffer is copied device to device — over xGMI when the
@@ -669,10 +684,9 @@ struct LaunchPlan {
     bool philox = false, stream = false, tile_kernel = false, stream_sync = false, cam_table = false, record_costs = false;
 };
 
-// Kernel choice, traversal stack and LDS, grid, frames per launch, spill buffers (kernel: 0 k_trace, 1 k_stream)
-int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n_frames, LaunchPlan& P)
+// The device scene every kernel reads
+int fill_scene(rt_ctx* c, rtk::DeviceScene& S)
 {
-    rtk::DeviceScene& S = P.S; rtk::FrameArgs& F = P.F; rtk::StreamArgs& A = P.A;
     S.sph_geom = c->d_sph_geom.p; S.sph_mat = c->d_sph_mat.p; S.nodes = c->d_nodes.p; S.nodes_h = c->d_nodes_h.p;
     S.tri_geo = c->d_tri_geo.p; S.tri_nrm = c->d_tri_nrm.p; S.chunk_mat = c->d_chunk_mat.p; S.chunk_box = c->d_chunk_box.p;
     S.raw_tris = c->d_raw_tris.p; S.raw_chunk_range = c->d_raw_range.p;
@@ -682,6 +696,24 @@ int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n
         return fail(c, -7, "scene too large for 32-bit record offsets (%zu BVH nodes)", c->n_nodes);
     S.nt = (int)c->n_tris;
     S.nm = (int)c->n_chunks;
+    return 0;
+}
+
+// LDS traversal-stack entries per lane of the kernels that trace one query per lane to its end (k_trace, k_ray_query): the BVH's worst
+// case, at most option "lds_stack", at most 64 — a very deep tree spills past 64 entries to the global overflow area instead of
+// overflowing the LDS
+int tile_stack_cap(const rt_ctx* c)
+{
+    int cap = std::max(1, c->bvh.maxStack);
+    if (c->opt_lds_stack > 0) cap = std::min(cap, c->opt_lds_stack);
+    return std::min(cap, 64);
+}
+
+// Kernel choice, traversal stack and LDS, grid, frames per launch, spill buffers (kernel: 0 k_trace, 1 k_stream)
+int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n_frames, LaunchPlan& P)
+{
+    rtk::DeviceScene& S = P.S; rtk::FrameArgs& F = P.F; rtk::StreamArgs& A = P.A;
+    { int r = fill_scene(c, S); if (r) return r; }
 
     F.p = c->params;
     F.row0 = c->target_row0; F.nrows = c->target_rows; F.row_stride = c->target_row_stride;
@@ -702,10 +734,9 @@ int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n
         return fail(c, -7, "the Philox mode takes at most 65000 rays per pixel per frame and 32000 bounces (sample and bounce share one signed 32-bit register)");
     const bool stream = P.stream = kernel == 1 && var != Variant::Flat && c->params.numRaysPerPixel >= 1   // PCG or Philox instantiation
                                    && c->target_w <= 65535 && c->target_rows <= 65535;                     // (16-bit pixel coordinates in k_stream's item tables)
-    F.stack_cap = std::max(1, c->bvh.maxStack) + (stream ? 3 : 0);    // the branch-free push writes up to 3 slots past the top
     const bool tile_kernel = P.tile_kernel = !stream && var != Variant::Flat;   // k_trace, PCG or Philox
-    if (tile_kernel && c->opt_lds_stack > 0) F.stack_cap = std::min(F.stack_cap, c->opt_lds_stack);
-    if (tile_kernel) F.stack_cap = std::min(F.stack_cap, 64);        // a very deep tree spills past 64 entries instead of overflowing the LDS
+    F.stack_cap = tile_kernel ? tile_stack_cap(c)
+                              : std::max(1, c->bvh.maxStack) + (stream ? 3 : 0);    // the branch-free push writes up to 3 slots past the top
     // k_stream: at most opt_stream_stack entries per lane in LDS (30 = five workgroups per CU); a deeper worst case spills
     const bool six_waves = stream && !philox && var == Variant::Fast && c->opt_compact_nodes != 0 && c->n_nodes > 0;       // rt_stream.hpp stream_waves()
     const int stream_stack = c->opt_stream_stack > 0 ? c->opt_stream_stack : (six_waves ? 24 : 30);
@@ -1111,6 +1142,117 @@ void queue_push(rt_ctx* c, int frame, const rt_params& p)
 // (the worker only changes c->params while it is busy)
 const rt_params& queue_tail(const rt_ctx* c) { return (c->q_frames.empty() && !c->q_busy) ? c->params : c->q_tail; }
 
+// ---- ray queries (rt_trace_rays / rt_occluded, csrc/rt_query.hpp) ---------------------------------------------------------------
+constexpr int kQuerySlice = 1 << 22;    // rays per launch (and per staging slice of the host entries: 128 MiB of rays, 256 MiB of hits)
+
+// Largest finite |origin coordinate| over the rays a query traces (tMax > 0)
+float query_origin_bound(const rt_ray* rays, int n)
+{
+    float m = 0.f;
+    for (int i = 0; i < n; ++i) {
+        if (!(rays[i].tMax > 0.0f)) continue;
+        for (int a = 0; a < 3; ++a) { const float v = std::fabs(rays[i].origin[a]); if (v > m && v <= 3.4028235e38f) m = v; }
+    }
+    return m;
+}
+
+// Settle, then make the scene current for rays whose origins reach |coordinate| G (host entries; the device entries measure G on the
+// device between the two steps, query_prepare_device)
+int query_prepare(rt_ctx* c, float G)
+{
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = prepare_scene(c); if (r) return r; }
+    return cover_origins(c, G);
+}
+
+// n rays (device, 2 float4 each) -> n rt_hit (4 float4 each) or n occlusion bytes, on the context's stream; no synchronisation
+int launch_query(rt_ctx* c, bool any, const float4* rays, int n, void* out)
+{
+    rtk::DeviceScene S{};
+    { int r = fill_scene(c, S); if (r) return r; }
+    rtk::QueryArgs Q{};
+    Q.order = c->d_order.p;
+    Q.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
+    Q.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    Q.stack_cap = tile_stack_cap(c);
+    Q.full_sort = c->opt_full_sort;
+    const size_t lds = (size_t)Q.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock;
+    const bool compact = c->opt_compact_nodes != 0;     // the node form the renderer's kernels traverse (plan_launch)
+    const void* fn = any ? (compact ? (const void*)rtk::k_ray_query<true, true> : (const void*)rtk::k_ray_query<true, false>)
+                         : (compact ? (const void*)rtk::k_ray_query<false, true> : (const void*)rtk::k_ray_query<false, false>);
+    if (lds > 64 * 1024) RT_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (int first = 0; first < n; first += kQuerySlice) {
+        const int cnt = std::min(kQuerySlice, n - first);
+        const int grid = (cnt + rtk::kBlock - 1) / rtk::kBlock;
+        const unsigned int stride = (unsigned int)grid * rtk::kBlock;
+        Q.rays = rays + 2 * (size_t)first; Q.n = cnt;
+        Q.hits = any ? nullptr : static_cast<float4*>(out) + 4 * (size_t)first;
+        Q.occluded = any ? static_cast<uint8_t*>(out) + first : nullptr;
+        Q.gstack = nullptr; Q.gstack_stride = stride;
+        if (c->bvh.maxStack > Q.stack_cap) {
+            RT_HIP(c, c->d_gstack.ensure((size_t)(c->bvh.maxStack - Q.stack_cap) * stride));
+            Q.gstack = c->d_gstack.p;
+        }
+        void* args[] = { &S, &Q };
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
+    }
+    return 0;
+}
+
+int query_host(rt_ctx* c, bool any, const rt_ray* rays, int n, void* out)
+{
+    RT_SETTLE(c);
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, out %p)", any ? "rt_occluded" : "rt_trace_rays", n, (const void*)rays, out);
+    if (n == 0) return 0;
+    { int r = query_prepare(c, query_origin_bound(rays, n)); if (r) return r; }
+    const size_t slice = (size_t)std::min(n, kQuerySlice);
+    RT_HIP(c, c->d_q_rays.ensure(2 * slice));
+    if (any) RT_HIP(c, c->d_q_occ.ensure(slice)); else RT_HIP(c, c->d_q_hits.ensure(4 * slice));
+    const size_t out_size = any ? 1 : sizeof(rt_hit);
+    for (int first = 0; first < n; first += kQuerySlice) {
+        const int cnt = std::min(kQuerySlice, n - first);
+        void* dev_out = any ? (void*)c->d_q_occ.p : (void*)c->d_q_hits.p;
+        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, rays + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+        { int r = launch_query(c, any, c->d_q_rays.p, cnt, dev_out); if (r) return r; }
+        RT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)first * out_size, dev_out, (size_t)cnt * out_size, hipMemcpyDeviceToHost, c->stream));
+    }
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// p lies in memory of the context's device (hipMalloc'ed or managed)
+bool on_ctx_device(const rt_ctx* c, const void* p)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged) && a.device == c->device;
+}
+
+int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
+{
+    const char* what = any ? "rt_occluded_device" : "rt_trace_rays_device";
+    RT_SETTLE(c);
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, out %p)", what, n, rays, out);
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!on_ctx_device(c, rays) || !on_ctx_device(c, out))
+        return fail(c, -2, "%s: rays and results must be device memory of the context's device %d", what, c->device);
+    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (!any && (reinterpret_cast<uintptr_t>(out) & 15u)))
+        return fail(c, -2, "%s: rays and hits must be 16-byte aligned", what);
+    { int r = prepare_scene(c); if (r) return r; }
+    // the origin bound of the batch, measured on the device: one small kernel and a 4-byte read-back (the call's one synchronisation)
+    RT_HIP(c, c->d_q_bound.ensure(1));
+    RT_HIP(c, hipMemsetAsync(c->d_q_bound.p, 0, sizeof(unsigned int), c->stream));
+    const int grid = std::max(1, std::min((n + 255) / 256, 4 * std::max(1, c->n_cu)));
+    hipLaunchKernelGGL(rtk::k_query_origin_bound<0>, dim3(grid), dim3(256), 0, c->stream, static_cast<const float4*>(rays), n, c->d_q_bound.p);
+    RT_HIP(c, hipGetLastError());
+    unsigned int bits = 0;
+    RT_HIP(c, hipMemcpyAsync(&bits, c->d_q_bound.p, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    { int r = cover_origins(c, u2f(bits)); if (r) return r; }
+    return launch_query(c, any, static_cast<const float4*>(rays), n, out);
+}
+
 } // namespace
 
 extern "C" {
@@ -1129,6 +1271,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_mesh_transform")) return (int)sizeof(rt_mesh_transform);
     if (!std::strcmp(name, "rt_local_chunk")) return (int)sizeof(rt_local_chunk);
     if (!std::strcmp(name, "rt_multi_info")) return (int)sizeof(rt_multi_info);
+    if (!std::strcmp(name, "rt_ray")) return (int)sizeof(rt_ray);
+    if (!std::strcmp(name, "rt_hit")) return (int)sizeof(rt_hit);
     return -1;
 }
 
@@ -1149,6 +1293,7 @@ rt_ctx* rt_create(int device)
     if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess
         || (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess
         || (e = hipEventCreate(&c->evg0)) != hipSuccess || (e = hipEventCreate(&c->evg1)) != hipSuccess
+        || (e = hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming)) != hipSuccess
         || (e = hipMalloc((void**)&c->d_tile_counter, sizeof(unsigned int))) != hipSuccess
         || (e = hipMalloc((void**)&c->d_counters, rtk::kNumCounters * sizeof(unsigned long long))) != hipSuccess) {
         fail(nullptr, -1, "context setup: %s", hipGetErrorString(e));
@@ -1179,8 +1324,10 @@ void rt_destroy(rt_ctx* c)
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->evg0) (void)hipEventDestroy(c->evg0);
     if (c->evg1) (void)hipEventDestroy(c->evg1);
+    if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
     c->bvh_ws.release();
     c->d_local_tris.release(); c->d_tri_mesh.release(); c->d_tri_chunk.release(); c->d_tri_rank.release(); c->d_order.release(); c->d_xf.release();
+    c->d_q_rays.release(); c->d_q_hits.release(); c->d_q_occ.release(); c->d_q_bound.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1189,7 +1336,15 @@ int rt_set_stream(rt_ctx* c, void* hip_stream)
 {
     if (!c) return -1;
     RT_SETTLE(c);
-    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    const hipStream_t next = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    if (next != c->stream) {
+        // ordered switch: what the context enqueued on the outgoing stream (a device query, say) completes before anything it enqueues
+        // on the incoming one — its buffers (scene, staging, traversal-stack overflow) are shared by the work of both
+        RT_HIP(c, hipSetDevice(c->device));
+        RT_HIP(c, hipEventRecord(c->ev_switch, c->stream));
+        RT_HIP(c, hipStreamWaitEvent(next, c->ev_switch, 0));
+        c->stream = next;
+    }
     return 0;
 }
 
@@ -1484,6 +1639,11 @@ int rt_read_bvh(rt_ctx* c, void* nodes_f32, void* nodes_f16, size_t n_nodes)
     return 0;
 }
 
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits) { return c ? query_host(c, false, rays, n, hits) : -1; }
+int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { return c ? query_host(c, true, rays, n, occluded) : -1; }
+int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return c ? query_device(c, false, rays, n, hits) : -1; }
+int rt_occluded_device(rt_ctx* c, const void* rays, int n, void* occluded) { return c ? query_device(c, true, rays, n, occluded) : -1; }
+
 int rt_get_stats(rt_ctx* c, rt_stats* out)
 {
     if (!c) return -1;
@@ -1661,10 +1821,9 @@ int rt_multi_reset_accum(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_acc
 } // extern "C"
 
 namespace {
-// rt_multi_render (params null) and rt_multi_render_params (frame f with params[f] on every context)
-int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
+// Every context holds the scene: after an upload the first context builds it (build_root) and the others receive the result
+template <class Fn> int multi_share_scene(rt_multi* m, Fn build_root)
 {
-    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
     const int N = (int)m->ctx.size();
     bool stale = m->scene_dirty;
     for (rt_ctx* c : m->ctx) stale = stale || c->scene_dirty;       // (a builder option set through rt_multi_context(i), a context never filled)
@@ -1677,7 +1836,7 @@ int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* pa
         // ---- scene change: the first context builds (one BVH build, one host -> device upload), the others receive the result
         const double t0 = now_ms();
         rt_ctx* root = m->ctx[0];
-        { int r = launch_frames(root, first_frame, 0, Variant::Fast); if (r) return mfail(m, r, "scene build on context 0: %s", rt_last_error(root)); }
+        { int r = build_root(root); if (r) return mfail(m, r, "scene build on context 0: %s", rt_last_error(root)); }
         std::vector<int> rcs(N, 0);
         {
             std::vector<std::thread> th;
@@ -1688,6 +1847,15 @@ int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* pa
         m->scene_dirty = false;
         m->lastSetupMs = now_ms() - t0;
     }
+    return 0;
+}
+
+// rt_multi_render (params null) and rt_multi_render_params (frame f with params[f] on every context)
+int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
+{
+    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
+    const int N = (int)m->ctx.size();
+    { int r = multi_share_scene(m, [&](rt_ctx* root) { return launch_frames(root, first_frame, 0, Variant::Fast); }); if (r) return r; }
     // every device renders its bands for all frames, concurrently: one host thread per context (a context is single-threaded,
     // the contexts are independent)
     std::vector<int> rc(N, 0);
@@ -1736,9 +1904,38 @@ int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* pa
     m->lastGatherMs = now_ms() - tg0;           // host wall time from the first copy's submission to the assembled image (the copies run on N - 1 streams)
     return 0;
 }
+
+// rt_multi_trace_rays / rt_multi_occluded: one contiguous slice of the batch per context, traced concurrently (one host thread per
+// context, as multi_render), each slice's results written in place
+int multi_query(rt_multi* m, bool any, const rt_ray* rays, int n, void* out)
+{
+    const char* what = any ? "rt_occluded" : "rt_trace_rays";
+    if (n < 0 || (n > 0 && (!rays || !out))) return mfail(m, -2, "rt_multi %s: bad arguments (n = %d)", what, n);
+    if (n == 0) return 0;
+    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
+    const int N = (int)m->ctx.size();
+    const int per = (n + N - 1) / N;
+    const size_t out_size = any ? 1 : sizeof(rt_hit);
+    std::vector<int> rc(N, 0);
+    {
+        auto run = [&](int i) {
+            const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
+            return query_host(m->ctx[i], any, rays + first, cnt, static_cast<char*>(out) + (size_t)first * out_size);
+        };
+        std::vector<std::thread> th;
+        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = run(i); });
+        rc[0] = run(0);
+        for (std::thread& t : th) t.join();
+    }
+    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "%s on context %d: %s", what, i, rt_last_error(m->ctx[i]));
+    return 0;
+}
 } // namespace
 
 extern "C" {
+
+int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { return m ? multi_query(m, false, rays, n, hits) : -1; }
+int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return m ? multi_query(m, true, rays, n, occluded) : -1; }
 
 int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
 {

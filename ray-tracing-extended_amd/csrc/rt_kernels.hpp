@@ -351,11 +351,12 @@ __device__ __forceinline__ bool ray_traceable(v3 o, v3 d, float dd)
 }
 
 // ---- closest hit: spheres, then BVH ---------------------------------------------------------------------
+// t_max: only hits with dst < t_max count (ray queries, rt_trace_rays); the renderer's rays are unbounded
 template <bool COUNT, bool H = false>
 __device__ __forceinline__ Hit closest_hit(const DeviceScene& S, int intersect_mode, bool full_sort, v3 o, v3 d,
-                                           const TravStack& stk, Counters& cnt)
+                                           const TravStack& stk, Counters& cnt, float t_max = __builtin_inff())
 {
-    Hit best; best.t = __builtin_inff(); best.id = kNone; best.u = 0.f; best.v = 0.f;
+    Hit best; best.t = t_max; best.id = kNone; best.u = 0.f; best.v = 0.f;
     cnt.rays++;                                  // rays are always counted (one add per cast)
 
     // CalculateRayCollision :263-273 — buffer order, strict '<' (first sphere wins ties)

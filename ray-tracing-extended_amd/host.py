@@ -24,7 +24,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from ._cabi import LOCAL_CHUNK, MATERIAL, MESH_TRANSFORM, MESHINFO, PARAMS, SPHERE, TRIANGLE, RT_INTERSECT_FLAT_CHUNKS
+from ._cabi import (LOCAL_CHUNK, MATERIAL, MESH_TRANSFORM, MESHINFO, PARAMS, RAY, RT_HIT_SPHERE, RT_HIT_TRIANGLE, SPHERE, TRIANGLE,
+                    RT_INTERSECT_FLAT_CHUNKS)
 
 f32 = np.float32
 
@@ -325,8 +326,10 @@ class RayTracingManager:
     def CreateMeshes(self):
         tris, infos = [], []
         count = 0
-        for mesh in self.meshes:
+        self._chunkMesh = []                                                      # chunk -> index in self.meshes (Raycast)
+        for mesh_index, mesh in enumerate(self.meshes):
             for chunk in mesh.GetSubMeshes():
+                self._chunkMesh.append(mesh_index)
                 mi = np.zeros((), MESHINFO)
                 mi["firstTriangleIndex"] = count
                 mi["numTriangles"] = len(chunk.triangles)
@@ -398,6 +401,21 @@ class RayTracingManager:
         if self._dirty:
             self.backend.upload(spheres=spheres, triangles=tris, meshinfo=infos)
             self._dirty = False
+
+    def Raycast(self, origin, direction, maxDistance: float = math.inf):
+        """The picking call: what the ray origin + t * direction (t < maxDistance, in units of |direction|) hits in the scene the next frame
+        traces — CalculateRayCollision (RayTracing.shader:256-297) through rt_trace_rays.  Returns (hit, component): the HIT record and the
+        RayTracedSphere or RayTracedMesh it belongs to, or None on a miss."""
+        self.InitFrame()                                     # the scene as OnRenderImage would trace it (uploads, mesh poses)
+        ray = np.zeros(1, RAY)
+        ray["origin"], ray["direction"], ray["tMax"] = _v3(origin), _v3(direction), f32(maxDistance)
+        hit = self.backend.trace_rays(ray)[0]
+        if hit["kind"] == RT_HIT_SPHERE:
+            return hit, self.spheres[int(hit["primitive"])]
+        if hit["kind"] == RT_HIT_TRIANGLE:
+            mesh = int(hit["mesh"]) if self.deviceGeometry else self._chunkMesh[int(hit["chunk"])]
+            return hit, self.meshes[mesh]
+        return hit, None
 
     def Start(self):                                                              # RayTracingManager.cs:43-46
         self.numRenderedFrames = 0

@@ -179,6 +179,42 @@ namespace RtMi355x
             else RtNative.Check(ctx, RtNative.rt_render_frame(ctx, frame), "rt_render_frame");
         }
 
+        // ---- ray queries (Physics.Raycast for the traced scene: picking, autofocus, line of sight) ------------------------------
+        static unsafe RtRay MakeRay(Vector3 origin, Vector3 direction, float maxDistance)
+        {
+            RtRay r = default;
+            r.origin[0] = origin.x; r.origin[1] = origin.y; r.origin[2] = origin.z;
+            r.direction[0] = direction.x; r.direction[1] = direction.y; r.direction[2] = direction.z;
+            r.tMax = maxDistance;
+            return r;
+        }
+
+        /// The closest hit of origin + t * direction, t < maxDistance (in units of |direction|), in the scene the next frame traces;
+        /// false on a miss.  hit.kind / primitive / chunk / mesh say what was hit (RtQuery.cs).
+        public bool Raycast(Vector3 origin, Vector3 direction, float maxDistance, out RtHit hit)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            RtRay[] rays = { MakeRay(origin, direction, maxDistance) };
+            RtHit[] hits = new RtHit[1];
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_trace_rays(multi, rays, 1, hits), "rt_multi_trace_rays");
+            else RtNative.Check(ctx, RtNative.rt_trace_rays(ctx, rays, 1, hits), "rt_trace_rays");
+            hit = hits[0];
+            return hit.kind != 0;
+        }
+
+        /// Line of sight: true when something lies on origin + t * direction for some t < maxDistance (an any-hit query).
+        public bool Occluded(Vector3 origin, Vector3 direction, float maxDistance)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            RtRay[] rays = { MakeRay(origin, direction, maxDistance) };
+            byte[] occ = new byte[1];
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_occluded(multi, rays, 1, occ), "rt_multi_occluded");
+            else RtNative.Check(ctx, RtNative.rt_occluded(ctx, rays, 1, occ), "rt_occluded");
+            return occ[0] != 0;
+        }
+
         /// Blit(resultTexture, target)
         public void Present(RenderTexture target)
         {

@@ -212,6 +212,13 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_multi_set_mesh_transforms(IntPtr multi, IntPtr transforms, int nMeshes);
         [DllImport(Lib)] public static extern int rt_multi_read_display(IntPtr multi, IntPtr rgba8, UIntPtr nPixels);
         [DllImport(Lib)] public static extern int rt_multi_write_accum(IntPtr multi, IntPtr rgba, UIntPtr nFloats, int framesRendered);
+        // ray queries (RtRay / RtHit: RtQuery.cs)
+        [DllImport(Lib)] public static extern int rt_trace_rays(IntPtr ctx, [In] RtRay[] rays, int n, [Out] RtHit[] hits);
+        [DllImport(Lib)] public static extern int rt_occluded(IntPtr ctx, [In] RtRay[] rays, int n, [Out] byte[] occluded);
+        [DllImport(Lib)] public static extern int rt_trace_rays_device(IntPtr ctx, IntPtr rays, int n, IntPtr hits);
+        [DllImport(Lib)] public static extern int rt_occluded_device(IntPtr ctx, IntPtr rays, int n, IntPtr occluded);
+        [DllImport(Lib)] public static extern int rt_multi_trace_rays(IntPtr multi, [In] RtRay[] rays, int n, [Out] RtHit[] hits);
+        [DllImport(Lib)] public static extern int rt_multi_occluded(IntPtr multi, [In] RtRay[] rays, int n, [Out] byte[] occluded);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -253,6 +260,8 @@ namespace RtMi355x
             Same("rt_params", Marshal.SizeOf<RtParams>());
             Same("rt_stats", Marshal.SizeOf<RtStats>());
             Same("rt_multi_info", Marshal.SizeOf<RtMultiInfo>());
+            Same("rt_ray", Marshal.SizeOf<RtRay>());
+            Same("rt_hit", Marshal.SizeOf<RtHit>());
         }
     }
 }
