@@ -405,6 +405,50 @@ int rt_occluded   (rt_ctx* ctx, const rt_ray* rays, int n, uint8_t* occluded);
 int rt_trace_rays_device(rt_ctx* ctx, const void* rays, int n, void* hits);
 int rt_occluded_device  (rt_ctx* ctx, const void* rays, int n, void* occluded);
 
+/* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
+ * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
+ * target is the colour of RayTracing.shader:388); the definition below is this library's, built from the reference's own steps.
+ * For pixel (x, y) of feature frame f, with N = numRaysPerPixel:
+ *
+ *   camera rays   sample s draws its ray exactly as frag does (:377-382), from the PHILOX stream with key (pixelIndex, f), counter
+ *                 (block 0, sample s) — whatever rngMode is.  In RT_RNG_PHILOX mode these are, bit for bit, the camera rays the frame
+ *                 traces (the same pixel footprint, the same anti-aliasing).  In RT_RNG_PCG mode they are an independent stream of the
+ *                 same distribution: the reference chains one PCG state through every bounce of a pixel, so its camera rays cannot be
+ *                 reproduced without tracing the paths.  The feature buffers therefore do not depend on rngMode.
+ *   surface       the hit at which Trace (:300-352) first reaches its scatter step: the first CalculateRayCollision hit, except that a
+ *                 hit on an InvisibleLight material (flag 2) is passed through once as Trace does at bounce 0 (origin = hitPoint +
+ *                 dir * 0.001, one more cast, only if maxBounceCount >= 1; the second cast's hit counts whatever its flag).
+ *                 intersectMode applies.  No surface = a miss.
+ *   per sample    hit: albedo = the material's colour with Trace's checker rule (flag 1: emissionColour where mod2(floor(x)) !=
+ *                 mod2(floor(z)), :313-317), normal = the hit's shading normal, depth = sqrt(dot(q, q)) with q = hitPoint - the camera
+ *                 ray's origin, coverage = 1.  A miss: 0 in all eight channels.
+ *   sum           the fixed tree of the Philox mode (RT_RNG_PHILOX above), each channel on its own; the root is divided by N.
+ *                 Plane RT_AOV_ALBEDO = (albedo.rgb, coverage), plane RT_AOV_NORMAL_DEPTH = (normal.xyz, depth), RGBA32F.  The mean
+ *                 normal is not normalised and depth is the mean over ALL samples (divide by coverage for the mean over the hits).
+ *   accumulate    per plane and channel acc = acc * (1 - w) + cur * w, w = 1 / (k + 1), k = feature frames accumulated so far — the
+ *                 running mean of Accumulate.shader:43-54 without its saturate (normals are signed, depths exceed 1).
+ *
+ * rt_render_aov settles the queue, makes the scene current as a frame does (pending uploads, moved meshes, box padding for the camera),
+ * honours rt_set_rows / rt_set_bands and rt_set_stream, and runs one kernel launch per feature frame.  It moves nothing of the image
+ * path: resultTexture, currentFrame, numRenderedFrames, rays and the work counters stay (only bvhBuilds / bvhRebuilds / bvhRepads move
+ * when the call triggered them, as for ray queries).  The planes are created zeroed at first use and again whenever the strip's size
+ * changes (as the accumulation target is); rt_reset_accum leaves them alone, rt_reset_aov zeroes them.  The strip layout of
+ * rt_read_aov / rt_copy_aov_to_device is rt_read_accum's (rows*width*4 floats).
+ * Errors: null context -1; no params set, n_frames < 0, an unknown plane, a wrong n_floats or a null buffer -2 with a message;
+ * n_frames == 0 returns 0.                                                                                                       */
+enum { RT_AOV_ALBEDO = 0, RT_AOV_NORMAL_DEPTH = 1, RT_AOV_COUNT = 2 };
+typedef struct rt_aov_info {
+    int32_t framesAccumulated;          /* feature frames in the planes                                                     */
+    int32_t lastSampleLanes;            /* lanes of a wave that shared a pixel's samples in the last launch (16, 4 or 1)      */
+    double  lastKernelMs;               /* HIP-event time of the launches of the last rt_render_aov call                     */
+    double  totalKernelMs;              /* sum over the calls since the planes were last zeroed                              */
+} rt_aov_info;
+int rt_render_aov(rt_ctx* ctx, int first_frame, int n_frames);
+int rt_read_aov(rt_ctx* ctx, int which, float* rgba, size_t n_floats);
+int rt_copy_aov_to_device(rt_ctx* ctx, int which, void* dst_device_ptr, size_t n_floats);
+int rt_reset_aov(rt_ctx* ctx);
+int rt_get_aov_info(rt_ctx* ctx, rt_aov_info* out);
+
 /* ---- several GPUs of one node behind one handle ---------------------------------------------------------------------
  * The reference renders on one GPU; its path shards into independent pixels (seed = global pixel index + Frame * 719393,
  * RayTracing.shader:360-362; Accumulate.shader is per pixel), so the frame tiles across devices by rows.  An rt_multi owns one
@@ -463,10 +507,16 @@ int rt_multi_get_info        (rt_multi* m, rt_multi_info* out);
  * concurrently against each context's copy of the scene and gathered in order — bitwise the single-context result.              */
 int rt_multi_trace_rays      (rt_multi* m, const rt_ray* rays, int n, rt_hit* hits);
 int rt_multi_occluded        (rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded);
+/* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
+ * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
+ * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
+int rt_multi_render_aov      (rt_multi* m, int first_frame, int n_frames);
+int rt_multi_read_aov        (rt_multi* m, int which, float* rgba, size_t n_floats);
+int rt_multi_reset_aov       (rt_multi* m);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" */
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,9 @@ HIT = np.dtype([("dst", "<f4"), ("hitPoint", "<f4", 3), ("normal", "<f4", 3), ("
                 ("mesh", "<i4"), ("u", "<f4"), ("v", "<f4"), ("_reserved", "<i4", 3)])
 RT_HIT_NONE, RT_HIT_SPHERE, RT_HIT_TRIANGLE = 0, 1, 2
 assert RAY.itemsize == 32 and HIT.itemsize == 64
+# feature buffers (rt_render_aov): the two planes and the state of their accumulation
+RT_AOV_ALBEDO, RT_AOV_NORMAL_DEPTH, RT_AOV_COUNT = 0, 1, 2
+AOV_INFO = np.dtype([("framesAccumulated", "<i4"), ("lastSampleLanes", "<i4"), ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 RT_INTERSECT_FLAT_CHUNKS = 0
@@ -74,6 +77,8 @@ SYMBOLS = [
     "rt_multi_upload_local_meshes", "rt_multi_set_mesh_transforms", "rt_multi_read_display", "rt_multi_write_accum",
     "rt_render_params", "rt_submit_frame_params", "rt_multi_render_params",
     "rt_trace_rays", "rt_occluded", "rt_trace_rays_device", "rt_occluded_device", "rt_multi_trace_rays", "rt_multi_occluded",
+    "rt_render_aov", "rt_read_aov", "rt_copy_aov_to_device", "rt_reset_aov", "rt_get_aov_info",
+    "rt_multi_render_aov", "rt_multi_read_aov", "rt_multi_reset_aov",
 ]
 
 _lib = None
@@ -151,6 +156,14 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_write_accum.argtypes = [c_void_p, POINTER(c_float), c_size_t, c_int]
     for n in ("rt_trace_rays", "rt_occluded", "rt_trace_rays_device", "rt_occluded_device", "rt_multi_trace_rays", "rt_multi_occluded"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.rt_render_aov.argtypes = [c_void_p, c_int, c_int]
+    lib.rt_read_aov.argtypes = [c_void_p, c_int, POINTER(c_float), c_size_t]
+    lib.rt_copy_aov_to_device.argtypes = [c_void_p, c_int, c_void_p, c_size_t]
+    lib.rt_reset_aov.argtypes = [c_void_p]
+    lib.rt_get_aov_info.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_render_aov.argtypes = [c_void_p, c_int, c_int]
+    lib.rt_multi_read_aov.argtypes = [c_void_p, c_int, POINTER(c_float), c_size_t]
+    lib.rt_multi_reset_aov.argtypes = [c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -160,7 +173,7 @@ def load_library() -> ctypes.CDLL:
     for name, dt in (("rt_material", MATERIAL), ("rt_sphere", SPHERE), ("rt_triangle", TRIANGLE),
                      ("rt_meshinfo", MESHINFO), ("rt_params", PARAMS), ("rt_stats", STATS),
                      ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO),
-                     ("rt_ray", RAY), ("rt_hit", HIT)):
+                     ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -405,6 +418,29 @@ class Tracer:
         self._check(self._lib.rt_read_bvh(self._ctx, f32.ctypes.data_as(c_void_p), f16.ctypes.data_as(c_void_p), n), "rt_read_bvh")
         return f32, f16
 
+    # -- feature buffers
+    def render_aov(self, first_frame: int, n_frames: int):
+        """rt_render_aov: accumulate the feature frames first_frame .. first_frame + n_frames - 1 into the two planes."""
+        self._check(self._lib.rt_render_aov(self._ctx, int(first_frame), int(n_frames)), "rt_render_aov")
+
+    def read_aov(self, which: int) -> np.ndarray:
+        """rt_read_aov: plane RT_AOV_ALBEDO (albedo.rgb, coverage) or RT_AOV_NORMAL_DEPTH (normal.xyz, depth) of this context's strip."""
+        rows, W = self._strip_shape()
+        out = np.empty((rows, W, 4), np.float32)
+        self._check(self._lib.rt_read_aov(self._ctx, int(which), out.ctypes.data_as(POINTER(c_float)), out.size), "rt_read_aov")
+        return out
+
+    def copy_aov_to_device(self, which: int, device_ptr: int, n_floats: int):
+        self._check(self._lib.rt_copy_aov_to_device(self._ctx, int(which), c_void_p(device_ptr), n_floats), "rt_copy_aov_to_device")
+
+    def reset_aov(self):
+        self._check(self._lib.rt_reset_aov(self._ctx), "rt_reset_aov")
+
+    def aov_info(self) -> dict:
+        s = np.zeros((), AOV_INFO)
+        self._check(self._lib.rt_get_aov_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_aov_info")
+        return {k: s[k].item() for k in AOV_INFO.names}
+
     def stats(self) -> dict:
         s = np.zeros((), STATS)
         self._check(self._lib.rt_get_stats(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_stats")
@@ -508,6 +544,32 @@ class MultiTracer:
         H, W = self._shape
         out = np.empty((H, W, 4), np.float32)
         self._check(self._lib.rt_multi_read_accum(self._m, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_accum")
+        return out
+
+    # -- feature buffers
+    def render_aov(self, first_frame: int, n_frames: int):
+        """rt_multi_render_aov: every context accumulates the feature frames of its bands."""
+        self._check(self._lib.rt_multi_render_aov(self._m, int(first_frame), int(n_frames)), "rt_multi_render_aov")
+
+    def read_aov(self, which: int) -> np.ndarray:
+        """rt_multi_read_aov: the assembled plane, shape (H, W, 4), row 0 = bottom."""
+        H, W = self._shape
+        out = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.rt_multi_read_aov(self._m, int(which), out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_aov")
+        return out
+
+    def reset_aov(self):
+        self._check(self._lib.rt_multi_reset_aov(self._m), "rt_multi_reset_aov")
+
+    def aov_info(self) -> list:
+        """rt_get_aov_info of every context, in order"""
+        out = []
+        for i in range(self.count()):
+            s = np.zeros((), AOV_INFO)
+            rc = self._lib.rt_get_aov_info(self._lib.rt_multi_context(self._m, i), s.ctypes.data_as(c_void_p))
+            if rc != 0:
+                raise RtError(f"rt_get_aov_info on context {i} failed ({rc})")
+            out.append({k: s[k].item() for k in AOV_INFO.names})
         return out
 
     def stats(self) -> dict:

@@ -30,6 +30,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_bvh_gpu.hpp"
 #include "rt_primary.hpp"
 #include "rt_query.hpp"
+#include "rt_aov.hpp"
 
 namespace {
 
@@ -164,6 +165,11 @@ struct rt_ctx {
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
     DevBuf<float4> d_q_rays, d_q_hits; DevBuf<uint8_t> d_q_occ;            // ray queries: staging of the host entries (one slice)
     DevBuf<unsigned int> d_q_bound;                                         // ... the device entries' origin bound
+    // feature buffers (rt_render_aov, csrc/rt_aov.hpp): the two accumulated planes of this context's strip and the layout they were made for
+    DevBuf<float4> d_aov[RT_AOV_COUNT];
+    size_t aov_pixels = 0;
+    int aov_w = 0, aov_h = 0, aov_row0 = 0, aov_rows = 0, aov_row_stride = 8;
+    rt_aov_info aov{};
     rt_stats stats{};
 
     // ---- queued submission (rt_submit_frame / rt_wait): frames handed in one by one — the reference's OnRenderImage pattern,
@@ -602,16 +608,25 @@ int clone_scene(rt_ctx* dst, rt_ctx* src)
     return 0;
 }
 
-int ensure_targets(rt_ctx* c)
+// The rows this context renders (rt_set_rows / rt_set_bands) of the image of c->params: first row, row count, distance between bands
+int strip_layout(rt_ctx* c, int& r0, int& nr, int& rstride)
 {
-    const int W = c->params.width, H = c->params.height;
-    int r0 = c->nrows < 0 ? 0 : c->row0, nr = c->nrows < 0 ? H : c->nrows, rstride = 8;
+    const int H = c->params.height;
+    r0 = c->nrows < 0 ? 0 : c->row0; nr = c->nrows < 0 ? H : c->nrows; rstride = 8;
     if (c->band_stride > 0) {
         // bands band_first, band_first + band_stride, ... of 8 rows each; the image's last band may be partial
         r0 = c->band_first * 8; rstride = c->band_stride * 8; nr = 0;
         for (int y = r0; y < H; y += rstride) nr += std::min(8, H - y);
         if (r0 > H) r0 = H;
     } else if (r0 < 0 || nr < 0 || r0 + nr > H) return fail(c, -6, "row strip [%d,%d) outside image height %d", r0, r0 + nr, H);
+    return 0;
+}
+
+int ensure_targets(rt_ctx* c)
+{
+    const int W = c->params.width, H = c->params.height;
+    int r0, nr, rstride;
+    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
     if (W == c->target_w && H == c->target_h && r0 == c->target_row0 && nr == c->target_rows && rstride == c->target_row_stride) return 0;
     const size_t px = (size_t)W * nr;
     RT_HIP(c, c->d_frame.ensure(px));
@@ -1253,6 +1268,93 @@ int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
     return launch_query(c, any, static_cast<const float4*>(rays), n, out);
 }
 
+// ---- feature buffers (rt_render_aov, csrc/rt_aov.hpp) -----------------------------------------------------------------------------
+// The two planes of the context's strip, zeroed when they are created and whenever the strip's layout changes (ensure_targets' rule for
+// the accumulation target, kept apart from it: a feature frame must not touch the image path's state)
+int ensure_aov(rt_ctx* c)
+{
+    const int W = c->params.width, H = c->params.height;
+    int r0, nr, rstride;
+    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
+    if (c->d_aov[0].p && W == c->aov_w && H == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride) return 0;
+    const size_t px = (size_t)W * nr;
+    for (DevBuf<float4>& b : c->d_aov) {
+        RT_HIP(c, b.ensure(px));
+        if (px) RT_HIP(c, hipMemsetAsync(b.p, 0, px * sizeof(float4), c->stream));
+    }
+    c->aov_pixels = px; c->aov_w = W; c->aov_h = H; c->aov_row0 = r0; c->aov_rows = nr; c->aov_row_stride = rstride;
+    c->aov.framesAccumulated = 0; c->aov.totalKernelMs = 0;
+    return 0;
+}
+
+int render_aov(rt_ctx* c, int first_frame, int n_frames)
+{
+    RT_SETTLE(c);
+    if (!c->have_params) return fail(c, -2, "rt_render_aov: rt_set_params has not been called");
+    if (n_frames < 0) return fail(c, -2, "rt_render_aov: n_frames < 0");
+    if (n_frames == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = prepare_scene(c); if (r) return r; }
+    { int r = ensure_aov(c); if (r) return r; }
+    rtk::DeviceScene S{};
+    { int r = fill_scene(c, S); if (r) return r; }
+    rtk::AovArgs A{};
+    A.p = c->params;
+    A.row0 = c->aov_row0; A.nrows = c->aov_rows; A.row_stride = c->aov_row_stride;
+    // S = 16 / 4 / 1 sub-streams of a pixel on adjacent lanes: a wave is a 2x2 / 4x4 / 8x8 tile (all divide the 8-row bands)
+    const int N = c->params.numRaysPerPixel;
+    A.sample_lanes_log2 = N >= 16 ? 4 : N >= 4 ? 2 : 0;
+    const int tile = 1 << ((6 - A.sample_lanes_log2) / 2);
+    const long long tiles_x = (c->aov_w + tile - 1) / tile, tiles_y = (c->aov_rows + tile - 1) / tile;
+    c->aov.lastSampleLanes = 1 << A.sample_lanes_log2;
+    if (tiles_x * tiles_y == 0) { c->aov.framesAccumulated += n_frames; c->aov.lastKernelMs = 0; return 0; }
+    if (tiles_x * tiles_y > (long long)1 << 30) return fail(c, -7, "rt_render_aov: %lld wave tiles exceed one launch", tiles_x * tiles_y);
+    A.tiles_x = (int)tiles_x; A.ntiles = (int)(tiles_x * tiles_y);
+    A.stack_cap = tile_stack_cap(c);
+    A.full_sort = c->opt_full_sort;
+    A.fixed_origin = camera_origin_is_fixed(c->params) ? 1 : 0;
+    A.albedo = c->d_aov[RT_AOV_ALBEDO].p; A.normal_depth = c->d_aov[RT_AOV_NORMAL_DEPTH].p;
+    const int grid = (A.ntiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock;
+    A.gstack_stride = (unsigned int)grid * rtk::kBlock;
+    if (c->bvh.maxStack > A.stack_cap) {
+        // (one overflow slot per lane of the launch and entry: a tree deeper than the LDS part pays for this launch's width)
+        const size_t need = (size_t)(c->bvh.maxStack - A.stack_cap) * A.gstack_stride;
+        if (need > ((size_t)4 << 30) / sizeof(uint32_t)) return fail(c, -7, "rt_render_aov: the traversal-stack overflow area would take %zu MiB (raise option lds_stack)", need >> 18);
+        RT_HIP(c, c->d_gstack.ensure(need));
+        A.gstack = c->d_gstack.p;
+    }
+    const size_t lds = (size_t)A.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock;
+    const void* fn = c->opt_compact_nodes != 0 ? (const void*)rtk::k_aov<true> : (const void*)rtk::k_aov<false>;     // the node form the renderer's kernels traverse
+    if (lds > 64 * 1024) RT_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RT_HIP(c, hipEventRecord(c->ev0, c->stream));
+    for (int f = 0; f < n_frames; ++f) {
+        A.frame = first_frame + f; A.accumulated = c->aov.framesAccumulated + f;
+        void* args[] = { &S, &A };
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
+    }
+    RT_HIP(c, hipEventRecord(c->ev1, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->aov.framesAccumulated += n_frames; c->aov.lastKernelMs = ms; c->aov.totalKernelMs += ms;
+    return 0;
+}
+
+int read_aov(rt_ctx* c, int which, void* dst, size_t n_floats, bool to_device)
+{
+    RT_SETTLE(c);
+    if (which < 0 || which >= RT_AOV_COUNT) return fail(c, -2, "unknown feature plane %d", which);
+    if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
+    if (!dst) return fail(c, -2, "null destination");
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = ensure_aov(c); if (r) return r; }
+    if (n_floats != c->aov_pixels * 4) return fail(c, -2, "expected %zu floats (rows*width*4), got %zu", c->aov_pixels * 4, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(c, hipMemcpyAsync(dst, c->d_aov[which].p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1273,6 +1375,7 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_multi_info")) return (int)sizeof(rt_multi_info);
     if (!std::strcmp(name, "rt_ray")) return (int)sizeof(rt_ray);
     if (!std::strcmp(name, "rt_hit")) return (int)sizeof(rt_hit);
+    if (!std::strcmp(name, "rt_aov_info")) return (int)sizeof(rt_aov_info);
     return -1;
 }
 
@@ -1328,6 +1431,7 @@ void rt_destroy(rt_ctx* c)
     c->bvh_ws.release();
     c->d_local_tris.release(); c->d_tri_mesh.release(); c->d_tri_chunk.release(); c->d_tri_rank.release(); c->d_order.release(); c->d_xf.release();
     c->d_q_rays.release(); c->d_q_hits.release(); c->d_q_occ.release(); c->d_q_bound.release();
+    for (DevBuf<float4>& b : c->d_aov) b.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1644,6 +1748,30 @@ int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { retur
 int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return c ? query_device(c, false, rays, n, hits) : -1; }
 int rt_occluded_device(rt_ctx* c, const void* rays, int n, void* occluded) { return c ? query_device(c, true, rays, n, occluded) : -1; }
 
+int rt_render_aov(rt_ctx* c, int first_frame, int n_frames) { return c ? render_aov(c, first_frame, n_frames) : -1; }
+int rt_read_aov(rt_ctx* c, int which, float* rgba, size_t n) { return c ? read_aov(c, which, rgba, n, false) : -1; }
+int rt_copy_aov_to_device(rt_ctx* c, int which, void* dst, size_t n) { return c ? read_aov(c, which, dst, n, true) : -1; }
+int rt_reset_aov(rt_ctx* c)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    RT_HIP(c, hipSetDevice(c->device));
+    if (c->aov_pixels) {
+        for (DevBuf<float4>& b : c->d_aov) RT_HIP(c, hipMemsetAsync(b.p, 0, c->aov_pixels * sizeof(float4), c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    c->aov.framesAccumulated = 0; c->aov.totalKernelMs = 0;
+    return 0;
+}
+int rt_get_aov_info(rt_ctx* c, rt_aov_info* out)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!out) return fail(c, -2, "null info");
+    *out = c->aov;
+    return 0;
+}
+
 int rt_get_stats(rt_ctx* c, rt_stats* out)
 {
     if (!c) return -1;
@@ -1667,6 +1795,7 @@ struct rt_multi {
     bool have_params = false;
     DevBuf<float4> d_image, d_staging;          // on the first context's device: the assembled image, the incoming strips
     DevBuf<uint32_t> d_display;                 // ... and its sRGB8 form (rt_multi_read_display)
+    DevBuf<float4> d_aov_image;                 // ... the assembled feature plane of the last rt_multi_read_aov
     std::vector<hipEvent_t> ev_strip;           // per context: its strip has arrived on the first device (recorded on the SOURCE context's stream)
     int max_rows = 0;
     double lastGatherMs = 0, lastSetupMs = 0;
@@ -1756,7 +1885,7 @@ void rt_multi_destroy(rt_multi* m)
     if (!m) return;
     for (size_t i = 0; i < m->ev_strip.size() && i < m->ctx.size(); ++i)
         if (m->ev_strip[i]) { (void)hipSetDevice(m->ctx[i]->device); (void)hipEventDestroy(m->ev_strip[i]); }
-    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); }
+    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); }
     for (rt_ctx* c : m->ctx) rt_destroy(c);
     delete m;
 }
@@ -1850,6 +1979,47 @@ template <class Fn> int multi_share_scene(rt_multi* m, Fn build_root)
     return 0;
 }
 
+// The gather: every context's strip (strip(c): its device buffer of rows(c) rows) -> the first device, rows to their places in `image`
+template <class Strip, class Rows> int gather_strips(rt_multi* m, DevBuf<float4>& image, double& gather_ms, Strip strip, Rows rows)
+{
+    const int N = (int)m->ctx.size();
+    rt_ctx* root = m->ctx[0];
+    const int W = m->width, H = m->height;
+    M_HIP(m, hipSetDevice(root->device));
+    int max_rows = 0;
+    for (rt_ctx* c : m->ctx) max_rows = std::max(max_rows, rows(c));
+    M_HIP(m, image.ensure((size_t)W * H));
+    M_HIP(m, m->d_staging.ensure((size_t)W * max_rows * (size_t)std::max(1, N - 1)));
+    M_HIP(m, hipStreamSynchronize(root->stream));           // (the staging area is allocated and idle: the sources may write)
+    const double tg0 = now_ms();
+    // every strip travels on ITS source context's stream — N - 1 independent transfers, each over its own xGMI link on a fully connected
+    // node, in flight together — and the first device's stream waits for the N - 1 arrival events before it scatters the rows
+    for (int i = 1; i < N; ++i) {
+        rt_ctx* c = m->ctx[i];
+        const size_t pixels = (size_t)W * rows(c);
+        if (pixels == 0) continue;
+        float4* dst = m->d_staging.p + (size_t)(i - 1) * W * max_rows;
+        M_HIP(m, hipSetDevice(c->device));
+        if (c->device == root->device && !root->opt_peer_copies) M_HIP(m, hipMemcpyAsync(dst, strip(c), pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        else M_HIP(m, hipMemcpyPeerAsync(dst, root->device, strip(c), c->device, pixels * sizeof(float4), c->stream));
+        M_HIP(m, hipEventRecord(m->ev_strip[i], c->stream));
+    }
+    M_HIP(m, hipSetDevice(root->device));
+    for (int i = 1; i < N; ++i)
+        if (rows(m->ctx[i]) != 0) M_HIP(m, hipStreamWaitEvent(root->stream, m->ev_strip[i], 0));
+    for (int i = 0; i < N; ++i) {
+        rt_ctx* c = m->ctx[i];
+        if (rows(c) == 0) continue;
+        const float4* src = i == 0 ? strip(c) : m->d_staging.p + (size_t)(i - 1) * W * max_rows;
+        const int bands = (rows(c) + 7) / 8;
+        hipLaunchKernelGGL(k_scatter_bands, dim3(std::max(1, std::min(64, (W * 8 + 255) / 256)), bands), dim3(256), 0, root->stream, src, image.p, W, H, i, N);
+    }
+    M_HIP(m, hipGetLastError());
+    M_HIP(m, hipStreamSynchronize(root->stream));
+    gather_ms = now_ms() - tg0;                 // host wall time from the first copy's submission to the assembled image (the copies run on N - 1 streams)
+    return 0;
+}
+
 // rt_multi_render (params null) and rt_multi_render_params (frame f with params[f] on every context)
 int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
 {
@@ -1868,41 +2038,8 @@ int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* pa
     }
     for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "%s on context %d: %s", params ? "rt_render_params" : "rt_render", i, rt_last_error(m->ctx[i]));
     // ---- the one gather: strips -> first device, rows to their places
-    rt_ctx* root = m->ctx[0];
-    const int W = m->width, H = m->height;
-    if ((size_t)W * H == 0) return 0;
-    M_HIP(m, hipSetDevice(root->device));
-    int max_rows = 0;
-    for (rt_ctx* c : m->ctx) max_rows = std::max(max_rows, c->target_rows);
-    M_HIP(m, m->d_image.ensure((size_t)W * H));
-    M_HIP(m, m->d_staging.ensure((size_t)W * max_rows * (size_t)std::max(1, N - 1)));
-    M_HIP(m, hipStreamSynchronize(root->stream));           // (the staging area is allocated and idle: the sources may write)
-    const double tg0 = now_ms();
-    // every strip travels on ITS source context's stream — N - 1 independent transfers, each over its own xGMI link on a fully connected
-    // node, in flight together — and the first device's stream waits for the N - 1 arrival events before it scatters the rows
-    for (int i = 1; i < N; ++i) {
-        rt_ctx* c = m->ctx[i];
-        if (c->target_pixels == 0) continue;
-        float4* dst = m->d_staging.p + (size_t)(i - 1) * W * max_rows;
-        M_HIP(m, hipSetDevice(c->device));
-        if (c->device == root->device && !root->opt_peer_copies) M_HIP(m, hipMemcpyAsync(dst, c->d_accum.p, c->target_pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-        else M_HIP(m, hipMemcpyPeerAsync(dst, root->device, c->d_accum.p, c->device, c->target_pixels * sizeof(float4), c->stream));
-        M_HIP(m, hipEventRecord(m->ev_strip[i], c->stream));
-    }
-    M_HIP(m, hipSetDevice(root->device));
-    for (int i = 1; i < N; ++i)
-        if (m->ctx[i]->target_pixels != 0) M_HIP(m, hipStreamWaitEvent(root->stream, m->ev_strip[i], 0));
-    for (int i = 0; i < N; ++i) {
-        rt_ctx* c = m->ctx[i];
-        if (c->target_pixels == 0) continue;
-        const float4* src = i == 0 ? c->d_accum.p : m->d_staging.p + (size_t)(i - 1) * W * max_rows;
-        const int bands = (c->target_rows + 7) / 8;
-        hipLaunchKernelGGL(k_scatter_bands, dim3(std::max(1, std::min(64, (W * 8 + 255) / 256)), bands), dim3(256), 0, root->stream, src, m->d_image.p, W, H, i, N);
-    }
-    M_HIP(m, hipGetLastError());
-    M_HIP(m, hipStreamSynchronize(root->stream));
-    m->lastGatherMs = now_ms() - tg0;           // host wall time from the first copy's submission to the assembled image (the copies run on N - 1 streams)
-    return 0;
+    if ((size_t)m->width * m->height == 0) return 0;
+    return gather_strips(m, m->d_image, m->lastGatherMs, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target_rows; });
 }
 
 // rt_multi_trace_rays / rt_multi_occluded: one contiguous slice of the batch per context, traced concurrently (one host thread per
@@ -1936,6 +2073,44 @@ extern "C" {
 
 int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { return m ? multi_query(m, false, rays, n, hits) : -1; }
 int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return m ? multi_query(m, true, rays, n, occluded) : -1; }
+
+// Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands
+int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)
+{
+    if (!m) return -1;
+    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
+    if (n_frames < 0) return mfail(m, -2, "rt_multi_render_aov: n_frames < 0");
+    if (n_frames == 0) return 0;
+    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
+    const int N = (int)m->ctx.size();
+    std::vector<int> rc(N, 0);
+    {
+        std::vector<std::thread> th;
+        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = rt_render_aov(m->ctx[i], first_frame, n_frames); });
+        rc[0] = rt_render_aov(m->ctx[0], first_frame, n_frames);
+        for (std::thread& t : th) t.join();
+    }
+    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "rt_render_aov on context %d: %s", i, rt_last_error(m->ctx[i]));
+    return 0;
+}
+
+int rt_multi_read_aov(rt_multi* m, int which, float* rgba, size_t n_floats)
+{
+    if (!m) return -1;
+    if (which < 0 || which >= RT_AOV_COUNT) return mfail(m, -2, "unknown feature plane %d", which);
+    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
+    if (!rgba) return mfail(m, -2, "null destination");
+    if (n_floats != (size_t)m->width * m->height * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", (size_t)m->width * m->height * 4, n_floats);
+    if (!n_floats) return 0;
+    // (a context that has rendered no feature frame yet holds zeroed planes of its strip)
+    { int r = for_each_ctx(m, "feature planes", [&](rt_ctx* c) { RT_SETTLE(c); RT_HIP(c, hipSetDevice(c->device)); return ensure_aov(c); }); if (r) return r; }
+    double gather_ms = 0;
+    { int r = gather_strips(m, m->d_aov_image, gather_ms, [&](rt_ctx* c) { return c->d_aov[which].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
+    M_HIP(m, hipMemcpy(rgba, m->d_aov_image.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rt_multi_reset_aov(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_aov", [&](rt_ctx* c) { return rt_reset_aov(c); }) : -1; }
 
 int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
 {

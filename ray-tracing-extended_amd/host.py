@@ -417,6 +417,15 @@ class RayTracingManager:
             return hit, self.meshes[mesh]
         return hit, None
 
+    def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
+        """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
+        the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices
+        continue from the planes' own count unless firstFrame is given.  The image and numRenderedFrames are left alone."""
+        self.InitFrame()
+        first = self.backend.aov_info()["framesAccumulated"] if firstFrame is None else firstFrame
+        self.backend.render_aov(first, frames)
+        return self.backend.read_aov(0), self.backend.read_aov(1)
+
     def Start(self):                                                              # RayTracingManager.cs:43-46
         self.numRenderedFrames = 0
         if self.backend is not None:

@@ -415,6 +415,20 @@ void RayTracingManager::OnRenderImage(rt_ctx* ctx, int frames, std::vector<float
     }
 }
 
+void RayTracingManager::RenderFeatures(rt_ctx* ctx, int frames, std::vector<float>* albedoCoverage, std::vector<float>* normalDepth)
+{
+    InitFrame(ctx);
+    rt_aov_info info{};
+    check(ctx, rt_get_aov_info(ctx, &info), "rt_get_aov_info");
+    check(ctx, rt_render_aov(ctx, info.framesAccumulated, frames), "rt_render_aov");
+    std::vector<float>* planes[RT_AOV_COUNT] = { albedoCoverage, normalDepth };
+    for (int which = 0; which < RT_AOV_COUNT; ++which)
+        if (planes[which]) {
+            planes[which]->resize((size_t)width * height * 4);
+            check(ctx, rt_read_aov(ctx, which, planes[which]->data(), planes[which]->size()), "rt_read_aov");
+        }
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

@@ -131,6 +131,10 @@ public:
     void InitFrame(rt_ctx* ctx);
     void OnRenderImage(rt_ctx* ctx, int frames, std::vector<float>* resultTexture = nullptr);
     void Start(rt_ctx* ctx);                                                     // :43-46
+    // Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, with frame indices
+    // that continue from the planes' own count; the planes (width * height * 4 floats each) are read back when asked for.  The image and
+    // numRenderedFrames are left alone.
+    void RenderFeatures(rt_ctx* ctx, int frames, std::vector<float>* albedoCoverage = nullptr, std::vector<float>* normalDepth = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

@@ -215,6 +215,28 @@ namespace RtMi355x
             return occ[0] != 0;
         }
 
+        // ---- feature buffers (what a denoiser takes beside the image: RtAov.cs) ------------------------------------------------
+        /// Accumulates the feature frame `frame` (albedo, normal, depth, coverage of the first visible surface) for the scene and camera
+        /// the next frame traces; the image and its frame counter are left alone.
+        public void RenderFeatures(int frame)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_render_aov(multi, frame, 1), "rt_multi_render_aov");
+            else RtNative.Check(ctx, RtNative.rt_render_aov(ctx, frame, 1), "rt_render_aov");
+        }
+
+        /// One accumulated plane, width * height * 4 floats, row 0 = bottom: RtAov.Albedo = (albedo.rgb, coverage),
+        /// RtAov.NormalDepth = (normal.xyz, depth).
+        public float[] ReadFeatures(int which)
+        {
+            float[] rgba = new float[(long)width * height * 4];
+            UIntPtr n = (UIntPtr)(ulong)rgba.LongLength;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_read_aov(multi, which, rgba, n), "rt_multi_read_aov");
+            else RtNative.Check(ctx, RtNative.rt_read_aov(ctx, which, rgba, n), "rt_read_aov");
+            return rgba;
+        }
+
         /// Blit(resultTexture, target)
         public void Present(RenderTexture target)
         {

@@ -219,6 +219,15 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_occluded_device(IntPtr ctx, IntPtr rays, int n, IntPtr occluded);
         [DllImport(Lib)] public static extern int rt_multi_trace_rays(IntPtr multi, [In] RtRay[] rays, int n, [Out] RtHit[] hits);
         [DllImport(Lib)] public static extern int rt_multi_occluded(IntPtr multi, [In] RtRay[] rays, int n, [Out] byte[] occluded);
+        // feature buffers (RtAovInfo: RtAov.cs)
+        [DllImport(Lib)] public static extern int rt_render_aov(IntPtr ctx, int firstFrame, int nFrames);
+        [DllImport(Lib)] public static extern int rt_read_aov(IntPtr ctx, int which, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_copy_aov_to_device(IntPtr ctx, int which, IntPtr dstDevicePtr, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_reset_aov(IntPtr ctx);
+        [DllImport(Lib)] public static extern int rt_get_aov_info(IntPtr ctx, out RtAovInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_render_aov(IntPtr multi, int firstFrame, int nFrames);
+        [DllImport(Lib)] public static extern int rt_multi_read_aov(IntPtr multi, int which, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_multi_reset_aov(IntPtr multi);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -262,6 +271,7 @@ namespace RtMi355x
             Same("rt_multi_info", Marshal.SizeOf<RtMultiInfo>());
             Same("rt_ray", Marshal.SizeOf<RtRay>());
             Same("rt_hit", Marshal.SizeOf<RtHit>());
+            Same("rt_aov_info", Marshal.SizeOf<RtAovInfo>());
         }
     }
 }

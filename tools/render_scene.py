@@ -26,6 +26,9 @@ def main(argv=None):
     ap.add_argument("--bounces", type=int, default=0, help="override maxBounceCount")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--png"); ap.add_argument("--exr"); ap.add_argument("--pfm")
+    ap.add_argument("--aov", metavar="PREFIX", help="also accumulate the feature buffers over the same frames (rt_render_aov) and write PREFIX.albedo "
+                    "(albedo, alpha = coverage), PREFIX.normal (mean shading normal, alpha = coverage) and PREFIX.depth (mean depth in every "
+                    "channel, alpha = coverage), as .exr, or as .pfm when --pfm is given and --exr is not")
     args = ap.parse_args(argv)
 
     import rtx_pkg
@@ -53,6 +56,18 @@ def main(argv=None):
         rtx.imageio.write_exr(args.exr, image)
     if args.pfm:
         rtx.imageio.write_pfm(args.pfm, image)
+    if args.aov:
+        import numpy as np
+        albedo, normal_depth = mgr.RenderFeatures(frames=args.frames, firstFrame=0)
+        info = tracer.aov_info()
+        coverage = albedo[..., 3:4]
+        planes = {"albedo": albedo, "normal": np.concatenate([normal_depth[..., :3], coverage], -1),
+                  "depth": np.concatenate([np.repeat(normal_depth[..., 3:4], 3, -1), coverage], -1)}
+        ext, write = (".pfm", rtx.imageio.write_pfm) if (args.pfm and not args.exr) else (".exr", rtx.imageio.write_exr)
+        for name, plane in planes.items():
+            write(f"{args.aov}.{name}{ext}", np.ascontiguousarray(plane, np.float32))
+        print(f"feature buffers: {info['framesAccumulated']} frames in {info['totalKernelMs']:.1f} ms of kernels "
+              f"({info['lastSampleLanes']} lanes per pixel) -> {args.aov}.{{albedo,normal,depth}}{ext}")
     tracer.close()
     return 0
 
