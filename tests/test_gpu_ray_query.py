@@ -6,45 +6,19 @@ padding, both intersect modes, both BVH builders, moving local meshes, and scene
 renderer's state alone."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from test_gpu_scenes import GOLDEN
+from ray_query_helpers import SCENES, camera_rays, make_rays, oracle_hits, random_rays, scene_of, shim      # noqa: F401 (shim is a fixture)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 FLOAT_COLS = [0, 1, 2, 3, 4, 5, 6, 11, 12]          # dst, hitPoint, normal, u, v (the rest are integers)
-SCENES = ["Balls_Outdoors", "Chess", "Knight", "Reflective_Balls", "Suzanne", "Thumbnail"]
-
-
-@pytest.fixture(scope="session")
-def shim(tmp_path_factory):
-    """tests/ray_query_oracle.c compiled with the CFLAGS of oracle/Makefile"""
-    mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-    cflags = re.search(r"^CFLAGS\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-    so = str(tmp_path_factory.mktemp("rq") / "librq.so")
-    subprocess.check_call(["gcc", *cflags, "-shared", "-o", so, os.path.join(HERE, "ray_query_oracle.c"), "-lm"])
-    lib = ctypes.CDLL(so)
-    lib.rq_trace.argtypes = [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    lib.rq_trace.restype = ctypes.c_int
-    return lib
-
-
-def oracle_hits(rtx, shim, spheres, tris, infos, mode, rays):
-    s = np.ascontiguousarray(spheres, rtx.SPHERE)
-    t = np.ascontiguousarray(tris, rtx.TRIANGLE)
-    m = np.ascontiguousarray(infos, rtx.MESHINFO)
-    r = np.ascontiguousarray(rays, rtx.RAY)
-    out = np.zeros(len(r), rtx.HIT)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
-    assert shim.rq_trace(p(s), len(s), p(t), len(t), p(m), len(m), int(mode), p(r), len(r), p(out)) == 0
-    return out
 
 
 def assert_hits(got, want, what):
@@ -72,33 +46,6 @@ def check_queries(rtx, shim, tracer, spheres, tris, infos, mode, rays, what, mes
     return got
 
 
-def make_rays(rtx, origins, directions, t_max=np.inf):
-    r = np.zeros(len(origins), rtx.RAY)
-    r["origin"], r["direction"], r["tMax"] = origins, directions, t_max
-    return r
-
-
-def camera_rays(rtx, params, w=64, h=48):
-    """pinhole rays through pixel centres (normalised directions, as the renderer's camera rays are)"""
-    M = np.asarray(params["camLocalToWorld"], np.float32).reshape(4, 4)
-    vp = np.asarray(params["viewParams"], np.float32)
-    ys, xs = np.mgrid[0:h, 0:w].astype(np.float32)
-    lx, ly = ((xs + 0.5) / w - 0.5) * vp[0], ((ys + 0.5) / h - 0.5) * vp[1]
-    local = np.stack([lx.ravel(), ly.ravel(), np.full(lx.size, vp[2], np.float32), np.ones(lx.size, np.float32)], 1)
-    focus = (local @ M.T)[:, :3]
-    pos = np.asarray(params["worldSpaceCameraPos"], np.float32)
-    d = focus - pos
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return make_rays(rtx, np.broadcast_to(pos, d.shape), d.astype(np.float32))
-
-
-def scene_of(rtx, name):
-    from rtx_amd import unity_scene
-    if name == "mesh_test_scene":
-        return rtx.scenes.mesh_test_scene(64, 48)
-    return unity_scene.load_scene_npz(os.path.join(GOLDEN, "scenes", name + ".npz"), 64, 48)
-
-
 def loaded_tracer(rtx, mgr, mode, **options):
     params, spheres, tris, infos = mgr.build_buffers()
     params["intersectMode"] = mode
@@ -108,21 +55,6 @@ def loaded_tracer(rtx, mgr, mode, **options):
     t.set_params(params)
     t.upload(spheres=spheres, triangles=tris, meshinfo=infos)
     return t, params, spheres, tris, infos
-
-
-def random_rays(rtx, tris, spheres, n, seed):
-    rng = np.random.default_rng(seed)
-    pts = [np.asarray(tris["posA"]).reshape(-1, 3), np.asarray(spheres["position"]).reshape(-1, 3)]
-    pts = np.concatenate([p for p in pts if len(p)]) if any(len(p) for p in pts) else np.zeros((1, 3), np.float32)
-    lo, hi = pts.min(0), pts.max(0)
-    ext = np.maximum(hi - lo, 1.0)
-    o = (lo - ext + rng.random((n, 3)) * 3 * ext).astype(np.float32)          # inside and outside the bounds
-    d = rng.standard_normal((n, 3)).astype(np.float32)                         # not normalised
-    k = n // 8                                                                 # axis-aligned, zero components
-    d[:k] = 0.0
-    d[np.arange(k), rng.integers(0, 3, k)] = rng.choice([-1.0, 1.0, 2.5], k)
-    d[k:2 * k, rng.integers(0, 3)] = 0.0
-    return make_rays(rtx, o, d)
 
 
 @pytest.mark.parametrize("mode", [0, 1])

@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from shader_twin import philox4x32_10 as _philox4x32_10          # Philox4x32-10 in plain Python integers, independent of the oracle's C
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -206,17 +208,6 @@ def test_philox_mode_is_a_different_stream_with_the_same_estimator(rtx, oracle):
     assert not np.array_equal(pcg, phx)
     lo = np.minimum(pcg[..., :3], 1).mean(), np.minimum(phx[..., :3], 1).mean()
     assert abs(lo[0] - lo[1]) < 0.05 * lo[0], lo
-
-
-def _philox4x32_10(ctr, key):
-    """Philox4x32-10 in plain Python integers (Salmon et al., SC'11) — independent of the oracle's C."""
-    c0, c1, c2, c3 = ctr
-    k0, k1 = key
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c3 ^ k1) & 0xFFFFFFFF, p0 & 0xFFFFFFFF
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c0, c1, c2, c3
 
 
 def test_philox_python_twin_matches_the_known_answers():
