@@ -352,6 +352,11 @@ int rt_get_stats(rt_ctx* ctx, rt_stats* out);
  * form (six plane arrays of 4 floats, child[4], meta[4]) and in the f16 form the kernels traverse (csrc/bvh.hpp Node4h).
  * Either destination may be NULL.  Tests check that every f16 box contains its f32 box.                                 */
 int rt_read_bvh(rt_ctx* ctx, void* nodes_f32, void* nodes_f16, size_t n_nodes);
+/* Diagnostics: the triangle order the leaf references of rt_read_bvh point into — order[i] = the uploaded triangle at BVH
+ * position i (rt_upload_triangles order for world-space uploads, rt_read_world_geometry order for local meshes: the `primitive`
+ * numbering of rt_hit).  n = the triangles in the tree (the sum of the leaf counts): every uploaded triangle after a device
+ * build, those a chunk addresses after a host build; 0 is legal.  Tests audit every box of every tree against its triangles.  */
+int rt_read_bvh_order(rt_ctx* ctx, uint32_t* order, size_t n);
 
 /* ---- ray queries: what a caller-supplied ray hits -------------------------------------------------------------------
  * The reference answers "what does this ray hit?" only inside its shader: CalculateRayCollision (RayTracing.shader:256-297) over

@@ -70,7 +70,7 @@ SYMBOLS = [
     "rt_upload_triangles", "rt_upload_meshinfo", "rt_set_rows", "rt_render_frame", "rt_render",
     "rt_render_counting", "rt_render_frame_flat", "rt_reset_accum", "rt_read_accum", "rt_read_last_frame",
     "rt_copy_accum_to_device", "rt_get_stats", "rt_abi_version", "rt_sizeof", "rt_set_option", "rt_set_bands", "rt_upload_local_meshes", "rt_set_mesh_transforms", "rt_read_world_geometry", "rt_read_display",
-    "rt_read_bvh", "rt_write_accum", "rt_submit_frame", "rt_wait",
+    "rt_read_bvh", "rt_read_bvh_order", "rt_write_accum", "rt_submit_frame", "rt_wait",
     "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error", "rt_multi_count", "rt_multi_context", "rt_multi_set_params",
     "rt_multi_upload_spheres", "rt_multi_upload_triangles", "rt_multi_upload_meshinfo", "rt_multi_set_option", "rt_multi_reset_accum",
     "rt_multi_render", "rt_multi_read_accum", "rt_multi_get_stats", "rt_multi_get_info",
@@ -129,6 +129,7 @@ def load_library() -> ctypes.CDLL:
     lib.rt_get_stats.argtypes = [c_void_p, c_void_p]
     lib.rt_read_display.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.rt_read_bvh.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t]
+    lib.rt_read_bvh_order.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.rt_write_accum.argtypes = [c_void_p, POINTER(c_float), c_size_t, c_int]
     lib.rt_abi_version.restype = c_int
     lib.rt_sizeof.argtypes = [c_char_p]
@@ -417,6 +418,14 @@ class Tracer:
         f32, f16 = np.zeros((n, 32), np.uint32), np.zeros((n, 32), np.uint32)
         self._check(self._lib.rt_read_bvh(self._ctx, f32.ctypes.data_as(c_void_p), f16.ctypes.data_as(c_void_p), n), "rt_read_bvh")
         return f32, f16
+
+    def read_bvh_order(self):
+        """BVH position -> uploaded triangle (see rt_read_bvh_order), uint32 [sum of the leaf counts of read_bvh()]."""
+        refs = self.read_bvh()[0][:, 24:28].ravel()
+        leaves = refs[((refs & 0x80000000) != 0) & (refs != 0xFFFFFFFF)]
+        order = np.zeros(int(((leaves & 3) + 1).sum()), np.uint32)
+        self._check(self._lib.rt_read_bvh_order(self._ctx, order.ctypes.data_as(c_void_p), order.size), "rt_read_bvh_order")
+        return order
 
     # -- feature buffers
     def render_aov(self, first_frame: int, n_frames: int):

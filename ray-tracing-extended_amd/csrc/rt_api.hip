@@ -1743,6 +1743,21 @@ int rt_read_bvh(rt_ctx* c, void* nodes_f32, void* nodes_f16, size_t n_nodes)
     return 0;
 }
 
+int rt_read_bvh_order(rt_ctx* c, uint32_t* order, size_t n)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (c->scene_dirty) return fail(c, -2, "the scene has not been built yet (render a frame first)");
+    const size_t have = c->n_nodes ? c->d_order.used : 0;
+    if (n != have) return fail(c, -2, "expected %zu triangles, got %zu", have, n);
+    if (!n) return 0;
+    if (!order) return fail(c, -2, "null destination");
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    RT_HIP(c, hipMemcpy(order, c->d_order.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits) { return c ? query_host(c, false, rays, n, hits) : -1; }
 int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { return c ? query_host(c, true, rays, n, occluded) : -1; }
 int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return c ? query_device(c, false, rays, n, hits) : -1; }

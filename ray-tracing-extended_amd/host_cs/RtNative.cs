@@ -187,6 +187,7 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_copy_accum_to_device(IntPtr ctx, IntPtr dstDevicePtr, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_read_display(IntPtr ctx, IntPtr rgba8, UIntPtr nPixels);
         [DllImport(Lib)] public static extern int rt_read_bvh(IntPtr ctx, IntPtr nodesF32, IntPtr nodesF16, UIntPtr nNodes);
+        [DllImport(Lib)] public static extern int rt_read_bvh_order(IntPtr ctx, IntPtr order, UIntPtr n);
         [DllImport(Lib)] public static extern int rt_get_stats(IntPtr ctx, out RtStats stats);
         // ---- ABI self-description
         [DllImport(Lib)] public static extern int rt_abi_version();

@@ -1,0 +1,308 @@
+"""The BVH auditor (tests/bvh_audit.py) proved on the CPU: it reports the host builder's trees (csrc/bvh.cpp through tests/bvh_dump.cpp,
+with the f16 form made by a numpy packer that follows Node4h in bvh.hpp) clean, and catches every single mutation of such a tree in the
+category it belongs to.  An auditor that passes a mutated tree is a failed test.  The rays the GPU tests aim at the box faces are checked
+here against the ray-query oracle alone: they must report the triangles they are aimed at, or the GPU comparison would pass vacuously."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bvh_audit as A
+from ray_query_helpers import oracle_hits, shim      # noqa: F401 (shim is a fixture)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ray-tracing-extended_amd", "csrc")
+AWKWARD_COUNTS = [1, 2, 3, 5, 47, 513, 1025]
+
+
+@pytest.fixture(scope="module")
+def dumper(tmp_path_factory):
+    d = tmp_path_factory.mktemp("bvh_dump")
+    exe = str(d / "bvh_dump")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", CSRC, os.path.join(ROOT, "tests", "bvh_dump.cpp"), os.path.join(CSRC, "bvh.cpp"), "-o", exe])
+
+    def host_tree(tris, collapse=0, max_leaf=2, passes=0, G=10.0):
+        """the host builder's tree over `tris` -> (f32 nodes [n, 32] uint32, f16 nodes, order, maxStack)"""
+        src, out = str(d / "t.f32"), str(d / "t.bvh")
+        A.triangle_positions(tris).astype(np.float32).tofile(src)
+        subprocess.check_call([exe, src, out, str(collapse), str(max_leaf), str(passes), repr(float(G))], timeout=120)
+        raw = np.fromfile(out, np.uint32)
+        n_nodes, n_order, stack = int(raw[0]), int(raw[1]), int(raw[2:3].view(np.int32)[0])
+        f32 = raw[4:4 + 32 * n_nodes].reshape(n_nodes, 32).copy()
+        order = raw[4 + 32 * n_nodes:].copy()
+        assert len(order) == n_order
+        return f32, A.pack_f16_nodes(f32), order, stack
+    return host_tree
+
+
+def test_the_packer_and_the_decoder_are_inverse_and_outward(dumper, rtx):
+    tris, _ = A.awkward_triangles(rtx, 513)
+    f32, f16, _, _ = dumper(tris)
+    mins, maxs, child, _ = A.decode_f32_nodes(f32)
+    mins16, maxs16 = A.decode_f16_nodes(f16)                       # (asserts that the plane sets agree)
+    used = np.broadcast_to((child != A.EMPTY)[:, None, :], mins.shape)
+    assert (mins16[used] <= mins[used]).all() and (maxs16[used] >= maxs[used]).all()
+    assert np.isposinf(mins16[~used]).all() and np.isneginf(maxs16[~used]).all()
+    assert np.array_equal(A.pack_f16_nodes(f32), f16) and np.array_equal(f16[:, 24:28], f32[:, 24:28])
+
+
+@pytest.mark.parametrize("max_leaf", [1, 2, 3, 4])
+@pytest.mark.parametrize("n", AWKWARD_COUNTS)
+def test_host_trees_over_awkward_triangle_counts_are_clean(dumper, rtx, n, max_leaf):
+    tris, _ = A.awkward_triangles(rtx, n)
+    f32, f16, order, stack = dumper(tris, max_leaf=max_leaf)
+    rep = A.audit(f32, f16, order, tris, max_stack=stack, exact_stack=True)
+    A.assert_clean(rep, f"host tree, {n} triangles, max_leaf {max_leaf}")
+    assert rep.n_triangles == n and rep.n_nodes >= 1
+
+
+@pytest.mark.parametrize("collapse,passes", [(0, 0), (0, 2), (1, 0), (1, 2), (2, 0), (2, 2)])
+def test_host_trees_of_the_mesh_test_scene_are_clean_and_nest(dumper, rtx, collapse, passes):
+    """every collapse mode, with and without the insertion passes: the host builder's trees nest (bvh_audit.py, `nesting`)"""
+    tris = rtx.scenes.mesh_test_scene(64, 48).build_buffers()[2]
+    for max_leaf in (1, 2, 3, 4):
+        f32, f16, order, stack = dumper(tris, collapse=collapse, max_leaf=max_leaf, passes=passes, G=14.0)
+        rep = A.audit(f32, f16, order, tris, max_stack=stack, exact_stack=True)
+        A.assert_clean(rep, f"host tree of the mesh-test scene, collapse {collapse}, max_leaf {max_leaf}, {passes} passes")
+        assert rep.n_triangles == len(tris) and rep.levels > 2
+
+
+def test_a_subset_of_the_triangles_is_audited_through_live(dumper, rtx):
+    tris, _ = A.awkward_triangles(rtx, 47)
+    live = np.array([i for i in range(47) if i % 5 != 1], np.uint32)
+    f32, f16, order, stack = dumper(tris[live])
+    rep = A.audit(f32, f16, live[order], tris, live=live, max_stack=stack)
+    A.assert_clean(rep, "live subset")
+    assert A.audit(f32, f16, live[order], tris, max_stack=stack).failed() == {"leaves"}        # the others are missing
+
+
+# ---- mutations ---------------------------------------------------------------------------------------------------------------------
+
+class Tree:
+    def __init__(self, dumper, rtx):
+        self.tris, _ = A.awkward_triangles(rtx, 513)
+        self.f32, self.f16, self.order, self.stack = dumper(self.tris)
+        self.P = A.triangle_positions(self.tris)
+        _, _, self.child, _ = A.decode_f32_nodes(self.f32)
+        c = self.child
+        self.leaf = (c != A.EMPTY) & ((c & A.LEAF) != 0)
+        self.internal = (c != A.EMPTY) & ((c & A.LEAF) == 0)
+        self.depth = np.zeros(len(c), int)
+        for i in range(len(c)):                                  # breadth-first order: a child's index is larger than its parent's
+            for s in range(4):
+                if self.internal[i, s]:
+                    self.depth[c[i, s]] = self.depth[i] + 1
+
+    def copies(self):
+        return self.f32.copy(), self.f16.copy(), self.order.copy()
+
+    def leaf_slot(self, want_count=None, skip=()):
+        """(node, slot, first, count) of a leaf without the NaN triangle (4)"""
+        for i, s in np.argwhere(self.leaf):
+            first, count = int(self.child[i, s] & 0x7FFFFFFF) >> 2, int(self.child[i, s] & 3) + 1
+            t = self.order[first:first + count]
+            if 4 not in t and (want_count is None or count == want_count) and (i, s) not in skip:
+                return int(i), int(s), first, count
+        raise AssertionError("no such leaf")
+
+    def audit(self, f32, f16, order, **kw):
+        kw.setdefault("max_stack", self.stack)
+        return A.audit(f32, f16, order, self.tris, **kw)
+
+
+def plane(f32, axis, is_max):
+    """float32 view [n, 4] of one plane array of the f32 nodes"""
+    k = (3 if is_max else 0) + axis
+    return f32[:, 4 * k:4 * k + 4].view(np.float32)
+
+
+def f16_plane_halves(axis, slot, is_max):
+    """indices into the 64 halves of a Node4h that hold the (axis, slot, min / max) plane"""
+    if axis == 2:
+        return [36 + slot, 40 + slot] if is_max else [32 + slot, 44 + slot]
+    bit = 1 << axis
+    return [8 * c + 4 * axis + slot for c in range(4) if bool(c & bit) == bool(is_max)]
+
+
+@pytest.fixture(scope="module")
+def tree(dumper, rtx):
+    t = Tree(dumper, rtx)
+    A.assert_clean(t.audit(*t.copies(), exact_stack=True), "the tree the mutations start from")
+    return t
+
+
+def test_mutation_leaf_face_one_ulp_inside_its_extreme_vertex(tree):
+    for is_max in (False, True):
+        for axis in range(3):
+            f32, f16, order = tree.copies()
+            i, s, first, count = tree.leaf_slot()
+            v = tree.P[order[first:first + count]][:, :, axis].astype(np.float32)
+            ext = v.max() if is_max else v.min()
+            plane(f32, axis, is_max)[i, s] = np.nextafter(ext, np.float32(-np.inf if is_max else np.inf))
+            rep = tree.audit(f32, f16, order)
+            assert "containment" in rep.failed() and rep.failed() <= {"containment", "padding"}, str(rep)
+            assert rep.counts["containment"] >= 1 and f"node {i} slot {s}" in rep.examples["containment"][0], str(rep)
+
+
+def test_mutation_root_level_box_shrunk_so_that_a_deep_triangle_pokes_out(tree):
+    f32, f16, order = tree.copies()
+    s = int(np.argmax(tree.internal[0]))
+    assert tree.internal[0, s]
+    lo, hi = plane(f32, 0, False)[0, s], plane(f32, 0, True)[0, s]
+    plane(f32, 0, True)[0, s] = np.float32(0.5) * (lo + hi)
+    rep = tree.audit(f32, A.pack_f16_nodes(f32), order)
+    assert "containment" in rep.failed() and rep.failed() <= {"containment", "nesting"}, str(rep)
+    assert f"of node 0 slot {s} (leaf: node" in rep.examples["containment"][0], str(rep)
+
+
+def test_mutation_padding_removed_from_one_leaf(tree):
+    f32, f16, order = tree.copies()
+    i, s, first, count = tree.leaf_slot()
+    v = tree.P[order[first:first + count]].astype(np.float32)
+    for axis in range(3):
+        plane(f32, axis, False)[i, s] = v[:, :, axis].min(); plane(f32, axis, True)[i, s] = v[:, :, axis].max()
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"padding"} and rep.counts["padding"] == 6, str(rep)
+
+
+def test_mutation_order_entries_of_two_leaves_swapped(tree):
+    f32, f16, order = tree.copies()
+    cen = tree.P[order].mean(axis=1)
+    with np.errstate(invalid="ignore"):
+        far = int(np.nanargmax(np.abs(cen - cen[0]).max(axis=1)))
+    order[0], order[far] = order[far], order[0]
+    rep = tree.audit(f32, f16, order)
+    assert "containment" in rep.failed() and rep.failed() <= {"containment", "padding"}, str(rep)
+
+
+def test_mutation_order_entry_duplicated(tree):
+    f32, f16, order = tree.copies()
+    order[10] = order[200]
+    rep = tree.audit(f32, f16, order)
+    assert "leaves" in rep.failed() and rep.failed() <= {"leaves", "containment", "padding"}, str(rep)
+
+
+def test_mutation_leaf_count_raised_by_one(tree):
+    f32, f16, order = tree.copies()
+    i, s, first, count = tree.leaf_slot(want_count=1)
+    f32[i, 24 + s] += 1; f16[i, 24 + s] += 1
+    rep = tree.audit(f32, f16, order)
+    assert "leaves" in rep.failed() and rep.failed() <= {"leaves", "containment", "padding"}, str(rep)
+
+
+def test_mutation_child_reference_to_an_ancestor(tree):
+    f32, f16, order = tree.copies()
+    i = int(np.argmax(np.where(tree.internal.any(1), tree.depth, -1)))      # the deepest node with an internal child
+    s = int(np.argmax(tree.internal[i]))
+    assert tree.depth[i] >= 2
+    f32[i, 24 + s] = 0; f16[i, 24 + s] = 0
+    rep = tree.audit(f32, f16, order)                                       # (and the walk ends)
+    assert "topology" in rep.failed() and rep.counts["topology"] >= 3, str(rep)    # root referenced, a node met again, a subtree unreachable
+
+
+def test_mutation_orphaned_node(tree):
+    f32, f16, order = tree.copies()
+    i = int(np.argmax(~tree.internal.any(1)))                               # a node of leaves only, once more at the end
+    f32, f16 = np.concatenate([f32, f32[i:i + 1]]), np.concatenate([f16, f16[i:i + 1]])
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"topology"} and rep.counts["topology"] == 2, str(rep)   # never referenced, never reached
+
+
+def test_mutation_meta0_lowered(tree):
+    f32, f16, order = tree.copies()
+    i = int(np.argmax(f32[:, 28] >= 2))
+    f32[i, 28] -= 1
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"topology"} and rep.counts["topology"] == 1, str(rep)
+
+
+def test_mutation_used_slot_made_empty_in_the_f16_form_only(tree):
+    f32, f16, order = tree.copies()
+    i, s, _, _ = tree.leaf_slot()
+    halves = f16[:, :32].view(np.uint16)
+    for axis in range(3):
+        halves[i, f16_plane_halves(axis, s, False)] = 0x7C00; halves[i, f16_plane_halves(axis, s, True)] = 0xFC00
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"f16"}, str(rep)
+
+
+def test_mutation_one_f16_plane_rounded_inward_by_one_step(tree):
+    mins, maxs, _, _ = A.decode_f32_nodes(tree.f32)
+    hits = 0
+    for is_max in (False, True):
+        for axis in range(3):
+            f32, f16, order = tree.copies()
+            halves = f16[:, :32].view(np.uint16)
+            # the first used slot whose plane, one f16 step inward, cuts the f32 box (a plane that f16 holds exactly has a step to spare)
+            for i, s in np.argwhere(tree.leaf):
+                idx = f16_plane_halves(axis, s, is_max)
+                h = halves[i, idx[0]:idx[0] + 1].view(np.float16)
+                stepped = np.nextafter(h, np.float16(-np.inf if is_max else np.inf))
+                org = float(f16[i, 28 + axis:29 + axis].view(np.float32)[0])
+                if np.isfinite(stepped[0]) and ((org + float(stepped[0]) < maxs[i, axis, s]) if is_max else (org + float(stepped[0]) > mins[i, axis, s])):
+                    halves[i, idx] = stepped.view(np.uint16)[0]
+                    break
+            else:
+                raise AssertionError("no plane to mutate")
+            rep = tree.audit(f32, f16, order)
+            assert rep.failed() == {"f16"} and f"node {i} slot {s}" in rep.examples["f16"][0], str(rep)
+            hits += 1
+    assert hits == 6
+
+
+def test_mutation_child_references_differ_between_the_forms(tree):
+    f32, f16, order = tree.copies()
+    i, s, _, _ = tree.leaf_slot()
+    f16[i, 24 + s] ^= 4
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"f16"}, str(rep)
+
+
+def test_mutation_f16_denormal(tree):
+    f32, f16, order = tree.copies()
+    i, s, _, _ = tree.leaf_slot()
+    halves = f16[:, :32].view(np.uint16)
+    halves[i, f16_plane_halves(1, s, False)] = 0x8001
+    rep = tree.audit(f32, f16, order)
+    assert rep.failed() == {"f16"} and any("denormal" in m for m in rep.examples["f16"]), str(rep)
+
+
+def test_mutation_empty_slot_not_infinite(tree):
+    f32, f16, order = tree.copies()
+    i, s = (int(v) for v in np.argwhere(tree.child == A.EMPTY)[0])
+    plane(f32, 2, True)[i, s] = np.float32(3.0)
+    rep = tree.audit(f32, f16, order)
+    assert "empty" in rep.failed() and rep.failed() <= {"empty", "nesting"}, str(rep)      # (the child node's union has grown with it)
+
+
+def test_mutation_max_stack_one_too_small(tree):
+    rep = tree.audit(*tree.copies(), max_stack=tree.stack - 1)
+    assert rep.failed() == {"stack"}, str(rep)
+    assert tree.audit(*tree.copies(), max_stack=tree.stack + 1).clean
+    assert tree.audit(*tree.copies(), max_stack=tree.stack + 1, exact_stack=True).failed() == {"stack"}
+
+
+def test_mutation_internal_box_no_longer_the_union_after_a_refit(tree):
+    """refitted=True asks for equality: a box that still contains its children but is wider passes the built tree's check only"""
+    f32, f16, order = tree.copies()
+    s = int(np.argmax(tree.internal[0]))
+    plane(f32, 1, True)[0, s] += np.float32(1.0)
+    f16 = A.pack_f16_nodes(f32)
+    assert tree.audit(f32, f16, order).clean
+    assert tree.audit(f32, f16, order, refitted=True).failed() == {"nesting"}
+
+
+# ---- the rays aimed at the box faces ----------------------------------------------------------------------------------------------
+
+def test_aimed_rays_report_the_triangles_they_are_aimed_at(rtx, shim):
+    """On the mesh-test scene the ray-query oracle alone (no hierarchy) reports the aimed-at triangle for 96.5 % of the rays (the
+    rest run parallel to their triangle: the floor, the light and the cubes are axis-aligned in y), and every triangle with a non-zero
+    normal through at least one of its nine rays — so a box face that cuts a triangle cannot go unnoticed by the GPU comparison."""
+    _, spheres, tris, infos = rtx.scenes.mesh_test_scene(64, 48).build_buffers()
+    rays, target = A.aimed_rays(rtx, tris)
+    assert len(rays) == 9 * len(tris)
+    for mode in (0, 1):
+        share, unreported = A.aimed_ray_shares(rtx, oracle_hits(rtx, shim, spheres, tris, infos, mode, rays), target, tris)
+        print(f"mode {mode}: {100 * share:.2f} % of {len(rays)} aimed rays report their triangle; unreported triangles {unreported.tolist()}")
+        assert share >= 0.90 and len(unreported) == 0, (mode, share, unreported)

@@ -5,6 +5,7 @@ within 15 % of the host tree)."""
 import numpy as np
 import pytest
 
+from bvh_audit import awkward_triangles
 from test_gpu_parity import assert_bitwise, run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -49,24 +50,8 @@ def test_device_built_tree_gives_the_oracles_image(rtx, oracle, tracer, mode, ra
 def test_device_builder_small_and_awkward_triangle_counts(rtx, oracle, tracer, n):
     """1 triangle (a root with one leaf), 2 (one leaf pair), counts around the single-workgroup threshold of the clustering
     (512 clusters), exact duplicates and a NaN triangle among them: image == oracle, every triangle reachable."""
-    rng = np.random.default_rng(n)
-    m = rtx.scenes.mesh_test_scene(48, 32)
-    params, spheres, _, _ = m.build_buffers()
-    tris = np.zeros(n, rtx.TRIANGLE)
-    c = rng.uniform([-3, 0, -2], [3, 3, 4], (n, 1, 3)).astype(np.float32)
-    p = c + rng.uniform(-0.6, 0.6, (n, 3, 3)).astype(np.float32)
-    if n >= 5:
-        p[3] = p[2]                               # an exact duplicate
-        p[4, 1, 0] = np.nan
-    tris["posA"], tris["posB"], tris["posC"] = p[:, 0], p[:, 1], p[:, 2]
-    nrm = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]).astype(np.float32)
-    for f in ("normalA", "normalB", "normalC"):
-        tris[f] = nrm
-    infos = np.zeros(1, rtx.MESHINFO)
-    infos["numTriangles"] = n
-    infos["material"]["colour"] = (0.8, 0.7, 0.6, 1); infos["material"]["emissionColour"] = (1, 1, 1, 1); infos["material"]["emissionStrength"] = 0.5
-    with np.errstate(invalid="ignore"):
-        infos["boundsMin"], infos["boundsMax"] = np.nanmin(p.reshape(-1, 3), 0) - 1, np.nanmax(p.reshape(-1, 3), 0) + 1
+    params, spheres, _, _ = rtx.scenes.mesh_test_scene(48, 32).build_buffers()
+    tris, infos = awkward_triangles(rtx, n)
     b = (params, spheres, tris, infos)
     got, st, (f32, _) = _render_with(tracer, b, 1, want_bvh=True)
     want, _, cnt = oracle.render(*b, 0, 2)

@@ -4,6 +4,7 @@ Every case: GPU (both kernels) == oracle, bit for bit."""
 import numpy as np
 import pytest
 
+from bvh_audit import ragged_chunk_scene
 from test_gpu_parity import assert_bitwise, run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -49,14 +50,7 @@ def test_many_bounces_specular_hall_of_mirrors(rtx, oracle, tracer):
 
 def test_ragged_chunks_zero_triangle_chunk_and_unreferenced_triangles(rtx, oracle, tracer):
     """A chunk with numTriangles = 0 and triangles no chunk refers to (the shader can never reach them)."""
-    m = rtx.scenes.mesh_test_scene(64, 40)
-    params, spheres, tris, infos = m.build_buffers()
-    infos = infos.copy()
-    empty = infos[:1].copy()
-    empty["numTriangles"] = 0
-    infos = np.concatenate([infos[:3], empty, infos[3:]])
-    infos["numTriangles"][5] -= 3                      # the last 3 triangles of that chunk become unreachable
-    b = (params, spheres, tris, infos)
+    b = ragged_chunk_scene(rtx, 64, 40)
     want, want_last, _ = oracle.render(*b, 0, 1)
     for k in (0, 1):
         acc, last = run_gpu(tracer, b, 0, 1, kernel=k)

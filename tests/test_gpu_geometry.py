@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from bvh_audit import random_pose
 from test_gpu_parity import assert_bitwise, run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -110,14 +111,7 @@ def test_random_transforms_device_geometry_equals_host_marshal(rtx, tracer, seed
     mgr = rtx.scenes.mesh_test_scene(64, 48)
 
     def pose():
-        for i, me in enumerate(mgr.meshes):
-            q = rng.normal(size=4)
-            q = q / np.linalg.norm(q) * (1.0001 if i == 1 else 1.0)
-            s = 10.0 ** rng.uniform(-1.5, 0.8, 3) * rng.choice([1, 1, 1, -1], 3)
-            if i == 2 and seed % 3 == 0:
-                s[int(rng.integers(0, 3))] = 0.0
-            big = 1e3 if seed % 4 == 3 else 6.0
-            me.transform = rtx.host.Transform(position=tuple(rng.uniform(-big, big, 3)), rotation=tuple(q), lossyScale=tuple(s))
+        random_pose(rtx, mgr, rng, seed)
 
     pose()
     upload_local(tracer, mgr)

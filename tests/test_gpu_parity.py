@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from bvh_audit import decode_f16_nodes as _decode_f16_nodes
+
 pytestmark = pytest.mark.gpu
 
 
@@ -412,22 +414,6 @@ def test_f32_nodes_and_f16_nodes_give_the_same_image(rtx, oracle, tracer, mode, 
         assert_bitwise(last, want_last, f"compact_nodes={compact} kernel {kernel} mode {mode}: last frame")
         assert_bitwise(acc, want, f"compact_nodes={compact} kernel {kernel} mode {mode}: accum")
         assert st["rays"] == cnt["rays"]
-
-
-def _decode_f16_nodes(h):
-    """Node4h words [n, 32] -> (mins [n, 3, 4], maxs [n, 3, 4]) as float64 = origin + offset, checking that the plane sets agree."""
-    n = h.shape[0]
-    halves = h[:, :24].copy().view(np.float16).astype(np.float64).reshape(n, 6, 8)          # six 16-byte sets of 8 halves
-    org = h[:, 28:31].copy().view(np.float32).astype(np.float64)                             # [n, 3]
-    sets = halves[:, :4].reshape(n, 4, 2, 4)                                                 # set c: (x planes, y planes)
-    minx, maxx, miny, maxy = sets[:, 0, 0], sets[:, 1, 0], sets[:, 0, 1], sets[:, 2, 1]
-    assert np.array_equal(sets[:, 2, 0], minx) and np.array_equal(sets[:, 3, 0], maxx)       # bit 0 of c picks the x planes
-    assert np.array_equal(sets[:, 1, 1], miny) and np.array_equal(sets[:, 3, 1], maxy)       # bit 1 the y planes
-    minz, maxz = halves[:, 4, :4], halves[:, 4, 4:]
-    assert np.array_equal(halves[:, 5, :4], maxz) and np.array_equal(halves[:, 5, 4:], minz)
-    mins = np.stack([minx, miny, minz], 1) + org[:, :, None]
-    maxs = np.stack([maxx, maxy, maxz], 1) + org[:, :, None]
-    return mins, maxs
 
 
 @pytest.mark.parametrize("scene", ["mesh_test", "config3", "far"])
