@@ -224,6 +224,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *   "kernel"          -1 = automatic (default): the first frames after a scene / camera change time k_trace and k_stream on
  *                     ordinary frames of the render and the faster one takes the rest; 0 = tile-per-wave megakernel k_trace,
  *                     1 = k_stream (resumable traversal, stragglers deferred; the only kernel of the Philox mode)
+ *                     k_stream takes at most 65000 rays per pixel per frame and 32000 bounces (sample and bounce counters share one register);
+ *                     a PCG frame with more is k_trace's whatever this option says (rt_stats.lastKernel = 0), a Philox frame with more is refused
  *   "max_leaf"        triangles per BVH leaf, 1..4 (default 2)
  *   "bvh_bins", "bvh_cost_exp", "bvh_reinsert"   BVH builder: SAH bins per axis (32); exponent, in percent, of the triangle
  *                     count in the SAH's subtree-cost model (100); passes of insertion-based optimisation of the binary tree (0:
@@ -232,8 +234,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     area (default); 1 = cost-driven dynamic programme that also forms the leaves; 2 = the same over the split search's
  *                     leaves; with a node step costing bvh_node_cost percent of a triangle test (130)
  *   "stream_stack"    k_stream: traversal-stack entries per lane kept in LDS; a BVH whose worst case is deeper spills the rest to global memory.
- *                     0 (default) = automatic: 24 for the six-waves-per-SIMD instantiation (PCG stream, f16 nodes: six workgroups per CU), 30 for the
- *                     five-wave ones (Philox mode, f32 nodes, counting build)
+ *                     0 (default) = automatic: 21 for the seven-waves-per-SIMD instantiation (PCG stream, f16 nodes: seven workgroups per CU), 30 for
+ *                     the five-wave ones (Philox mode, f32 nodes, counting build)
  *   "full_sort"       1 = sort all four children of a node by entry distance, 0 = nearest first only (default)
  *   "tile_lpt"        k_trace: 1 = hand tiles out costliest first, by the costs the previous launch measured (default), 0 = in order
  *   "frame_batch"     k_trace: frames traced per launch by rt_render (0 = auto: as many as fit 4 GiB, at most 256; 1 = one per launch)

@@ -748,13 +748,14 @@ int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n
     if (philox && (c->params.numRaysPerPixel > 65000 || c->params.maxBounceCount > 32000))
         return fail(c, -7, "the Philox mode takes at most 65000 rays per pixel per frame and 32000 bounces (sample and bounce share one signed 32-bit register)");
     const bool stream = P.stream = kernel == 1 && var != Variant::Flat && c->params.numRaysPerPixel >= 1   // PCG or Philox instantiation
-                                   && c->target_w <= 65535 && c->target_rows <= 65535;                     // (16-bit pixel coordinates in k_stream's item tables)
+                                   && c->target_w <= 65535 && c->target_rows <= 65535                      // (16-bit pixel coordinates in k_stream's item tables)
+                                   && c->params.numRaysPerPixel <= 65000 && c->params.maxBounceCount <= 32000;     // (sample and bounce share one register; beyond that PCG frames are k_trace's)
     const bool tile_kernel = P.tile_kernel = !stream && var != Variant::Flat;   // k_trace, PCG or Philox
     F.stack_cap = tile_kernel ? tile_stack_cap(c)
                               : std::max(1, c->bvh.maxStack) + (stream ? 3 : 0);    // the branch-free push writes up to 3 slots past the top
-    // k_stream: at most opt_stream_stack entries per lane in LDS (30 = five workgroups per CU); a deeper worst case spills
-    const bool six_waves = stream && !philox && var == Variant::Fast && c->opt_compact_nodes != 0 && c->n_nodes > 0;       // rt_stream.hpp stream_waves()
-    const int stream_stack = c->opt_stream_stack > 0 ? c->opt_stream_stack : (six_waves ? 24 : 30);
+    // k_stream: at most opt_stream_stack entries per lane in LDS (30 = five workgroups per CU, 21 = seven); a deeper worst case spills
+    const bool seven_waves = stream && !philox && var == Variant::Fast && c->opt_compact_nodes != 0 && c->n_nodes > 0;     // rt_stream.hpp stream_waves()
+    const int stream_stack = c->opt_stream_stack > 0 ? c->opt_stream_stack : (seven_waves ? (RT_STREAM_WAVES >= 7 ? 21 : 24) : 30);
     const bool stream_spill = stream && F.stack_cap > stream_stack;
     if (stream_spill) F.stack_cap = stream_stack;
     F.full_sort = c->opt_full_sort;

@@ -125,10 +125,12 @@ constexpr int kNumCounters = 15 + kNumRegions;
 #define RT_MARK(TEXT) asm volatile("; RTMARK " TEXT)
 #define RT_RARE_PATH() asm volatile("; RTRARE")      /* a block the benchmark configurations do not execute (option off, stack within its LDS part) */
 #define RT_RARE_PATH_EXPR() ({ asm volatile("; RTRARE"); 0; })                     /* the same inside a condition: (RT_RARE_PATH_EXPR(), test) */
+#define RT_QUARTER_PATH() asm volatile("; RTQUARTER") /* a block that runs in one of four executions of its region by construction: a quarter of it is counted */
 #else
 #define RT_MARK(TEXT) do { } while (0)
 #define RT_RARE_PATH() do { } while (0)
 #define RT_RARE_PATH_EXPR() 0
+#define RT_QUARTER_PATH() do { } while (0)
 #endif
 // (COUNT and cnt are the enclosing kernel's; the tick is one increment on the first active lane, in the counting build only)
 #define RT_REGION_BEGIN(NAME) do { RT_MARK("begin " #NAME); if (COUNT) { const unsigned long long rm_ = rtk::ballot_(true); \
@@ -224,7 +226,8 @@ template <> struct RaySlabT<false> {
 // far planes, and one of two 16-B (near z, far z) sets
 template <> struct RaySlabT<true> {
     v3 inv, oinv;
-    uint32_t nxy, fxy, zo; // byte offsets inside the node: near (x,y) set, far (x,y) set, z set
+    uint32_t sets;      // byte offsets inside the node in one register: near (x,y) set (0 / 16 / 32 / 48) | z set (64 / 80) << 8.  The far
+                        // (x,y) set is the complementary one, 48 - near = near ^ 48: one VALU per node step instead of two registers per ray
 };
 using RaySlab = RaySlabT<false>;
 
@@ -235,9 +238,7 @@ __device__ __forceinline__ RaySlabT<H> make_slab(v3 o, v3 d)
     r.inv = rtm::mk(rtm::rcp_(d.x), rtm::rcp_(d.y), rtm::rcp_(d.z));
     r.oinv = rtm::mk(o.x * r.inv.x, o.y * r.inv.y, o.z * r.inv.z);
     if constexpr (H) {
-        r.nxy = (d.x < 0.0f ? 16u : 0u) + (d.y < 0.0f ? 32u : 0u);
-        r.fxy = 48u - r.nxy;
-        r.zo = d.z < 0.0f ? 80u : 64u;
+        r.sets = ((d.x < 0.0f ? 16u : 0u) + (d.y < 0.0f ? 32u : 0u)) | (d.z < 0.0f ? 80u << 8 : 64u << 8);
     } else {
         r.nx = d.x < 0.0f ? 48u : 0u;
         r.ny = d.y < 0.0f ? 64u : 16u;
@@ -263,8 +264,9 @@ __device__ __forceinline__ void node_step(const float4* __restrict__ nodes, uint
     const uint32_t base = cur << 7;
     const float INF = __builtin_inff();
     if constexpr (H) {
-        const uint4 na = *reinterpret_cast<const uint4*>(nb + (base + r.nxy)), fa = *reinterpret_cast<const uint4*>(nb + (base + r.fxy));
-        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + r.zo));
+        const uint32_t nxy = r.sets & 0xFFu;
+        const uint4 na = *reinterpret_cast<const uint4*>(nb + (base + nxy)), fa = *reinterpret_cast<const uint4*>(nb + (base + (nxy ^ 48u)));
+        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + (r.sets >> 8)));
         const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
         const float4 og = *reinterpret_cast<const float4*>(nb + (base + 112u));
         c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;

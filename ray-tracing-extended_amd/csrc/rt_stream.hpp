@@ -70,12 +70,15 @@ static_assert(offsetof(StreamCamKernArgs, A) == offsetof(StreamKernArgs, A)
               && offsetof(StreamCamKernArgs, cams) == ((offsetof(StreamCamKernArgs, A) + sizeof(StreamArgs) + 7) & ~size_t(7)), "kernarg layout = struct layout");
 
 #ifndef RT_STREAM_WAVES
-#define RT_STREAM_WAVES 6           // waves per SIMD of the PCG / f16-node instantiation (see below)
+#define RT_STREAM_WAVES 7           // waves per SIMD of the PCG / f16-node instantiation (see below; 6 and 5 still build: -DRT_STREAM_WAVES=)
 #endif
 #ifndef RT_STREAM_WAVES_PHILOX
 #define RT_STREAM_WAVES_PHILOX 5    // (six waves = 80 VGPRs: 34 of them spilled, 13.9 against 16.9 Grays/s — round 4, one box, interleaved)
 #endif
 constexpr int stream_waves(bool count, bool philox, bool h, bool tri) { return count ? 3 : !tri ? 6 : philox ? RT_STREAM_WAVES_PHILOX : !h ? 5 : RT_STREAM_WAVES; }     // (counting build: 47 counters in registers)
+// Which instantiation holds how many: PCG / f16 nodes seven (72 VGPRs); PCG / f32 nodes five (94) and Philox with triangles five (96): the register
+// diet below does not bring either under 80 without scratch; the sphere-only ones six as before (PCG 75; Philox 80, of which k_stream keeps one
+// spilled VGPR, 8 B of scratch — measured with it: 32.6 -> 35.1 Grays/s against five waves, see below — and k_cam_stream none).
 
 
 // Waves per SIMD.  The kernel hides its memory and LDS latencies with resident waves.  Round 2 chose five (96 VGPRs; six = 80 VGPRs spilled
@@ -84,7 +87,13 @@ constexpr int stream_waves(bool count, bool philox, bool h, bool tri) { return c
 // entries per lane, so that six workgroups fit a CU — measure 18.3 against 17.1 Grays/s at five on the 100k-triangle workload, 16.2
 // against 15.1 on the million-triangle one (seven: 72 VGPRs + 5 dwords of scratch, 17.2; eight: 15.1).  The Philox instantiation spills
 // at 80 VGPRs (14 dwords: 13.1 against 15.8 Grays/s) and stays at five, like the f32-node and the counting instantiations.
-// TRI = false: the instantiation for scenes without triangles (spheres only) — no traversal state, no burst; 76 / 86 VGPRs (PCG / Philox),
+// Seven waves: 72 VGPRs and NO scratch, since three per-lane registers went away — the f16 slab keeps its three node offsets in one
+// register (RaySlabT<true>::sets, rt_kernels.hpp: one more VALU per node step) and bounce shares `sample`'s register in the PCG
+// instantiations as it always did in the Philox ones.  Seven workgroups per CU need an LDS stack of <= 21 entries per lane (7 x 22,016 B
+// of the 160 KiB); the stack guard is a scalar test while no lane can be near the end of that part (`ub`, rt_stream_body.hpp).  One box,
+// five interleaved pairs, 16 frames each (profiles/ab_seven_waves.txt): 20.65-20.76 against 19.76-19.94 Grays/s at six on the 100k-triangle
+// workload (+4.2 %), 17.9 against 17.3 on the million-triangle one (medians; its runs scatter more at seven).
+// TRI = false: the instantiation for scenes without triangles (spheres only) — no traversal state, no burst; 75 / 86 VGPRs by itself (PCG / Philox),
 // compiled for six waves per SIMD: 36.4 -> 39.3 (PCG; k_trace's sphere instantiation stays ahead at 41.7) and 32.6 -> 35.1 Grays/s (Philox)
 // on the sphere workload, eight waves (64 VGPRs, scratch): 37.6 / 29.7.
 template <bool COUNT, bool PHILOX = false, bool H = false, bool TRI = true>

@@ -19,12 +19,18 @@
     uint32_t top = stk0;
     auto slot = [](uint32_t a) -> lds_u32& { return *reinterpret_cast<lds_u32*>((uintptr_t)a); };
     const uint32_t capb = (uint32_t)cap << 8;
-    // pop: plain ds_read when nothing can spill (wave-uniform test); otherwise an LDS read from a clamped slot, replaced by
+    // With a spill part the wave keeps a bound on how deep any of its lanes can be: top - stk0 <= ub for all 64 lanes, in a scalar
+    // register.  A node step adds three entries to it (its pushes), SHADE's list set-up starts a query at three at most, pops are not
+    // followed.  While ub stays within the LDS part the pushes and pops are the plain ones under a scalar branch; when it gets
+    // there the node loop looks at the real depths (one or two ballots over the whole wave, `tighten` below) and only a wave with a
+    // lane that really is within three entries of the LDS part takes the checked forms.
+    uint32_t ub = 0u;
+    // pop: plain ds_read when nothing can have spilled (wave-uniform test); otherwise an LDS read from a clamped slot, replaced by
     // the global entry for the rare lane above the LDS part (a select between the two address spaces would turn every pop
     // into a flat load)
     auto pop = [&]() -> uint32_t {
         top -= 256u;
-        if (gstk == nullptr) return slot(top);
+        if (gstk == nullptr || ub <= capb) return slot(top);
         RT_RARE_PATH();
         const uint32_t depth = top - stk0;
         uint32_t v = slot(stk0 + min(depth, capb - 256u));
@@ -53,8 +59,8 @@
     uint32_t pxy = kNoPixel;            // current pixel: x | local row << 16 (the host keeps k_stream to targets of at most 65535 x 65535); kNoPixel: none
     uint32_t rng = 0u;                  // RT_RNG_PCG: the reference's stream, a serial chain through the pixel's samples and bounces.  RT_RNG_PHILOX keeps
                                         // no generator state at all: a draw is a function of (pixel, frame, sample, bounce) — rtm::PhiloxScope
-    int sample = 0, bounce = 0;         // PCG.  PHILOX keeps both in `sample` (sample | bounce << 16: the host refuses more than 65000 samples or 32000 bounces, so the signed shift stays positive) — the
-                                        // generator's temporaries need the register in the scatter code
+    int sample = 0;                     // sample | bounce << 16 in one register (k_stream takes at most 65000 samples and 32000 bounces, rt_api.hip plan_launch:
+                                        // the signed shift stays positive)
     v3 total = rtm::mk(0.f, 0.f, 0.f), light = total, rayColour = total, o = total, d = total;
     RaySlabT<H> slab = make_slab<H>(rtm::mk(0.f, 0.f, 0.f), rtm::mk(1.f, 1.f, 1.f));
     uint32_t cur = kNone;
@@ -304,7 +310,7 @@
                             float cx = mod2(__builtin_floorf(hitPoint.x)), cz = mod2(__builtin_floorf(hitPoint.z));
                             if (!(cx == cz)) colour = rtm::mk(memi.x, memi.y, memi.z);
                             RT_REGION_END(hit_checker);
-                        } else if (flag == 2 && (PHILOX ? (sample >> 16) : bounce) == 0) {   // InvisibleLightSource :318-322
+                        } else if (flag == 2 && (sample >> 16) == 0) {   // InvisibleLightSource :318-322
                             o = hitPoint + d * 0.001f;
                             skip = true;
                         }
@@ -332,12 +338,12 @@
                             } else scatter(rng);
                             RT_REGION_END(hit_scatter);
                         }
-                        if constexpr (PHILOX) { sample += 0x10000; if ((sample >> 16) > p.maxBounceCount) path_done = true; }
-                        else { ++bounce; if (bounce > p.maxBounceCount) path_done = true; }   // loop bound :305
+                        sample += 0x10000;
+                        if ((sample >> 16) > p.maxBounceCount) path_done = true;               // loop bound :305
                         RT_REGION_END(hit);
                     } else {
                         RT_REGION_BEGIN(env);
-#if !defined(RT_DIAG_IDLE) && !defined(RT_DIAG_PRIMARY) && !defined(RT_DIAG_TOP)
+#if !defined(RT_DIAG_IDLE) && !defined(RT_DIAG_PRIMARY) && !defined(RT_DIAG_TOP) && !defined(RT_DIAG_STACK)
                         phase_tick<COUNT>(cnt, 3);
 #endif
                         light = light + environment_light(p, d) * rayColour;           // :346-347
@@ -346,7 +352,7 @@
                     }
                     if (path_done) {
                         total = total + light;                                         // :384
-                        if constexpr (PHILOX) sample = (sample & 0xFFFF) + (1 << A.sample_lanes_log2); else ++sample;       // (Philox: next sample of the sub-stream, bounce 0)
+                        sample = (sample & 0xFFFF) + (PHILOX ? 1 << A.sample_lanes_log2 : 1);        // bounce 0 of the next sample (Philox: of the sub-stream)
                         if (PHILOX && sample >= p.numRaysPerPixel) {
                             // ---- this unit (one sub-stream of a pixel) is complete: park its sum (the wave adds the sub-streams up when the
                             // group is done) and ask for the next unit
@@ -420,7 +426,7 @@
                     if (need_ray) {
                         // ---- frag :364-382
                         RT_REGION_BEGIN(camera);
-#if !defined(RT_DIAG_IDLE) && !defined(RT_DIAG_PRIMARY) && !defined(RT_DIAG_TOP)
+#if !defined(RT_DIAG_IDLE) && !defined(RT_DIAG_PRIMARY) && !defined(RT_DIAG_TOP) && !defined(RT_DIAG_STACK)
                         phase_tick<COUNT>(cnt, 4);
 #endif
                         Camera cam;
@@ -481,7 +487,7 @@
                             camera_ray(p, cam, R, o, d, F.fixed_origin != 0);
                         } else camera_ray(p, cam, rng, o, d, F.fixed_origin != 0);
                         }   // (CAMS)
-                        if constexpr (PHILOX) sample &= 0xFFFF; else bounce = 0;
+                        sample &= 0xFFFF;
                         rayColour = rtm::mk(1.f, 1.f, 1.f); light = rtm::mk(0.f, 0.f, 0.f);
                         RT_REGION_END(camera);
                     }
@@ -526,6 +532,7 @@
                     }
                 }
             }
+            ub = max(ub, 768u);             // (setup_list: a new query starts with up to three entries)
             RT_REGION_END(shade);
         } else {
             // ================================ TRAVERSAL BURST ================================
@@ -550,6 +557,26 @@
                         if (lane == 0) { cnt.phase_execs[3]++; cnt.phase_execs[4]++; }
                     }
 #endif
+                    // the pushes of this step: plain while no lane of the wave can reach the end of the LDS part with them
+                    bool plain = true;
+                    if (gstk != nullptr) {
+                        if (ub + 768u > capb) {
+                            // tighten: ub only ever grows, the lanes' real depths (all 64: this is wave-uniform control flow) are mostly far
+                            // below it.  No lane above `low` = three more steps of plain pushes; else no lane within three entries = this one
+                            RT_QUARTER_PATH();
+                            const uint32_t depth = top - stk0, low = capb > 2304u ? capb - 2304u : 0u;
+#ifdef RT_DIAG_STACK     // diagnostic build only (tools/diag_stack.py): counters 3 / 4 re-used.  execs[3] = iterations that tightened the bound, lanes[4] = of those, the
+                         // ones that needed the second ballot; lanes[3] = deepest stack of any lane (a maximum: see the epilogue); execs[4] = node steps in which a
+                         // lane at a node is within three entries of the LDS part (the guard this bound replaces: one ballot on every node step)
+                            if (COUNT) { const bool above_ = ballot_(depth > low) != 0; if (lane == 0) { cnt.phase_execs[3]++; if (above_) cnt.phase_lanes[4]++; } }
+#endif
+                            if (ballot_(depth > low) == 0) ub = low;
+                            else if (ballot_(depth + 768u > capb) == 0) ub = capb - 768u;
+                            else ub = min(ub, 0x40000000u);
+                        }
+                        plain = ub + 768u <= capb;
+                        ub += 768u;         // (after this step; its pops read ub as it is now)
+                    }
                     if ((int)cur >= 0) {
                         RT_REGION_BEGIN(node);
                         if (COUNT) cnt.nodes++;
@@ -561,18 +588,22 @@
                         if (COUNT && ballot_(cur >= 4u * RT_DIAG_TOP + 1u) == 0ull && (unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[4]++;
 #endif
 #ifdef RT_DIAG_PRIMARY   // diagnostic build only (tools/diag_primary.py): node steps / triangle tests of camera rays (bounce 0) in counters 3 / 4; execs = steps with any such lane
-                        if (COUNT && (PHILOX ? (sample >> 16) : bounce) == 0) { cnt.phase_lanes[3]++; if ((unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[3]++; }
+                        if (COUNT && (sample >> 16) == 0) { cnt.phase_lanes[3]++; if ((unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[3]++; }
 #endif
                         float t0, t1, t2, t3;
                         uint32_t c0, c1, c2, c3;
                         node_step<H>(H ? S.nodes_h : S.nodes, cur, slab, best.t, F.full_sort != 0, t0, t1, t2, t3, c0, c1, c2, c3);
-                        if (gstk == nullptr || ((void)RT_RARE_PATH_EXPR(), ballot_(top - stk0 + 768u > capb) == 0)) {
+#ifdef RT_DIAG_STACK
+                        if (COUNT && gstk != nullptr && ballot_(top - stk0 + 768u > capb) != 0 && (unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[4]++;
+#endif
+                        if (plain) {
                             // branch-free push of the three farther children (far -> near); slots past the new top are garbage
                             slot(top) = c3; top = (t3 < INF) ? top + 256u : top;
                             slot(top) = c2; top = (t2 < INF) ? top + 256u : top;
                             slot(top) = c1; top = (t1 < INF) ? top + 256u : top;
                         } else {
-                            // some lane is within three entries of the LDS part: checked pushes, spilling past it
+                            // some lane of the wave is within three entries of the LDS part: checked pushes, spilling past it
+                            RT_RARE_PATH();
                             RT_REGION_BEGIN(node_spill);
                             auto push = [&](uint32_t c) {
                                 const uint32_t depth = top - stk0;
@@ -584,6 +615,11 @@
                             if (t1 < INF) push(c1);
                             RT_REGION_END(node_spill);
                         }
+#ifdef RT_DIAG_STACK
+                        if (COUNT) {
+                            cnt.phase_lanes[3] = max(cnt.phase_lanes[3], (top - stk0) >> 8);
+                        }
+#endif
                         if (t0 < INF) cur = c0;
                         else {
                             RT_REGION_BEGIN(node_pop);
@@ -608,7 +644,7 @@
                         if (COUNT) cnt.tris++;
                         phase_tick<COUNT>(cnt, 1);
 #ifdef RT_DIAG_PRIMARY
-                        if (COUNT && (PHILOX ? (sample >> 16) : bounce) == 0) { cnt.phase_lanes[4]++; if ((unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[4]++; }
+                        if (COUNT && (sample >> 16) == 0) { cnt.phase_lanes[4]++; if ((unsigned)__builtin_ctzll(ballot_(true)) == (unsigned)lane) cnt.phase_execs[4]++; }
 #endif
                         const bool hit = ray_triangle(o, d, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y),
                                                       rtm::mk(g1.z, g1.w, g2.x), rtm::mk(g2.y, g2.z, g2.w), dst, u, v);
@@ -657,6 +693,13 @@
         for (int k = 0; k < kNumRegions; ++k) v[15 + k] = cnt.region[k];
         for (int k = 0; k < (COUNT ? kNumCounters : 1); ++k) {
             unsigned long long s = v[k];
+#ifdef RT_DIAG_STACK
+            if (k == 8) {       // phase_lanes[3]: a maximum over the lanes and waves of the launch
+                for (int off = 32; off > 0; off >>= 1) s = max(s, (unsigned long long)__shfl_down(s, off, 64));
+                if (lane == 0) atomicMax(&fresh_kernargs<StreamKernArgs>().F.counters[k], s);
+                continue;
+            }
+#endif
             for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
             if (lane == 0) atomicAdd(&fresh_kernargs<StreamKernArgs>().F.counters[k], s);     // (read here: not held across the persistent loop)
         }

@@ -101,8 +101,16 @@ def count(lines, marked):
         cur["lines"].append(t)
     blocks.append(cur)
     # cold blocks
-    prev_skip = None
+    prev_skip = prev_any = None
     for i, b in enumerate(blocks):
+        # RTQUARTER: a block that runs in one of four executions of its region by construction (the stack bound's tightening, rt_stream_body.hpp;
+        # measured 25.5 % / 28.2 % of node-loop iterations, profiles/stack_depth.txt): a quarter of its instructions are the region's, the rest cold
+        if any(t.startswith("; RTQUARTER") for t in b["lines"]):
+            b["weight"] = 0.25
+            ahead = [blocks[j]["label"] for j in range(i + 1, min(i + 8, len(blocks)))]
+            if prev_any in ahead:
+                for j in range(i + 1, i + 1 + ahead.index(prev_any)):
+                    blocks[j]["weight"] = 0.25
         if not b.get("cold") and any(t.startswith(("; RTCOLD", "; RTRARE")) for t in b["lines"]):
             b["cold"] = True
             # the skip branch that ends the block in front names the join label: cold up to it when it follows within a few blocks
@@ -113,6 +121,8 @@ def count(lines, marked):
         code = [t for t in b["lines"] if not t.startswith((";", "."))]
         m = re.match(r"^s_cbranch_exec\w*\s+(\.LBB\d+_\d+)", code[-1]) if code else None
         prev_skip = m.group(1) if m else None
+        m = re.match(r"^s_cbranch_\w+\s+(\.LBB\d+_\d+)", code[-1]) if code else None
+        prev_any = m.group(1) if m else None               # (the tightening sits behind a scalar branch)
     # option regions — code behind a branch that is uniform for the whole launch (depth of field, spheres, sun, no cached focus points, the
     # stack's spill path, pixel-by-pixel refill): the assembler comment can sit anywhere inside its block, so these are attributed by
     # whole blocks, from the block that holds the `begin` comment to the label the branch in front of that block jumps to
@@ -178,7 +188,10 @@ def count(lines, marked):
             r = b.get("option") or whole or lead or stack[-1]
             if r == "loop" and not b.get("in_loop"):            # straight-line code outside the persistent loop: before it or after it
                 r = "epilogue" if b.get("after_loop") else "prologue"
-            (cold if b.get("cold") else regions[r])[k] += 1
+            w = 1 if b.get("cold") else b.get("weight", 1)
+            (cold if b.get("cold") else regions[r])[k] += w
+            if w != 1:
+                cold[k] += 1 - w
             if k == "valu" and DETAIL is not None:
                 key = ("cold" if b.get("cold") else r, b["label"])
                 DETAIL[key] = DETAIL.get(key, 0) + 1

@@ -55,8 +55,9 @@ __device__ __forceinline__ void node_step4(const float4* __restrict__ nodes, uin
     const char* nb = reinterpret_cast<const char*>(nodes);
     const uint32_t base = cur << 7;
     const float INF = __builtin_inff();
-    const uint4 na = *reinterpret_cast<const uint4*>(nb + (base + r.nxy)), fa = *reinterpret_cast<const uint4*>(nb + (base + r.fxy));
-    const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + r.zo));
+    const uint32_t nxy = r.sets & 0xFFu;
+    const uint4 na = *reinterpret_cast<const uint4*>(nb + (base + nxy)), fa = *reinterpret_cast<const uint4*>(nb + (base + (nxy ^ 48u)));
+    const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + (r.sets >> 8)));
     const uint4 hd = *reinterpret_cast<const uint4*>(nb + (base + 112u));
     const uint32_t d0 = hd.w & ~3u;
     c0 = hd.w; c1 = d0 + (hd.x & 0xFFu); c2 = d0 + (hd.y & 0xFFu); c3 = d0 + (hd.z & 0xFFu);
