@@ -456,6 +456,65 @@ int rt_copy_aov_to_device(rt_ctx* ctx, int which, void* dst_device_ptr, size_t n
 int rt_reset_aov(rt_ctx* ctx);
 int rt_get_aov_info(rt_ctx* ctx, rt_aov_info* out);
 
+/* ---- denoiser: an edge-avoiding A-trous wavelet filter guided by the feature buffers --------------------------------------
+ * rt_denoise filters the context's current resultTexture into a further RGBA32F plane, the denoised plane, guided by the context's
+ * current feature planes: the step between resultTexture and the display blit.  The reference has no such step (its resultTexture goes
+ * to the screen as it is, RayTracingManager.cs:84); the definition below is this library's: the edge-avoiding A-trous wavelet transform
+ * of Dammertz et al. (HPG 2010) with albedo demodulation, frozen to the bit.  All arithmetic is IEEE float32 without FMA contraction,
+ * every '/' a correctly rounded quotient, exp2_ the polynomial of csrc/rt_math.hpp (rtm::exp2_).  Per pixel p, with C = resultTexture
+ * (rgb, a), A = plane RT_AOV_ALBEDO (albedo.rgb, coverage), G = plane RT_AOV_NORMAL_DEPTH (n.xyz, z):
+ *
+ *   demodulate    cov1 = 1.0f - A.w; per channel d = max(A.ch + cov1, 0.01f) and e0.ch = C.ch / d: the sky part of a pixel counts as
+ *                 albedo 1.  With demodulate == 0, d = 1 and e0 = C.rgb.
+ *   constants     kn = 1.0f / (sigmaNormal * sigmaNormal), kz = 1.0f / (sigmaDepth * sigmaDepth),
+ *                 kc_i = (1.0f / (sigmaColour * sigmaColour)) * (float)(1 << (2 * i)): the colour sigma halves every pass, as in the
+ *                 paper; per pixel zs = kz / (G_p.w * G_p.w + 1e-6f): the depth difference is relative to the centre's depth.
+ *   pass i        for i = 0 .. iterations - 1, with step s = 1 << i: the taps q = p + (dx * s, dy * s), dy = -2..2 outer, dx = -2..2
+ *                 inner, in that order; a tap outside the image is skipped, not clamped.  Per tap
+ *                     dn2 = (dnx*dnx + dny*dny) + dnz*dnz        (dn = G_p.xyz - G_q.xyz)
+ *                     dz  = G_p.w - G_q.w
+ *                     dc2 = (dcx*dcx + dcy*dcy) + dcz*dcz        (dc = e_i(p) - e_i(q))
+ *                     x   = (dn2*kn + (dz*dz)*zs) + dc2*kc_i
+ *                     w   = (h[dy+2] * h[dx+2]) * exp2_(-x)         h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *                 accumulated in tap order: sw = sw + w, s.ch = s.ch + w * e_i(q).ch; then e_{i+1}(p).ch = s.ch / sw.  The centre tap
+ *                 has x = 0, so sw >= 9/64.
+ *   output        out.ch = e_last.ch * d per channel, out.a = C.a.
+ *
+ * Non-finite inputs give whatever this arithmetic gives; the call does not fault on them.
+ * rt_denoise settles the queue, runs on the context's stream (rt_set_stream) and moves nothing else: resultTexture, currentFrame,
+ * numRenderedFrames, the feature planes, rt_aov_info and every rt_stats field stay.  It needs the whole image in one context: a context
+ * that rt_set_rows / rt_set_bands has given less returns -2 (use rt_multi_denoise).  The work planes and the denoised plane are created
+ * at first use and again when the image size changes.  params == NULL means the defaults: iterations 5 and the values of
+ * RT_DENOISE_DEFAULT_* (chosen by the sweep of profiles/denoise_defaults.txt).
+ * Errors: null handle -1; no params set, no feature frame accumulated (rt_aov_info.framesAccumulated == 0), iterations outside 1..6,
+ * demodulate neither 0 nor 1, a sigma that is <= 0 or not finite, a wrong n_floats / n_pixels, a null buffer, a read before any
+ * rt_denoise: -2 with a message, and nothing changed.                                                                             */
+typedef struct rt_denoise_params {      /* 32 B */
+    int32_t iterations;                 /* 1..6; pass i uses tap spacing 2^i                                                */
+    int32_t demodulate;                 /* 0 / 1                                                                            */
+    float   sigmaColour, sigmaNormal, sigmaDepth;   /* each finite and > 0                                                  */
+    int32_t _reserved[3];
+} rt_denoise_params;
+#define RT_DENOISE_DEFAULT_ITERATIONS   5
+#define RT_DENOISE_DEFAULT_DEMODULATE   0
+#define RT_DENOISE_DEFAULT_SIGMA_COLOUR 16.0f
+#define RT_DENOISE_DEFAULT_SIGMA_NORMAL 1.0f
+#define RT_DENOISE_DEFAULT_SIGMA_DEPTH  0.5f
+typedef struct rt_denoise_info {        /* 32 B */
+    int32_t iterations;                 /* of the last call                                                                 */
+    int32_t demodulate;                 /* of the last call                                                                 */
+    int32_t width, height;
+    double  lastKernelMs;               /* HIP-event time of the last call's launches                                       */
+    double  totalKernelMs;
+} rt_denoise_info;
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
+/* the denoised plane: height*width*4 floats, row 0 = bottom (rt_read_accum's layout for a whole image) */
+int rt_read_denoised(rt_ctx* ctx, float* rgba, size_t n_floats);
+int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device_ptr, size_t n_floats);
+/* the display step of rt_read_display applied to the denoised plane (height*width pixels) */
+int rt_read_denoised_display(rt_ctx* ctx, uint32_t* rgba8, size_t n_pixels);
+int rt_get_denoise_info(rt_ctx* ctx, rt_denoise_info* out);
+
 /* ---- several GPUs of one node behind one handle ---------------------------------------------------------------------
  * The reference renders on one GPU; its path shards into independent pixels (seed = global pixel index + Frame * 719393,
  * RayTracing.shader:360-362; Accumulate.shader is per pixel), so the frame tiles across devices by rows.  An rt_multi owns one
@@ -520,10 +579,16 @@ int rt_multi_occluded        (rt_multi* m, const rt_ray* rays, int n, uint8_t* o
 int rt_multi_render_aov      (rt_multi* m, int first_frame, int n_frames);
 int rt_multi_read_aov        (rt_multi* m, int which, float* rgba, size_t n_floats);
 int rt_multi_reset_aov       (rt_multi* m);
+/* The denoiser behind the handle: the accumulated strips and the strips of both feature planes are gathered to the first device (the
+ * gather of rt_multi_render) and the filter of rt_denoise runs there, on the first context's stream — bitwise the single-context result.
+ * Every context must hold at least one feature frame.  Per-context state is left alone.                                            */
+int rt_multi_denoise              (rt_multi* m, const rt_denoise_params* params);
+int rt_multi_read_denoised        (rt_multi* m, float* rgba, size_t n_floats);
+int rt_multi_read_denoised_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" */
 
 #ifdef __cplusplus
 }

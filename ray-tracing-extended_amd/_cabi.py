@@ -59,7 +59,16 @@ assert RAY.itemsize == 32 and HIT.itemsize == 64
 # feature buffers (rt_render_aov): the two planes and the state of their accumulation
 RT_AOV_ALBEDO, RT_AOV_NORMAL_DEPTH, RT_AOV_COUNT = 0, 1, 2
 AOV_INFO = np.dtype([("framesAccumulated", "<i4"), ("lastSampleLanes", "<i4"), ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+# denoiser (rt_denoise): the parameters of a call and the state of the last one
+DENOISE_PARAMS = np.dtype([("iterations", "<i4"), ("demodulate", "<i4"), ("sigmaColour", "<f4"), ("sigmaNormal", "<f4"), ("sigmaDepth", "<f4"),
+                           ("_reserved", "<i4", 3)])
+DENOISE_INFO = np.dtype([("iterations", "<i4"), ("demodulate", "<i4"), ("width", "<i4"), ("height", "<i4"),
+                         ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert DENOISE_PARAMS.itemsize == 32 and DENOISE_INFO.itemsize == 32
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
+
+# RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
+DENOISE_DEFAULTS = {"iterations": 5, "demodulate": 0, "sigmaColour": 16.0, "sigmaNormal": 1.0, "sigmaDepth": 0.5}
 
 RT_INTERSECT_FLAT_CHUNKS = 0
 RT_INTERSECT_BRUTE = 1
@@ -79,6 +88,8 @@ SYMBOLS = [
     "rt_trace_rays", "rt_occluded", "rt_trace_rays_device", "rt_occluded_device", "rt_multi_trace_rays", "rt_multi_occluded",
     "rt_render_aov", "rt_read_aov", "rt_copy_aov_to_device", "rt_reset_aov", "rt_get_aov_info",
     "rt_multi_render_aov", "rt_multi_read_aov", "rt_multi_reset_aov",
+    "rt_denoise", "rt_read_denoised", "rt_copy_denoised_to_device", "rt_read_denoised_display", "rt_get_denoise_info",
+    "rt_multi_denoise", "rt_multi_read_denoised", "rt_multi_read_denoised_display",
 ]
 
 _lib = None
@@ -165,6 +176,14 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_render_aov.argtypes = [c_void_p, c_int, c_int]
     lib.rt_multi_read_aov.argtypes = [c_void_p, c_int, POINTER(c_float), c_size_t]
     lib.rt_multi_reset_aov.argtypes = [c_void_p]
+    lib.rt_denoise.argtypes = [c_void_p, c_void_p]
+    lib.rt_read_denoised.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_copy_denoised_to_device.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_read_denoised_display.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_get_denoise_info.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_denoise.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_read_denoised.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_multi_read_denoised_display.argtypes = [c_void_p, c_void_p, c_size_t]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -174,7 +193,8 @@ def load_library() -> ctypes.CDLL:
     for name, dt in (("rt_material", MATERIAL), ("rt_sphere", SPHERE), ("rt_triangle", TRIANGLE),
                      ("rt_meshinfo", MESHINFO), ("rt_params", PARAMS), ("rt_stats", STATS),
                      ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO),
-                     ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO)):
+                     ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO),
+                     ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -204,6 +224,21 @@ def _query_host(call, handle, rays, any_hit: bool, check, what):
     out = np.zeros(r.shape[0], np.uint8) if any_hit else np.zeros(r.shape[0], HIT)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
     return out
+
+
+def _denoise_params(params: dict):
+    """None (the library's defaults) when no field is given; else a DENOISE_PARAMS record: the defaults of include/rt.h with the given
+    fields (iterations, demodulate, sigmaColour, sigmaNormal, sigmaDepth) replaced"""
+    if not params:
+        return None
+    p = np.zeros((), DENOISE_PARAMS)
+    for k, v in DENOISE_DEFAULTS.items():
+        p[k] = v
+    for k, v in params.items():
+        if k not in DENOISE_DEFAULTS:
+            raise TypeError(f"denoise: unknown parameter {k!r} (one of {sorted(DENOISE_DEFAULTS)})")
+        p[k] = v
+    return p
 
 
 def _as_buffer(arr, dtype):
@@ -450,6 +485,37 @@ class Tracer:
         self._check(self._lib.rt_get_aov_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_aov_info")
         return {k: s[k].item() for k in AOV_INFO.names}
 
+    # -- denoiser
+    def denoise(self, **params):
+        """rt_denoise: filter resultTexture, guided by the feature planes, into the denoised plane.  Keywords: iterations, demodulate,
+        sigmaColour, sigmaNormal, sigmaDepth; none = the library's defaults."""
+        p = _denoise_params(params)
+        self._check(self._lib.rt_denoise(self._ctx, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_denoise")
+
+    def _image_shape(self):
+        return int(self._params["height"]), int(self._params["width"])
+
+    def read_denoised(self) -> np.ndarray:
+        H, W = self._image_shape()
+        out = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.rt_read_denoised(self._ctx, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_read_denoised")
+        return out
+
+    def read_denoised_display(self) -> np.ndarray:
+        """the denoised plane as sRGB RGBA8, shape (H, W, 4) uint8, row 0 = bottom"""
+        H, W = self._image_shape()
+        out = np.empty((H, W), np.uint32)
+        self._check(self._lib.rt_read_denoised_display(self._ctx, out.ctypes.data_as(c_void_p), out.size), "rt_read_denoised_display")
+        return out.view(np.uint8).reshape(H, W, 4)
+
+    def copy_denoised_to_device(self, device_ptr: int, n_floats: int):
+        self._check(self._lib.rt_copy_denoised_to_device(self._ctx, c_void_p(device_ptr), n_floats), "rt_copy_denoised_to_device")
+
+    def denoise_info(self) -> dict:
+        s = np.zeros((), DENOISE_INFO)
+        self._check(self._lib.rt_get_denoise_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_denoise_info")
+        return {k: s[k].item() for k in DENOISE_INFO.names}
+
     def stats(self) -> dict:
         s = np.zeros((), STATS)
         self._check(self._lib.rt_get_stats(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_stats")
@@ -580,6 +646,33 @@ class MultiTracer:
                 raise RtError(f"rt_get_aov_info on context {i} failed ({rc})")
             out.append({k: s[k].item() for k in AOV_INFO.names})
         return out
+
+    # -- denoiser
+    def denoise(self, **params):
+        """rt_multi_denoise: image and feature planes gathered to the first device, Tracer.denoise's filter there."""
+        p = _denoise_params(params)
+        self._check(self._lib.rt_multi_denoise(self._m, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_multi_denoise")
+        self._denoise_last = dict(DENOISE_DEFAULTS, **params)
+
+    def read_denoised(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.rt_multi_read_denoised(self._m, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_denoised")
+        return out
+
+    def read_denoised_display(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W), np.uint32)
+        self._check(self._lib.rt_multi_read_denoised_display(self._m, out.ctypes.data_as(c_void_p), out.size), "rt_multi_read_denoised_display")
+        return out.view(np.uint8).reshape(H, W, 4)
+
+    def denoise_info(self) -> dict:
+        """the parameters of the last denoise() and the image size (the C-ABI keeps kernel times per context only)"""
+        last = getattr(self, "_denoise_last", None)
+        if last is None:
+            return {"iterations": 0, "demodulate": 0, "width": 0, "height": 0}
+        H, W = self._shape
+        return {"iterations": int(last["iterations"]), "demodulate": int(last["demodulate"]), "width": W, "height": H}
 
     def stats(self) -> dict:
         s = np.zeros((), STATS)

@@ -31,6 +31,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_primary.hpp"
 #include "rt_query.hpp"
 #include "rt_aov.hpp"
+#include "rt_denoise.hpp"
 
 namespace {
 
@@ -54,6 +55,15 @@ template <class T> struct DevBuf {
         return e;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; used = 0; }
+};
+
+// the denoiser's planes for one image size (rt_denoise, csrc/rt_denoise.hpp): e_i ping and pong, (d.rgb, C.a), the denoised plane
+struct DenoisePlanes {
+    DevBuf<float4> e[2], d, out;
+    int w = 0, h = 0;
+    bool filled = false;            // `out` holds the result of a call
+    rt_denoise_info info{};
+    void release() { e[0].release(); e[1].release(); d.release(); out.release(); w = h = 0; filled = false; }
 };
 
 } // namespace
@@ -170,6 +180,8 @@ struct rt_ctx {
     size_t aov_pixels = 0;
     int aov_w = 0, aov_h = 0, aov_row0 = 0, aov_rows = 0, aov_row_stride = 8;
     rt_aov_info aov{};
+    DenoisePlanes dn;                   // rt_denoise
+    hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
     rt_stats stats{};
 
     // ---- queued submission (rt_submit_frame / rt_wait): frames handed in one by one — the reference's OnRenderImage pattern,
@@ -1356,6 +1368,109 @@ int read_aov(rt_ctx* c, int which, void* dst, size_t n_floats, bool to_device)
     return 0;
 }
 
+// ---- denoiser (rt_denoise, csrc/rt_denoise.hpp) -----------------------------------------------------------------------------------
+static_assert(sizeof(rt_denoise_params) == 32 && sizeof(rt_denoise_info) == 32, "denoiser ABI");
+
+// the parameters of a call: the caller's, or the defaults; nullptr (and a message) when they are out of range
+const char* denoise_params(const rt_denoise_params* in, rt_denoise_params& P)
+{
+    if (in) P = *in;
+    else {
+        P = rt_denoise_params{};
+        P.iterations = RT_DENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_DENOISE_DEFAULT_DEMODULATE;
+        P.sigmaColour = RT_DENOISE_DEFAULT_SIGMA_COLOUR; P.sigmaNormal = RT_DENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_DENOISE_DEFAULT_SIGMA_DEPTH;
+    }
+    if (P.iterations < 1 || P.iterations > 6) return "iterations outside 1..6";
+    if (P.demodulate != 0 && P.demodulate != 1) return "demodulate is neither 0 nor 1";
+    for (float sg : { P.sigmaColour, P.sigmaNormal, P.sigmaDepth })
+        if (!std::isfinite(sg) || !(sg > 0.0f)) return "a sigma is not finite or not > 0";
+    return nullptr;
+}
+
+// The filter: C (resultTexture), A and G (the feature planes), all W x H float4 on the current device -> D.out, on `stream`, timed by
+// ev0 / ev1 and waited for.  Shared by rt_denoise and rt_multi_denoise; P has passed denoise_params.
+hipError_t run_denoise(DenoisePlanes& D, const float4* C, const float4* A, const float4* G, int W, int H, const rt_denoise_params& P,
+                       hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const size_t px = (size_t)W * H;
+    hipError_t e;
+    if (D.w != W || D.h != H || !D.out.p) {
+        for (DevBuf<float4>* b : { &D.e[0], &D.e[1], &D.d, &D.out }) if ((e = b->ensure(px)) != hipSuccess) return e;
+        D.w = W; D.h = H; D.filled = false; D.info.totalKernelMs = 0;
+    }
+    float ms = 0.f;
+    if (px) {
+        const float kn = 1.0f / (P.sigmaNormal * P.sigmaNormal), kz = 1.0f / (P.sigmaDepth * P.sigmaDepth);
+        const float kc0 = 1.0f / (P.sigmaColour * P.sigmaColour);
+        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(rtk::k_denoise_prep, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, C, A, D.e[0].p, D.d.p, px, P.demodulate);
+        const dim3 grid((W + rtk::kDenoiseTileW - 1) / rtk::kDenoiseTileW, (H + rtk::kDenoiseTileH - 1) / rtk::kDenoiseTileH);
+        for (int i = 0; i < P.iterations; ++i) {
+            const bool last = i == P.iterations - 1;
+            rtk::AtrousArgs a{};
+            a.e_in = D.e[i & 1].p; a.guide = G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[(i + 1) & 1].p;
+            a.W = W; a.H = H; a.step = 1 << i;
+            a.kn = kn; a.kz = kz; a.kc = kc0 * (float)(1 << (2 * i));
+            if (last) hipLaunchKernelGGL(rtk::k_atrous<true>, grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL(rtk::k_atrous<false>, grid, dim3(256), 0, stream, a);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
+    }
+    D.filled = true;
+    D.info.iterations = P.iterations; D.info.demodulate = P.demodulate; D.info.width = W; D.info.height = H;
+    D.info.lastKernelMs = ms; D.info.totalKernelMs += ms;
+    return hipSuccess;
+}
+
+int denoise(rt_ctx* c, const rt_denoise_params* in)
+{
+    RT_SETTLE(c);
+    if (!c->have_params) return fail(c, -2, "rt_denoise: rt_set_params has not been called");
+    rt_denoise_params P;
+    if (const char* why = denoise_params(in, P)) return fail(c, -2, "rt_denoise: %s", why);
+    const int W = c->params.width, H = c->params.height;
+    int r0, nr, rstride;
+    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
+    if (c->band_stride > 1 || r0 != 0 || nr != H)
+        return fail(c, -2, "rt_denoise: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise", nr, H);
+    // the feature planes of THIS image layout, with at least one frame in them (planes of another layout would be re-created, zeroed)
+    const bool aov_current = c->d_aov[0].p && W == c->aov_w && H == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride;
+    if (!aov_current || c->aov.framesAccumulated == 0) return fail(c, -2, "rt_denoise: no feature frame accumulated (call rt_render_aov first)");
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = ensure_targets(c); if (r) return r; }             // (a no-op unless the image was never created at this size: then it is a cleared image)
+    RT_HIP(c, run_denoise(c->dn, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, W, H, P, c->stream, c->ev_dn0, c->ev_dn1));
+    return 0;
+}
+
+int read_denoised(rt_ctx* c, void* dst, size_t n_floats, bool to_device)
+{
+    RT_SETTLE(c);
+    if (!c->dn.filled) return fail(c, -2, "rt_denoise has not been called");
+    if (!dst) return fail(c, -2, "null destination");
+    const size_t px = (size_t)c->dn.w * c->dn.h;
+    if (n_floats != px * 4) return fail(c, -2, "expected %zu floats (height*width*4), got %zu", px * 4, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(dst, c->dn.out.p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// the display step (rt_read_display's kernel) on a denoised plane, through `display` on the current device
+hipError_t display_plane(const float4* plane, DevBuf<uint32_t>& display, uint32_t* rgba8, size_t n_pixels, int n_cu, hipStream_t stream)
+{
+    hipError_t e = display.ensure(n_pixels);
+    if (e != hipSuccess) return e;
+    const int grid = (int)std::min<size_t>((n_pixels + 255) / 256, (size_t)std::max(1, n_cu) * 8);
+    hipLaunchKernelGGL(rtg::k_display_srgb8, dim3(grid), dim3(256), 0, stream, plane, display.p, n_pixels);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(rgba8, display.p, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+    return hipStreamSynchronize(stream);
+}
+
 } // namespace
 
 extern "C" {
@@ -1377,6 +1492,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_ray")) return (int)sizeof(rt_ray);
     if (!std::strcmp(name, "rt_hit")) return (int)sizeof(rt_hit);
     if (!std::strcmp(name, "rt_aov_info")) return (int)sizeof(rt_aov_info);
+    if (!std::strcmp(name, "rt_denoise_params")) return (int)sizeof(rt_denoise_params);
+    if (!std::strcmp(name, "rt_denoise_info")) return (int)sizeof(rt_denoise_info);
     return -1;
 }
 
@@ -1398,6 +1515,7 @@ rt_ctx* rt_create(int device)
         || (e = hipEventCreate(&c->ev0)) != hipSuccess || (e = hipEventCreate(&c->ev1)) != hipSuccess
         || (e = hipEventCreate(&c->evg0)) != hipSuccess || (e = hipEventCreate(&c->evg1)) != hipSuccess
         || (e = hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming)) != hipSuccess
+        || (e = hipEventCreate(&c->ev_dn0)) != hipSuccess || (e = hipEventCreate(&c->ev_dn1)) != hipSuccess
         || (e = hipMalloc((void**)&c->d_tile_counter, sizeof(unsigned int))) != hipSuccess
         || (e = hipMalloc((void**)&c->d_counters, rtk::kNumCounters * sizeof(unsigned long long))) != hipSuccess) {
         fail(nullptr, -1, "context setup: %s", hipGetErrorString(e));
@@ -1429,10 +1547,13 @@ void rt_destroy(rt_ctx* c)
     if (c->evg0) (void)hipEventDestroy(c->evg0);
     if (c->evg1) (void)hipEventDestroy(c->evg1);
     if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
+    if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
+    if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
     c->bvh_ws.release();
     c->d_local_tris.release(); c->d_tri_mesh.release(); c->d_tri_chunk.release(); c->d_tri_rank.release(); c->d_order.release(); c->d_xf.release();
     c->d_q_rays.release(); c->d_q_hits.release(); c->d_q_occ.release(); c->d_q_bound.release();
     for (DevBuf<float4>& b : c->d_aov) b.release();
+    c->dn.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1788,6 +1909,31 @@ int rt_get_aov_info(rt_ctx* c, rt_aov_info* out)
     return 0;
 }
 
+int rt_denoise(rt_ctx* c, const rt_denoise_params* params) { return c ? denoise(c, params) : -1; }
+int rt_read_denoised(rt_ctx* c, float* rgba, size_t n) { return c ? read_denoised(c, rgba, n, false) : -1; }
+int rt_copy_denoised_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_denoised(c, dst, n, true) : -1; }
+int rt_read_denoised_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!c->dn.filled) return fail(c, -2, "rt_denoise has not been called");
+    if (!rgba8) return fail(c, -2, "null destination");
+    const size_t px = (size_t)c->dn.w * c->dn.h;
+    if (n_pixels != px) return fail(c, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
+    if (!n_pixels) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, display_plane(c->dn.out.p, c->d_display, rgba8, n_pixels, c->n_cu, c->stream));
+    return 0;
+}
+int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!out) return fail(c, -2, "null info");
+    *out = c->dn.info;
+    return 0;
+}
+
 int rt_get_stats(rt_ctx* c, rt_stats* out)
 {
     if (!c) return -1;
@@ -1812,6 +1958,8 @@ struct rt_multi {
     DevBuf<float4> d_image, d_staging;          // on the first context's device: the assembled image, the incoming strips
     DevBuf<uint32_t> d_display;                 // ... and its sRGB8 form (rt_multi_read_display)
     DevBuf<float4> d_aov_image;                 // ... the assembled feature plane of the last rt_multi_read_aov
+    DevBuf<float4> d_dn_albedo, d_dn_guide;     // ... both assembled feature planes of the last rt_multi_denoise
+    DenoisePlanes dn;                           // ... its work planes and the denoised plane
     std::vector<hipEvent_t> ev_strip;           // per context: its strip has arrived on the first device (recorded on the SOURCE context's stream)
     int max_rows = 0;
     double lastGatherMs = 0, lastSetupMs = 0;
@@ -1901,7 +2049,7 @@ void rt_multi_destroy(rt_multi* m)
     if (!m) return;
     for (size_t i = 0; i < m->ev_strip.size() && i < m->ctx.size(); ++i)
         if (m->ev_strip[i]) { (void)hipSetDevice(m->ctx[i]->device); (void)hipEventDestroy(m->ev_strip[i]); }
-    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); }
+    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); m->d_dn_albedo.release(); m->d_dn_guide.release(); m->dn.release(); }
     for (rt_ctx* c : m->ctx) rt_destroy(c);
     delete m;
 }
@@ -2127,6 +2275,60 @@ int rt_multi_read_aov(rt_multi* m, int which, float* rgba, size_t n_floats)
 }
 
 int rt_multi_reset_aov(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_aov", [&](rt_ctx* c) { return rt_reset_aov(c); }) : -1; }
+
+// The denoiser behind the handle: image and both feature planes gathered to the first device, rt_denoise's filter there.
+int rt_multi_denoise(rt_multi* m, const rt_denoise_params* params)
+{
+    if (!m) return -1;
+    if (!m->have_params) return mfail(m, -2, "rt_multi_denoise: rt_multi_set_params has not been called");
+    rt_denoise_params P;
+    if (const char* why = denoise_params(params, P)) return mfail(m, -2, "rt_multi_denoise: %s", why);
+    for (size_t i = 0; i < m->ctx.size(); ++i) {
+        rt_ctx* c = m->ctx[i];
+        { const int r = settle(c); if (r) return mfail(m, r, "context %zu: %s", i, rt_last_error(c)); }
+        int r0, nr, rstride;
+        if (strip_layout(c, r0, nr, rstride)) return mfail(m, -2, "context %zu: %s", i, rt_last_error(c));
+        const bool aov_current = c->d_aov[0].p && m->width == c->aov_w && m->height == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride;
+        const bool image_current = m->width == c->target_w && m->height == c->target_h && r0 == c->target_row0 && nr == c->target_rows && rstride == c->target_row_stride;
+        if (nr != 0 && (!aov_current || c->aov.framesAccumulated == 0)) return mfail(m, -2, "rt_multi_denoise: no feature frame accumulated on context %zu (call rt_multi_render_aov first)", i);
+        if (!image_current) return mfail(m, -2, "rt_multi_denoise: nothing rendered yet on context %zu", i);
+    }
+    double gather_ms = 0;
+    { int r = gather_strips(m, m->d_image, gather_ms, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target_rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_albedo, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_ALBEDO].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
+    rt_ctx* root = m->ctx[0];
+    M_HIP(m, hipSetDevice(root->device));
+    M_HIP(m, run_denoise(m->dn, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
+    return 0;
+}
+
+int rt_multi_read_denoised(rt_multi* m, float* rgba, size_t n_floats)
+{
+    if (!m) return -1;
+    if (!m->dn.filled) return mfail(m, -2, "rt_multi_denoise has not been called");
+    if (!rgba) return mfail(m, -2, "null destination");
+    const size_t px = (size_t)m->dn.w * m->dn.h;
+    if (n_floats != px * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", px * 4, n_floats);
+    if (!n_floats) return 0;
+    M_HIP(m, hipSetDevice(m->ctx[0]->device));
+    M_HIP(m, hipMemcpy(rgba, m->dn.out.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rt_multi_read_denoised_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
+{
+    if (!m) return -1;
+    if (!m->dn.filled) return mfail(m, -2, "rt_multi_denoise has not been called");
+    if (!rgba8) return mfail(m, -2, "null destination");
+    const size_t px = (size_t)m->dn.w * m->dn.h;
+    if (n_pixels != px) return mfail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
+    if (!n_pixels) return 0;
+    rt_ctx* root = m->ctx[0];
+    M_HIP(m, hipSetDevice(root->device));
+    M_HIP(m, display_plane(m->dn.out.p, m->d_display, rgba8, n_pixels, root->n_cu, root->stream));
+    return 0;
+}
 
 int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
 {

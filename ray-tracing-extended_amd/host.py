@@ -426,6 +426,13 @@ class RayTracingManager:
         self.backend.render_aov(first, frames)
         return self.backend.read_aov(0), self.backend.read_aov(1)
 
+    def Denoise(self, **params):
+        """Beyond the reference: the step between resultTexture and the display blit (rt_denoise): the accumulated image filtered by the
+        edge-avoiding A-trous transform, guided by the planes RenderFeatures accumulated.  Keywords as Tracer.denoise (none = the library's
+        defaults).  Returns the denoised image (H, W, 4); the image, the planes and numRenderedFrames are left alone."""
+        self.backend.denoise(**params)
+        return self.backend.read_denoised()
+
     def Start(self):                                                              # RayTracingManager.cs:43-46
         self.numRenderedFrames = 0
         if self.backend is not None:

@@ -429,6 +429,24 @@ void RayTracingManager::RenderFeatures(rt_ctx* ctx, int frames, std::vector<floa
         }
 }
 
+void RayTracingManager::Denoise(rt_ctx* ctx, const rt_denoise_params* params, std::vector<float>* denoised)
+{
+    check(ctx, rt_denoise(ctx, params), "rt_denoise");
+    if (denoised) {
+        denoised->resize((size_t)width * height * 4);
+        check(ctx, rt_read_denoised(ctx, denoised->data(), denoised->size()), "rt_read_denoised");
+    }
+}
+
+void RayTracingManager::Denoise(rt_multi* m, const rt_denoise_params* params, std::vector<float>* denoised)
+{
+    mcheck(m, rt_multi_denoise(m, params), "rt_multi_denoise");
+    if (denoised) {
+        denoised->resize((size_t)width * height * 4);
+        mcheck(m, rt_multi_read_denoised(m, denoised->data(), denoised->size()), "rt_multi_read_denoised");
+    }
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

@@ -135,6 +135,10 @@ public:
     // that continue from the planes' own count; the planes (width * height * 4 floats each) are read back when asked for.  The image and
     // numRenderedFrames are left alone.
     void RenderFeatures(rt_ctx* ctx, int frames, std::vector<float>* albedoCoverage = nullptr, std::vector<float>* normalDepth = nullptr);
+    // Beyond the reference: resultTexture filtered into the denoised plane (rt_denoise; params null = the library's defaults), guided by
+    // the planes RenderFeatures accumulated; the plane (width * height * 4 floats) is read back when asked for.
+    void Denoise(rt_ctx* ctx, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
+    void Denoise(rt_multi* multi, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

@@ -237,6 +237,36 @@ namespace RtMi355x
             return rgba;
         }
 
+        // ---- denoiser (the step between resultTexture and the display blit: RtDenoise.cs) ---------------------------------------
+        /// Filters the accumulated image into the denoised plane, guided by the planes RenderFeatures accumulated; the image, the planes
+        /// and the frame counter are left alone.
+        public void Denoise(RtDenoiseParams p)
+        {
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_denoise(multi, ref p), "rt_multi_denoise");
+            else RtNative.Check(ctx, RtNative.rt_denoise(ctx, ref p), "rt_denoise");
+        }
+        public void Denoise() { Denoise(RtDenoiseParams.Defaults); }
+
+        /// The denoised plane, width * height * 4 floats, row 0 = bottom.
+        public float[] ReadDenoised()
+        {
+            float[] rgba = new float[(long)width * height * 4];
+            UIntPtr n = (UIntPtr)(ulong)rgba.LongLength;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_read_denoised(multi, rgba, n), "rt_multi_read_denoised");
+            else RtNative.Check(ctx, RtNative.rt_read_denoised(ctx, rgba, n), "rt_read_denoised");
+            return rgba;
+        }
+
+        /// The denoised plane through the display step (linear -> sRGB8, R | G<<8 | B<<16 | A<<24), width * height pixels.
+        public uint[] ReadDenoisedDisplay()
+        {
+            uint[] rgba8 = new uint[(long)width * height];
+            UIntPtr n = (UIntPtr)(ulong)rgba8.LongLength;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_read_denoised_display(multi, rgba8, n), "rt_multi_read_denoised_display");
+            else RtNative.Check(ctx, RtNative.rt_read_denoised_display(ctx, rgba8, n), "rt_read_denoised_display");
+            return rgba8;
+        }
+
         /// Blit(resultTexture, target)
         public void Present(RenderTexture target)
         {

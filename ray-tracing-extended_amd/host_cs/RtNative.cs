@@ -229,6 +229,15 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_multi_render_aov(IntPtr multi, int firstFrame, int nFrames);
         [DllImport(Lib)] public static extern int rt_multi_read_aov(IntPtr multi, int which, [Out] float[] rgba, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_multi_reset_aov(IntPtr multi);
+        // denoiser (RtDenoiseParams, RtDenoiseInfo: RtDenoise.cs; RtDenoiseParams.Defaults = what a null pointer means in C)
+        [DllImport(Lib)] public static extern int rt_denoise(IntPtr ctx, ref RtDenoiseParams p);
+        [DllImport(Lib)] public static extern int rt_read_denoised(IntPtr ctx, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_copy_denoised_to_device(IntPtr ctx, IntPtr dstDevicePtr, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_read_denoised_display(IntPtr ctx, [Out] uint[] rgba8, UIntPtr nPixels);
+        [DllImport(Lib)] public static extern int rt_get_denoise_info(IntPtr ctx, out RtDenoiseInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_denoise(IntPtr multi, ref RtDenoiseParams p);
+        [DllImport(Lib)] public static extern int rt_multi_read_denoised(IntPtr multi, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_multi_read_denoised_display(IntPtr multi, [Out] uint[] rgba8, UIntPtr nPixels);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -273,6 +282,8 @@ namespace RtMi355x
             Same("rt_ray", Marshal.SizeOf<RtRay>());
             Same("rt_hit", Marshal.SizeOf<RtHit>());
             Same("rt_aov_info", Marshal.SizeOf<RtAovInfo>());
+            Same("rt_denoise_params", Marshal.SizeOf<RtDenoiseParams>());
+            Same("rt_denoise_info", Marshal.SizeOf<RtDenoiseInfo>());
         }
     }
 }

@@ -29,6 +29,9 @@ def main(argv=None):
     ap.add_argument("--aov", metavar="PREFIX", help="also accumulate the feature buffers over the same frames (rt_render_aov) and write PREFIX.albedo "
                     "(albedo, alpha = coverage), PREFIX.normal (mean shading normal, alpha = coverage) and PREFIX.depth (mean depth in every "
                     "channel, alpha = coverage), as .exr, or as .pfm when --pfm is given and --exr is not")
+    ap.add_argument("--denoise", action="store_true", help="after the frames (and the feature frames: accumulated over the same frames even without --aov) "
+                    "run rt_denoise with the library's defaults and write the denoised image beside the noisy one: NAME.denoised.EXT for "
+                    "every --png / --exr / --pfm given")
     args = ap.parse_args(argv)
 
     import rtx_pkg
@@ -68,6 +71,23 @@ def main(argv=None):
             write(f"{args.aov}.{name}{ext}", np.ascontiguousarray(plane, np.float32))
         print(f"feature buffers: {info['framesAccumulated']} frames in {info['totalKernelMs']:.1f} ms of kernels "
               f"({info['lastSampleLanes']} lanes per pixel) -> {args.aov}.{{albedo,normal,depth}}{ext}")
+    if args.denoise:
+        if not args.aov:
+            mgr.RenderFeatures(frames=args.frames, firstFrame=0)
+        denoised = mgr.Denoise()
+        info = tracer.denoise_info()
+
+        def beside(path):
+            stem, ext = os.path.splitext(path)
+            return stem + ".denoised" + ext
+        written = []
+        if args.png:
+            rtx.imageio.write_png(beside(args.png), tracer.read_denoised_display()); written.append(beside(args.png))
+        if args.exr:
+            rtx.imageio.write_exr(beside(args.exr), denoised); written.append(beside(args.exr))
+        if args.pfm:
+            rtx.imageio.write_pfm(beside(args.pfm), denoised); written.append(beside(args.pfm))
+        print(f"denoised: {info['iterations']} passes in {info['lastKernelMs']:.3f} ms of kernels -> {', '.join(written) or 'nothing written (give --png, --exr or --pfm)'}")
     tracer.close()
     return 0
 
