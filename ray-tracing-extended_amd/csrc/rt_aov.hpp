@@ -40,10 +40,7 @@ __global__ __launch_bounds__(kBlock) void k_aov(DeviceScene S, AovArgs A)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned int tile = blockIdx.x * kWavesPerBlock + wave;
     if (tile >= (unsigned)A.ntiles) return;                             // (wave-uniform)
-    TravStack stk;
-    stk.lds = lds_stack + (size_t)wave * A.stack_cap * 64 + lane;
-    stk.cap = A.stack_cap; stk.stride = A.gstack_stride;
-    stk.glb = A.gstack ? A.gstack + (blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    const TravStack stk = lane_stack(lds_stack, A.stack_cap, A.gstack, A.gstack_stride);
 
     const rt_params& p = A.p;
     const int sl = A.sample_lanes_log2, tl = (6 - sl) >> 1;
@@ -92,18 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_aov(DeviceScene S, AovArgs A)
         if (h.id != kNone) {
             const v3 hitPoint = o + d * h.t;
             v3 normal; const float4* mat;
-            if (h.id & kTriBit) {
-                const uint32_t ti = h.id & ~kTriBit;
-                const float4* tn = S.tri_nrm + (size_t)ti * 3;
-                const float4 n0 = tn[0], n1 = tn[1], n2 = tn[2];
-                const float w = 1.0f - h.u - h.v;
-                normal = rtm::normalize((rtm::mk(n0.x, n0.y, n0.z) * w + rtm::mk(n1.x, n1.y, n1.z) * h.u) + rtm::mk(n2.x, n2.y, n2.z) * h.v);
-                mat = S.chunk_mat + (size_t)__float_as_uint(n0.w) * 4;
-            } else {
-                const float4 s = S.sph_geom[h.id];
-                normal = rtm::normalize(hitPoint - rtm::mk(s.x, s.y, s.z));
-                mat = S.sph_mat + (size_t)h.id * 4;
-            }
+            surface_of(S, h, hitPoint, normal, mat);
             const float4 mcol = mat[0], mprm = mat[3];
             const int flag = (int)__float_as_uint(mprm.w);
             if (flag == 2 && cast == 0) {                                   // InvisibleLightSource :318-322

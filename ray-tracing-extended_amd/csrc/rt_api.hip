@@ -36,6 +36,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 namespace {
 
 thread_local std::string g_create_error;
+struct ErrOwner { std::string err; };       // what rt_ctx and rt_multi are to fail(): the text rt_last_error / rt_multi_last_error return
 
 #define RT_HIP(ctx, expr)                                                                          \
     do {                                                                                           \
@@ -66,13 +67,20 @@ struct DenoisePlanes {
     void release() { e[0].release(); e[1].release(); d.release(); out.release(); w = h = 0; filled = false; }
 };
 
+// The rows of the image a context renders (rt_set_rows / rt_set_bands) and so the layout of the planes that hold them: local row ly is
+// image row row0 + (ly / 8) * row_stride + ly % 8
+struct StripLayout {
+    int w = 0, h = 0, row0 = 0, rows = 0, row_stride = 8;
+    size_t pixels() const { return (size_t)w * rows; }
+    bool operator==(const StripLayout& o) const { return w == o.w && h == o.h && row0 == o.row0 && rows == o.rows && row_stride == o.row_stride; }
+};
+
 } // namespace
 
-struct rt_ctx {
+struct rt_ctx : ErrOwner {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::string err;
 
     rt_params params{};
     bool have_params = false;
@@ -108,8 +116,7 @@ struct rt_ctx {
     DevBuf<uint32_t> d_tile_order, d_tile_cost, d_tile_hist;
     bool lpt_active = true;             // the last launch used (or could have used) a costliest-first order: the automatic kernel choice waits for it
     bool tile_order_valid = false, tile_order_stale = false; int tile_order_n = 0;   // stale: usable, re-measured by the next launch
-    size_t target_pixels = 0;
-    int target_w = 0, target_h = 0, target_row0 = 0, target_rows = 0, target_row_stride = 8;
+    StripLayout target;                 // the layout d_frame / d_accum were made for (ensure_targets)
     unsigned int* d_tile_counter = nullptr;
     unsigned long long* d_counters = nullptr;
 
@@ -177,9 +184,8 @@ struct rt_ctx {
     DevBuf<unsigned int> d_q_bound;                                         // ... the device entries' origin bound
     // feature buffers (rt_render_aov, csrc/rt_aov.hpp): the two accumulated planes of this context's strip and the layout they were made for
     DevBuf<float4> d_aov[RT_AOV_COUNT];
-    size_t aov_pixels = 0;
-    int aov_w = 0, aov_h = 0, aov_row0 = 0, aov_rows = 0, aov_row_stride = 8;
-    rt_aov_info aov{};
+    StripLayout aov;                    // (meaningful once d_aov[0].p is set: ensure_aov)
+    rt_aov_info aov_info{};
     DenoisePlanes dn;                   // rt_denoise
     hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
     rt_stats stats{};
@@ -199,11 +205,11 @@ struct rt_ctx {
 
 namespace {
 
-int fail(rt_ctx* ctx, int code, const char* fmt, ...)
+int fail(ErrOwner* owner, int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (ctx) ctx->err = buf; else g_create_error = buf;
+    if (owner) owner->err = buf; else g_create_error = buf;
     return code;
 }
 
@@ -620,35 +626,40 @@ int clone_scene(rt_ctx* dst, rt_ctx* src)
     return 0;
 }
 
-// The rows this context renders (rt_set_rows / rt_set_bands) of the image of c->params: first row, row count, distance between bands
-int strip_layout(rt_ctx* c, int& r0, int& nr, int& rstride)
+// The rows this context renders (rt_set_rows / rt_set_bands) of the image of c->params
+int strip_layout(rt_ctx* c, StripLayout& L)
 {
     const int H = c->params.height;
-    r0 = c->nrows < 0 ? 0 : c->row0; nr = c->nrows < 0 ? H : c->nrows; rstride = 8;
+    L.w = c->params.width; L.h = H;
+    L.row0 = c->nrows < 0 ? 0 : c->row0; L.rows = c->nrows < 0 ? H : c->nrows; L.row_stride = 8;
     if (c->band_stride > 0) {
         // bands band_first, band_first + band_stride, ... of 8 rows each; the image's last band may be partial
-        r0 = c->band_first * 8; rstride = c->band_stride * 8; nr = 0;
-        for (int y = r0; y < H; y += rstride) nr += std::min(8, H - y);
-        if (r0 > H) r0 = H;
-    } else if (r0 < 0 || nr < 0 || r0 + nr > H) return fail(c, -6, "row strip [%d,%d) outside image height %d", r0, r0 + nr, H);
+        L.row0 = c->band_first * 8; L.row_stride = c->band_stride * 8; L.rows = 0;
+        for (int y = L.row0; y < H; y += L.row_stride) L.rows += std::min(8, H - y);
+        if (L.row0 > H) L.row0 = H;
+    } else if (L.row0 < 0 || L.rows < 0 || L.row0 + L.rows > H) return fail(c, -6, "row strip [%d,%d) outside image height %d", L.row0, L.row0 + L.rows, H);
+    return 0;
+}
+
+// `planes` are (re)created for the layout L, cleared: a re-created render texture starts cleared (ShaderHelper.CreateRenderTexture,
+// ShaderHelper.cs:186-205)
+int create_planes(rt_ctx* c, const StripLayout& L, std::initializer_list<DevBuf<float4>*> planes)
+{
+    const size_t px = L.pixels();
+    for (DevBuf<float4>* b : planes) {
+        RT_HIP(c, b->ensure(px));
+        if (px) RT_HIP(c, hipMemsetAsync(b->p, 0, px * sizeof(float4), c->stream));
+    }
     return 0;
 }
 
 int ensure_targets(rt_ctx* c)
 {
-    const int W = c->params.width, H = c->params.height;
-    int r0, nr, rstride;
-    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
-    if (W == c->target_w && H == c->target_h && r0 == c->target_row0 && nr == c->target_rows && rstride == c->target_row_stride) return 0;
-    const size_t px = (size_t)W * nr;
-    RT_HIP(c, c->d_frame.ensure(px));
-    RT_HIP(c, c->d_accum.ensure(px));
-    // a re-created render texture starts cleared (ShaderHelper.CreateRenderTexture, ShaderHelper.cs:186-205)
-    if (px) {
-        RT_HIP(c, hipMemsetAsync(c->d_frame.p, 0, px * sizeof(float4), c->stream));
-        RT_HIP(c, hipMemsetAsync(c->d_accum.p, 0, px * sizeof(float4), c->stream));
-    }
-    c->target_pixels = px; c->target_w = W; c->target_h = H; c->target_row0 = r0; c->target_rows = nr; c->target_row_stride = rstride; c->tile_order_valid = false;
+    StripLayout L;
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (L == c->target) return 0;           // (a context that never rendered holds the layout of an empty image)
+    { int r = create_planes(c, L, { &c->d_frame, &c->d_accum }); if (r) return r; }
+    c->target = L; c->tile_order_valid = false;
     c->stats.numRenderedFrames = 0; c->stats.totalKernelMs = 0;
     return 0;
 }
@@ -736,6 +747,27 @@ int tile_stack_cap(const rt_ctx* c)
     return std::min(cap, 64);
 }
 
+// The traversal stack of a launch of such a kernel (k_trace, k_ray_query, k_aov) over `lanes` lanes: tile_stack_cap entries per lane in
+// `lds` bytes of LDS per workgroup, and for a deeper tree the global overflow area — one slot per lane of the launch and entry beyond cap,
+// so such a tree pays for the launch's width.  refuse_4g_for: the entry point whose launches are as wide as its image and that refuses
+// an area above 4 GiB (null: the launch's width is bounded and the area is allocated whatever it takes)
+struct LaneStack { int cap = 0; size_t lds = 0; uint32_t* gstack = nullptr; unsigned int stride = 0; };
+int plan_lane_stack(rt_ctx* c, size_t lanes, LaneStack& st, const char* refuse_4g_for = nullptr)
+{
+    st.cap = tile_stack_cap(c);
+    st.lds = (size_t)st.cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock;
+    static_assert(64 * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock <= 64 * 1024, "the largest cap needs no opt-in to more than 64 KiB of dynamic LDS");
+    st.stride = (unsigned int)lanes; st.gstack = nullptr;
+    if (c->bvh.maxStack > st.cap) {
+        const size_t need = (size_t)(c->bvh.maxStack - st.cap) * lanes;
+        if (refuse_4g_for && need > ((size_t)4 << 30) / sizeof(uint32_t))
+            return fail(c, -7, "%s: the traversal-stack overflow area would take %zu MiB (raise option lds_stack)", refuse_4g_for, need >> 18);
+        RT_HIP(c, c->d_gstack.ensure(need));
+        st.gstack = c->d_gstack.p;
+    }
+    return 0;
+}
+
 // Kernel choice, traversal stack and LDS, grid, frames per launch, spill buffers (kernel: 0 k_trace, 1 k_stream)
 int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n_frames, LaunchPlan& P)
 {
@@ -743,24 +775,24 @@ int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n
     { int r = fill_scene(c, S); if (r) return r; }
 
     F.p = c->params;
-    F.row0 = c->target_row0; F.nrows = c->target_rows; F.row_stride = c->target_row_stride;
+    F.row0 = c->target.row0; F.nrows = c->target.rows; F.row_stride = c->target.row_stride;
     F.tile_w_log2 = 3;
-    F.tiles_x = (c->target_w + 7) / 8; F.tiles_y = (c->target_rows + 7) / 8;
+    F.tiles_x = (c->target.w + 7) / 8; F.tiles_y = (c->target.rows + 7) / 8;
     if (kernel == 0 && c->opt_tile_w_log2 != 3) {        // k_trace only: other tile shapes (same 64 pixels per wave)
         F.tile_w_log2 = c->opt_tile_w_log2;
         const int tw = 1 << F.tile_w_log2, th = 64 >> F.tile_w_log2;
-        F.tiles_x = (c->target_w + tw - 1) / tw; F.tiles_y = (c->target_rows + th - 1) / th;
+        F.tiles_x = (c->target.w + tw - 1) / tw; F.tiles_y = (c->target.rows + th - 1) / th;
     }
     // the counter-based mode is k_stream's Philox instantiation whatever kernel was asked for (its estimator spreads a pixel's samples
     // over the lanes of a wave); NumRaysPerPixel < 1 draws nothing in either mode and goes to k_trace
     const bool philox = P.philox = c->params.rngMode == RT_RNG_PHILOX && c->params.numRaysPerPixel >= 1;
     if (philox && var == Variant::Flat) return fail(c, -2, "the flat validation kernel implements the PCG stream only");
     if (philox) kernel = 1;
-    if (philox && (c->target_w > 65535 || c->target_rows > 65535)) return fail(c, -7, "the Philox mode addresses at most 65535 x 65535 pixels per context");
+    if (philox && (c->target.w > 65535 || c->target.rows > 65535)) return fail(c, -7, "the Philox mode addresses at most 65535 x 65535 pixels per context");
     if (philox && (c->params.numRaysPerPixel > 65000 || c->params.maxBounceCount > 32000))
         return fail(c, -7, "the Philox mode takes at most 65000 rays per pixel per frame and 32000 bounces (sample and bounce share one signed 32-bit register)");
     const bool stream = P.stream = kernel == 1 && var != Variant::Flat && c->params.numRaysPerPixel >= 1   // PCG or Philox instantiation
-                                   && c->target_w <= 65535 && c->target_rows <= 65535                      // (16-bit pixel coordinates in k_stream's item tables)
+                                   && c->target.w <= 65535 && c->target.rows <= 65535                      // (16-bit pixel coordinates in k_stream's item tables)
                                    && c->params.numRaysPerPixel <= 65000 && c->params.maxBounceCount <= 32000;     // (sample and bounce share one register; beyond that PCG frames are k_trace's)
     const bool tile_kernel = P.tile_kernel = !stream && var != Variant::Flat;   // k_trace, PCG or Philox
     F.stack_cap = tile_kernel ? tile_stack_cap(c)
@@ -820,20 +852,21 @@ int plan_launch(rt_ctx* c, Variant var, int kernel, const rt_params* cams, int n
         RT_HIP(c, c->d_gstack.ensure((size_t)(c->bvh.maxStack + 3 - F.stack_cap) * gstack_stride));
         F.gstack = c->d_gstack.p; F.gstack_stride = gstack_stride;
     }
-    if (tile_kernel && c->bvh.maxStack > F.stack_cap) {
-        RT_HIP(c, c->d_gstack.ensure((size_t)(c->bvh.maxStack - F.stack_cap) * gstack_stride));
-        F.gstack = c->d_gstack.p; F.gstack_stride = gstack_stride;
+    if (tile_kernel) {
+        LaneStack st;
+        { int r = plan_lane_stack(c, gstack_stride, st); if (r) return r; }
+        F.gstack = st.gstack; F.gstack_stride = st.gstack ? st.stride : 0;
     }
     // k_trace can trace several frames per launch (work items = (frame, tile)): the persistent waves then balance over
     // frames as well — what matters when a rank's strip has about as many tiles as the chip has wave slots.
     // k_stream taking whole tiles (stream_sync) has the same (frame, tile) items as k_trace
     if ((tile_kernel || stream_sync) && n_frames > 1 && c->opt_frame_batch != 1) {
         const size_t budget = (size_t)4 << 30;                                  // <= 4 GiB of per-frame outputs (16 frames at 3840x2160)
-        const size_t per_frame = c->target_pixels * sizeof(float4);
+        const size_t per_frame = c->target.pixels() * sizeof(float4);
         int batch = (int)std::min<size_t>((size_t)n_frames, std::max<size_t>(1, budget / per_frame));
         if (c->opt_frame_batch > 1) batch = std::min(batch, c->opt_frame_batch);
         P.batch = batch = std::min(batch, 256);
-        if (batch > 1) RT_HIP(c, c->d_batch.ensure((size_t)batch * c->target_pixels));
+        if (batch > 1) RT_HIP(c, c->d_batch.ensure((size_t)batch * c->target.pixels()));
     }
     return 0;
 }
@@ -860,20 +893,20 @@ int plan_tile_order(rt_ctx* c, LaunchPlan& P)
 // Camera rays' candidate lists: every pixel's camera rays start from <= 4 leaves found once per camera / scene (rt_primary.hpp)
 int ensure_primary_lists(rt_ctx* c, LaunchPlan& P)
 {
-    const bool eligible = P.stream && !P.cam_table && c->opt_primary_lists && c->n_nodes > 0 && P.F.fixed_origin && c->target_pixels > 0
+    const bool eligible = P.stream && !P.cam_table && c->opt_primary_lists && c->n_nodes > 0 && P.F.fixed_origin && c->target.pixels() > 0
                           && c->bvh.maxStack <= 160;
     if (!eligible) return 0;
     std::string key((const char*)&c->params, sizeof c->params);
-    const unsigned long long geo[6] = { c->scene_version, (unsigned long long)c->target_row0, (unsigned long long)c->target_rows,
-                                        (unsigned long long)c->target_row_stride, (unsigned long long)c->target_w, (unsigned long long)c->target_h };
+    const unsigned long long geo[6] = { c->scene_version, (unsigned long long)c->target.row0, (unsigned long long)c->target.rows,
+                                        (unsigned long long)c->target.row_stride, (unsigned long long)c->target.w, (unsigned long long)c->target.h };
     key.append((const char*)geo, sizeof geo);
     if (key != c->primary_key) {     // (the build takes well under a millisecond at 1080p: a camera that moves every frame pays it every frame and still gains)
-        RT_HIP(c, c->d_primary.ensure(c->target_pixels)); RT_HIP(c, c->d_focus.ensure(c->target_pixels)); RT_HIP(c, c->d_primary_counts.ensure(4));
+        RT_HIP(c, c->d_primary.ensure(c->target.pixels())); RT_HIP(c, c->d_focus.ensure(c->target.pixels())); RT_HIP(c, c->d_primary_counts.ensure(4));
         RT_HIP(c, hipMemsetAsync(c->d_primary_counts.p, 0, 4 * sizeof(unsigned int), c->stream));
         rtp::PrimaryArgs PA{};
-        PA.p = c->params; PA.row0 = c->target_row0; PA.nrows = c->target_rows; PA.row_stride = c->target_row_stride;
+        PA.p = c->params; PA.row0 = c->target.row0; PA.nrows = c->target.rows; PA.row_stride = c->target.row_stride;
         PA.lists = c->d_primary.p; PA.focus = c->d_focus.p; PA.counts = c->d_primary_counts.p;
-        const int tiles = ((c->target_w + 7) / 8) * ((c->target_rows + 7) / 8);
+        const int tiles = ((c->target.w + 7) / 8) * ((c->target.rows + 7) / 8);
         PA.stack_cap = std::max(1, c->bvh.maxStack);                       // (the whole worst case in LDS: at most 160 entries x 64 lanes x 4 B = 40 KB per wave)
         const size_t plds = (size_t)PA.stack_cap * 64 * sizeof(uint32_t);
         RT_HIP(c, hipEventRecord(c->evg0, c->stream));
@@ -934,7 +967,7 @@ int run_launches(rt_ctx* c, LaunchPlan& P, int first_frame, int n_frames)
             A.guide_div = std::max(1, P.grid * rtk::kWavesPerBlock * (P.philox ? std::max(1, c->opt_fetch_guide_philox) : std::max(1, c->opt_fetch_guide)));
         }
         F.frame = first_frame + i;
-        F.frames_in_launch = nb; F.frame_stride = (unsigned int)c->target_pixels;
+        F.frames_in_launch = nb; F.frame_stride = (unsigned int)c->target.pixels();
         F.out_frame = nb > 1 ? c->d_batch.p : c->d_frame.p;
         RT_HIP(c, hipMemsetAsync(c->d_tile_counter, 0, sizeof(unsigned int), c->stream));
         {
@@ -944,9 +977,9 @@ int run_launches(rt_ctx* c, LaunchPlan& P, int first_frame, int n_frames)
         }
         RT_HIP(c, hipGetLastError());
         if (nb > 1) {
-            const int ag = (int)std::min<size_t>((c->target_pixels + 255) / 256, (size_t)c->n_cu * 8);
+            const int ag = (int)std::min<size_t>((c->target.pixels() + 255) / 256, (size_t)c->n_cu * 8);
             hipLaunchKernelGGL(rtk::k_accumulate<>, dim3(ag), dim3(256), 0, c->stream, c->d_batch.p, c->d_accum.p, c->d_frame.p,
-                               c->target_pixels, F.frame_stride, F.frame, nb);
+                               c->target.pixels(), F.frame_stride, F.frame, nb);
             RT_HIP(c, hipGetLastError());
         }
         i += nb;
@@ -1024,7 +1057,7 @@ int launch_frames_k(rt_ctx* c, int first_frame, int n_frames, Variant var, int k
     { int r = prepare_scene(c); if (r) return r; }
     if (cams) use_camera(c, cams[n_frames - 1]);      // (from here on only the settings of c->params are read; the context ends with the last frame's)
     { int r = ensure_targets(c); if (r) return r; }
-    if (c->target_pixels == 0 || n_frames == 0) return 0;
+    if (c->target.pixels() == 0 || n_frames == 0) return 0;
     LaunchPlan P;
     int r = plan_launch(c, var, kernel, cams, n_frames, P);
     if (!r) r = plan_tile_order(c, P);
@@ -1076,7 +1109,7 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var, const r
         int r = launch_frames_k(c, first_frame + done, count, var, kernel, cams ? cams + done : nullptr);
         if (r) return r;
         add();
-        if (c->target_pixels == 0) { done += count; continue; }
+        if (c->target.pixels() == 0) { done += count; continue; }
         // a kernel variant's very first launch in a context also pays its one-off set-up (code upload, the scratch ring of
         // k_stream): that frame is rendered like any other but not used as the timing
         const int variant = kernel * 4 + (c->params.rngMode == RT_RNG_PHILOX ? 2 : 0) + (c->opt_compact_nodes ? 1 : 0);
@@ -1093,19 +1126,24 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var, const r
     return 0;
 }
 
+// The end of every read of a plane: n_floats must be the plane's expect_floats (`shape`: what the message calls its rows), then one copy
+// on the context's stream, waited for.  What a null destination means is the entry point's own rule, checked before.
+int copy_plane(rt_ctx* c, const float4* src, size_t expect_floats, const char* shape, void* dst, size_t n_floats, bool to_device)
+{
+    if (n_floats != expect_floats) return fail(c, -2, "expected %zu floats (%s*width*4), got %zu", expect_floats, shape, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(dst, src, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int read_target(rt_ctx* c, bool accum, float* dst, size_t n_floats, bool to_device)
 {
     if (!c) return -1;
     if (!dst && n_floats) return fail(c, -2, "null destination");
     if (c->have_params) { int r = ensure_targets(c); if (r) return r; }
-    if (n_floats != c->target_pixels * 4)
-        return fail(c, -2, "expected %zu floats (rows*width*4), got %zu", c->target_pixels * 4, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    const float4* src = accum ? c->d_accum.p : c->d_frame.p;
-    RT_HIP(c, hipMemcpyAsync(dst, src, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return copy_plane(c, accum ? c->d_accum.p : c->d_frame.p, c->target.pixels() * 4, "rows", dst, n_floats, to_device);
 }
 
 // Frames first .. first + n - 1 with the uniforms params[f] (all with the settings of c->params).  One camera for all: today's path
@@ -1202,27 +1240,21 @@ int launch_query(rt_ctx* c, bool any, const float4* rays, int n, void* out)
     Q.order = c->d_order.p;
     Q.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
     Q.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
-    Q.stack_cap = tile_stack_cap(c);
     Q.full_sort = c->opt_full_sort;
-    const size_t lds = (size_t)Q.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock;
     const bool compact = c->opt_compact_nodes != 0;     // the node form the renderer's kernels traverse (plan_launch)
     const void* fn = any ? (compact ? (const void*)rtk::k_ray_query<true, true> : (const void*)rtk::k_ray_query<true, false>)
                          : (compact ? (const void*)rtk::k_ray_query<false, true> : (const void*)rtk::k_ray_query<false, false>);
-    if (lds > 64 * 1024) RT_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (int first = 0; first < n; first += kQuerySlice) {
         const int cnt = std::min(kQuerySlice, n - first);
         const int grid = (cnt + rtk::kBlock - 1) / rtk::kBlock;
-        const unsigned int stride = (unsigned int)grid * rtk::kBlock;
+        LaneStack st;
+        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st); if (r) return r; }
+        Q.stack_cap = st.cap; Q.gstack = st.gstack; Q.gstack_stride = st.stride;
         Q.rays = rays + 2 * (size_t)first; Q.n = cnt;
         Q.hits = any ? nullptr : static_cast<float4*>(out) + 4 * (size_t)first;
         Q.occluded = any ? static_cast<uint8_t*>(out) + first : nullptr;
-        Q.gstack = nullptr; Q.gstack_stride = stride;
-        if (c->bvh.maxStack > Q.stack_cap) {
-            RT_HIP(c, c->d_gstack.ensure((size_t)(c->bvh.maxStack - Q.stack_cap) * stride));
-            Q.gstack = c->d_gstack.p;
-        }
         void* args[] = { &S, &Q };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
     }
     return 0;
 }
@@ -1284,19 +1316,16 @@ int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
 // ---- feature buffers (rt_render_aov, csrc/rt_aov.hpp) -----------------------------------------------------------------------------
 // The two planes of the context's strip, zeroed when they are created and whenever the strip's layout changes (ensure_targets' rule for
 // the accumulation target, kept apart from it: a feature frame must not touch the image path's state)
+bool aov_current(const rt_ctx* c, const StripLayout& L) { return c->d_aov[0].p && L == c->aov; }
 int ensure_aov(rt_ctx* c)
 {
-    const int W = c->params.width, H = c->params.height;
-    int r0, nr, rstride;
-    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
-    if (c->d_aov[0].p && W == c->aov_w && H == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride) return 0;
-    const size_t px = (size_t)W * nr;
-    for (DevBuf<float4>& b : c->d_aov) {
-        RT_HIP(c, b.ensure(px));
-        if (px) RT_HIP(c, hipMemsetAsync(b.p, 0, px * sizeof(float4), c->stream));
-    }
-    c->aov_pixels = px; c->aov_w = W; c->aov_h = H; c->aov_row0 = r0; c->aov_rows = nr; c->aov_row_stride = rstride;
-    c->aov.framesAccumulated = 0; c->aov.totalKernelMs = 0;
+    StripLayout L;
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (aov_current(c, L)) return 0;
+    static_assert(RT_AOV_COUNT == 2, "the planes listed below");
+    { int r = create_planes(c, L, { &c->d_aov[0], &c->d_aov[1] }); if (r) return r; }
+    c->aov = L;
+    c->aov_info.framesAccumulated = 0; c->aov_info.totalKernelMs = 0;
     return 0;
 }
 
@@ -1313,43 +1342,35 @@ int render_aov(rt_ctx* c, int first_frame, int n_frames)
     { int r = fill_scene(c, S); if (r) return r; }
     rtk::AovArgs A{};
     A.p = c->params;
-    A.row0 = c->aov_row0; A.nrows = c->aov_rows; A.row_stride = c->aov_row_stride;
+    A.row0 = c->aov.row0; A.nrows = c->aov.rows; A.row_stride = c->aov.row_stride;
     // S = 16 / 4 / 1 sub-streams of a pixel on adjacent lanes: a wave is a 2x2 / 4x4 / 8x8 tile (all divide the 8-row bands)
     const int N = c->params.numRaysPerPixel;
     A.sample_lanes_log2 = N >= 16 ? 4 : N >= 4 ? 2 : 0;
     const int tile = 1 << ((6 - A.sample_lanes_log2) / 2);
-    const long long tiles_x = (c->aov_w + tile - 1) / tile, tiles_y = (c->aov_rows + tile - 1) / tile;
-    c->aov.lastSampleLanes = 1 << A.sample_lanes_log2;
-    if (tiles_x * tiles_y == 0) { c->aov.framesAccumulated += n_frames; c->aov.lastKernelMs = 0; return 0; }
+    const long long tiles_x = (c->aov.w + tile - 1) / tile, tiles_y = (c->aov.rows + tile - 1) / tile;
+    c->aov_info.lastSampleLanes = 1 << A.sample_lanes_log2;
+    if (tiles_x * tiles_y == 0) { c->aov_info.framesAccumulated += n_frames; c->aov_info.lastKernelMs = 0; return 0; }
     if (tiles_x * tiles_y > (long long)1 << 30) return fail(c, -7, "rt_render_aov: %lld wave tiles exceed one launch", tiles_x * tiles_y);
     A.tiles_x = (int)tiles_x; A.ntiles = (int)(tiles_x * tiles_y);
-    A.stack_cap = tile_stack_cap(c);
     A.full_sort = c->opt_full_sort;
     A.fixed_origin = camera_origin_is_fixed(c->params) ? 1 : 0;
     A.albedo = c->d_aov[RT_AOV_ALBEDO].p; A.normal_depth = c->d_aov[RT_AOV_NORMAL_DEPTH].p;
     const int grid = (A.ntiles + rtk::kWavesPerBlock - 1) / rtk::kWavesPerBlock;
-    A.gstack_stride = (unsigned int)grid * rtk::kBlock;
-    if (c->bvh.maxStack > A.stack_cap) {
-        // (one overflow slot per lane of the launch and entry: a tree deeper than the LDS part pays for this launch's width)
-        const size_t need = (size_t)(c->bvh.maxStack - A.stack_cap) * A.gstack_stride;
-        if (need > ((size_t)4 << 30) / sizeof(uint32_t)) return fail(c, -7, "rt_render_aov: the traversal-stack overflow area would take %zu MiB (raise option lds_stack)", need >> 18);
-        RT_HIP(c, c->d_gstack.ensure(need));
-        A.gstack = c->d_gstack.p;
-    }
-    const size_t lds = (size_t)A.stack_cap * 64 * sizeof(uint32_t) * rtk::kWavesPerBlock;
+    LaneStack st;
+    { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_render_aov"); if (r) return r; }
+    A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
     const void* fn = c->opt_compact_nodes != 0 ? (const void*)rtk::k_aov<true> : (const void*)rtk::k_aov<false>;     // the node form the renderer's kernels traverse
-    if (lds > 64 * 1024) RT_HIP(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RT_HIP(c, hipEventRecord(c->ev0, c->stream));
     for (int f = 0; f < n_frames; ++f) {
-        A.frame = first_frame + f; A.accumulated = c->aov.framesAccumulated + f;
+        A.frame = first_frame + f; A.accumulated = c->aov_info.framesAccumulated + f;
         void* args[] = { &S, &A };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, lds, c->stream));
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
     }
     RT_HIP(c, hipEventRecord(c->ev1, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
     RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->aov.framesAccumulated += n_frames; c->aov.lastKernelMs = ms; c->aov.totalKernelMs += ms;
+    c->aov_info.framesAccumulated += n_frames; c->aov_info.lastKernelMs = ms; c->aov_info.totalKernelMs += ms;
     return 0;
 }
 
@@ -1361,11 +1382,7 @@ int read_aov(rt_ctx* c, int which, void* dst, size_t n_floats, bool to_device)
     if (!dst) return fail(c, -2, "null destination");
     RT_HIP(c, hipSetDevice(c->device));
     { int r = ensure_aov(c); if (r) return r; }
-    if (n_floats != c->aov_pixels * 4) return fail(c, -2, "expected %zu floats (rows*width*4), got %zu", c->aov_pixels * 4, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(c, hipMemcpyAsync(dst, c->d_aov[which].p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return copy_plane(c, c->d_aov[which].p, c->aov.pixels() * 4, "rows", dst, n_floats, to_device);
 }
 
 // ---- denoiser (rt_denoise, csrc/rt_denoise.hpp) -----------------------------------------------------------------------------------
@@ -1431,17 +1448,15 @@ int denoise(rt_ctx* c, const rt_denoise_params* in)
     if (!c->have_params) return fail(c, -2, "rt_denoise: rt_set_params has not been called");
     rt_denoise_params P;
     if (const char* why = denoise_params(in, P)) return fail(c, -2, "rt_denoise: %s", why);
-    const int W = c->params.width, H = c->params.height;
-    int r0, nr, rstride;
-    { int r = strip_layout(c, r0, nr, rstride); if (r) return r; }
-    if (c->band_stride > 1 || r0 != 0 || nr != H)
-        return fail(c, -2, "rt_denoise: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise", nr, H);
+    StripLayout L;
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
+        return fail(c, -2, "rt_denoise: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise", L.rows, L.h);
     // the feature planes of THIS image layout, with at least one frame in them (planes of another layout would be re-created, zeroed)
-    const bool aov_current = c->d_aov[0].p && W == c->aov_w && H == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride;
-    if (!aov_current || c->aov.framesAccumulated == 0) return fail(c, -2, "rt_denoise: no feature frame accumulated (call rt_render_aov first)");
+    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "rt_denoise: no feature frame accumulated (call rt_render_aov first)");
     RT_HIP(c, hipSetDevice(c->device));
     { int r = ensure_targets(c); if (r) return r; }             // (a no-op unless the image was never created at this size: then it is a cleared image)
-    RT_HIP(c, run_denoise(c->dn, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, W, H, P, c->stream, c->ev_dn0, c->ev_dn1));
+    RT_HIP(c, run_denoise(c->dn, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
     return 0;
 }
 
@@ -1450,25 +1465,23 @@ int read_denoised(rt_ctx* c, void* dst, size_t n_floats, bool to_device)
     RT_SETTLE(c);
     if (!c->dn.filled) return fail(c, -2, "rt_denoise has not been called");
     if (!dst) return fail(c, -2, "null destination");
-    const size_t px = (size_t)c->dn.w * c->dn.h;
-    if (n_floats != px * 4) return fail(c, -2, "expected %zu floats (height*width*4), got %zu", px * 4, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(dst, c->dn.out.p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return copy_plane(c, c->dn.out.p, (size_t)c->dn.w * c->dn.h * 4, "height", dst, n_floats, to_device);
 }
 
-// the display step (rt_read_display's kernel) on a denoised plane, through `display` on the current device
-hipError_t display_plane(const float4* plane, DevBuf<uint32_t>& display, uint32_t* rgba8, size_t n_pixels, int n_cu, hipStream_t stream)
+// The display step: linear -> sRGB8 of a plane of n_pixels > 0 on c's device (already current), through `display` there, on c's stream;
+// kernel_ms, if asked for, is the kernel's time
+hipError_t display_plane(rt_ctx* c, const float4* plane, DevBuf<uint32_t>& display, uint32_t* rgba8, size_t n_pixels, float* kernel_ms = nullptr)
 {
     hipError_t e = display.ensure(n_pixels);
     if (e != hipSuccess) return e;
-    const int grid = (int)std::min<size_t>((n_pixels + 255) / 256, (size_t)std::max(1, n_cu) * 8);
-    hipLaunchKernelGGL(rtg::k_display_srgb8, dim3(grid), dim3(256), 0, stream, plane, display.p, n_pixels);
+    if (kernel_ms && (e = hipEventRecord(c->evg0, c->stream)) != hipSuccess) return e;
+    const int grid = (int)std::min<size_t>((n_pixels + 255) / 256, (size_t)std::max(1, c->n_cu) * 8);
+    hipLaunchKernelGGL(rtg::k_display_srgb8, dim3(grid), dim3(256), 0, c->stream, plane, display.p, n_pixels);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(rgba8, display.p, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
+    if (kernel_ms && (e = hipEventRecord(c->evg1, c->stream)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(rgba8, display.p, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
+    return kernel_ms ? hipEventElapsedTime(kernel_ms, c->evg0, c->evg1) : hipSuccess;
 }
 
 } // namespace
@@ -1797,9 +1810,9 @@ int rt_reset_accum(rt_ctx* c)
     if (!c) return -1;
     RT_SETTLE(c);
     RT_HIP(c, hipSetDevice(c->device));
-    if (c->target_pixels) {
-        RT_HIP(c, hipMemsetAsync(c->d_accum.p, 0, c->target_pixels * sizeof(float4), c->stream));
-        RT_HIP(c, hipMemsetAsync(c->d_frame.p, 0, c->target_pixels * sizeof(float4), c->stream));
+    if (c->target.pixels()) {
+        RT_HIP(c, hipMemsetAsync(c->d_accum.p, 0, c->target.pixels() * sizeof(float4), c->stream));
+        RT_HIP(c, hipMemsetAsync(c->d_frame.p, 0, c->target.pixels() * sizeof(float4), c->stream));
         RT_HIP(c, hipStreamSynchronize(c->stream));
     }
     c->stats.numRenderedFrames = 0; c->stats.totalKernelMs = 0; c->stats.queuedLaunches = 0;
@@ -1815,7 +1828,7 @@ int rt_write_accum(rt_ctx* c, const float* rgba, size_t n_floats, int frames_ren
     if (!c->have_params) return fail(c, -2, "rt_set_params has not been called");
     RT_HIP(c, hipSetDevice(c->device));
     { int r = ensure_targets(c); if (r) return r; }
-    if (n_floats != c->target_pixels * 4) return fail(c, -2, "expected %zu floats (rows*width*4), got %zu", c->target_pixels * 4, n_floats);
+    if (n_floats != c->target.pixels() * 4) return fail(c, -2, "expected %zu floats (rows*width*4), got %zu", c->target.pixels() * 4, n_floats);
     if (n_floats) {
         RT_HIP(c, hipMemcpyAsync(c->d_accum.p, rgba, n_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
         RT_HIP(c, hipStreamSynchronize(c->stream));
@@ -1834,19 +1847,11 @@ int rt_read_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
     RT_SETTLE(c);
     if (!rgba8 && n_pixels) return fail(c, -2, "null destination");
     if (c->have_params) { int r = ensure_targets(c); if (r) return r; }
-    if (n_pixels != c->target_pixels) return fail(c, -2, "expected %zu pixels (rows*width), got %zu", c->target_pixels, n_pixels);
+    if (n_pixels != c->target.pixels()) return fail(c, -2, "expected %zu pixels (rows*width), got %zu", c->target.pixels(), n_pixels);
     if (!n_pixels) return 0;
     RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, c->d_display.ensure(n_pixels));
-    RT_HIP(c, hipEventRecord(c->evg0, c->stream));
-    const int grid = (int)std::min<size_t>((n_pixels + 255) / 256, (size_t)c->n_cu * 8);
-    hipLaunchKernelGGL(rtg::k_display_srgb8, dim3(grid), dim3(256), 0, c->stream, c->d_accum.p, c->d_display.p, n_pixels);
-    RT_HIP(c, hipGetLastError());
-    RT_HIP(c, hipEventRecord(c->evg1, c->stream));
-    RT_HIP(c, hipMemcpyAsync(rgba8, c->d_display.p, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    RT_HIP(c, hipEventElapsedTime(&ms, c->evg0, c->evg1));
+    RT_HIP(c, display_plane(c, c->d_accum.p, c->d_display, rgba8, n_pixels, &ms));
     c->stats.lastDisplayMs = ms;
     return 0;
 }
@@ -1893,11 +1898,11 @@ int rt_reset_aov(rt_ctx* c)
     if (!c) return -1;
     RT_SETTLE(c);
     RT_HIP(c, hipSetDevice(c->device));
-    if (c->aov_pixels) {
-        for (DevBuf<float4>& b : c->d_aov) RT_HIP(c, hipMemsetAsync(b.p, 0, c->aov_pixels * sizeof(float4), c->stream));
+    if (c->aov.pixels()) {
+        for (DevBuf<float4>& b : c->d_aov) RT_HIP(c, hipMemsetAsync(b.p, 0, c->aov.pixels() * sizeof(float4), c->stream));
         RT_HIP(c, hipStreamSynchronize(c->stream));
     }
-    c->aov.framesAccumulated = 0; c->aov.totalKernelMs = 0;
+    c->aov_info.framesAccumulated = 0; c->aov_info.totalKernelMs = 0;
     return 0;
 }
 int rt_get_aov_info(rt_ctx* c, rt_aov_info* out)
@@ -1905,7 +1910,7 @@ int rt_get_aov_info(rt_ctx* c, rt_aov_info* out)
     if (!c) return -1;
     RT_SETTLE(c);
     if (!out) return fail(c, -2, "null info");
-    *out = c->aov;
+    *out = c->aov_info;
     return 0;
 }
 
@@ -1922,7 +1927,7 @@ int rt_read_denoised_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
     if (n_pixels != px) return fail(c, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
     if (!n_pixels) return 0;
     RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, display_plane(c->dn.out.p, c->d_display, rgba8, n_pixels, c->n_cu, c->stream));
+    RT_HIP(c, display_plane(c, c->dn.out.p, c->d_display, rgba8, n_pixels));
     return 0;
 }
 int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out)
@@ -1950,9 +1955,8 @@ int rt_get_stats(rt_ctx* c, rt_stats* out)
 // pixel), so every device holds the whole scene, renders the 8-row bands b with b % N == its rank for all frames, and one
 // gather at the end of rt_multi_render brings the strips to the first device: N - 1 peer copies (xGMI point-to-point, each over
 // its own link on a fully connected node) and a row scatter.  No other exchange exists on the path.
-struct rt_multi {
+struct rt_multi : ErrOwner {
     std::vector<rt_ctx*> ctx;
-    std::string err;
     int width = 0, height = 0;
     bool have_params = false;
     DevBuf<float4> d_image, d_staging;          // on the first context's device: the assembled image, the incoming strips
@@ -1969,27 +1973,41 @@ struct rt_multi {
 
 namespace {
 
-int mfail(rt_multi* m, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (m) m->err = buf; else g_create_error = buf;
-    return code;
-}
-
-// HIP calls of the gather / distribution phases: the failure goes to the rt_multi's own error string (rt_multi_last_error)
-#define M_HIP(m, expr)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return mfail(m, -100, "%s failed: %s", #expr, hipGetErrorString(e_));  \
-    } while (0)
-
 template <class Fn> int for_each_ctx(rt_multi* m, const char* what, Fn f)
 {
     for (size_t i = 0; i < m->ctx.size(); ++i) {
         const int r = f(m->ctx[i]);
-        if (r) return mfail(m, r, "%s on context %zu: %s", what, i, rt_last_error(m->ctx[i]));
+        if (r) return fail(m, r, "%s on context %zu: %s", what, i, rt_last_error(m->ctx[i]));
     }
+    return 0;
+}
+
+// fn(i) for every context at once — one host thread per context (a context is single-threaded, the contexts are independent), context
+// 0 on the caller's; the first context that failed is reported as a failure of `what`
+template <class Fn> int on_every_context(rt_multi* m, const char* what, Fn fn)
+{
+    const int N = (int)m->ctx.size();
+    std::vector<int> rc(N, 0);
+    {
+        std::vector<std::thread> th;
+        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = fn(i); });
+        rc[0] = fn(0);
+        for (std::thread& t : th) t.join();
+    }
+    for (int i = 0; i < N; ++i) if (rc[i]) return fail(m, rc[i], "%s on context %d: %s", what, i, rt_last_error(m->ctx[i]));
+    return 0;
+}
+
+// copy_plane's counterpart for the handle: a whole-image plane on the first device -> the host.  source(src) says where the plane is,
+// assembling it first if need be; it runs once the size is known to be right and not zero
+template <class Source> int read_image(rt_multi* m, size_t expect_floats, float* dst, size_t n_floats, Source source)
+{
+    if (n_floats != expect_floats) return fail(m, -2, "expected %zu floats (height*width*4), got %zu", expect_floats, n_floats);
+    if (!n_floats) return 0;
+    const float4* src = nullptr;
+    { int r = source(src); if (r) return r; }
+    RT_HIP(m, hipSetDevice(m->ctx[0]->device));
+    RT_HIP(m, hipMemcpy(dst, src, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2012,7 +2030,7 @@ extern "C" {
 
 rt_multi* rt_multi_create(const int* devices, int n_devices)
 {
-    if (n_devices < 1 || !devices) { mfail(nullptr, -1, "rt_multi_create: no devices given"); return nullptr; }
+    if (n_devices < 1 || !devices) { fail(nullptr, -1, "rt_multi_create: no devices given"); return nullptr; }
     rt_multi* m = new rt_multi();
     for (int i = 0; i < n_devices; ++i) {
         rt_ctx* c = rt_create(devices[i]);
@@ -2025,7 +2043,7 @@ rt_multi* rt_multi_create(const int* devices, int n_devices)
     m->ev_strip.assign(n_devices, nullptr);
     for (int i = 1; i < n_devices; ++i) {
         (void)hipSetDevice(m->ctx[i]->device);
-        if (hipEventCreateWithFlags(&m->ev_strip[i], hipEventDisableTiming) != hipSuccess) { mfail(nullptr, -1, "rt_multi_create: event for context %d", i); rt_multi_destroy(m); return nullptr; }
+        if (hipEventCreateWithFlags(&m->ev_strip[i], hipEventDisableTiming) != hipSuccess) { fail(nullptr, -1, "rt_multi_create: event for context %d", i); rt_multi_destroy(m); return nullptr; }
     }
     for (int i = 1; i < n_devices; ++i)
         if (m->ctx[i]->device != m->ctx[0]->device) {
@@ -2061,12 +2079,12 @@ rt_ctx* rt_multi_context(rt_multi* m, int i) { return (m && i >= 0 && i < (int)m
 int rt_multi_set_params(rt_multi* m, const rt_params* p)
 {
     if (!m) return -1;
-    if (!p) return mfail(m, -2, "null params");
+    if (!p) return fail(m, -2, "null params");
     const int N = (int)m->ctx.size();
     for (int i = 0; i < N; ++i) {
         int r = rt_set_params(m->ctx[i], p);
         if (!r) r = rt_set_bands(m->ctx[i], i, N);
-        if (r) return mfail(m, r, "rt_set_params on context %d: %s", i, rt_last_error(m->ctx[i]));
+        if (r) return fail(m, r, "rt_set_params on context %d: %s", i, rt_last_error(m->ctx[i]));
     }
     m->width = p->width; m->height = p->height; m->have_params = true;
     return 0;
@@ -2075,7 +2093,7 @@ int rt_multi_set_params(rt_multi* m, const rt_params* p)
 // contexts receive the built scene device to device (clone_scene) — one build and one host -> device upload per scene change, whatever N.
 static int multi_upload(rt_multi* m, int r, const char* what)
 {
-    if (r) return mfail(m, r, "%s on context 0: %s", what, rt_last_error(m->ctx[0]));
+    if (r) return fail(m, r, "%s on context 0: %s", what, rt_last_error(m->ctx[0]));
     m->scene_dirty = true;
     return 0;
 }
@@ -2122,21 +2140,21 @@ template <class Fn> int multi_share_scene(rt_multi* m, Fn build_root)
     for (rt_ctx* c : m->ctx) stale = stale || c->scene_dirty;       // (a builder option set through rt_multi_context(i), a context never filled)
     if (m->ctx[0]->geom_local) {
         // geometry pipeline: every context holds the local meshes and builds / refits on its own device, inside its rt_render below
-        for (rt_ctx* c : m->ctx) if (!c->geom_local) return mfail(m, -2, "rt_multi: some contexts hold local meshes and some do not (use the rt_multi_upload_* calls)");
+        for (rt_ctx* c : m->ctx) if (!c->geom_local) return fail(m, -2, "rt_multi: some contexts hold local meshes and some do not (use the rt_multi_upload_* calls)");
         stale = false; m->scene_dirty = false;
     }
     if (stale) {
         // ---- scene change: the first context builds (one BVH build, one host -> device upload), the others receive the result
         const double t0 = now_ms();
         rt_ctx* root = m->ctx[0];
-        { int r = build_root(root); if (r) return mfail(m, r, "scene build on context 0: %s", rt_last_error(root)); }
+        { int r = build_root(root); if (r) return fail(m, r, "scene build on context 0: %s", rt_last_error(root)); }
         std::vector<int> rcs(N, 0);
         {
             std::vector<std::thread> th;
             for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rcs[i] = clone_scene(m->ctx[i], root); });
             for (std::thread& t : th) t.join();
         }
-        for (int i = 1; i < N; ++i) if (rcs[i]) return mfail(m, rcs[i], "scene transfer to context %d: %s", i, rt_last_error(m->ctx[i]));
+        for (int i = 1; i < N; ++i) if (rcs[i]) return fail(m, rcs[i], "scene transfer to context %d: %s", i, rt_last_error(m->ctx[i]));
         m->scene_dirty = false;
         m->lastSetupMs = now_ms() - t0;
     }
@@ -2149,12 +2167,12 @@ template <class Strip, class Rows> int gather_strips(rt_multi* m, DevBuf<float4>
     const int N = (int)m->ctx.size();
     rt_ctx* root = m->ctx[0];
     const int W = m->width, H = m->height;
-    M_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, hipSetDevice(root->device));
     int max_rows = 0;
     for (rt_ctx* c : m->ctx) max_rows = std::max(max_rows, rows(c));
-    M_HIP(m, image.ensure((size_t)W * H));
-    M_HIP(m, m->d_staging.ensure((size_t)W * max_rows * (size_t)std::max(1, N - 1)));
-    M_HIP(m, hipStreamSynchronize(root->stream));           // (the staging area is allocated and idle: the sources may write)
+    RT_HIP(m, image.ensure((size_t)W * H));
+    RT_HIP(m, m->d_staging.ensure((size_t)W * max_rows * (size_t)std::max(1, N - 1)));
+    RT_HIP(m, hipStreamSynchronize(root->stream));           // (the staging area is allocated and idle: the sources may write)
     const double tg0 = now_ms();
     // every strip travels on ITS source context's stream — N - 1 independent transfers, each over its own xGMI link on a fully connected
     // node, in flight together — and the first device's stream waits for the N - 1 arrival events before it scatters the rows
@@ -2163,14 +2181,14 @@ template <class Strip, class Rows> int gather_strips(rt_multi* m, DevBuf<float4>
         const size_t pixels = (size_t)W * rows(c);
         if (pixels == 0) continue;
         float4* dst = m->d_staging.p + (size_t)(i - 1) * W * max_rows;
-        M_HIP(m, hipSetDevice(c->device));
-        if (c->device == root->device && !root->opt_peer_copies) M_HIP(m, hipMemcpyAsync(dst, strip(c), pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-        else M_HIP(m, hipMemcpyPeerAsync(dst, root->device, strip(c), c->device, pixels * sizeof(float4), c->stream));
-        M_HIP(m, hipEventRecord(m->ev_strip[i], c->stream));
+        RT_HIP(m, hipSetDevice(c->device));
+        if (c->device == root->device && !root->opt_peer_copies) RT_HIP(m, hipMemcpyAsync(dst, strip(c), pixels * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+        else RT_HIP(m, hipMemcpyPeerAsync(dst, root->device, strip(c), c->device, pixels * sizeof(float4), c->stream));
+        RT_HIP(m, hipEventRecord(m->ev_strip[i], c->stream));
     }
-    M_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, hipSetDevice(root->device));
     for (int i = 1; i < N; ++i)
-        if (rows(m->ctx[i]) != 0) M_HIP(m, hipStreamWaitEvent(root->stream, m->ev_strip[i], 0));
+        if (rows(m->ctx[i]) != 0) RT_HIP(m, hipStreamWaitEvent(root->stream, m->ev_strip[i], 0));
     for (int i = 0; i < N; ++i) {
         rt_ctx* c = m->ctx[i];
         if (rows(c) == 0) continue;
@@ -2178,8 +2196,8 @@ template <class Strip, class Rows> int gather_strips(rt_multi* m, DevBuf<float4>
         const int bands = (rows(c) + 7) / 8;
         hipLaunchKernelGGL(k_scatter_bands, dim3(std::max(1, std::min(64, (W * 8 + 255) / 256)), bands), dim3(256), 0, root->stream, src, image.p, W, H, i, N);
     }
-    M_HIP(m, hipGetLastError());
-    M_HIP(m, hipStreamSynchronize(root->stream));
+    RT_HIP(m, hipGetLastError());
+    RT_HIP(m, hipStreamSynchronize(root->stream));
     gather_ms = now_ms() - tg0;                 // host wall time from the first copy's submission to the assembled image (the copies run on N - 1 streams)
     return 0;
 }
@@ -2187,49 +2205,32 @@ template <class Strip, class Rows> int gather_strips(rt_multi* m, DevBuf<float4>
 // rt_multi_render (params null) and rt_multi_render_params (frame f with params[f] on every context)
 int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
 {
-    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
-    const int N = (int)m->ctx.size();
+    if (!m->have_params) return fail(m, -2, "rt_multi_set_params has not been called");
     { int r = multi_share_scene(m, [&](rt_ctx* root) { return launch_frames(root, first_frame, 0, Variant::Fast); }); if (r) return r; }
-    // every device renders its bands for all frames, concurrently: one host thread per context (a context is single-threaded,
-    // the contexts are independent)
-    std::vector<int> rc(N, 0);
-    {
-        std::vector<std::thread> th;
-        auto render = [&](int i) { return params ? rt_render_params(m->ctx[i], first_frame, n_frames, params) : rt_render(m->ctx[i], first_frame, n_frames); };
-        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = render(i); });
-        rc[0] = render(0);
-        for (std::thread& t : th) t.join();
-    }
-    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "%s on context %d: %s", params ? "rt_render_params" : "rt_render", i, rt_last_error(m->ctx[i]));
+    // every device renders its bands for all frames, concurrently
+    { int r = on_every_context(m, params ? "rt_render_params" : "rt_render", [&](int i) {
+          return params ? rt_render_params(m->ctx[i], first_frame, n_frames, params) : rt_render(m->ctx[i], first_frame, n_frames); });
+      if (r) return r; }
     // ---- the one gather: strips -> first device, rows to their places
     if ((size_t)m->width * m->height == 0) return 0;
-    return gather_strips(m, m->d_image, m->lastGatherMs, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target_rows; });
+    return gather_strips(m, m->d_image, m->lastGatherMs, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target.rows; });
 }
 
-// rt_multi_trace_rays / rt_multi_occluded: one contiguous slice of the batch per context, traced concurrently (one host thread per
-// context, as multi_render), each slice's results written in place
+// rt_multi_trace_rays / rt_multi_occluded: one contiguous slice of the batch per context, traced concurrently, each slice's results
+// written in place
 int multi_query(rt_multi* m, bool any, const rt_ray* rays, int n, void* out)
 {
     const char* what = any ? "rt_occluded" : "rt_trace_rays";
-    if (n < 0 || (n > 0 && (!rays || !out))) return mfail(m, -2, "rt_multi %s: bad arguments (n = %d)", what, n);
+    if (n < 0 || (n > 0 && (!rays || !out))) return fail(m, -2, "rt_multi %s: bad arguments (n = %d)", what, n);
     if (n == 0) return 0;
     { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
     const int N = (int)m->ctx.size();
     const int per = (n + N - 1) / N;
     const size_t out_size = any ? 1 : sizeof(rt_hit);
-    std::vector<int> rc(N, 0);
-    {
-        auto run = [&](int i) {
-            const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-            return query_host(m->ctx[i], any, rays + first, cnt, static_cast<char*>(out) + (size_t)first * out_size);
-        };
-        std::vector<std::thread> th;
-        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = run(i); });
-        rc[0] = run(0);
-        for (std::thread& t : th) t.join();
-    }
-    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "%s on context %d: %s", what, i, rt_last_error(m->ctx[i]));
-    return 0;
+    return on_every_context(m, what, [&](int i) {
+        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
+        return query_host(m->ctx[i], any, rays + first, cnt, static_cast<char*>(out) + (size_t)first * out_size);
+    });
 }
 } // namespace
 
@@ -2242,36 +2243,27 @@ int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded)
 int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)
 {
     if (!m) return -1;
-    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
-    if (n_frames < 0) return mfail(m, -2, "rt_multi_render_aov: n_frames < 0");
+    if (!m->have_params) return fail(m, -2, "rt_multi_set_params has not been called");
+    if (n_frames < 0) return fail(m, -2, "rt_multi_render_aov: n_frames < 0");
     if (n_frames == 0) return 0;
     { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
-    const int N = (int)m->ctx.size();
-    std::vector<int> rc(N, 0);
-    {
-        std::vector<std::thread> th;
-        for (int i = 1; i < N; ++i) th.emplace_back([&, i]() { rc[i] = rt_render_aov(m->ctx[i], first_frame, n_frames); });
-        rc[0] = rt_render_aov(m->ctx[0], first_frame, n_frames);
-        for (std::thread& t : th) t.join();
-    }
-    for (int i = 0; i < N; ++i) if (rc[i]) return mfail(m, rc[i], "rt_render_aov on context %d: %s", i, rt_last_error(m->ctx[i]));
-    return 0;
+    return on_every_context(m, "rt_render_aov", [&](int i) { return rt_render_aov(m->ctx[i], first_frame, n_frames); });
 }
 
 int rt_multi_read_aov(rt_multi* m, int which, float* rgba, size_t n_floats)
 {
     if (!m) return -1;
-    if (which < 0 || which >= RT_AOV_COUNT) return mfail(m, -2, "unknown feature plane %d", which);
-    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
-    if (!rgba) return mfail(m, -2, "null destination");
-    if (n_floats != (size_t)m->width * m->height * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", (size_t)m->width * m->height * 4, n_floats);
-    if (!n_floats) return 0;
-    // (a context that has rendered no feature frame yet holds zeroed planes of its strip)
-    { int r = for_each_ctx(m, "feature planes", [&](rt_ctx* c) { RT_SETTLE(c); RT_HIP(c, hipSetDevice(c->device)); return ensure_aov(c); }); if (r) return r; }
-    double gather_ms = 0;
-    { int r = gather_strips(m, m->d_aov_image, gather_ms, [&](rt_ctx* c) { return c->d_aov[which].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
-    M_HIP(m, hipMemcpy(rgba, m->d_aov_image.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    if (which < 0 || which >= RT_AOV_COUNT) return fail(m, -2, "unknown feature plane %d", which);
+    if (!m->have_params) return fail(m, -2, "rt_multi_set_params has not been called");
+    if (!rgba) return fail(m, -2, "null destination");
+    return read_image(m, (size_t)m->width * m->height * 4, rgba, n_floats, [&](const float4*& src) {
+        // (a context that has rendered no feature frame yet holds zeroed planes of its strip)
+        { int r = for_each_ctx(m, "feature planes", [&](rt_ctx* c) { RT_SETTLE(c); RT_HIP(c, hipSetDevice(c->device)); return ensure_aov(c); }); if (r) return r; }
+        double gather_ms = 0;
+        { int r = gather_strips(m, m->d_aov_image, gather_ms, [&](rt_ctx* c) { return c->d_aov[which].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
+        src = m->d_aov_image.p;
+        return 0;
+    });
 }
 
 int rt_multi_reset_aov(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_aov", [&](rt_ctx* c) { return rt_reset_aov(c); }) : -1; }
@@ -2280,53 +2272,48 @@ int rt_multi_reset_aov(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_aov",
 int rt_multi_denoise(rt_multi* m, const rt_denoise_params* params)
 {
     if (!m) return -1;
-    if (!m->have_params) return mfail(m, -2, "rt_multi_denoise: rt_multi_set_params has not been called");
+    if (!m->have_params) return fail(m, -2, "rt_multi_denoise: rt_multi_set_params has not been called");
     rt_denoise_params P;
-    if (const char* why = denoise_params(params, P)) return mfail(m, -2, "rt_multi_denoise: %s", why);
+    if (const char* why = denoise_params(params, P)) return fail(m, -2, "rt_multi_denoise: %s", why);
     for (size_t i = 0; i < m->ctx.size(); ++i) {
         rt_ctx* c = m->ctx[i];
-        { const int r = settle(c); if (r) return mfail(m, r, "context %zu: %s", i, rt_last_error(c)); }
-        int r0, nr, rstride;
-        if (strip_layout(c, r0, nr, rstride)) return mfail(m, -2, "context %zu: %s", i, rt_last_error(c));
-        const bool aov_current = c->d_aov[0].p && m->width == c->aov_w && m->height == c->aov_h && r0 == c->aov_row0 && nr == c->aov_rows && rstride == c->aov_row_stride;
-        const bool image_current = m->width == c->target_w && m->height == c->target_h && r0 == c->target_row0 && nr == c->target_rows && rstride == c->target_row_stride;
-        if (nr != 0 && (!aov_current || c->aov.framesAccumulated == 0)) return mfail(m, -2, "rt_multi_denoise: no feature frame accumulated on context %zu (call rt_multi_render_aov first)", i);
-        if (!image_current) return mfail(m, -2, "rt_multi_denoise: nothing rendered yet on context %zu", i);
+        { const int r = settle(c); if (r) return fail(m, r, "context %zu: %s", i, rt_last_error(c)); }
+        StripLayout L;
+        if (strip_layout(c, L)) return fail(m, -2, "context %zu: %s", i, rt_last_error(c));
+        L.w = m->width; L.h = m->height;        // (the image the handle assembles, whatever a context was told directly)
+        const bool image_current = L == c->target;
+        if (L.rows != 0 && (!aov_current(c, L) || c->aov_info.framesAccumulated == 0)) return fail(m, -2, "rt_multi_denoise: no feature frame accumulated on context %zu (call rt_multi_render_aov first)", i);
+        if (!image_current) return fail(m, -2, "rt_multi_denoise: nothing rendered yet on context %zu", i);
     }
     double gather_ms = 0;
-    { int r = gather_strips(m, m->d_image, gather_ms, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target_rows; }); if (r) return r; }
-    { int r = gather_strips(m, m->d_dn_albedo, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_ALBEDO].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
-    { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov_rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_image, gather_ms, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target.rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_albedo, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_ALBEDO].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
     rt_ctx* root = m->ctx[0];
-    M_HIP(m, hipSetDevice(root->device));
-    M_HIP(m, run_denoise(m->dn, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, run_denoise(m->dn, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
     return 0;
 }
 
 int rt_multi_read_denoised(rt_multi* m, float* rgba, size_t n_floats)
 {
     if (!m) return -1;
-    if (!m->dn.filled) return mfail(m, -2, "rt_multi_denoise has not been called");
-    if (!rgba) return mfail(m, -2, "null destination");
-    const size_t px = (size_t)m->dn.w * m->dn.h;
-    if (n_floats != px * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", px * 4, n_floats);
-    if (!n_floats) return 0;
-    M_HIP(m, hipSetDevice(m->ctx[0]->device));
-    M_HIP(m, hipMemcpy(rgba, m->dn.out.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    if (!m->dn.filled) return fail(m, -2, "rt_multi_denoise has not been called");
+    if (!rgba) return fail(m, -2, "null destination");
+    return read_image(m, (size_t)m->dn.w * m->dn.h * 4, rgba, n_floats, [&](const float4*& src) { src = m->dn.out.p; return 0; });
 }
 
 int rt_multi_read_denoised_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 {
     if (!m) return -1;
-    if (!m->dn.filled) return mfail(m, -2, "rt_multi_denoise has not been called");
-    if (!rgba8) return mfail(m, -2, "null destination");
+    if (!m->dn.filled) return fail(m, -2, "rt_multi_denoise has not been called");
+    if (!rgba8) return fail(m, -2, "null destination");
     const size_t px = (size_t)m->dn.w * m->dn.h;
-    if (n_pixels != px) return mfail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
+    if (n_pixels != px) return fail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
     if (!n_pixels) return 0;
     rt_ctx* root = m->ctx[0];
-    M_HIP(m, hipSetDevice(root->device));
-    M_HIP(m, display_plane(m->dn.out.p, m->d_display, rgba8, n_pixels, root->n_cu, root->stream));
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, display_plane(root, m->dn.out.p, m->d_display, rgba8, n_pixels));
     return 0;
 }
 
@@ -2339,10 +2326,10 @@ int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
 int rt_multi_render_params(rt_multi* m, int first_frame, int n_frames, const rt_params* params)
 {
     if (!m) return -1;
-    if (n_frames < 0) return mfail(m, -2, "n_frames < 0");
+    if (n_frames < 0) return fail(m, -2, "n_frames < 0");
     if (n_frames == 0) return 0;
-    if (!params) return mfail(m, -2, "null params");
-    if (const int f = other_settings(params, n_frames)) return mfail(m, -2, "rt_multi_render_params: entry %d differs from entry 0 outside the camera fields", f);
+    if (!params) return fail(m, -2, "null params");
+    if (const int f = other_settings(params, n_frames)) return fail(m, -2, "rt_multi_render_params: entry %d differs from entry 0 outside the camera fields", f);
     if (!m->have_params || !same_settings(m->ctx[0]->params, params[0])) { const int r = rt_multi_set_params(m, &params[0]); if (r) return r; }
     return multi_render(m, first_frame, n_frames, params);
 }
@@ -2351,18 +2338,13 @@ int rt_multi_render_params(rt_multi* m, int first_frame, int n_frames, const rt_
 int rt_multi_read_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 {
     if (!m) return -1;
-    if (!rgba8 && n_pixels) return mfail(m, -2, "null destination");
-    if (n_pixels != (size_t)m->width * m->height) return mfail(m, -2, "expected %zu pixels (height*width), got %zu", (size_t)m->width * m->height, n_pixels);
+    if (!rgba8 && n_pixels) return fail(m, -2, "null destination");
+    if (n_pixels != (size_t)m->width * m->height) return fail(m, -2, "expected %zu pixels (height*width), got %zu", (size_t)m->width * m->height, n_pixels);
     if (!n_pixels) return 0;
-    if (!m->d_image.p) return mfail(m, -2, "nothing rendered yet");
+    if (!m->d_image.p) return fail(m, -2, "nothing rendered yet");
     rt_ctx* root = m->ctx[0];
-    M_HIP(m, hipSetDevice(root->device));
-    M_HIP(m, m->d_display.ensure(n_pixels));
-    const int grid = (int)std::min<size_t>((n_pixels + 255) / 256, (size_t)root->n_cu * 8);
-    hipLaunchKernelGGL(rtg::k_display_srgb8, dim3(grid), dim3(256), 0, root->stream, m->d_image.p, m->d_display.p, n_pixels);
-    M_HIP(m, hipGetLastError());
-    M_HIP(m, hipMemcpyAsync(rgba8, m->d_display.p, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, root->stream));
-    M_HIP(m, hipStreamSynchronize(root->stream));
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, display_plane(root, m->d_image.p, m->d_display, rgba8, n_pixels));
     return 0;
 }
 
@@ -2370,10 +2352,10 @@ int rt_multi_read_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 int rt_multi_write_accum(rt_multi* m, const float* rgba, size_t n_floats, int frames_rendered)
 {
     if (!m) return -1;
-    if (!m->have_params) return mfail(m, -2, "rt_multi_set_params has not been called");
-    if (!rgba && n_floats) return mfail(m, -2, "null source");
+    if (!m->have_params) return fail(m, -2, "rt_multi_set_params has not been called");
+    if (!rgba && n_floats) return fail(m, -2, "null source");
     const int W = m->width, H = m->height, N = (int)m->ctx.size();
-    if (n_floats != (size_t)W * H * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", (size_t)W * H * 4, n_floats);
+    if (n_floats != (size_t)W * H * 4) return fail(m, -2, "expected %zu floats (height*width*4), got %zu", (size_t)W * H * 4, n_floats);
     std::vector<float> strip;
     for (int i = 0; i < N; ++i) {
         strip.clear();
@@ -2382,33 +2364,30 @@ int rt_multi_write_accum(rt_multi* m, const float* rgba, size_t n_floats, int fr
             strip.insert(strip.end(), rgba + (size_t)y0 * W * 4, rgba + (size_t)(y0 + rows) * W * 4);
         }
         const int r = rt_write_accum(m->ctx[i], strip.data(), strip.size(), frames_rendered);
-        if (r) return mfail(m, r, "rt_write_accum on context %d: %s", i, rt_last_error(m->ctx[i]));
+        if (r) return fail(m, r, "rt_write_accum on context %d: %s", i, rt_last_error(m->ctx[i]));
     }
     // the assembled image follows, so that rt_multi_read_accum / rt_multi_read_display show the restored state before the next render
     rt_ctx* root = m->ctx[0];
-    M_HIP(m, hipSetDevice(root->device));
-    M_HIP(m, m->d_image.ensure((size_t)W * H));
-    if (n_floats) M_HIP(m, hipMemcpy(m->d_image.p, rgba, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, m->d_image.ensure((size_t)W * H));
+    if (n_floats) RT_HIP(m, hipMemcpy(m->d_image.p, rgba, n_floats * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
 int rt_multi_read_accum(rt_multi* m, float* rgba, size_t n_floats)
 {
     if (!m) return -1;
-    if (!rgba && n_floats) return mfail(m, -2, "null destination");
-    if (n_floats != (size_t)m->width * m->height * 4) return mfail(m, -2, "expected %zu floats (height*width*4), got %zu", (size_t)m->width * m->height * 4, n_floats);
-    if (!n_floats) return 0;
-    if (!m->d_image.p) return mfail(m, -2, "nothing rendered yet");
-    rt_ctx* root = m->ctx[0];
-    M_HIP(m, hipSetDevice(root->device));
-    M_HIP(m, hipMemcpy(rgba, m->d_image.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    if (!rgba && n_floats) return fail(m, -2, "null destination");
+    return read_image(m, (size_t)m->width * m->height * 4, rgba, n_floats, [&](const float4*& src) {
+        src = m->d_image.p;
+        return src ? 0 : fail(m, -2, "nothing rendered yet");
+    });
 }
 
 int rt_multi_get_stats(rt_multi* m, rt_stats* out, double* gather_ms)
 {
     if (!m) return -1;
-    if (!out) return mfail(m, -2, "null stats");
+    if (!out) return fail(m, -2, "null stats");
     rt_stats sum = m->ctx[0]->stats;
     for (size_t i = 1; i < m->ctx.size(); ++i) {
         const rt_stats& s = m->ctx[i]->stats;
@@ -2424,7 +2403,7 @@ int rt_multi_get_stats(rt_multi* m, rt_stats* out, double* gather_ms)
 int rt_multi_get_info(rt_multi* m, rt_multi_info* out)
 {
     if (!m) return -1;
-    if (!out) return mfail(m, -2, "null info");
+    if (!out) return fail(m, -2, "null info");
     std::memset(out, 0, sizeof *out);
     out->numContexts = (int32_t)m->ctx.size();
     for (rt_ctx* c : m->ctx) out->bvhBuilds += c->stats.bvhBuilds;

@@ -507,6 +507,23 @@ __device__ __forceinline__ float mod2(float x) { return x - 2.0f * __builtin_flo
 
 struct Camera { v3 focusPoint, right, up, pos; float W; };
 
+// Trace :309-312 — the surface of a closest_hit answer (h.id != kNone): shading normal and material record (a triangle's is its chunk's)
+__device__ __forceinline__ void surface_of(const DeviceScene& S, const Hit& h, v3 hitPoint, v3& normal, const float4*& mat)
+{
+    if (h.id & kTriBit) {
+        const uint32_t ti = h.id & ~kTriBit;
+        const float4* tn = S.tri_nrm + (size_t)ti * 3;
+        const float4 n0 = tn[0], n1 = tn[1], n2 = tn[2];
+        const float w = 1.0f - h.u - h.v;
+        normal = rtm::normalize((rtm::mk(n0.x, n0.y, n0.z) * w + rtm::mk(n1.x, n1.y, n1.z) * h.u) + rtm::mk(n2.x, n2.y, n2.z) * h.v);
+        mat = S.chunk_mat + (size_t)__float_as_uint(n0.w) * 4;
+    } else {
+        const float4 s = S.sph_geom[h.id];
+        normal = rtm::normalize(hitPoint - rtm::mk(s.x, s.y, s.z));
+        mat = S.sph_mat + (size_t)h.id * 4;
+    }
+}
+
 // A *fresh* view of a kernel's argument segment (KA = the kernel's parameters as one struct, in order).  The megakernels are
 // persistent loops with regions that need different arguments (traversal: node / triangle arrays; shading: materials, camera,
 // environment; scheduling: queue and tile tables).  Read through the kernel's own parameters they are all loop invariants: the
@@ -663,6 +680,18 @@ __device__ __forceinline__ v3 render_pixel(const DeviceScene& S, const rt_params
 constexpr int kBlock = 256;         // 4 waves
 constexpr int kGroupMax = 32;       // k_stream: most work items in a wave's group (the LDS table of their decoded positions: 256 B per wave)
 constexpr int kWavesPerBlock = kBlock / 64;
+
+// This lane's traversal stack in a launch of kBlock-thread blocks, one query per lane: column `lane` of its wave's stack[entry][lane] in
+// LDS (cap entries), deeper entries in its column of gstack[entry][lane of the launch] (null: the tree fits)
+__device__ __forceinline__ TravStack lane_stack(uint32_t* lds_stack, int cap, uint32_t* gstack, unsigned int stride)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    TravStack stk;
+    stk.lds = lds_stack + (size_t)wave * cap * 64 + lane;
+    stk.cap = cap; stk.stride = stride;
+    stk.glb = gstack ? gstack + (blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    return stk;
+}
 
 // WAVES = waves per SIMD the register allocation aims at.  With a BVH the LDS stacks allow four workgroups per CU and the 95 VGPRs
 // the kernel takes by itself (five waves) are left alone (0); a scene of spheres only has no stack to speak of and is shading-bound:

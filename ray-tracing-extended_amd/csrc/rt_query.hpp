@@ -98,13 +98,9 @@ template <bool ANY, bool H>
 __global__ __launch_bounds__(kBlock) void k_ray_query(DeviceScene S, QueryArgs Q)
 {
     extern __shared__ uint32_t lds_stack[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= (unsigned)Q.n) return;
-    TravStack stk;
-    stk.lds = lds_stack + (size_t)wave * Q.stack_cap * 64 + lane;
-    stk.cap = Q.stack_cap; stk.stride = Q.gstack_stride;
-    stk.glb = Q.gstack ? Q.gstack + i : nullptr;
+    const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
     const float4 r0 = Q.rays[2 * (size_t)i], r1 = Q.rays[2 * (size_t)i + 1];
     const v3 o = rtm::mk(r0.x, r0.y, r0.z), d = rtm::mk(r1.x, r1.y, r1.z);
     const float t_max = r0.w;
@@ -128,20 +124,15 @@ __global__ __launch_bounds__(kBlock) void k_ray_query(DeviceScene S, QueryArgs Q
         w2 = make_float4(NEG1, NEG1, NEG1, ZERO);
     } else {
         const v3 hitPoint = o + d * h.t;                                // render_pixel (Trace :309)
-        v3 normal;
+        v3 normal; const float4* mat;
+        surface_of(S, h, hitPoint, normal, mat);
         if (h.id & kTriBit) {
             const uint32_t ti = h.id & ~kTriBit;
-            const float4* tn = S.tri_nrm + (size_t)ti * 3;
-            const float4 n0 = tn[0], n1 = tn[1], n2 = tn[2];
-            const float w = 1.0f - h.u - h.v;
-            normal = rtm::normalize((rtm::mk(n0.x, n0.y, n0.z) * w + rtm::mk(n1.x, n1.y, n1.z) * h.u) + rtm::mk(n2.x, n2.y, n2.z) * h.v);
             const uint32_t prim = Q.order[ti];
             const int mesh = Q.tri_mesh ? (int)Q.tri_mesh[prim] : -1;
             w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_TRIANGLE));
-            w2 = make_float4(__uint_as_float(prim), n0.w, __int_as_float(mesh), h.u);      // (n0.w: the chunk index's bits)
+            w2 = make_float4(__uint_as_float(prim), S.tri_nrm[(size_t)ti * 3].w, __int_as_float(mesh), h.u);      // (.w: the chunk index's bits)
         } else {
-            const float4 s = S.sph_geom[h.id];
-            normal = rtm::normalize(hitPoint - rtm::mk(s.x, s.y, s.z));
             w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_SPHERE));
             w2 = make_float4(__uint_as_float(h.id), NEG1, NEG1, ZERO);
         }
