@@ -515,6 +515,84 @@ int rt_copy_denoised_to_device(rt_ctx* ctx, void* dst_device_ptr, size_t n_float
 int rt_read_denoised_display(rt_ctx* ctx, uint32_t* rgba8, size_t n_pixels);
 int rt_get_denoise_info(rt_ctx* ctx, rt_denoise_info* out);
 
+/* ---- temporal reprojection: carry the image along with a moving camera ---------------------------------------------------
+ * rt_temporal is the step between resultTexture and rt_denoise for a camera that moves between displayed frames.  The reference has
+ * none: it keeps accumulating, and resultTexture smears.  The caller here resets the accumulation at every pose,
+ *     rt_set_params(pose); rt_reset_accum; rt_render(f, k); rt_reset_aov; rt_render_aov(f, k);
+ *     rt_temporal(NULL); rt_denoise_temporal(NULL); rt_read_denoised_display(...)
+ * and rt_temporal reprojects its previous result into the new view through the first-hit depth, rejects history that belongs to
+ * another surface and blends the new samples in with a per-pixel history length (the temporal stage of SVGF, Schied et al., HPG 2017,
+ * without its variance estimate).  The step keeps its own state: the temporal colour T (RGBA32F), the history length N (one float per
+ * pixel), the guide (normal, depth) and the camera of its previous call.
+ * SCOPE: a static scene seen by a moving camera.  There are no motion vectors: the history of a mesh that moved is reprojected as if
+ * it had stood still, and the depth and normal test rejects most of it, not all.  rt_reset_temporal is the caller's tool for a scene
+ * change.
+ *
+ * The definition is frozen to the bit.  All arithmetic is IEEE float32 without FMA contraction, every '/' a correctly rounded quotient,
+ * sqrt correctly rounded, normalize(v) = v / sqrt(dot(v, v)) (three quotients, csrc/rt_math.hpp), floor the IEEE floor,
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z everywhere, |v|^2 = dot(v, v), and the operations of an expression are evaluated in the
+ * order written, left to right within the brackets given.  Inputs of call k: C = resultTexture, A and G = the feature planes, the
+ * camera fields of the context's current rt_params M = camLocalToWorld, O = worldSpaceCameraPos, V = viewParams, and from call k - 1
+ * the temporal colour T', the history length N', the guide G' and the camera M', O', V'.  Call 0 (the first call, the first after
+ * rt_reset_temporal or after a change of the image size) has N' = 0 everywhere, so every pixel takes "no history".  W and H below are
+ * (float)width and (float)height.  Per pixel p = (x, y):
+ *
+ *   surface       cov = A.w, surf = cov > 0; nc = (G.x / cov, G.y / cov, G.z / cov) and zc = G.w / cov if surf, else all 0.
+ *   centre ray    frag's ray without jitter (RayTracing.shader:364-372): uv = (((float)x + 0.5f) / W, ((float)y + 0.5f) / H),
+ *                 l = ((uv.x - 0.5f) * V.x, (uv.y - 0.5f) * V.y, 1.0f * V.z),
+ *                 F.r = ((M[4r] * l.x + M[4r+1] * l.y) + M[4r+2] * l.z) + M[4r+3] * 1.0f for r = 0, 1, 2,  dir = normalize(F - O).
+ *   point         X = O + dir * zc (X.i = O.i + dir.i * zc).  Surface: q = X - t' with t' = (M'[3], M'[7], M'[11]), d = X - O',
+ *                 ze = sqrt(dot(d, d)).  Sky: q = dir (the sky is at infinity: only the rotation counts).
+ *   previous view with c_i = (M'[i], M'[4+i], M'[8+i]), the columns of the upper 3 x 3: l'_i = dot(c_i, q) / dot(c_i, c_i), i = 0, 1, 2.
+ *                 s = V'.z / l'_2;  px = ((l'_0 * s) / V'.x + 0.5f) * W - 0.5f,  py = ((l'_1 * s) / V'.y + 0.5f) * H - 0.5f.
+ *                 valid = l'_2 > 0 && px > -1 && px < W && py > -1 && py < H (NaN fails each comparison).  Not valid: no tap counts.
+ *   taps          x0 = floor(px), fx = px - x0, y0 = floor(py), fy = py - y0.  The taps (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1
+ *                 inner, weigh b = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy).  A tap counts if it lies inside the image, N'(tap) > 0
+ *                 and, for a surface pixel, G'.w > 0 && fabs(G'.w - ze) <= depthTolerance * ze && dot(e, e) <= normalTolerance *
+ *                 normalTolerance with e = nc - G'.xyz; for a sky pixel, G'.w == 0.  A tap that does not count is skipped, not
+ *                 clamped.  In tap order: sw = sw + b, h.ch = h.ch + b * T'.ch (ch = r, g, b), hn = hn + b * N'.
+ *   blend         if sw >= 0.01f: t = hn / sw + 1.0f, n = t < (float)maxHistory ? t : (float)maxHistory, a = 1.0f / n,
+ *                 T.ch = (h.ch / sw) * (1.0f - a) + C.ch * a.  Otherwise (no history) n = 1 and T.rgb = C.rgb, the same bits.
+ *                 In both cases T.a = C.a and N = n.
+ *   afterwards    G' = (nc, zc), the camera becomes the previous camera, T and N become T' and N'.
+ *
+ * Non-finite inputs give whatever this arithmetic gives; the call does not fault on them and forms no index outside the planes.
+ * rt_temporal settles the queue, runs on the context's stream (rt_set_stream) and moves nothing else: resultTexture, currentFrame,
+ * numRenderedFrames, the feature planes, rt_aov_info, rt_denoise_info and every rt_stats field stay.  It needs the whole image in one
+ * context: a context that rt_set_rows / rt_set_bands has given less returns -2 (use rt_multi_temporal).  Its planes are created at
+ * first use and again when the image size changes, which also drops the history.  params == NULL means RT_TEMPORAL_DEFAULT_* (chosen
+ * by the sweep of profiles/temporal_defaults.txt).  rt_denoise_temporal is rt_denoise with C = T: the same kernels, the same
+ * denoised plane (rt_read_denoised*), the same rt_denoise_info.
+ * Errors: null handle -1; no params set, no feature frame accumulated, maxHistory outside 1..4096, a tolerance that is <= 0 or not
+ * finite, a wrong n_floats / n_pixels, a null buffer, a read before any rt_temporal (or after rt_reset_temporal),
+ * rt_denoise_temporal before any rt_temporal or at another image size: -2 with a message, and nothing changed.                   */
+typedef struct rt_temporal_params {     /* 32 B */
+    int32_t maxHistory;                 /* 1..4096: the history length is capped here (a = 1 / maxHistory at the least)        */
+    float   depthTolerance;             /* relative to the reprojected point's distance; finite and > 0                       */
+    float   normalTolerance;            /* on |nc - G'.xyz|; finite and > 0                                                   */
+    int32_t _reserved[5];
+} rt_temporal_params;
+#define RT_TEMPORAL_DEFAULT_MAX_HISTORY      32
+#define RT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE  0.05f
+#define RT_TEMPORAL_DEFAULT_NORMAL_TOLERANCE 0.5f
+typedef struct rt_temporal_info {       /* 32 B */
+    int32_t calls;                      /* rt_temporal calls since the history was last dropped                              */
+    int32_t width, height;
+    int32_t _reserved;
+    double  lastKernelMs;               /* HIP-event time of the last call's launch                                          */
+    double  totalKernelMs;
+} rt_temporal_info;
+int rt_temporal(rt_ctx* ctx, const rt_temporal_params* params);
+int rt_reset_temporal(rt_ctx* ctx);
+/* T: height*width*4 floats, row 0 = bottom (rt_read_accum's layout for a whole image); N: height*width floats */
+int rt_read_temporal(rt_ctx* ctx, float* rgba, size_t n_floats);
+int rt_read_temporal_history(rt_ctx* ctx, float* n, size_t n_floats);
+int rt_copy_temporal_to_device(rt_ctx* ctx, void* dst_device_ptr, size_t n_floats);
+/* the display step of rt_read_display applied to T (height*width pixels) */
+int rt_read_temporal_display(rt_ctx* ctx, uint32_t* rgba8, size_t n_pixels);
+int rt_get_temporal_info(rt_ctx* ctx, rt_temporal_info* out);
+int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params);
+
 /* ---- several GPUs of one node behind one handle ---------------------------------------------------------------------
  * The reference renders on one GPU; its path shards into independent pixels (seed = global pixel index + Frame * 719393,
  * RayTracing.shader:360-362; Accumulate.shader is per pixel), so the frame tiles across devices by rows.  An rt_multi owns one
@@ -585,10 +663,20 @@ int rt_multi_reset_aov       (rt_multi* m);
 int rt_multi_denoise              (rt_multi* m, const rt_denoise_params* params);
 int rt_multi_read_denoised        (rt_multi* m, float* rgba, size_t n_floats);
 int rt_multi_read_denoised_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels);
+/* Temporal reprojection behind the handle: the strips of C, A and G are gathered to the first device as for rt_multi_denoise and the
+ * step of rt_temporal runs there, on the first context's stream, with the camera of the handle's current params; T, N, the previous
+ * guide and the previous camera are kept on the handle — bitwise the single-context result.  rt_multi_denoise_temporal is
+ * rt_multi_denoise with C = the handle's T (the feature planes are gathered again); its result is read with rt_multi_read_denoised*. */
+int rt_multi_temporal             (rt_multi* m, const rt_temporal_params* params);
+int rt_multi_reset_temporal       (rt_multi* m);
+int rt_multi_read_temporal        (rt_multi* m, float* rgba, size_t n_floats);
+int rt_multi_read_temporal_history(rt_multi* m, float* n, size_t n_floats);
+int rt_multi_read_temporal_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels);
+int rt_multi_denoise_temporal     (rt_multi* m, const rt_denoise_params* params);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" */
 
 #ifdef __cplusplus
 }

@@ -65,10 +65,17 @@ DENOISE_PARAMS = np.dtype([("iterations", "<i4"), ("demodulate", "<i4"), ("sigma
 DENOISE_INFO = np.dtype([("iterations", "<i4"), ("demodulate", "<i4"), ("width", "<i4"), ("height", "<i4"),
                          ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert DENOISE_PARAMS.itemsize == 32 and DENOISE_INFO.itemsize == 32
+# temporal reprojection (rt_temporal): the parameters of a call and the state of the step
+TEMPORAL_PARAMS = np.dtype([("maxHistory", "<i4"), ("depthTolerance", "<f4"), ("normalTolerance", "<f4"), ("_reserved", "<i4", 5)])
+TEMPORAL_INFO = np.dtype([("calls", "<i4"), ("width", "<i4"), ("height", "<i4"), ("_reserved", "<i4"),
+                          ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert TEMPORAL_PARAMS.itemsize == 32 and TEMPORAL_INFO.itemsize == 32
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
 DENOISE_DEFAULTS = {"iterations": 5, "demodulate": 0, "sigmaColour": 16.0, "sigmaNormal": 1.0, "sigmaDepth": 0.5}
+# RT_TEMPORAL_DEFAULT_* of include/rt.h (what a null rt_temporal_params means)
+TEMPORAL_DEFAULTS = {"maxHistory": 32, "depthTolerance": 0.05, "normalTolerance": 0.5}
 
 RT_INTERSECT_FLAT_CHUNKS = 0
 RT_INTERSECT_BRUTE = 1
@@ -90,6 +97,10 @@ SYMBOLS = [
     "rt_multi_render_aov", "rt_multi_read_aov", "rt_multi_reset_aov",
     "rt_denoise", "rt_read_denoised", "rt_copy_denoised_to_device", "rt_read_denoised_display", "rt_get_denoise_info",
     "rt_multi_denoise", "rt_multi_read_denoised", "rt_multi_read_denoised_display",
+    "rt_temporal", "rt_reset_temporal", "rt_read_temporal", "rt_read_temporal_history", "rt_copy_temporal_to_device",
+    "rt_read_temporal_display", "rt_get_temporal_info", "rt_denoise_temporal",
+    "rt_multi_temporal", "rt_multi_reset_temporal", "rt_multi_read_temporal", "rt_multi_read_temporal_history", "rt_multi_read_temporal_display",
+    "rt_multi_denoise_temporal",
 ]
 
 _lib = None
@@ -184,6 +195,20 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_denoise.argtypes = [c_void_p, c_void_p]
     lib.rt_multi_read_denoised.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     lib.rt_multi_read_denoised_display.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_temporal.argtypes = [c_void_p, c_void_p]
+    lib.rt_reset_temporal.argtypes = [c_void_p]
+    lib.rt_read_temporal.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_read_temporal_history.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_copy_temporal_to_device.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_read_temporal_display.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_get_temporal_info.argtypes = [c_void_p, c_void_p]
+    lib.rt_denoise_temporal.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_temporal.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_reset_temporal.argtypes = [c_void_p]
+    lib.rt_multi_read_temporal.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_multi_read_temporal_history.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_multi_read_temporal_display.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_multi_denoise_temporal.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -194,7 +219,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_meshinfo", MESHINFO), ("rt_params", PARAMS), ("rt_stats", STATS),
                      ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO),
                      ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO),
-                     ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO)):
+                     ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO),
+                     ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -237,6 +263,21 @@ def _denoise_params(params: dict):
     for k, v in params.items():
         if k not in DENOISE_DEFAULTS:
             raise TypeError(f"denoise: unknown parameter {k!r} (one of {sorted(DENOISE_DEFAULTS)})")
+        p[k] = v
+    return p
+
+
+def _temporal_params(params: dict):
+    """None (the library's defaults) when no field is given; else a TEMPORAL_PARAMS record: the defaults of include/rt.h with the given
+    fields (maxHistory, depthTolerance, normalTolerance) replaced"""
+    if not params:
+        return None
+    p = np.zeros((), TEMPORAL_PARAMS)
+    for k, v in TEMPORAL_DEFAULTS.items():
+        p[k] = v
+    for k, v in params.items():
+        if k not in TEMPORAL_DEFAULTS:
+            raise TypeError(f"temporal: unknown parameter {k!r} (one of {sorted(TEMPORAL_DEFAULTS)})")
         p[k] = v
     return p
 
@@ -516,6 +557,49 @@ class Tracer:
         self._check(self._lib.rt_get_denoise_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_denoise_info")
         return {k: s[k].item() for k in DENOISE_INFO.names}
 
+    # -- temporal reprojection
+    def temporal(self, **params):
+        """rt_temporal: reproject the previous temporal colour into the current camera's view and blend resultTexture in.  Keywords:
+        maxHistory, depthTolerance, normalTolerance; none = the library's defaults."""
+        p = _temporal_params(params)
+        self._check(self._lib.rt_temporal(self._ctx, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_temporal")
+
+    def reset_temporal(self):
+        self._check(self._lib.rt_reset_temporal(self._ctx), "rt_reset_temporal")
+
+    def read_temporal(self) -> np.ndarray:
+        H, W = self._image_shape()
+        out = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.rt_read_temporal(self._ctx, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_read_temporal")
+        return out
+
+    def read_temporal_history(self) -> np.ndarray:
+        """the history length N per pixel, shape (H, W)"""
+        H, W = self._image_shape()
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.rt_read_temporal_history(self._ctx, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_read_temporal_history")
+        return out
+
+    def read_temporal_display(self) -> np.ndarray:
+        """the temporal colour as sRGB RGBA8, shape (H, W, 4) uint8, row 0 = bottom"""
+        H, W = self._image_shape()
+        out = np.empty((H, W), np.uint32)
+        self._check(self._lib.rt_read_temporal_display(self._ctx, out.ctypes.data_as(c_void_p), out.size), "rt_read_temporal_display")
+        return out.view(np.uint8).reshape(H, W, 4)
+
+    def copy_temporal_to_device(self, device_ptr: int, n_floats: int):
+        self._check(self._lib.rt_copy_temporal_to_device(self._ctx, c_void_p(device_ptr), n_floats), "rt_copy_temporal_to_device")
+
+    def temporal_info(self) -> dict:
+        s = np.zeros((), TEMPORAL_INFO)
+        self._check(self._lib.rt_get_temporal_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_temporal_info")
+        return {k: s[k].item() for k in TEMPORAL_INFO.names if k != "_reserved"}
+
+    def denoise_temporal(self, **params):
+        """rt_denoise_temporal: Tracer.denoise with the temporal colour in place of resultTexture; read with read_denoised*"""
+        p = _denoise_params(params)
+        self._check(self._lib.rt_denoise_temporal(self._ctx, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_denoise_temporal")
+
     def stats(self) -> dict:
         s = np.zeros((), STATS)
         self._check(self._lib.rt_get_stats(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_stats")
@@ -673,6 +757,45 @@ class MultiTracer:
             return {"iterations": 0, "demodulate": 0, "width": 0, "height": 0}
         H, W = self._shape
         return {"iterations": int(last["iterations"]), "demodulate": int(last["demodulate"]), "width": W, "height": H}
+
+    # -- temporal reprojection
+    def temporal(self, **params):
+        """rt_multi_temporal: image and feature planes gathered to the first device, Tracer.temporal's step there"""
+        p = _temporal_params(params)
+        self._check(self._lib.rt_multi_temporal(self._m, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_multi_temporal")
+        self._temporal_calls = getattr(self, "_temporal_calls", 0) + 1
+
+    def reset_temporal(self):
+        self._check(self._lib.rt_multi_reset_temporal(self._m), "rt_multi_reset_temporal")
+        self._temporal_calls = 0
+
+    def read_temporal(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W, 4), np.float32)
+        self._check(self._lib.rt_multi_read_temporal(self._m, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_temporal")
+        return out
+
+    def read_temporal_history(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.rt_multi_read_temporal_history(self._m, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_temporal_history")
+        return out
+
+    def read_temporal_display(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W), np.uint32)
+        self._check(self._lib.rt_multi_read_temporal_display(self._m, out.ctypes.data_as(c_void_p), out.size), "rt_multi_read_temporal_display")
+        return out.view(np.uint8).reshape(H, W, 4)
+
+    def temporal_info(self) -> dict:
+        """the calls since the history was last dropped and the image size (the C-ABI keeps kernel times per context only)"""
+        H, W = self._shape
+        return {"calls": getattr(self, "_temporal_calls", 0), "width": W, "height": H}
+
+    def denoise_temporal(self, **params):
+        p = _denoise_params(params)
+        self._check(self._lib.rt_multi_denoise_temporal(self._m, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_multi_denoise_temporal")
+        self._denoise_last = dict(DENOISE_DEFAULTS, **params)
 
     def stats(self) -> dict:
         s = np.zeros((), STATS)

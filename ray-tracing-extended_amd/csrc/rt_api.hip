@@ -32,6 +32,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_query.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
+#include "rt_temporal.hpp"
 
 namespace {
 
@@ -65,6 +66,18 @@ struct DenoisePlanes {
     bool filled = false;            // `out` holds the result of a call
     rt_denoise_info info{};
     void release() { e[0].release(); e[1].release(); d.release(); out.release(); w = h = 0; filled = false; }
+};
+
+// the state of temporal reprojection for one image size (rt_temporal, csrc/rt_temporal.hpp): T, N and the guide G' as ping-pong pairs
+// (`cur` is the pair the last call wrote) and the camera of the last call
+struct TemporalPlanes {
+    DevBuf<float4> t[2], g[2];
+    DevBuf<float> n[2];
+    int w = 0, h = 0, cur = 0;
+    bool filled = false;            // t[cur], n[cur] and g[cur] hold the result of a call; `cam` is that call's camera
+    rt_params cam{};                // (its camera fields)
+    rt_temporal_info info{};
+    void release() { for (int i = 0; i < 2; ++i) { t[i].release(); g[i].release(); n[i].release(); } w = h = 0; filled = false; info = rt_temporal_info{}; }
 };
 
 // The rows of the image a context renders (rt_set_rows / rt_set_bands) and so the layout of the planes that hold them: local row ly is
@@ -187,6 +200,7 @@ struct rt_ctx : ErrOwner {
     StripLayout aov;                    // (meaningful once d_aov[0].p is set: ensure_aov)
     rt_aov_info aov_info{};
     DenoisePlanes dn;                   // rt_denoise
+    TemporalPlanes tp;                  // rt_temporal
     hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
     rt_stats stats{};
 
@@ -1484,6 +1498,133 @@ hipError_t display_plane(rt_ctx* c, const float4* plane, DevBuf<uint32_t>& displ
     return kernel_ms ? hipEventElapsedTime(kernel_ms, c->evg0, c->evg1) : hipSuccess;
 }
 
+// ---- temporal reprojection (rt_temporal, csrc/rt_temporal.hpp) --------------------------------------------------------------------
+static_assert(sizeof(rt_temporal_params) == 32 && sizeof(rt_temporal_info) == 32, "temporal ABI");
+
+const char* temporal_params(const rt_temporal_params* in, rt_temporal_params& P)
+{
+    if (in) P = *in;
+    else {
+        P = rt_temporal_params{};
+        P.maxHistory = RT_TEMPORAL_DEFAULT_MAX_HISTORY;
+        P.depthTolerance = RT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE; P.normalTolerance = RT_TEMPORAL_DEFAULT_NORMAL_TOLERANCE;
+    }
+    if (P.maxHistory < 1 || P.maxHistory > 4096) return "maxHistory outside 1..4096";
+    for (float tol : { P.depthTolerance, P.normalTolerance })
+        if (!std::isfinite(tol) || !(tol > 0.0f)) return "a tolerance is not finite or not > 0";
+    return nullptr;
+}
+
+// The step: C (resultTexture), A and G (the feature planes), all W x H float4 on the current device, and the camera fields of `cam`
+// -> the other pair of S's planes, on `stream`, timed by ev0 / ev1 and waited for.  Shared by rt_temporal and rt_multi_temporal; P has
+// passed temporal_params.  Without history (call 0) N' is zeroed, so no tap counts, and the previous camera is this call's.
+hipError_t run_temporal(TemporalPlanes& S, const float4* C, const float4* A, const float4* G, int W, int H, const rt_params& cam,
+                        const rt_temporal_params& P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const size_t px = (size_t)W * H;
+    hipError_t e;
+    if (S.w != W || S.h != H || !S.t[0].p) {
+        for (int i = 0; i < 2; ++i)
+            if ((e = S.t[i].ensure(px)) != hipSuccess || (e = S.g[i].ensure(px)) != hipSuccess || (e = S.n[i].ensure(px)) != hipSuccess) return e;
+        S.w = W; S.h = H; S.filled = false; S.info = rt_temporal_info{};
+    }
+    const int prev = S.cur, next = S.cur ^ 1;
+    float ms = 0.f;
+    if (px) {
+        if (!S.filled) {            // no history: T', N' and G' read as zero
+            if ((e = hipMemsetAsync(S.t[prev].p, 0, px * sizeof(float4), stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(S.g[prev].p, 0, px * sizeof(float4), stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(S.n[prev].p, 0, px * sizeof(float), stream)) != hipSuccess) return e;
+        }
+        const rt_params& pc = S.filled ? S.cam : cam;
+        rtk::TemporalArgs a{};
+        a.C = C; a.A = A; a.G = G;
+        a.Tp = S.t[prev].p; a.Np = S.n[prev].p; a.Gp = S.g[prev].p;
+        a.T = S.t[next].p; a.N = S.n[next].p; a.Gn = S.g[next].p;
+        a.W = W; a.H = H;
+        for (int i = 0; i < 12; ++i) a.M[i] = cam.camLocalToWorld[i];
+        const float* Mp = pc.camLocalToWorld;
+        for (int i = 0; i < 3; ++i) {
+            a.O[i] = cam.worldSpaceCameraPos[i]; a.V[i] = cam.viewParams[i];
+            a.pO[i] = pc.worldSpaceCameraPos[i]; a.pV[i] = pc.viewParams[i];
+            a.pt[i] = Mp[4 * i + 3];
+            const float cx = Mp[i], cy = Mp[4 + i], cz = Mp[8 + i];
+            a.pc[i][0] = cx; a.pc[i][1] = cy; a.pc[i][2] = cz;
+            a.pcc[i] = (cx * cx + cy * cy) + cz * cz;
+        }
+        a.depthTol = P.depthTolerance; a.normalTol2 = P.normalTolerance * P.normalTolerance; a.maxHistory = (float)P.maxHistory;
+        const dim3 grid((W + rtk::kTemporalTileW - 1) / rtk::kTemporalTileW, (H + rtk::kTemporalTileH - 1) / rtk::kTemporalTileH);
+        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(rtk::k_temporal, grid, dim3(256), 0, stream, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
+    }
+    S.cur = next; S.filled = true; S.cam = cam;
+    S.info.calls += 1; S.info.width = W; S.info.height = H;
+    S.info.lastKernelMs = ms; S.info.totalKernelMs += ms;
+    return hipSuccess;
+}
+
+// what rt_temporal and rt_denoise_temporal ask of a context before they run: params, the whole image, current feature planes with a
+// frame in them
+int whole_image_with_features(rt_ctx* c, const char* what, StripLayout& L)
+{
+    if (!c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", what);
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
+        return fail(c, -2, "%s: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_temporal", what, L.rows, L.h);
+    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "%s: no feature frame accumulated (call rt_render_aov first)", what);
+    return 0;
+}
+
+int temporal(rt_ctx* c, const rt_temporal_params* in)
+{
+    RT_SETTLE(c);
+    if (!c->have_params) return fail(c, -2, "rt_temporal: rt_set_params has not been called");
+    rt_temporal_params P;
+    if (const char* why = temporal_params(in, P)) return fail(c, -2, "rt_temporal: %s", why);
+    StripLayout L;
+    { int r = whole_image_with_features(c, "rt_temporal", L); if (r) return r; }
+    RT_HIP(c, hipSetDevice(c->device));
+    { int r = ensure_targets(c); if (r) return r; }             // (as in rt_denoise)
+    RT_HIP(c, run_temporal(c->tp, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, c->params, P,
+                           c->stream, c->ev_dn0, c->ev_dn1));
+    return 0;
+}
+
+int denoise_temporal(rt_ctx* c, const rt_denoise_params* in)
+{
+    RT_SETTLE(c);
+    if (!c->have_params) return fail(c, -2, "rt_denoise_temporal: rt_set_params has not been called");
+    rt_denoise_params P;
+    if (const char* why = denoise_params(in, P)) return fail(c, -2, "rt_denoise_temporal: %s", why);
+    StripLayout L;
+    { int r = whole_image_with_features(c, "rt_denoise_temporal", L); if (r) return r; }
+    if (!c->tp.filled) return fail(c, -2, "rt_denoise_temporal: rt_temporal has not been called");
+    if (c->tp.w != L.w || c->tp.h != L.h) return fail(c, -2, "rt_denoise_temporal: the temporal image is %d x %d, the context's image %d x %d", c->tp.w, c->tp.h, L.w, L.h);
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, run_denoise(c->dn, c->tp.t[c->tp.cur].p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
+    return 0;
+}
+
+// T (history false: height*width*4 floats) or N (history true: height*width floats) of the last call
+int read_temporal(rt_ctx* c, bool history, void* dst, size_t n_floats, bool to_device)
+{
+    RT_SETTLE(c);
+    if (!c->tp.filled) return fail(c, -2, "rt_temporal has not been called");
+    if (!dst) return fail(c, -2, "null destination");
+    const size_t px = (size_t)c->tp.w * c->tp.h;
+    if (!history) return copy_plane(c, c->tp.t[c->tp.cur].p, px * 4, "height", dst, n_floats, to_device);
+    if (n_floats != px) return fail(c, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(dst, c->tp.n[c->tp.cur].p, n_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1507,6 +1648,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_aov_info")) return (int)sizeof(rt_aov_info);
     if (!std::strcmp(name, "rt_denoise_params")) return (int)sizeof(rt_denoise_params);
     if (!std::strcmp(name, "rt_denoise_info")) return (int)sizeof(rt_denoise_info);
+    if (!std::strcmp(name, "rt_temporal_params")) return (int)sizeof(rt_temporal_params);
+    if (!std::strcmp(name, "rt_temporal_info")) return (int)sizeof(rt_temporal_info);
     return -1;
 }
 
@@ -1567,6 +1710,7 @@ void rt_destroy(rt_ctx* c)
     c->d_q_rays.release(); c->d_q_hits.release(); c->d_q_occ.release(); c->d_q_bound.release();
     for (DevBuf<float4>& b : c->d_aov) b.release();
     c->dn.release();
+    c->tp.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1939,6 +2083,40 @@ int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out)
     return 0;
 }
 
+int rt_temporal(rt_ctx* c, const rt_temporal_params* params) { return c ? temporal(c, params) : -1; }
+int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* params) { return c ? denoise_temporal(c, params) : -1; }
+int rt_reset_temporal(rt_ctx* c)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    c->tp.filled = false; c->tp.info.calls = 0; c->tp.info.lastKernelMs = 0; c->tp.info.totalKernelMs = 0;
+    return 0;
+}
+int rt_read_temporal(rt_ctx* c, float* rgba, size_t n) { return c ? read_temporal(c, false, rgba, n, false) : -1; }
+int rt_read_temporal_history(rt_ctx* c, float* hist, size_t n) { return c ? read_temporal(c, true, hist, n, false) : -1; }
+int rt_copy_temporal_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_temporal(c, false, dst, n, true) : -1; }
+int rt_read_temporal_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!c->tp.filled) return fail(c, -2, "rt_temporal has not been called");
+    if (!rgba8) return fail(c, -2, "null destination");
+    const size_t px = (size_t)c->tp.w * c->tp.h;
+    if (n_pixels != px) return fail(c, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
+    if (!n_pixels) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, display_plane(c, c->tp.t[c->tp.cur].p, c->d_display, rgba8, n_pixels));
+    return 0;
+}
+int rt_get_temporal_info(rt_ctx* c, rt_temporal_info* out)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!out) return fail(c, -2, "null info");
+    *out = c->tp.info;
+    return 0;
+}
+
 int rt_get_stats(rt_ctx* c, rt_stats* out)
 {
     if (!c) return -1;
@@ -1964,6 +2142,7 @@ struct rt_multi : ErrOwner {
     DevBuf<float4> d_aov_image;                 // ... the assembled feature plane of the last rt_multi_read_aov
     DevBuf<float4> d_dn_albedo, d_dn_guide;     // ... both assembled feature planes of the last rt_multi_denoise
     DenoisePlanes dn;                           // ... its work planes and the denoised plane
+    TemporalPlanes tp;                          // ... the state of rt_multi_temporal
     std::vector<hipEvent_t> ev_strip;           // per context: its strip has arrived on the first device (recorded on the SOURCE context's stream)
     int max_rows = 0;
     double lastGatherMs = 0, lastSetupMs = 0;
@@ -2067,7 +2246,7 @@ void rt_multi_destroy(rt_multi* m)
     if (!m) return;
     for (size_t i = 0; i < m->ev_strip.size() && i < m->ctx.size(); ++i)
         if (m->ev_strip[i]) { (void)hipSetDevice(m->ctx[i]->device); (void)hipEventDestroy(m->ev_strip[i]); }
-    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); m->d_dn_albedo.release(); m->d_dn_guide.release(); m->dn.release(); }
+    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); m->d_dn_albedo.release(); m->d_dn_guide.release(); m->dn.release(); m->tp.release(); }
     for (rt_ctx* c : m->ctx) rt_destroy(c);
     delete m;
 }
@@ -2232,6 +2411,27 @@ int multi_query(rt_multi* m, bool any, const rt_ray* rays, int n, void* out)
         return query_host(m->ctx[i], any, rays + first, cnt, static_cast<char*>(out) + (size_t)first * out_size);
     });
 }
+
+// What the denoiser and the temporal step share behind the handle: every context settled and holding current strips of the image
+// (if `image`) and of both feature planes with a frame in them, then those strips gathered to the first device
+int multi_gather_inputs(rt_multi* m, const char* what, bool image)
+{
+    for (size_t i = 0; i < m->ctx.size(); ++i) {
+        rt_ctx* c = m->ctx[i];
+        { const int r = settle(c); if (r) return fail(m, r, "context %zu: %s", i, rt_last_error(c)); }
+        StripLayout L;
+        if (strip_layout(c, L)) return fail(m, -2, "context %zu: %s", i, rt_last_error(c));
+        L.w = m->width; L.h = m->height;        // (the image the handle assembles, whatever a context was told directly)
+        const bool image_current = L == c->target;
+        if (L.rows != 0 && (!aov_current(c, L) || c->aov_info.framesAccumulated == 0)) return fail(m, -2, "%s: no feature frame accumulated on context %zu (call rt_multi_render_aov first)", what, i);
+        if (image && !image_current) return fail(m, -2, "%s: nothing rendered yet on context %zu", what, i);
+    }
+    double gather_ms = 0;
+    if (image) { int r = gather_strips(m, m->d_image, gather_ms, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target.rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_albedo, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_ALBEDO].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
+    { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
+    return 0;
+}
 } // namespace
 
 extern "C" {
@@ -2275,23 +2475,81 @@ int rt_multi_denoise(rt_multi* m, const rt_denoise_params* params)
     if (!m->have_params) return fail(m, -2, "rt_multi_denoise: rt_multi_set_params has not been called");
     rt_denoise_params P;
     if (const char* why = denoise_params(params, P)) return fail(m, -2, "rt_multi_denoise: %s", why);
-    for (size_t i = 0; i < m->ctx.size(); ++i) {
-        rt_ctx* c = m->ctx[i];
-        { const int r = settle(c); if (r) return fail(m, r, "context %zu: %s", i, rt_last_error(c)); }
-        StripLayout L;
-        if (strip_layout(c, L)) return fail(m, -2, "context %zu: %s", i, rt_last_error(c));
-        L.w = m->width; L.h = m->height;        // (the image the handle assembles, whatever a context was told directly)
-        const bool image_current = L == c->target;
-        if (L.rows != 0 && (!aov_current(c, L) || c->aov_info.framesAccumulated == 0)) return fail(m, -2, "rt_multi_denoise: no feature frame accumulated on context %zu (call rt_multi_render_aov first)", i);
-        if (!image_current) return fail(m, -2, "rt_multi_denoise: nothing rendered yet on context %zu", i);
-    }
-    double gather_ms = 0;
-    { int r = gather_strips(m, m->d_image, gather_ms, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target.rows; }); if (r) return r; }
-    { int r = gather_strips(m, m->d_dn_albedo, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_ALBEDO].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
-    { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
+    { int r = multi_gather_inputs(m, "rt_multi_denoise", true); if (r) return r; }
     rt_ctx* root = m->ctx[0];
     RT_HIP(m, hipSetDevice(root->device));
     RT_HIP(m, run_denoise(m->dn, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
+    return 0;
+}
+
+// Temporal reprojection behind the handle: the same gather, rt_temporal's step on the first device, the state on the handle.
+int rt_multi_temporal(rt_multi* m, const rt_temporal_params* params)
+{
+    if (!m) return -1;
+    if (!m->have_params) return fail(m, -2, "rt_multi_temporal: rt_multi_set_params has not been called");
+    rt_temporal_params P;
+    if (const char* why = temporal_params(params, P)) return fail(m, -2, "rt_multi_temporal: %s", why);
+    { int r = multi_gather_inputs(m, "rt_multi_temporal", true); if (r) return r; }
+    rt_ctx* root = m->ctx[0];
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, run_temporal(m->tp, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, root->params, P, root->stream, root->ev_dn0, root->ev_dn1));
+    return 0;
+}
+
+int rt_multi_reset_temporal(rt_multi* m)
+{
+    if (!m) return -1;
+    m->tp.filled = false; m->tp.info.calls = 0; m->tp.info.lastKernelMs = 0; m->tp.info.totalKernelMs = 0;
+    return 0;
+}
+
+int rt_multi_read_temporal(rt_multi* m, float* rgba, size_t n_floats)
+{
+    if (!m) return -1;
+    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
+    if (!rgba) return fail(m, -2, "null destination");
+    return read_image(m, (size_t)m->tp.w * m->tp.h * 4, rgba, n_floats, [&](const float4*& src) { src = m->tp.t[m->tp.cur].p; return 0; });
+}
+
+int rt_multi_read_temporal_history(rt_multi* m, float* hist, size_t n_floats)
+{
+    if (!m) return -1;
+    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
+    if (!hist) return fail(m, -2, "null destination");
+    const size_t px = (size_t)m->tp.w * m->tp.h;
+    if (n_floats != px) return fail(m, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(m, hipSetDevice(m->ctx[0]->device));
+    RT_HIP(m, hipMemcpy(hist, m->tp.n[m->tp.cur].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int rt_multi_read_temporal_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
+{
+    if (!m) return -1;
+    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
+    if (!rgba8) return fail(m, -2, "null destination");
+    const size_t px = (size_t)m->tp.w * m->tp.h;
+    if (n_pixels != px) return fail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
+    if (!n_pixels) return 0;
+    rt_ctx* root = m->ctx[0];
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, display_plane(root, m->tp.t[m->tp.cur].p, m->d_display, rgba8, n_pixels));
+    return 0;
+}
+
+int rt_multi_denoise_temporal(rt_multi* m, const rt_denoise_params* params)
+{
+    if (!m) return -1;
+    if (!m->have_params) return fail(m, -2, "rt_multi_denoise_temporal: rt_multi_set_params has not been called");
+    rt_denoise_params P;
+    if (const char* why = denoise_params(params, P)) return fail(m, -2, "rt_multi_denoise_temporal: %s", why);
+    if (!m->tp.filled) return fail(m, -2, "rt_multi_denoise_temporal: rt_multi_temporal has not been called");
+    if (m->tp.w != m->width || m->tp.h != m->height) return fail(m, -2, "rt_multi_denoise_temporal: the temporal image is %d x %d, the handle's image %d x %d", m->tp.w, m->tp.h, m->width, m->height);
+    { int r = multi_gather_inputs(m, "rt_multi_denoise_temporal", false); if (r) return r; }
+    rt_ctx* root = m->ctx[0];
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, run_denoise(m->dn, m->tp.t[m->tp.cur].p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
     return 0;
 }
 

@@ -433,6 +433,14 @@ class RayTracingManager:
         self.backend.denoise(**params)
         return self.backend.read_denoised()
 
+    def Temporal(self, **params):
+        """Beyond the reference: the step in front of Denoise for a moving camera (rt_temporal).  After a frame rendered from a fresh
+        accumulation at the current pose and RenderFeatures at that pose, the previous result is reprojected into the new view and the
+        new samples are blended in.  Keywords as Tracer.temporal (none = the library's defaults).  Returns the temporal colour
+        (H, W, 4); the image, the planes and numRenderedFrames are left alone."""
+        self.backend.temporal(**params)
+        return self.backend.read_temporal()
+
     def Start(self):                                                              # RayTracingManager.cs:43-46
         self.numRenderedFrames = 0
         if self.backend is not None:

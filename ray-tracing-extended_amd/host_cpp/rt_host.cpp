@@ -447,6 +447,24 @@ void RayTracingManager::Denoise(rt_multi* m, const rt_denoise_params* params, st
     }
 }
 
+void RayTracingManager::Temporal(rt_ctx* ctx, const rt_temporal_params* params, std::vector<float>* temporal)
+{
+    check(ctx, rt_temporal(ctx, params), "rt_temporal");
+    if (temporal) {
+        temporal->resize((size_t)width * height * 4);
+        check(ctx, rt_read_temporal(ctx, temporal->data(), temporal->size()), "rt_read_temporal");
+    }
+}
+
+void RayTracingManager::Temporal(rt_multi* m, const rt_temporal_params* params, std::vector<float>* temporal)
+{
+    mcheck(m, rt_multi_temporal(m, params), "rt_multi_temporal");
+    if (temporal) {
+        temporal->resize((size_t)width * height * 4);
+        mcheck(m, rt_multi_read_temporal(m, temporal->data(), temporal->size()), "rt_multi_read_temporal");
+    }
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

@@ -139,6 +139,12 @@ public:
     // the planes RenderFeatures accumulated; the plane (width * height * 4 floats) is read back when asked for.
     void Denoise(rt_ctx* ctx, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
     void Denoise(rt_multi* multi, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
+    // Beyond the reference: the step in front of Denoise for a moving camera (rt_temporal; params null = the library's defaults): the
+    // previous temporal colour reprojected into the current camera's view, the accumulated image blended in.  Call it after a frame
+    // rendered from a fresh accumulation and RenderFeatures at the new pose; the colour (width * height * 4 floats) is read back when
+    // asked for.  rt_denoise_temporal / rt_multi_denoise_temporal then filter it.
+    void Temporal(rt_ctx* ctx, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
+    void Temporal(rt_multi* multi, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

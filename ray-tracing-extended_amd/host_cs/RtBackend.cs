@@ -267,6 +267,42 @@ namespace RtMi355x
             return rgba8;
         }
 
+        // ---- temporal reprojection (the step in front of the denoiser for a moving camera: RtTemporal.cs) -------------------------
+        /// Reprojects the previous temporal colour into the current camera's view and blends the accumulated image in; call it after a
+        /// frame rendered from a fresh accumulation and RenderFeatures at the new pose.  The image, the planes and the frame counter are
+        /// left alone.
+        public void Temporal(RtTemporalParams p)
+        {
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_temporal(multi, ref p), "rt_multi_temporal");
+            else RtNative.Check(ctx, RtNative.rt_temporal(ctx, ref p), "rt_temporal");
+        }
+        public void Temporal() { Temporal(RtTemporalParams.Defaults); }
+
+        /// Drops the history (a scene change): the next Temporal() starts again from the image.
+        public void ResetTemporal()
+        {
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_reset_temporal(multi), "rt_multi_reset_temporal");
+            else RtNative.Check(ctx, RtNative.rt_reset_temporal(ctx), "rt_reset_temporal");
+        }
+
+        /// The temporal colour, width * height * 4 floats, row 0 = bottom.
+        public float[] ReadTemporal()
+        {
+            float[] rgba = new float[(long)width * height * 4];
+            UIntPtr n = (UIntPtr)(ulong)rgba.LongLength;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_read_temporal(multi, rgba, n), "rt_multi_read_temporal");
+            else RtNative.Check(ctx, RtNative.rt_read_temporal(ctx, rgba, n), "rt_read_temporal");
+            return rgba;
+        }
+
+        /// The denoiser on the temporal colour; read the result with ReadDenoised / ReadDenoisedDisplay.
+        public void DenoiseTemporal(RtDenoiseParams p)
+        {
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_denoise_temporal(multi, ref p), "rt_multi_denoise_temporal");
+            else RtNative.Check(ctx, RtNative.rt_denoise_temporal(ctx, ref p), "rt_denoise_temporal");
+        }
+        public void DenoiseTemporal() { DenoiseTemporal(RtDenoiseParams.Defaults); }
+
         /// Blit(resultTexture, target)
         public void Present(RenderTexture target)
         {

@@ -238,6 +238,21 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_multi_denoise(IntPtr multi, ref RtDenoiseParams p);
         [DllImport(Lib)] public static extern int rt_multi_read_denoised(IntPtr multi, [Out] float[] rgba, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_multi_read_denoised_display(IntPtr multi, [Out] uint[] rgba8, UIntPtr nPixels);
+        // temporal reprojection (RtTemporalParams, RtTemporalInfo: RtTemporal.cs; RtTemporalParams.Defaults = what a null pointer means in C)
+        [DllImport(Lib)] public static extern int rt_temporal(IntPtr ctx, ref RtTemporalParams p);
+        [DllImport(Lib)] public static extern int rt_reset_temporal(IntPtr ctx);
+        [DllImport(Lib)] public static extern int rt_read_temporal(IntPtr ctx, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_read_temporal_history(IntPtr ctx, [Out] float[] n, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_copy_temporal_to_device(IntPtr ctx, IntPtr dstDevicePtr, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_read_temporal_display(IntPtr ctx, [Out] uint[] rgba8, UIntPtr nPixels);
+        [DllImport(Lib)] public static extern int rt_get_temporal_info(IntPtr ctx, out RtTemporalInfo info);
+        [DllImport(Lib)] public static extern int rt_denoise_temporal(IntPtr ctx, ref RtDenoiseParams p);
+        [DllImport(Lib)] public static extern int rt_multi_temporal(IntPtr multi, ref RtTemporalParams p);
+        [DllImport(Lib)] public static extern int rt_multi_reset_temporal(IntPtr multi);
+        [DllImport(Lib)] public static extern int rt_multi_read_temporal(IntPtr multi, [Out] float[] rgba, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_multi_read_temporal_history(IntPtr multi, [Out] float[] n, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_multi_read_temporal_display(IntPtr multi, [Out] uint[] rgba8, UIntPtr nPixels);
+        [DllImport(Lib)] public static extern int rt_multi_denoise_temporal(IntPtr multi, ref RtDenoiseParams p);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }

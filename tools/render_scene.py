@@ -32,6 +32,12 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true", help="after the frames (and the feature frames: accumulated over the same frames even without --aov) "
                     "run rt_denoise with the library's defaults and write the denoised image beside the noisy one: NAME.denoised.EXT for "
                     "every --png / --exr / --pfm given")
+    ap.add_argument("--temporal", type=int, default=0, metavar="POSES", help="after the image: a camera path of POSES poses, each --temporal-step "
+                    "world units further along the camera's right axis; at every pose a fresh accumulation of --temporal-frames frames, fresh "
+                    "feature frames, rt_temporal and rt_denoise_temporal with the library's defaults.  Writes, for the last pose, "
+                    "NAME.temporal.EXT and NAME.temporal.denoised.EXT for every --png / --exr / --pfm given")
+    ap.add_argument("--temporal-step", type=float, default=0.05)
+    ap.add_argument("--temporal-frames", type=int, default=1, help="frames per pose of the camera path")
     args = ap.parse_args(argv)
 
     import rtx_pkg
@@ -88,6 +94,38 @@ def main(argv=None):
         if args.pfm:
             rtx.imageio.write_pfm(beside(args.pfm), denoised); written.append(beside(args.pfm))
         print(f"denoised: {info['iterations']} passes in {info['lastKernelMs']:.3f} ms of kernels -> {', '.join(written) or 'nothing written (give --png, --exr or --pfm)'}")
+    if args.temporal > 0:
+        import numpy as np
+        cam = mgr.camera.transform
+        start = np.array(cam.position, np.float32)
+        right = cam.localToWorldMatrix[:3, 0]
+        right = right / np.linalg.norm(right)
+        tracer.reset_temporal()
+        for pose in range(args.temporal):
+            cam.position = (start + right * np.float32(args.temporal_step * pose)).astype(np.float32)
+            mgr.Start()                                     # a fresh accumulation at the new pose
+            mgr.OnRenderImage(frames=args.temporal_frames)
+            tracer.reset_aov()
+            mgr.RenderFeatures(frames=args.temporal_frames, firstFrame=0)
+            temporal = mgr.Temporal()
+        tracer.denoise_temporal()
+        denoised, info, history = tracer.read_denoised(), tracer.temporal_info(), tracer.read_temporal_history()
+        cam.position = start
+        written = []
+        for path, kind in ((args.png, "png"), (args.exr, "exr"), (args.pfm, "pfm")):
+            if not path:
+                continue
+            stem, ext = os.path.splitext(path)
+            if kind == "png":
+                rtx.imageio.write_png(stem + ".temporal" + ext, tracer.read_temporal_display())
+                rtx.imageio.write_png(stem + ".temporal.denoised" + ext, tracer.read_denoised_display())
+            else:
+                write = rtx.imageio.write_exr if kind == "exr" else rtx.imageio.write_pfm
+                write(stem + ".temporal" + ext, temporal)
+                write(stem + ".temporal.denoised" + ext, denoised)
+            written += [stem + ".temporal" + ext, stem + ".temporal.denoised" + ext]
+        print(f"temporal: {info['calls']} poses, {args.temporal_frames} frames each, {info['totalKernelMs']:.3f} ms of kernels for the step; mean history "
+              f"length {float(history.mean()):.2f} -> {', '.join(written) or 'nothing written (give --png, --exr or --pfm)'}")
     tracer.close()
     return 0
 
