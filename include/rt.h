@@ -240,6 +240,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *   "tile_lpt"        k_trace: 1 = hand tiles out costliest first, by the costs the previous launch measured (default), 0 = in order
  *   "frame_batch"     k_trace: frames traced per launch by rt_render (0 = auto: as many as fit 4 GiB, at most 256; 1 = one per launch)
  *   "lds_stack"       k_trace: traversal-stack entries kept in LDS, deeper ones spill to global memory (0 = all in LDS)
+ *   "radiance_slice"  rt_trace_radiance: rays per launch and per staging slice, 1..4194304 (default 4194304, the ray queries' slice); the
+ *                     result never depends on it
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -411,6 +413,55 @@ int rt_occluded   (rt_ctx* ctx, const rt_ray* rays, int n, uint8_t* occluded);
  * its 4-byte result (a stream synchronisation) before it enqueues the query.                                                     */
 int rt_trace_rays_device(rt_ctx* ctx, const void* rays, int n, void* hits);
 int rt_occluded_device  (rt_ctx* ctx, const void* rays, int n, void* occluded);
+
+/* ---- radiance queries: how much light arrives along a caller-supplied ray ---------------------------------------------
+ * Between "what image does the camera see?" (the frame calls) and "what does this ray hit?" (the ray queries): Trace
+ * (RayTracing.shader:300-352) for rays the caller makes — light probes, lightmap texels, a reflection probe, a fisheye or stereo camera,
+ * the radiance behind a picked pixel.  For ray i of a call, with o its origin, d its direction (not normalised by the library: Trace
+ * runs on it as given, so a caller who wants the shader's behaviour passes unit directions), t its tMax and K = firstIndex + i:
+ *
+ *   settings      the context's current rt_params (without any the call fails): maxBounceCount, intersectMode, environmentEnabled, the
+ *                 sky fields and worldSpaceLightPos0 apply; the camera fields, numRaysPerPixel and rngMode do not.  The stream is always
+ *                 the Philox one, as for the feature buffers.
+ *   sample s      (0 <= s < N = samples) Trace(o, d) exactly as RT_RNG_PHILOX defines it, with key (K, seed) and counter (block, s, 0,
+ *                 0): the hit at loop index b draws from blocks 1 + 2b and 2 + 2b.  Block 0, a frame's camera ray, is unused: the caller
+ *                 made the ray.  One change: the cast at loop index 0 counts only hits with dst < t (rt_trace_rays' rule:
+ *                 CalculateRayCollision, then the comparison).  The cast after an InvisibleLight pass-through and every later cast is
+ *                 unbounded, as in the shader.
+ *   sum           the fixed tree of the Philox mode: S = 16 / 4 / 1 sub-streams for N >= 16 / >= 4 / else, sample s in sub-stream s mod
+ *                 S, each sub-stream added in increasing order from 0.0f, the S sub-sums added pairwise ((k, k + 1), then (k, k + 2),
+ *                 ...), the root divided by (float)N per channel: rgba[i] = (r, g, b, 1.0f).
+ *   not traced    t <= 0 or NaN: rgba[i] = (0, 0, 0, 0), no cast.
+ *   defaults      params == NULL: samples = the context's numRaysPerPixel, seed 0, firstIndex 0.
+ *   non-finite    ray components that are not finite give whatever this arithmetic gives; the call does not fault and a path ends
+ *                 after maxBounceCount + 1 casts.
+ *   scene, state  as for ray queries: the queue is settled, the scene made current, the box padding widened for the batch's largest
+ *                 finite |origin coordinate| among rays with t > 0 (the device entry measures it with the ray queries' reduction kernel
+ *                 and the same single synchronisation).  Nothing of the image path, the feature planes, the denoiser or the temporal
+ *                 state moves, and no rt_stats field except bvhBuilds / bvhRebuilds / bvhRepads when the call triggered them.
+ *   splitting     a batch split anywhere into two calls, the second with firstIndex advanced by the first's length, gives the bits of
+ *                 one call: the library's own slices (option "radiance_slice", rays per launch) and rt_multi are invisible.
+ *   errors        a null handle -1; n == 0 returns 0; no params set, n < 0, a null buffer with n > 0, samples outside 1..65536, a
+ *                 non-zero reserved word, and for the device entry a pointer of another device or one not 16-byte aligned: -2 with a
+ *                 message, and nothing changes.                                                                                   */
+typedef struct rt_radiance_params {     /* 32 B */
+    int32_t  samples;                   /* N, 1..65536: independent runs of Trace per ray                                    */
+    uint32_t seed;                      /* second key word of the Philox stream (what Frame is for a frame)                  */
+    uint32_t firstIndex;                /* ray i of the call has stream index firstIndex + i (wraps mod 2^32)                */
+    int32_t  _reserved[5];              /* must be 0                                                                         */
+} rt_radiance_params;
+typedef struct rt_radiance_info {       /* 32 B */
+    int32_t samples;                    /* of the last call                                                                  */
+    int32_t lastSampleLanes;            /* lanes of a wave that shared a ray's samples in the last launch: 16, 4 or 1        */
+    int32_t calls, _reserved;
+    double  lastKernelMs, totalKernelMs;   /* HIP-event time of the launches of the last host-entry call / summed            */
+} rt_radiance_info;
+/* Host memory (rgba: n * 4 floats); returns when the results are in rgba.  Slices as for rt_trace_rays.                            */
+int rt_trace_radiance       (rt_ctx* ctx, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba);
+/* Device memory of the context's GPU (rays: n rt_ray, rgba: n float4, both 16-byte aligned), ordered on the context's stream as
+ * rt_trace_rays_device is; rt_radiance_info counts the call and keeps the host entry's times.                                     */
+int rt_trace_radiance_device(rt_ctx* ctx, const void* rays, int n, const rt_radiance_params* params, void* rgba);
+int rt_get_radiance_info    (rt_ctx* ctx, rt_radiance_info* out);
 
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
@@ -651,6 +702,9 @@ int rt_multi_get_info        (rt_multi* m, rt_multi_info* out);
  * concurrently against each context's copy of the scene and gathered in order — bitwise the single-context result.              */
 int rt_multi_trace_rays      (rt_multi* m, const rt_ray* rays, int n, rt_hit* hits);
 int rt_multi_occluded        (rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded);
+/* Radiance queries behind the handle: the same slices, context i's rays keeping their stream indices (firstIndex + their offset in the
+ * batch) — bitwise the single-context result.                                                                                    */
+int rt_multi_trace_radiance  (rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba);
 /* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
  * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
  * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
@@ -676,7 +730,7 @@ int rt_multi_denoise_temporal     (rt_multi* m, const rt_denoise_params* params)
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" */
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,11 @@ TEMPORAL_PARAMS = np.dtype([("maxHistory", "<i4"), ("depthTolerance", "<f4"), ("
 TEMPORAL_INFO = np.dtype([("calls", "<i4"), ("width", "<i4"), ("height", "<i4"), ("_reserved", "<i4"),
                           ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert TEMPORAL_PARAMS.itemsize == 32 and TEMPORAL_INFO.itemsize == 32
+# radiance queries (rt_trace_radiance): the parameters of a call and the state of the last one
+RADIANCE_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", "<u4"), ("_reserved", "<i4", 5)])
+RADIANCE_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("_reserved", "<i4"),
+                          ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert RADIANCE_PARAMS.itemsize == 32 and RADIANCE_INFO.itemsize == 32
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
@@ -101,6 +106,7 @@ SYMBOLS = [
     "rt_read_temporal_display", "rt_get_temporal_info", "rt_denoise_temporal",
     "rt_multi_temporal", "rt_multi_reset_temporal", "rt_multi_read_temporal", "rt_multi_read_temporal_history", "rt_multi_read_temporal_display",
     "rt_multi_denoise_temporal",
+    "rt_trace_radiance", "rt_trace_radiance_device", "rt_get_radiance_info", "rt_multi_trace_radiance",
 ]
 
 _lib = None
@@ -209,6 +215,9 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_read_temporal_history.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     lib.rt_multi_read_temporal_display.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.rt_multi_denoise_temporal.argtypes = [c_void_p, c_void_p]
+    for n in ("rt_trace_radiance", "rt_trace_radiance_device", "rt_multi_trace_radiance"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.rt_get_radiance_info.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -220,7 +229,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_mesh_transform", MESH_TRANSFORM), ("rt_local_chunk", LOCAL_CHUNK), ("rt_multi_info", MULTI_INFO),
                      ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO),
                      ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO),
-                     ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO)):
+                     ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO),
+                     ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -249,6 +259,26 @@ def _query_host(call, handle, rays, any_hit: bool, check, what):
     r = _ray_array(rays)
     out = np.zeros(r.shape[0], np.uint8) if any_hit else np.zeros(r.shape[0], HIT)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
+def _radiance_params(samples, seed, first_index):
+    """None (the library's defaults: the context's numRaysPerPixel samples, seed 0, firstIndex 0) when samples is None; else a
+    RADIANCE_PARAMS record"""
+    if samples is None:
+        if seed or first_index:
+            raise TypeError("trace_radiance: seed and first_index need samples")
+        return None
+    p = np.zeros((), RADIANCE_PARAMS)
+    p["samples"], p["seed"], p["firstIndex"] = int(samples), int(seed) & 0xFFFFFFFF, int(first_index) & 0xFFFFFFFF
+    return p
+
+
+def _radiance_host(call, handle, rays, params, check, what):
+    r = _ray_array(rays)
+    out = np.zeros((r.shape[0], 4), np.float32)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
+               out.ctypes.data_as(c_void_p)), what)
     return out
 
 
@@ -396,28 +426,60 @@ class Tracer:
         library can take (NULL means the context's own stream), so there the call is fenced: torch's stream is synchronised before it and
         the device after it.  (torch ships its own HIP runtime: import torch before the library is loaded, so that both use that one.)"""
         import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError(f"rays: a float32 (n, 8) tensor, not {rays.dtype} {tuple(rays.shape)}")
-        rays = rays.contiguous()
+        rays = self._ray_tensor(rays)
         n = int(rays.shape[0])
         out = torch.empty((n,), dtype=torch.uint8, device=rays.device) if any_hit else torch.empty((n, 16), dtype=torch.float32, device=rays.device)
-        stream = torch.cuda.current_stream(rays.device)
-        handle = int(stream.cuda_stream)
         call = self._lib.rt_occluded_device if any_hit else self._lib.rt_trace_rays_device
         what = "rt_occluded_device" if any_hit else "rt_trace_rays_device"
+        self._on_torch_stream(rays.device, lambda: call(self._ctx, c_void_p(rays.data_ptr()), n, c_void_p(out.data_ptr())), what)
+        return out
+
+    @staticmethod
+    def _ray_tensor(rays):
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays: a float32 (n, 8) tensor, not {rays.dtype} {tuple(rays.shape)}")
+        return rays.contiguous()
+
+    def _on_torch_stream(self, device, call, what):
+        """call() — a device entry — ordered with torch's current stream of `device` as _query_device describes"""
+        import torch
+        stream = torch.cuda.current_stream(device)
+        handle = int(stream.cuda_stream)
         if handle == 0:
             stream.synchronize()
-            rc = call(self._ctx, c_void_p(rays.data_ptr()), n, c_void_p(out.data_ptr()))
-            torch.cuda.synchronize(rays.device)
+            rc = call()
+            torch.cuda.synchronize(device)
             self._check(rc, what)
-            return out
+            return
         self._check(self._lib.rt_set_stream(self._ctx, c_void_p(handle)), "rt_set_stream")
         try:
-            rc = call(self._ctx, c_void_p(rays.data_ptr()), n, c_void_p(out.data_ptr()))
+            rc = call()
         finally:
             self._lib.rt_set_stream(self._ctx, c_void_p(getattr(self, "_stream", None) or None))
         self._check(rc, what)
+
+    # -- radiance queries
+    def trace_radiance(self, rays, samples=None, seed=0, first_index=0):
+        """rt_trace_radiance: Trace along every ray, averaged over `samples` runs (None: the context's numRaysPerPixel, seed 0, first
+        index 0).  rays: a RAY array or float32 (n, 8) -> float32 (n, 4).  A float32 CUDA tensor (n, 8) on the context's device takes the
+        device entry, ordered with torch's current stream as trace_rays is, and returns a float32 (n, 4) tensor."""
+        q = _radiance_params(samples, seed, first_index)
+        if not _is_tensor(rays):
+            return _radiance_host(self._lib.rt_trace_radiance, self._ctx, rays, q, self._check, "rt_trace_radiance")
+        import torch
+        rays = self._ray_tensor(rays)
+        n = int(rays.shape[0])
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        qp = None if q is None else q.ctypes.data_as(c_void_p)
+        self._on_torch_stream(rays.device, lambda: self._lib.rt_trace_radiance_device(self._ctx, c_void_p(rays.data_ptr()), n, qp, c_void_p(out.data_ptr())),
+                              "rt_trace_radiance_device")
         return out
+
+    def radiance_info(self) -> dict:
+        s = np.zeros((), RADIANCE_INFO)
+        self._check(self._lib.rt_get_radiance_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_radiance_info")
+        return {k: s[k].item() for k in RADIANCE_INFO.names if k != "_reserved"}
 
     # -- rendering
     def render_frame(self, frame: int):
@@ -691,6 +753,11 @@ class MultiTracer:
     def occluded(self, rays) -> np.ndarray:
         """rt_multi_occluded: Tracer.occluded over the contexts (host arrays)."""
         return _query_host(self._lib.rt_multi_occluded, self._m, rays, True, self._check, "rt_multi_occluded")
+
+    def trace_radiance(self, rays, samples=None, seed=0, first_index=0) -> np.ndarray:
+        """rt_multi_trace_radiance: Tracer.trace_radiance over the contexts (host arrays), every ray keeping its stream index."""
+        return _radiance_host(self._lib.rt_multi_trace_radiance, self._m, rays, _radiance_params(samples, seed, first_index), self._check,
+                              "rt_multi_trace_radiance")
 
     def render_params(self, first_frame: int, params):
         """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""

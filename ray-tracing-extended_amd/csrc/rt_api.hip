@@ -30,6 +30,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_bvh_gpu.hpp"
 #include "rt_primary.hpp"
 #include "rt_query.hpp"
+#include "rt_radiance.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -195,6 +196,9 @@ struct rt_ctx : ErrOwner {
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
     DevBuf<float4> d_q_rays, d_q_hits; DevBuf<uint8_t> d_q_occ;            // ray queries: staging of the host entries (one slice)
     DevBuf<unsigned int> d_q_bound;                                         // ... the device entries' origin bound
+    DevBuf<float4> d_q_rgba;                                                // radiance queries: the host entry's results (one slice)
+    rt_radiance_info radiance_info{};
+    int opt_radiance_slice = 1 << 22;   // radiance queries: rays per launch (and per staging slice of the host entry); the result never depends on it
     // feature buffers (rt_render_aov, csrc/rt_aov.hpp): the two accumulated planes of this context's strip and the layout they were made for
     DevBuf<float4> d_aov[RT_AOV_COUNT];
     StripLayout aov;                    // (meaningful once d_aov[0].p is set: ensure_aov)
@@ -1302,6 +1306,21 @@ bool on_ctx_device(const rt_ctx* c, const void* p)
     return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged) && a.device == c->device;
 }
 
+// cover_origins for rays in device memory: the origin bound of the batch is measured on the device — one small kernel and a 4-byte
+// read-back (the call's one synchronisation)
+int cover_origins_device(rt_ctx* c, const float4* rays, int n)
+{
+    RT_HIP(c, c->d_q_bound.ensure(1));
+    RT_HIP(c, hipMemsetAsync(c->d_q_bound.p, 0, sizeof(unsigned int), c->stream));
+    const int grid = std::max(1, std::min((n + 255) / 256, 4 * std::max(1, c->n_cu)));
+    hipLaunchKernelGGL(rtk::k_query_origin_bound<0>, dim3(grid), dim3(256), 0, c->stream, rays, n, c->d_q_bound.p);
+    RT_HIP(c, hipGetLastError());
+    unsigned int bits = 0;
+    RT_HIP(c, hipMemcpyAsync(&bits, c->d_q_bound.p, sizeof bits, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return cover_origins(c, u2f(bits));
+}
+
 int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
 {
     const char* what = any ? "rt_occluded_device" : "rt_trace_rays_device";
@@ -1314,17 +1333,98 @@ int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
     if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (!any && (reinterpret_cast<uintptr_t>(out) & 15u)))
         return fail(c, -2, "%s: rays and hits must be 16-byte aligned", what);
     { int r = prepare_scene(c); if (r) return r; }
-    // the origin bound of the batch, measured on the device: one small kernel and a 4-byte read-back (the call's one synchronisation)
-    RT_HIP(c, c->d_q_bound.ensure(1));
-    RT_HIP(c, hipMemsetAsync(c->d_q_bound.p, 0, sizeof(unsigned int), c->stream));
-    const int grid = std::max(1, std::min((n + 255) / 256, 4 * std::max(1, c->n_cu)));
-    hipLaunchKernelGGL(rtk::k_query_origin_bound<0>, dim3(grid), dim3(256), 0, c->stream, static_cast<const float4*>(rays), n, c->d_q_bound.p);
-    RT_HIP(c, hipGetLastError());
-    unsigned int bits = 0;
-    RT_HIP(c, hipMemcpyAsync(&bits, c->d_q_bound.p, sizeof bits, hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    { int r = cover_origins(c, u2f(bits)); if (r) return r; }
+    { int r = cover_origins_device(c, static_cast<const float4*>(rays), n); if (r) return r; }
     return launch_query(c, any, static_cast<const float4*>(rays), n, out);
+}
+
+// ---- radiance queries (rt_trace_radiance, csrc/rt_radiance.hpp) -------------------------------------------------------------------
+// The arguments of a call as the kernel takes them; params == NULL: the context's numRaysPerPixel samples, seed 0, firstIndex 0
+int radiance_arguments(rt_ctx* c, const char* what, const void* rays, int n, const rt_radiance_params* params, const void* rgba, rt_radiance_params& q)
+{
+    if (!c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", what);
+    if (n < 0 || (n > 0 && (!rays || !rgba))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, rgba %p)", what, n, rays, rgba);
+    q = rt_radiance_params{};
+    if (params) q = *params; else q.samples = c->params.numRaysPerPixel;
+    if (q.samples < 1 || q.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", what, q.samples);
+    for (int r : q._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_radiance_params is not 0", what);
+    return 0;
+}
+
+// n rays (device, 2 float4 each) -> n float4, on the context's stream; no synchronisation.  One launch per opt_radiance_slice rays, each
+// with firstIndex advanced by the rays before it.
+int launch_radiance(rt_ctx* c, const float4* rays, int n, const rt_radiance_params& q, float4* rgba)
+{
+    rtk::DeviceScene S{};
+    { int r = fill_scene(c, S); if (r) return r; }
+    rtk::RadianceArgs A{};
+    A.p = c->params;
+    A.samples = q.samples; A.seed = q.seed;
+    A.sample_lanes_log2 = q.samples >= 16 ? 4 : q.samples >= 4 ? 2 : 0;       // S = 16 / 4 / 1 (include/rt.h RT_RNG_PHILOX)
+    A.full_sort = c->opt_full_sort;
+    c->radiance_info.samples = q.samples; c->radiance_info.lastSampleLanes = 1 << A.sample_lanes_log2;
+    const void* fn = c->opt_compact_nodes != 0 ? (const void*)rtk::k_radiance<true> : (const void*)rtk::k_radiance<false>;     // the node form the renderer's kernels traverse
+    const int slice = c->opt_radiance_slice;
+    for (int first = 0; first < n; first += slice) {
+        const int cnt = std::min(slice, n - first);
+        const size_t lanes = (size_t)cnt << A.sample_lanes_log2;
+        const int grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
+        LaneStack st;
+        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_trace_radiance"); if (r) return r; }
+        A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
+        A.rays = rays + 2 * (size_t)first; A.rgba = rgba + first; A.n = cnt;
+        A.first_index = q.firstIndex + (uint32_t)first;
+        void* args[] = { &S, &A };
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
+    }
+    return 0;
+}
+
+int radiance_host(rt_ctx* c, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba)
+{
+    RT_SETTLE(c);
+    rt_radiance_params q;
+    { int r = radiance_arguments(c, "rt_trace_radiance", rays, n, params, rgba, q); if (r) return r; }
+    if (n == 0) return 0;
+    { int r = query_prepare(c, query_origin_bound(rays, n)); if (r) return r; }
+    const int slice = c->opt_radiance_slice;
+    RT_HIP(c, c->d_q_rays.ensure(2 * (size_t)std::min(n, slice)));
+    RT_HIP(c, c->d_q_rgba.ensure((size_t)std::min(n, slice)));
+    double ms_sum = 0;
+    for (int first = 0; first < n; first += slice) {
+        const int cnt = std::min(slice, n - first);
+        rt_radiance_params qs = q;
+        qs.firstIndex = q.firstIndex + (uint32_t)first;
+        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, rays + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+        RT_HIP(c, hipEventRecord(c->ev0, c->stream));
+        { int r = launch_radiance(c, c->d_q_rays.p, cnt, qs, c->d_q_rgba.p); if (r) return r; }
+        RT_HIP(c, hipEventRecord(c->ev1, c->stream));
+        RT_HIP(c, hipMemcpyAsync(rgba + 4 * (size_t)first, c->d_q_rgba.p, (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));     // (the events are the context's one pair: read before the next slice records them)
+        float ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_sum += ms;
+    }
+    c->radiance_info.calls++; c->radiance_info.lastKernelMs = ms_sum; c->radiance_info.totalKernelMs += ms_sum;
+    return 0;
+}
+
+int radiance_device(rt_ctx* c, const void* rays, int n, const rt_radiance_params* params, void* rgba)
+{
+    const char* what = "rt_trace_radiance_device";
+    RT_SETTLE(c);
+    rt_radiance_params q;
+    { int r = radiance_arguments(c, what, rays, n, params, rgba, q); if (r) return r; }
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!on_ctx_device(c, rays) || !on_ctx_device(c, rgba))
+        return fail(c, -2, "%s: rays and results must be device memory of the context's device %d", what, c->device);
+    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (reinterpret_cast<uintptr_t>(rgba) & 15u))
+        return fail(c, -2, "%s: rays and rgba must be 16-byte aligned", what);
+    { int r = prepare_scene(c); if (r) return r; }
+    { int r = cover_origins_device(c, static_cast<const float4*>(rays), n); if (r) return r; }
+    { int r = launch_radiance(c, static_cast<const float4*>(rays), n, q, static_cast<float4*>(rgba)); if (r) return r; }
+    c->radiance_info.calls++;                           // (asynchronous: the times are the host entry's)
+    return 0;
 }
 
 // ---- feature buffers (rt_render_aov, csrc/rt_aov.hpp) -----------------------------------------------------------------------------
@@ -1650,6 +1750,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_denoise_info")) return (int)sizeof(rt_denoise_info);
     if (!std::strcmp(name, "rt_temporal_params")) return (int)sizeof(rt_temporal_params);
     if (!std::strcmp(name, "rt_temporal_info")) return (int)sizeof(rt_temporal_info);
+    if (!std::strcmp(name, "rt_radiance_params")) return (int)sizeof(rt_radiance_params);
+    if (!std::strcmp(name, "rt_radiance_info")) return (int)sizeof(rt_radiance_info);
     return -1;
 }
 
@@ -1874,6 +1976,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "primary_lists")) { if (value != 0 && value != 1) return fail(c, -2, "primary_lists must be 0 or 1"); c->opt_primary_lists = value; }
     else if (!std::strcmp(name, "queue_depth")) { if (value < 1 || value > 256) return fail(c, -2, "queue_depth must be in [1,256]"); c->opt_queue_depth = value; }
     else if (!std::strcmp(name, "queue_linger_us")) { if (value < 0 || value > 1000000) return fail(c, -2, "queue_linger_us must be in [0,1000000]"); c->opt_queue_linger_us = value; }
+    else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
     else return fail(c, -2, "unknown option '%s'", name);
     return 0;
@@ -2033,6 +2136,16 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits) { return c
 int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { return c ? query_host(c, true, rays, n, occluded) : -1; }
 int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return c ? query_device(c, false, rays, n, hits) : -1; }
 int rt_occluded_device(rt_ctx* c, const void* rays, int n, void* occluded) { return c ? query_device(c, true, rays, n, occluded) : -1; }
+
+int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return c ? radiance_host(c, rays, n, params, rgba) : -1; }
+int rt_trace_radiance_device(rt_ctx* c, const void* rays, int n, const rt_radiance_params* params, void* rgba) { return c ? radiance_device(c, rays, n, params, rgba) : -1; }
+int rt_get_radiance_info(rt_ctx* c, rt_radiance_info* out)
+{
+    if (!c) return -1;
+    if (!out) return fail(c, -2, "null out");
+    *out = c->radiance_info;
+    return 0;
+}
 
 int rt_render_aov(rt_ctx* c, int first_frame, int n_frames) { return c ? render_aov(c, first_frame, n_frames) : -1; }
 int rt_read_aov(rt_ctx* c, int which, float* rgba, size_t n) { return c ? read_aov(c, which, rgba, n, false) : -1; }
@@ -2412,6 +2525,24 @@ int multi_query(rt_multi* m, bool any, const rt_ray* rays, int n, void* out)
     });
 }
 
+// rt_multi_trace_radiance: multi_query's slices; context i's rays keep the stream indices they have in the whole batch
+int multi_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba)
+{
+    if (!m->have_params) return fail(m, -2, "rt_multi_trace_radiance: rt_multi_set_params has not been called");
+    rt_radiance_params q;
+    if (radiance_arguments(m->ctx[0], "rt_multi_trace_radiance", rays, n, params, rgba, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
+    if (n == 0) return 0;
+    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
+    const int N = (int)m->ctx.size();
+    const int per = (n + N - 1) / N;
+    return on_every_context(m, "rt_trace_radiance", [&](int i) {
+        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
+        rt_radiance_params qi = q;
+        qi.firstIndex = q.firstIndex + (uint32_t)first;
+        return radiance_host(m->ctx[i], rays + first, cnt, &qi, rgba + 4 * (size_t)first);
+    });
+}
+
 // What the denoiser and the temporal step share behind the handle: every context settled and holding current strips of the image
 // (if `image`) and of both feature planes with a frame in them, then those strips gathered to the first device
 int multi_gather_inputs(rt_multi* m, const char* what, bool image)
@@ -2438,6 +2569,7 @@ extern "C" {
 
 int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { return m ? multi_query(m, false, rays, n, hits) : -1; }
 int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return m ? multi_query(m, true, rays, n, occluded) : -1; }
+int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return m ? multi_radiance(m, rays, n, params, rgba) : -1; }
 
 // Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands
 int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)

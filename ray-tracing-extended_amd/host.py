@@ -417,6 +417,21 @@ class RayTracingManager:
             return hit, self.meshes[mesh]
         return hit, None
 
+    def TraceRadiance(self, rays, samples: int = None, seed: int = 0, firstIndex: int = 0):
+        """Beyond the reference: how much light arrives along each ray in the scene the next frame traces — Trace (RayTracing.shader:300-352)
+        through rt_trace_radiance, averaged over `samples` runs (None: numRaysPerPixel): light probes, lightmap texels, a camera the
+        reference does not have.  rays: a RAY array or float32 (n, 8) -> float32 (n, 4), (r, g, b, 1)."""
+        self.InitFrame()
+        return self.backend.trace_radiance(rays, samples, seed, firstIndex)
+
+    def TraceRadianceTensor(self, rays, samples: int = None, seed: int = 0, firstIndex: int = 0):
+        """TraceRadiance for a float32 (n, 8) tensor on the tracer's device (rt_trace_radiance_device): the rays never leave the GPU and
+        the result, a float32 (n, 4) tensor, is ordered with torch's current stream."""
+        if not hasattr(rays, "data_ptr"):
+            raise TypeError("TraceRadianceTensor: rays must be a torch tensor on the tracer's device (host arrays: TraceRadiance)")
+        self.InitFrame()
+        return self.backend.trace_radiance(rays, samples, seed, firstIndex)
+
     def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
         """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
         the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices

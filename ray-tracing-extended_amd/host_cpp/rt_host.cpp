@@ -465,6 +465,22 @@ void RayTracingManager::Temporal(rt_multi* m, const rt_temporal_params* params, 
     }
 }
 
+std::vector<float> RayTracingManager::TraceRadiance(rt_ctx* ctx, const std::vector<rt_ray>& rays, const rt_radiance_params* params)
+{
+    InitFrame(ctx);
+    std::vector<float> rgba(rays.size() * 4);
+    check(ctx, rt_trace_radiance(ctx, rays.data(), (int)rays.size(), params, rgba.data()), "rt_trace_radiance");
+    return rgba;
+}
+
+std::vector<float> RayTracingManager::TraceRadiance(rt_multi* m, const std::vector<rt_ray>& rays, const rt_radiance_params* params)
+{
+    InitFrame(m);
+    std::vector<float> rgba(rays.size() * 4);
+    mcheck(m, rt_multi_trace_radiance(m, rays.data(), (int)rays.size(), params, rgba.data()), "rt_multi_trace_radiance");
+    return rgba;
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

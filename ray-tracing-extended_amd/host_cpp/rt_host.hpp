@@ -145,6 +145,11 @@ public:
     // asked for.  rt_denoise_temporal / rt_multi_denoise_temporal then filter it.
     void Temporal(rt_ctx* ctx, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
     void Temporal(rt_multi* multi, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
+    // Beyond the reference: how much light arrives along each of the caller's rays in the scene OnRenderImage would trace — Trace through
+    // rt_trace_radiance / rt_multi_trace_radiance (params null = numRaysPerPixel samples, seed 0, firstIndex 0).  Returns rays.size() * 4
+    // floats, (r, g, b, 1) per ray.
+    std::vector<float> TraceRadiance(rt_ctx* ctx, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
+    std::vector<float> TraceRadiance(rt_multi* multi, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

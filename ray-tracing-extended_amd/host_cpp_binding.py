@@ -5,7 +5,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
 import numpy as np
 
-from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError
+from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _radiance_params, _ray_array
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_host.so")
 _lib = None
@@ -26,6 +26,7 @@ def load_host_library():
         L.rth_render.argtypes = [c_void_p, c_int, c_int, POINTER(c_float)]
         L.rth_render_multi.argtypes = [c_void_p, POINTER(c_int), c_int, c_int, POINTER(c_float)]
         L.rth_render_animated.argtypes = [c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float)]
+        L.rth_trace_radiance.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_split_mesh.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]
         L.rth_split_info.argtypes = [c_void_p, c_void_p, c_void_p]
         L.rth_split_triangles.argtypes = [c_void_p]
@@ -116,4 +117,17 @@ class CppScene:
         if self._L.rth_render_animated(self._h, arr, len(devices), 1 if device_geometry else 0, steps, frames_per_step, q4, sh,
                                        out.ctypes.data_as(POINTER(c_float))):
             raise RtError("render_animated: " + self._L.rth_last_error().decode())
+        return out
+
+    def trace_radiance(self, rays, samples=None, seed=0, first_index=0, devices=(), device: int = 0) -> np.ndarray:
+        """RayTracingManager::TraceRadiance on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: rays (a RAY array or float32
+        (n, 8)) -> float32 (n, 4); samples None = the library's defaults."""
+        r = _ray_array(rays)
+        q = _radiance_params(samples, seed, first_index)
+        out = np.zeros((r.shape[0], 4), np.float32)
+        devs = list(devices) if devices else [device]
+        arr = (c_int * len(devs))(*devs)
+        if self._L.rth_trace_radiance(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
+                                      None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
+            raise RtError("TraceRadiance: " + self._L.rth_last_error().decode())
         return out

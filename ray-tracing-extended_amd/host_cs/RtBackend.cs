@@ -215,6 +215,28 @@ namespace RtMi355x
             return occ[0] != 0;
         }
 
+        // ---- radiance queries (light probes, lightmap texels, cameras the reference does not have: RtRadiance.cs) -------------------
+        /// How much light arrives along each ray in the scene the next frame traces: Trace (RayTracing.shader:300-352) averaged over
+        /// `samples` runs per ray (0 = numRaysPerPixel, with seed 0).  Returns rays.Length * 4 floats, (r, g, b, 1) per ray; a ray with
+        /// tMax <= 0 gives four zeros.
+        public float[] TraceRadiance(RtRay[] rays, int samples = 0, uint seed = 0)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            float[] rgba = new float[(long)rays.Length * 4];
+            RtRadianceParams[] p = samples > 0 ? new[] { new RtRadianceParams { samples = samples, seed = seed } } : null;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_trace_radiance(multi, rays, rays.Length, p, rgba), "rt_multi_trace_radiance");
+            else RtNative.Check(ctx, RtNative.rt_trace_radiance(ctx, rays, rays.Length, p, rgba), "rt_trace_radiance");
+            return rgba;
+        }
+
+        /// The radiance along one ray (a probe, the light behind a picked pixel).
+        public Color Radiance(Vector3 origin, Vector3 direction, float maxDistance, int samples = 0, uint seed = 0)
+        {
+            float[] c = TraceRadiance(new[] { MakeRay(origin, direction, maxDistance) }, samples, seed);
+            return new Color(c[0], c[1], c[2], c[3]);
+        }
+
         // ---- feature buffers (what a denoiser takes beside the image: RtAov.cs) ------------------------------------------------
         /// Accumulates the feature frame `frame` (albedo, normal, depth, coverage of the first visible surface) for the scene and camera
         /// the next frame traces; the image and its frame counter are left alone.

@@ -253,6 +253,11 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_multi_read_temporal_history(IntPtr multi, [Out] float[] n, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_multi_read_temporal_display(IntPtr multi, [Out] uint[] rgba8, UIntPtr nPixels);
         [DllImport(Lib)] public static extern int rt_multi_denoise_temporal(IntPtr multi, ref RtDenoiseParams p);
+        // radiance queries (RtRadianceParams, RtRadianceInfo: RtRadiance.cs; p: one entry, or null = the context's numRaysPerPixel samples, seed 0, firstIndex 0)
+        [DllImport(Lib)] public static extern int rt_trace_radiance(IntPtr ctx, [In] RtRay[] rays, int n, [In] RtRadianceParams[] p, [Out] float[] rgba);
+        [DllImport(Lib)] public static extern int rt_trace_radiance_device(IntPtr ctx, IntPtr rays, int n, [In] RtRadianceParams[] p, IntPtr rgba);
+        [DllImport(Lib)] public static extern int rt_get_radiance_info(IntPtr ctx, out RtRadianceInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_trace_radiance(IntPtr multi, [In] RtRay[] rays, int n, [In] RtRadianceParams[] p, [Out] float[] rgba);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -299,6 +304,8 @@ namespace RtMi355x
             Same("rt_aov_info", Marshal.SizeOf<RtAovInfo>());
             Same("rt_denoise_params", Marshal.SizeOf<RtDenoiseParams>());
             Same("rt_denoise_info", Marshal.SizeOf<RtDenoiseInfo>());
+            Same("rt_radiance_params", Marshal.SizeOf<RtRadianceParams>());
+            Same("rt_radiance_info", Marshal.SizeOf<RtRadianceInfo>());
         }
     }
 }
