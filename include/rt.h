@@ -242,6 +242,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *   "lds_stack"       k_trace: traversal-stack entries kept in LDS, deeper ones spill to global memory (0 = all in LDS)
  *   "radiance_slice"  rt_trace_radiance: rays per launch and per staging slice, 1..4194304 (default 4194304, the ray queries' slice); the
  *                     result never depends on it
+ *   "gather_slice"    rt_gather: points per launch and per staging slice, 1..4194304 (default 1048576: an SH9 result is 144 B per point);
+ *                     the result never depends on it
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -462,6 +464,68 @@ int rt_trace_radiance       (rt_ctx* ctx, const rt_ray* rays, int n, const rt_ra
  * rt_trace_rays_device is; rt_radiance_info counts the call and keeps the host entry's times.                                     */
 int rt_trace_radiance_device(rt_ctx* ctx, const void* rays, int n, const rt_radiance_params* params, void* rgba);
 int rt_get_radiance_info    (rt_ctx* ctx, rt_radiance_info* out);
+
+/* ---- gather queries: the light that arrives at a point, over a hemisphere or the sphere ------------------------------------
+ * What a lightmap texel, an irradiance probe or an SH light probe asks.  A radiance query averages N runs of Trace along ONE direction;
+ * here the library draws a direction per sample on the device, from the same counter-based stream, and sums in the wave: n points go
+ * up, n (or 9 n) float4 come back.  A point is an rt_ray: origin is the position, direction is the NORMAL n (used as given: pass a unit
+ * normal, or zero), tMax bounds the first cast.  For point i of a call, K = firstIndex + i, and sample s (0 <= s < N = samples):
+ *
+ *   direction     R = RandomDirection as the shader defines it (RayTracing.shader:216-223: six draws, the shader's order) from the
+ *                 Philox stream with key (K, seed) and counter (block, s, 0, 0): words 0..3 of block 0xFFFFFFFE, then words 0, 1 of
+ *                 block 0xFFFFFFFF.  Trace's hits use blocks 1 + 2b and 2 + 2b with b <= 32000, so the two never meet; block 0 stays
+ *                 unused, as for radiance queries.
+ *                 RT_GATHER_COSINE (mode 0): d = normalize(n + R), the diffuse lobe of :328 — cosine-distributed about a unit n,
+ *                 uniform over the sphere when n = 0.  RT_GATHER_SH9 (mode 1): d = R; n is ignored.
+ *   sample        L_s = Trace(origin, d) exactly as a radiance query runs it for key (K, seed) and sample s: the cast at loop index 0
+ *                 counts only hits with dst < tMax, every later cast is unbounded, the context's rt_params apply as they do there.
+ *                 origin is used as given — the library adds NO offset: a caller on a surface moves the point off it along n
+ *                 themselves (the tests use 1e-3 * n).
+ *   sum           the fixed tree of the Philox mode over the N samples, per channel (S = 16 / 4 / 1 sub-streams for N >= 16 / >= 4 /
+ *                 else, sample s in sub-stream s mod S, each added in increasing order from 0.0f, then pairwise (k, k + 1), (k, k + 2),
+ *                 ...).
+ *   mode 0 output one float4 per point: (root.rgb / (float)N, 1.0f) — the MEAN RADIANCE over the lobe.  For a unit n the irradiance
+ *                 is pi times it (the cosine-weighted integral with the lobe's pdf cos / pi).
+ *   mode 1 output nine float4 per point (144 B), coefficient k = 0..8 of the real SH basis, bands 0..2.  With d = (x, y, z) the
+ *                 per-sample term is L_s.c * Y_k for each channel c; in float32, every product a separate rounding, no FMA:
+ *                   Y0 = 0.28209479f            Y1 = 0.48860251f*y          Y2 = 0.48860251f*z         Y3 = 0.48860251f*x
+ *                   Y4 = 1.09254843f*(x*y)      Y5 = 1.09254843f*(y*z)      Y6 = 0.31539157f*(3.0f*(z*z) - 1.0f)
+ *                   Y7 = 1.09254843f*(x*z)      Y8 = 0.54627421f*(x*x - y*y)
+ *                 The 27 channels go through the same tree; out[k] = ((root / (float)N) * 12.566371f, w), dividing first, with
+ *                 w = 1.0f for k = 0 and 0.0f otherwise: the projection of the incoming radiance (uniform pdf 1 / (4 pi)).
+ *   not traced    tMax <= 0 or NaN: every output float of the point is 0; no draw, no cast.
+ *   defaults      params == NULL: samples = the context's numRaysPerPixel, seed 0, firstIndex 0, mode 0.
+ *   non-finite    components that are not finite give whatever this arithmetic gives; the call does not fault and a path ends after
+ *                 maxBounceCount + 1 casts.
+ *   scene, state  as for radiance queries: the queue is settled, the scene made current, the box padding widened for the largest finite
+ *                 |origin coordinate| among points with tMax > 0.  Nothing of the image, feature, denoiser, temporal or radiance state
+ *                 moves, and no rt_stats field except bvhBuilds / bvhRebuilds / bvhRepads.
+ *   splitting     a batch cut anywhere into two calls, the second with firstIndex advanced by the first's length, gives the bits of one
+ *                 call: the library's own slices (option "gather_slice", points per launch) and rt_multi are invisible.
+ *   errors        a null handle -1; n == 0 returns 0; no params set, n < 0, a null buffer with n > 0, samples outside 1..65536, a
+ *                 non-zero reserved word, a mode that is not 0 or 1, and for the device entry a pointer of another device or one not
+ *                 16-byte aligned: -2 with a message, and nothing changes.                                                        */
+enum { RT_GATHER_COSINE = 0, RT_GATHER_SH9 = 1 };
+typedef struct rt_gather_params {       /* 32 B */
+    int32_t  samples;                   /* N, 1..65536: directions per point                                                 */
+    uint32_t seed;                      /* second key word of the Philox stream                                              */
+    uint32_t firstIndex;                /* point i of the call has stream index firstIndex + i (wraps mod 2^32)              */
+    int32_t  mode;                      /* RT_GATHER_*                                                                       */
+    int32_t  _reserved[4];              /* must be 0                                                                         */
+} rt_gather_params;
+typedef struct rt_gather_info {         /* 32 B */
+    int32_t samples;                    /* of the last call                                                                  */
+    int32_t lastSampleLanes;            /* lanes of a wave that shared a point's samples in the last launch: 16, 4 or 1      */
+    int32_t calls, mode;                /* calls so far / the last call's mode                                               */
+    double  lastKernelMs, totalKernelMs;   /* HIP-event time of the launches of the last host-entry call / summed            */
+} rt_gather_info;
+/* Host memory (out: n * 4 floats in mode 0, n * 36 in mode 1); returns when the results are in out.  The points go through device
+ * buffers of the context in slices of "gather_slice" points, sized to min(n, slice).                                              */
+int rt_gather        (rt_ctx* ctx, const rt_ray* points, int n, const rt_gather_params* params, float* out);
+/* Device memory of the context's GPU (points: n rt_ray, out: n or 9 n float4, both 16-byte aligned), ordered on the context's stream
+ * as rt_trace_rays_device is; rt_gather_info counts the call and keeps the host entry's times.                                     */
+int rt_gather_device (rt_ctx* ctx, const void* points, int n, const rt_gather_params* params, void* out);
+int rt_get_gather_info(rt_ctx* ctx, rt_gather_info* out);
 
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
@@ -705,6 +769,9 @@ int rt_multi_occluded        (rt_multi* m, const rt_ray* rays, int n, uint8_t* o
 /* Radiance queries behind the handle: the same slices, context i's rays keeping their stream indices (firstIndex + their offset in the
  * batch) — bitwise the single-context result.                                                                                    */
 int rt_multi_trace_radiance  (rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba);
+/* Gather queries behind the handle: the same slices, context i's points keeping their stream indices — bitwise the single-context
+ * result.                                                                                                                        */
+int rt_multi_gather          (rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out);
 /* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
  * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
  * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
@@ -730,7 +797,7 @@ int rt_multi_denoise_temporal     (rt_multi* m, const rt_denoise_params* params)
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" */
 
 #ifdef __cplusplus
 }

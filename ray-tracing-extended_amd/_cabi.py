@@ -75,6 +75,12 @@ RADIANCE_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", 
 RADIANCE_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("_reserved", "<i4"),
                           ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert RADIANCE_PARAMS.itemsize == 32 and RADIANCE_INFO.itemsize == 32
+# gather queries (rt_gather): the parameters of a call and the state of the last one
+GATHER_COSINE, GATHER_SH9 = 0, 1
+GATHER_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", "<u4"), ("mode", "<i4"), ("_reserved", "<i4", 4)])
+GATHER_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("mode", "<i4"),
+                        ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert GATHER_PARAMS.itemsize == 32 and GATHER_INFO.itemsize == 32
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
@@ -107,6 +113,7 @@ SYMBOLS = [
     "rt_multi_temporal", "rt_multi_reset_temporal", "rt_multi_read_temporal", "rt_multi_read_temporal_history", "rt_multi_read_temporal_display",
     "rt_multi_denoise_temporal",
     "rt_trace_radiance", "rt_trace_radiance_device", "rt_get_radiance_info", "rt_multi_trace_radiance",
+    "rt_gather", "rt_gather_device", "rt_get_gather_info", "rt_multi_gather",
 ]
 
 _lib = None
@@ -218,6 +225,9 @@ def load_library() -> ctypes.CDLL:
     for n in ("rt_trace_radiance", "rt_trace_radiance_device", "rt_multi_trace_radiance"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.rt_get_radiance_info.argtypes = [c_void_p, c_void_p]
+    for n in ("rt_gather", "rt_gather_device", "rt_multi_gather"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.rt_get_gather_info.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -230,7 +240,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO),
                      ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO),
                      ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO),
-                     ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO)):
+                     ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO),
+                     ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -277,6 +288,33 @@ def _radiance_params(samples, seed, first_index):
 def _radiance_host(call, handle, rays, params, check, what):
     r = _ray_array(rays)
     out = np.zeros((r.shape[0], 4), np.float32)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
+               out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
+def _gather_params(samples, seed, first_index, mode, default_samples=None):
+    """None (the library's defaults: the context's numRaysPerPixel samples, seed 0, firstIndex 0, mode 0) when nothing is given; else a
+    GATHER_PARAMS record, samples None standing for default_samples (the numRaysPerPixel of the params the caller set last)"""
+    if samples is None:
+        if not (seed or first_index or mode):
+            return None
+        if default_samples is None:
+            raise TypeError("gather: samples=None with a seed, first_index or mode needs set_params first")
+        samples = default_samples
+    p = np.zeros((), GATHER_PARAMS)
+    p["samples"], p["seed"], p["firstIndex"], p["mode"] = int(samples), int(seed) & 0xFFFFFFFF, int(first_index) & 0xFFFFFFFF, int(mode)
+    return p
+
+
+def _gather_shape(n, params):
+    """(n, 4) in mode 0, (n, 9, 4) in mode 1"""
+    return (n, 9, 4) if params is not None and int(params["mode"]) == GATHER_SH9 else (n, 4)
+
+
+def _gather_host(call, handle, points, params, check, what):
+    r = _ray_array(points)
+    out = np.zeros(_gather_shape(r.shape[0], params), np.float32)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
                out.ctypes.data_as(c_void_p)), what)
     return out
@@ -480,6 +518,31 @@ class Tracer:
         s = np.zeros((), RADIANCE_INFO)
         self._check(self._lib.rt_get_radiance_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_radiance_info")
         return {k: s[k].item() for k in RADIANCE_INFO.names if k != "_reserved"}
+
+    # -- gather queries
+    def gather(self, points, samples=None, seed=0, first_index=0, mode=GATHER_COSINE):
+        """rt_gather: the light arriving at every point over `samples` directions drawn on the device (None: the context's
+        numRaysPerPixel, seed 0, first index 0, mode 0).  points: a RAY array or float32 (n, 8) — origin, tMax, NORMAL, - .  mode
+        GATHER_COSINE -> float32 (n, 4), the mean radiance over the cosine lobe (irradiance = pi times it); GATHER_SH9 -> float32
+        (n, 9, 4), the SH coefficients of the incoming radiance.  A float32 CUDA tensor (n, 8) on the context's device takes the device
+        entry, ordered with torch's current stream as trace_rays is, and returns a tensor of that shape.  samples=None with a seed, first
+        index or mode (gather(points, mode=GATHER_SH9)) is the numRaysPerPixel of the params set last, as the library's own default is."""
+        q = _gather_params(samples, seed, first_index, mode, None if self._params is None else int(self._params["numRaysPerPixel"]))
+        if not _is_tensor(points):
+            return _gather_host(self._lib.rt_gather, self._ctx, points, q, self._check, "rt_gather")
+        import torch
+        points = self._ray_tensor(points)
+        n = int(points.shape[0])
+        out = torch.empty(_gather_shape(n, q), dtype=torch.float32, device=points.device)
+        qp = None if q is None else q.ctypes.data_as(c_void_p)
+        self._on_torch_stream(points.device, lambda: self._lib.rt_gather_device(self._ctx, c_void_p(points.data_ptr()), n, qp, c_void_p(out.data_ptr())),
+                              "rt_gather_device")
+        return out
+
+    def gather_info(self) -> dict:
+        s = np.zeros((), GATHER_INFO)
+        self._check(self._lib.rt_get_gather_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_gather_info")
+        return {k: s[k].item() for k in GATHER_INFO.names}
 
     # -- rendering
     def render_frame(self, frame: int):
@@ -707,6 +770,7 @@ class MultiTracer:
     def set_params(self, params):
         p = np.ascontiguousarray(params, dtype=PARAMS).reshape(())
         self._shape = (int(p["height"]), int(p["width"]))
+        self._rays_per_pixel = int(p["numRaysPerPixel"])
         self._check(self._lib.rt_multi_set_params(self._m, p.ctypes.data_as(c_void_p)), "rt_multi_set_params")
 
     def upload(self, spheres=None, triangles=None, meshinfo=None):
@@ -759,12 +823,19 @@ class MultiTracer:
         return _radiance_host(self._lib.rt_multi_trace_radiance, self._m, rays, _radiance_params(samples, seed, first_index), self._check,
                               "rt_multi_trace_radiance")
 
+    def gather(self, points, samples=None, seed=0, first_index=0, mode=GATHER_COSINE) -> np.ndarray:
+        """rt_multi_gather: Tracer.gather over the contexts (host arrays), every point keeping its stream index."""
+        q = _gather_params(samples, seed, first_index, mode, getattr(self, "_rays_per_pixel", None))
+        return _gather_host(self._lib.rt_multi_gather, self._m, points, q, self._check,
+                            "rt_multi_gather")
+
     def render_params(self, first_frame: int, params):
         """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""
         p, n = _params_run(params)
         self._check(self._lib.rt_multi_render_params(self._m, int(first_frame), n, p.ctypes.data_as(c_void_p)), "rt_multi_render_params")
         if n:
             self._shape = (int(p[0]["height"]), int(p[0]["width"]))
+            self._rays_per_pixel = int(p[-1]["numRaysPerPixel"])
 
     def read_accum(self) -> np.ndarray:
         H, W = self._shape

@@ -432,6 +432,15 @@ class RayTracingManager:
         self.InitFrame()
         return self.backend.trace_radiance(rays, samples, seed, firstIndex)
 
+    def Gather(self, points, samples: int = None, seed: int = 0, firstIndex: int = 0, mode: int = 0):
+        """Beyond the reference: the light that arrives at each point of the scene the next frame traces, over `samples` directions the
+        device draws (rt_gather; None: numRaysPerPixel).  points: a RAY array or float32 (n, 8) with the NORMAL in the direction field
+        (a point on a surface is moved off it by the caller).  mode 0 -> float32 (n, 4): the mean radiance over the cosine lobe about the
+        normal (irradiance = pi times it) — a lightmap texel; mode 1 -> float32 (n, 9, 4): nine SH coefficients — a light probe.  A
+        tensor on the tracer's device takes rt_gather_device and returns a tensor."""
+        self.InitFrame()
+        return self.backend.gather(points, samples, seed, firstIndex, mode)
+
     def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
         """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
         the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices

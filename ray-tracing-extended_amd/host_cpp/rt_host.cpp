@@ -481,6 +481,24 @@ std::vector<float> RayTracingManager::TraceRadiance(rt_multi* m, const std::vect
     return rgba;
 }
 
+static size_t gather_floats(const rt_gather_params* params) { return params && params->mode == RT_GATHER_SH9 ? 36 : 4; }
+
+std::vector<float> RayTracingManager::Gather(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_gather_params* params)
+{
+    InitFrame(ctx);
+    std::vector<float> out(points.size() * gather_floats(params));
+    check(ctx, rt_gather(ctx, points.data(), (int)points.size(), params, out.data()), "rt_gather");
+    return out;
+}
+
+std::vector<float> RayTracingManager::Gather(rt_multi* m, const std::vector<rt_ray>& points, const rt_gather_params* params)
+{
+    InitFrame(m);
+    std::vector<float> out(points.size() * gather_floats(params));
+    mcheck(m, rt_multi_gather(m, points.data(), (int)points.size(), params, out.data()), "rt_multi_gather");
+    return out;
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

@@ -150,6 +150,11 @@ public:
     // floats, (r, g, b, 1) per ray.
     std::vector<float> TraceRadiance(rt_ctx* ctx, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
     std::vector<float> TraceRadiance(rt_multi* multi, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
+    // Beyond the reference: the light that arrives at each of the caller's points (rt_ray: origin, tMax, the NORMAL in direction) over
+    // directions the device draws — rt_gather / rt_multi_gather (params null = numRaysPerPixel samples, seed 0, firstIndex 0, mode
+    // RT_GATHER_COSINE).  Returns points.size() * 4 floats (mode 0: mean radiance, 1) or points.size() * 36 (mode 1: nine SH coefficients).
+    std::vector<float> Gather(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
+    std::vector<float> Gather(rt_multi* multi, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

@@ -230,6 +230,23 @@ namespace RtMi355x
             return rgba;
         }
 
+        // ---- gather queries (lightmap texels, irradiance and SH light probes: RtGather.cs) -------------------------------------------
+        /// The light that arrives at each point of the scene the next frame traces, over `samples` directions the device draws (0 =
+        /// numRaysPerPixel, with seed 0).  A point is an RtRay with the surface NORMAL in its direction (MakeRay(position, normal,
+        /// maxDistance)); a point on a surface is moved off it by the caller.  sh9 false: rays.Length * 4 floats, the mean radiance over
+        /// the cosine lobe about the normal (irradiance = pi times it); sh9 true: rays.Length * 36 floats, nine SH coefficients (r, g, b, -).
+        public float[] Gather(RtRay[] points, int samples = 0, uint seed = 0, bool sh9 = false)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            if (sh9 && samples <= 0) samples = p.numRaysPerPixel;
+            float[] result = new float[(long)points.Length * (sh9 ? 36 : 4)];
+            RtGatherParams[] q = samples > 0 ? new[] { new RtGatherParams { samples = samples, seed = seed, mode = sh9 ? 1 : 0 } } : null;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_gather(multi, points, points.Length, q, result), "rt_multi_gather");
+            else RtNative.Check(ctx, RtNative.rt_gather(ctx, points, points.Length, q, result), "rt_gather");
+            return result;
+        }
+
         /// The radiance along one ray (a probe, the light behind a picked pixel).
         public Color Radiance(Vector3 origin, Vector3 direction, float maxDistance, int samples = 0, uint seed = 0)
         {

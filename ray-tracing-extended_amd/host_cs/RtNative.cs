@@ -258,6 +258,11 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_trace_radiance_device(IntPtr ctx, IntPtr rays, int n, [In] RtRadianceParams[] p, IntPtr rgba);
         [DllImport(Lib)] public static extern int rt_get_radiance_info(IntPtr ctx, out RtRadianceInfo info);
         [DllImport(Lib)] public static extern int rt_multi_trace_radiance(IntPtr multi, [In] RtRay[] rays, int n, [In] RtRadianceParams[] p, [Out] float[] rgba);
+        // gather queries (RtGatherParams, RtGatherInfo: RtGather.cs; p: one entry, or null = numRaysPerPixel samples, seed 0, firstIndex 0, mode 0; result: n * 4 or n * 36 floats)
+        [DllImport(Lib)] public static extern int rt_gather(IntPtr ctx, [In] RtRay[] points, int n, [In] RtGatherParams[] p, [Out] float[] result);
+        [DllImport(Lib)] public static extern int rt_gather_device(IntPtr ctx, IntPtr points, int n, [In] RtGatherParams[] p, IntPtr result);
+        [DllImport(Lib)] public static extern int rt_get_gather_info(IntPtr ctx, out RtGatherInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_gather(IntPtr multi, [In] RtRay[] points, int n, [In] RtGatherParams[] p, [Out] float[] result);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -306,6 +311,8 @@ namespace RtMi355x
             Same("rt_denoise_info", Marshal.SizeOf<RtDenoiseInfo>());
             Same("rt_radiance_params", Marshal.SizeOf<RtRadianceParams>());
             Same("rt_radiance_info", Marshal.SizeOf<RtRadianceInfo>());
+            Same("rt_gather_params", Marshal.SizeOf<RtGatherParams>());
+            Same("rt_gather_info", Marshal.SizeOf<RtGatherInfo>());
         }
     }
 }
