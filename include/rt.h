@@ -244,6 +244,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     result never depends on it
  *   "gather_slice"    rt_gather: points per launch and per staging slice, 1..4194304 (default 1048576: an SH9 result is 144 B per point);
  *                     the result never depends on it
+ *   "visibility_slice" rt_visibility: points per launch and per staging slice, 1..4194304 (default 4194304, the ray queries' slice);
+ *                     the result never depends on it
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -527,6 +529,69 @@ int rt_gather        (rt_ctx* ctx, const rt_ray* points, int n, const rt_gather_
 int rt_gather_device (rt_ctx* ctx, const void* points, int n, const rt_gather_params* params, void* out);
 int rt_get_gather_info(rt_ctx* ctx, rt_gather_info* out);
 
+/* ---- visibility gathers: how open a point is, in which direction, and how far away the surfaces are ------------------------------
+ * The geometry-only question beside a gather query: ambient occlusion and bent normals of a lightmap texel or vertex, the sky
+ * visibility and a visibility SH9 of a probe (to multiply with a sky SH9), the mean distance and mean squared distance that place
+ * probes and detect probes inside walls.  Nothing is shaded and no rt_params are needed.  A point is an rt_ray as for rt_gather: origin
+ * is the position, direction is the NORMAL n (used as given: pass a unit normal, or zero), tMax is the REACH t of every cast.  For point
+ * i of a call, K = firstIndex + i, and sample s (0 <= s < N = samples):
+ *
+ *   direction     R = RandomDirection exactly as rt_gather draws it: the Philox stream with key (K, seed) and counter (block, s, 0, 0),
+ *                 words 0..3 of block 0xFFFFFFFE, then words 0, 1 of block 0xFFFFFFFF.
+ *                 RT_VIS_COSINE (mode 0) and RT_VIS_DISTANCE (mode 2): d = normalize(n + R) — cosine-distributed about a unit n,
+ *                 uniform over the sphere when n = 0.  RT_VIS_SH9 (mode 1): d = R; n is ignored.  For equal (K, seed, s, n) these are
+ *                 the bits rt_gather's modes 0 / 1 trace along: one set of directions serves a probe's lighting and its visibility.
+ *   cast, 0 and 1 occ = what rt_occluded answers for the ray (origin, d, t): the any-hit rule with dst < t.  The context's intersectMode
+ *                 applies (RT_INTERSECT_FLAT_CHUNKS when rt_set_params was never called).  v = occ ? 0.0f : 1.0f.
+ *   cast, mode 2  h = what rt_trace_rays answers for (origin, d, t); r = h is a hit ? h.dst : t; hit = 1.0f for a hit, 0.0f for a miss.
+ *   channels      (a select, so that 0 x NaN cannot appear)
+ *                 mode 0, four:  (v ? d.x : 0, v ? d.y : 0, v ? d.z : 0, v)
+ *                 mode 1, ten:   v ? Y_k(d) : 0 for k = 0..8, then v; Y_k as the gather section writes it, every product a separate
+ *                                rounding, no FMA
+ *                 mode 2, three: (r, r * r, hit)
+ *   sum           the fixed tree of the Philox mode over the N samples, per channel, as in rt_gather (S = 16 / 4 / 1 sub-streams for
+ *                 N >= 16 / >= 4 / else, sample s in sub-stream s mod S, each added in increasing order from 0.0f, then pairwise); the
+ *                 root is divided by (float)N.
+ *   mode 0 output one float4 per point: (bent.xyz, visibility).  bent is the mean open direction, NOT normalised: its length tells how
+ *                 one-sided the opening is.  Ambient occlusion = 1 - visibility.
+ *   mode 1 output three float4 per point (48 B): floats 0..8 = (root_k / (float)N) * 12.566371f, dividing first — the projection of the
+ *                 visibility function onto the real SH basis of bands 0..2; float 9 = the visibility fraction; floats 10, 11 = 0.0f.
+ *   mode 2 output one float4 per point: (mean r, mean r * r, hit fraction, 1.0f).  With an infinite t a miss makes both means +inf.
+ *                 The 0 / 1 channels sum exactly up to 2^24, so visibility and hit fraction equal count / (float)N whatever the tree.
+ *   not traced    t <= 0 or NaN: every output float of the point is 0; no draw, no cast.
+ *   non-finite    components that are not finite, or n + R = 0, give whatever this arithmetic gives; the call does not fault.
+ *   scene, state  as for ray queries: the queue is settled, the scene made current, the box padding widened for the largest finite
+ *                 |origin coordinate| among points with t > 0.  Nothing else moves — not the image, feature, denoiser, temporal,
+ *                 radiance or gather state, and no rt_stats field except bvhBuilds / bvhRebuilds / bvhRepads.
+ *   splitting     a batch cut anywhere into two calls, the second with firstIndex advanced by the first's length, gives the bits of one
+ *                 call: the library's own slices (option "visibility_slice", points per launch) and rt_multi are invisible.
+ *   defaults      params == NULL: samples = RT_VISIBILITY_DEFAULT_SAMPLES (64), seed 0, firstIndex 0, mode 0.
+ *   errors        a null handle -1; n == 0 returns 0; n < 0, a null buffer with n > 0, samples outside 1..65536, a non-zero reserved
+ *                 word, a mode outside 0..2, and for the device entry a pointer of another device or one not 16-byte aligned: -2 with
+ *                 a message, and nothing changes.                                                                                  */
+enum { RT_VIS_COSINE = 0, RT_VIS_SH9 = 1, RT_VIS_DISTANCE = 2 };
+#define RT_VISIBILITY_DEFAULT_SAMPLES 64
+typedef struct rt_visibility_params {   /* 32 B */
+    int32_t  samples;                   /* N, 1..65536: directions per point                                                 */
+    uint32_t seed;                      /* second key word of the Philox stream                                              */
+    uint32_t firstIndex;                /* point i of the call has stream index firstIndex + i (wraps mod 2^32)              */
+    int32_t  mode;                      /* RT_VIS_*                                                                          */
+    int32_t  _reserved[4];              /* must be 0                                                                         */
+} rt_visibility_params;
+typedef struct rt_visibility_info {     /* 32 B */
+    int32_t samples;                    /* of the last call                                                                  */
+    int32_t lastSampleLanes;            /* lanes of a wave that shared a point's samples in the last launch: 16, 4 or 1      */
+    int32_t calls, mode;                /* calls so far / the last call's mode                                               */
+    double  lastKernelMs, totalKernelMs;   /* HIP-event time of the launches of the last host-entry call / summed            */
+} rt_visibility_info;
+/* Host memory (out: n * 4 floats in modes 0 and 2, n * 12 in mode 1); returns when the results are in out.  The points go through
+ * device buffers of the context in slices of "visibility_slice" points, sized to min(n, slice).                                   */
+int rt_visibility        (rt_ctx* ctx, const rt_ray* points, int n, const rt_visibility_params* params, float* out);
+/* Device memory of the context's GPU (points: n rt_ray, out: n or 3 n float4, both 16-byte aligned), ordered on the context's stream
+ * as rt_trace_rays_device is; rt_visibility_info counts the call and keeps the host entry's times.                                */
+int rt_visibility_device (rt_ctx* ctx, const void* points, int n, const rt_visibility_params* params, void* out);
+int rt_get_visibility_info(rt_ctx* ctx, rt_visibility_info* out);
+
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
  * target is the colour of RayTracing.shader:388); the definition below is this library's, built from the reference's own steps.
@@ -772,6 +837,9 @@ int rt_multi_trace_radiance  (rt_multi* m, const rt_ray* rays, int n, const rt_r
 /* Gather queries behind the handle: the same slices, context i's points keeping their stream indices — bitwise the single-context
  * result.                                                                                                                        */
 int rt_multi_gather          (rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out);
+/* Visibility gathers behind the handle: the same slices, context i's points keeping their stream indices — bitwise the single-context
+ * result.                                                                                                                        */
+int rt_multi_visibility      (rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out);
 /* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
  * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
  * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
@@ -797,7 +865,7 @@ int rt_multi_denoise_temporal     (rt_multi* m, const rt_denoise_params* params)
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" */
 
 #ifdef __cplusplus
 }

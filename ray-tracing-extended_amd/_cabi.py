@@ -81,6 +81,13 @@ GATHER_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", "<
 GATHER_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("mode", "<i4"),
                         ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert GATHER_PARAMS.itemsize == 32 and GATHER_INFO.itemsize == 32
+# visibility gathers (rt_visibility): the parameters of a call and the state of the last one
+VIS_COSINE, VIS_SH9, VIS_DISTANCE = 0, 1, 2
+VISIBILITY_DEFAULT_SAMPLES = 64          # RT_VISIBILITY_DEFAULT_SAMPLES of include/rt.h (what a null rt_visibility_params means)
+VISIBILITY_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", "<u4"), ("mode", "<i4"), ("_reserved", "<i4", 4)])
+VISIBILITY_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("mode", "<i4"),
+                            ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert VISIBILITY_PARAMS.itemsize == 32 and VISIBILITY_INFO.itemsize == 32
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
@@ -114,6 +121,7 @@ SYMBOLS = [
     "rt_multi_denoise_temporal",
     "rt_trace_radiance", "rt_trace_radiance_device", "rt_get_radiance_info", "rt_multi_trace_radiance",
     "rt_gather", "rt_gather_device", "rt_get_gather_info", "rt_multi_gather",
+    "rt_visibility", "rt_visibility_device", "rt_get_visibility_info", "rt_multi_visibility",
 ]
 
 _lib = None
@@ -228,6 +236,9 @@ def load_library() -> ctypes.CDLL:
     for n in ("rt_gather", "rt_gather_device", "rt_multi_gather"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.rt_get_gather_info.argtypes = [c_void_p, c_void_p]
+    for n in ("rt_visibility", "rt_visibility_device", "rt_multi_visibility"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.rt_get_visibility_info.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -241,7 +252,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO),
                      ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO),
                      ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO),
-                     ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO)):
+                     ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO),
+                     ("rt_visibility_params", VISIBILITY_PARAMS), ("rt_visibility_info", VISIBILITY_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -315,6 +327,30 @@ def _gather_shape(n, params):
 def _gather_host(call, handle, points, params, check, what):
     r = _ray_array(points)
     out = np.zeros(_gather_shape(r.shape[0], params), np.float32)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
+               out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
+def _visibility_params(samples, seed, first_index, mode):
+    """None (the library's defaults: 64 samples, seed 0, firstIndex 0, mode 0) when nothing is given; else a VISIBILITY_PARAMS record,
+    samples None standing for the library's default count"""
+    if samples is None and not (seed or first_index or mode):
+        return None
+    p = np.zeros((), VISIBILITY_PARAMS)
+    p["samples"] = VISIBILITY_DEFAULT_SAMPLES if samples is None else int(samples)
+    p["seed"], p["firstIndex"], p["mode"] = int(seed) & 0xFFFFFFFF, int(first_index) & 0xFFFFFFFF, int(mode)
+    return p
+
+
+def _visibility_shape(n, params):
+    """(n, 4) in modes 0 and 2, (n, 12) in mode 1"""
+    return (n, 12) if params is not None and int(params["mode"]) == VIS_SH9 else (n, 4)
+
+
+def _visibility_host(call, handle, points, params, check, what):
+    r = _ray_array(points)
+    out = np.zeros(_visibility_shape(r.shape[0], params), np.float32)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
                out.ctypes.data_as(c_void_p)), what)
     return out
@@ -543,6 +579,34 @@ class Tracer:
         s = np.zeros((), GATHER_INFO)
         self._check(self._lib.rt_get_gather_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_gather_info")
         return {k: s[k].item() for k in GATHER_INFO.names}
+
+    # -- visibility gathers
+    def visibility(self, points, samples=None, seed=0, first_index=0, mode=VIS_COSINE):
+        """rt_visibility: how open every point is over `samples` directions drawn on the device — rt_gather's directions, bit for bit
+        (None: 64 samples).  points: a RAY array or float32 (n, 8) — origin, the reach tMax, NORMAL, - .  No params are needed.  mode
+        VIS_COSINE -> float32 (n, 4): the bent normal (the mean open direction, not normalised) and the visibility fraction (ambient
+        occlusion = 1 - it); VIS_SH9 -> float32 (n, 12): nine SH coefficients of the visibility function, the visibility fraction, 0, 0;
+        VIS_DISTANCE -> float32 (n, 4): mean distance (a miss counts the reach), mean squared distance, hit fraction, 1.  A float32 CUDA
+        tensor (n, 8) on the context's device takes the device entry, ordered with torch's current stream as trace_rays is, and returns a
+        tensor of that shape."""
+        q = _visibility_params(samples, seed, first_index, mode)
+        if not _is_tensor(points):
+            return _visibility_host(self._lib.rt_visibility, self._ctx, points, q, self._check, "rt_visibility")
+        import torch
+        points = self._ray_tensor(points)
+        n = int(points.shape[0])
+        out = torch.empty(_visibility_shape(n, q), dtype=torch.float32, device=points.device)
+        qp = None if q is None else q.ctypes.data_as(c_void_p)
+        self._on_torch_stream(points.device, lambda: self._lib.rt_visibility_device(self._ctx, c_void_p(points.data_ptr()), n, qp, c_void_p(out.data_ptr())),
+                              "rt_visibility_device")
+        return out
+
+    visibility_device = visibility          # (a tensor takes rt_visibility_device; the name says so at the call site)
+
+    def visibility_info(self) -> dict:
+        s = np.zeros((), VISIBILITY_INFO)
+        self._check(self._lib.rt_get_visibility_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_visibility_info")
+        return {k: s[k].item() for k in VISIBILITY_INFO.names}
 
     # -- rendering
     def render_frame(self, frame: int):
@@ -828,6 +892,11 @@ class MultiTracer:
         q = _gather_params(samples, seed, first_index, mode, getattr(self, "_rays_per_pixel", None))
         return _gather_host(self._lib.rt_multi_gather, self._m, points, q, self._check,
                             "rt_multi_gather")
+
+    def visibility(self, points, samples=None, seed=0, first_index=0, mode=VIS_COSINE) -> np.ndarray:
+        """rt_multi_visibility: Tracer.visibility over the contexts (host arrays), every point keeping its stream index."""
+        return _visibility_host(self._lib.rt_multi_visibility, self._m, points, _visibility_params(samples, seed, first_index, mode), self._check,
+                                "rt_multi_visibility")
 
     def render_params(self, first_frame: int, params):
         """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""

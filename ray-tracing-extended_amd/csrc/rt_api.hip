@@ -32,6 +32,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_query.hpp"
 #include "rt_radiance.hpp"
 #include "rt_gather.hpp"
+#include "rt_visibility.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -201,6 +202,9 @@ struct rt_ctx : ErrOwner {
     rt_radiance_info radiance_info{};
     DevBuf<float4> d_q_gather;                                              // gather queries: the host entry's results (one slice: 1 or 9 float4 per point)
     rt_gather_info gather_info{};
+    DevBuf<float4> d_q_vis;                                                 // visibility gathers: the host entry's results (one slice: 1 or 3 float4 per point)
+    rt_visibility_info visibility_info{};
+    int opt_visibility_slice = 1 << 22; // visibility gathers: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_gather_slice = 1 << 20;     // gather queries: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_radiance_slice = 1 << 22;   // radiance queries: rays per launch (and per staging slice of the host entry); the result never depends on it
     // feature buffers (rt_render_aov, csrc/rt_aov.hpp): the two accumulated planes of this context's strip and the layout they were made for
@@ -1527,6 +1531,109 @@ int gather_device(rt_ctx* c, const void* points, int n, const rt_gather_params* 
     return 0;
 }
 
+// ---- visibility gathers (rt_visibility, csrc/rt_visibility.hpp) -------------------------------------------------------------------
+// The arguments of a call as the kernel takes them; params == NULL: RT_VISIBILITY_DEFAULT_SAMPLES samples, seed 0, firstIndex 0, mode 0.
+// No rt_params are needed: the kernel reads intersectMode alone, as the ray queries do
+int visibility_arguments(rt_ctx* c, const char* what, const void* points, int n, const rt_visibility_params* params, const void* out, rt_visibility_params& q)
+{
+    if (n < 0 || (n > 0 && (!points || !out))) return fail(c, -2, "%s: bad arguments (n = %d, points %p, out %p)", what, n, points, out);
+    q = rt_visibility_params{};
+    if (params) q = *params; else q.samples = RT_VISIBILITY_DEFAULT_SAMPLES;
+    if (q.samples < 1 || q.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", what, q.samples);
+    if (q.mode < RT_VIS_COSINE || q.mode > RT_VIS_DISTANCE) return fail(c, -2, "%s: mode = %d is none of RT_VIS_COSINE, RT_VIS_SH9, RT_VIS_DISTANCE", what, q.mode);
+    for (int r : q._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_visibility_params is not 0", what);
+    return 0;
+}
+inline size_t visibility_out_float4(int mode) { return mode == RT_VIS_SH9 ? 3 : 1; }      // float4 per point
+
+const void* visibility_kernel(int mode, bool compact)
+{
+    switch (mode) {
+    case RT_VIS_SH9:      return compact ? (const void*)rtk::k_visibility<RT_VIS_SH9, true> : (const void*)rtk::k_visibility<RT_VIS_SH9, false>;
+    case RT_VIS_DISTANCE: return compact ? (const void*)rtk::k_visibility<RT_VIS_DISTANCE, true> : (const void*)rtk::k_visibility<RT_VIS_DISTANCE, false>;
+    default:              return compact ? (const void*)rtk::k_visibility<RT_VIS_COSINE, true> : (const void*)rtk::k_visibility<RT_VIS_COSINE, false>;
+    }
+}
+
+// n points (device, 2 float4 each) -> n or 3 n float4, on the context's stream; no synchronisation.  launch_gather's slices: one launch
+// per opt_visibility_slice points, each with firstIndex advanced by the points before it.
+int launch_visibility(rt_ctx* c, const float4* points, int n, const rt_visibility_params& q, float4* out)
+{
+    rtk::DeviceScene S{};
+    { int r = fill_scene(c, S); if (r) return r; }
+    rtk::VisibilityArgs A{};
+    A.samples = q.samples; A.seed = q.seed;
+    A.sample_lanes_log2 = q.samples >= 16 ? 4 : q.samples >= 4 ? 2 : 0;       // S = 16 / 4 / 1 (include/rt.h RT_RNG_PHILOX)
+    A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    A.full_sort = c->opt_full_sort;
+    c->visibility_info.samples = q.samples; c->visibility_info.lastSampleLanes = 1 << A.sample_lanes_log2; c->visibility_info.mode = q.mode;
+    const void* fn = visibility_kernel(q.mode, c->opt_compact_nodes != 0);     // the node form the renderer's kernels traverse
+    const size_t per = visibility_out_float4(q.mode);
+    const int slice = c->opt_visibility_slice;          // (at most 2^22 points: points * S stays below 2^31)
+    for (int first = 0; first < n; first += slice) {
+        const int cnt = std::min(slice, n - first);
+        const size_t lanes = (size_t)cnt << A.sample_lanes_log2;
+        const int grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
+        LaneStack st;
+        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_visibility"); if (r) return r; }
+        A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
+        A.points = points + 2 * (size_t)first; A.out = out + per * (size_t)first; A.n = cnt;
+        A.first_index = q.firstIndex + (uint32_t)first;
+        void* args[] = { &S, &A };
+        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
+    }
+    return 0;
+}
+
+int visibility_host(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out)
+{
+    RT_SETTLE(c);
+    rt_visibility_params q;
+    { int r = visibility_arguments(c, "rt_visibility", points, n, params, out, q); if (r) return r; }
+    if (n == 0) return 0;
+    { int r = query_prepare(c, query_origin_bound(points, n)); if (r) return r; }
+    const size_t per = visibility_out_float4(q.mode);
+    const int slice = c->opt_visibility_slice;
+    RT_HIP(c, c->d_q_rays.ensure(2 * (size_t)std::min(n, slice)));
+    RT_HIP(c, c->d_q_vis.ensure(per * (size_t)std::min(n, slice)));
+    double ms_sum = 0;
+    for (int first = 0; first < n; first += slice) {
+        const int cnt = std::min(slice, n - first);
+        rt_visibility_params qs = q;
+        qs.firstIndex = q.firstIndex + (uint32_t)first;
+        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, points + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+        RT_HIP(c, hipEventRecord(c->ev0, c->stream));
+        { int r = launch_visibility(c, c->d_q_rays.p, cnt, qs, c->d_q_vis.p); if (r) return r; }
+        RT_HIP(c, hipEventRecord(c->ev1, c->stream));
+        RT_HIP(c, hipMemcpyAsync(out + 4 * per * (size_t)first, c->d_q_vis.p, per * (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));     // (the events are the context's one pair: read before the next slice records them)
+        float ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_sum += ms;
+    }
+    c->visibility_info.calls++; c->visibility_info.lastKernelMs = ms_sum; c->visibility_info.totalKernelMs += ms_sum;
+    return 0;
+}
+
+int visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out)
+{
+    const char* what = "rt_visibility_device";
+    RT_SETTLE(c);
+    rt_visibility_params q;
+    { int r = visibility_arguments(c, what, points, n, params, out, q); if (r) return r; }
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!on_ctx_device(c, points) || !on_ctx_device(c, out))
+        return fail(c, -2, "%s: points and results must be device memory of the context's device %d", what, c->device);
+    if ((reinterpret_cast<uintptr_t>(points) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
+        return fail(c, -2, "%s: points and out must be 16-byte aligned", what);
+    { int r = prepare_scene(c); if (r) return r; }
+    { int r = cover_origins_device(c, static_cast<const float4*>(points), n); if (r) return r; }
+    { int r = launch_visibility(c, static_cast<const float4*>(points), n, q, static_cast<float4*>(out)); if (r) return r; }
+    c->visibility_info.calls++;                         // (asynchronous: the times are the host entry's)
+    return 0;
+}
+
 // ---- feature buffers (rt_render_aov, csrc/rt_aov.hpp) -----------------------------------------------------------------------------
 // The two planes of the context's strip, zeroed when they are created and whenever the strip's layout changes (ensure_targets' rule for
 // the accumulation target, kept apart from it: a feature frame must not touch the image path's state)
@@ -1854,6 +1961,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_radiance_info")) return (int)sizeof(rt_radiance_info);
     if (!std::strcmp(name, "rt_gather_params")) return (int)sizeof(rt_gather_params);
     if (!std::strcmp(name, "rt_gather_info")) return (int)sizeof(rt_gather_info);
+    if (!std::strcmp(name, "rt_visibility_params")) return (int)sizeof(rt_visibility_params);
+    if (!std::strcmp(name, "rt_visibility_info")) return (int)sizeof(rt_visibility_info);
     return -1;
 }
 
@@ -2079,6 +2188,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "queue_depth")) { if (value < 1 || value > 256) return fail(c, -2, "queue_depth must be in [1,256]"); c->opt_queue_depth = value; }
     else if (!std::strcmp(name, "queue_linger_us")) { if (value < 0 || value > 1000000) return fail(c, -2, "queue_linger_us must be in [0,1000000]"); c->opt_queue_linger_us = value; }
     else if (!std::strcmp(name, "gather_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "gather_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_gather_slice = value; }
+    else if (!std::strcmp(name, "visibility_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "visibility_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_visibility_slice = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
     else return fail(c, -2, "unknown option '%s'", name);
@@ -2248,6 +2358,14 @@ int rt_get_gather_info(rt_ctx* c, rt_gather_info* out)
 {
     if (!c || !out) return -1;
     *out = c->gather_info;
+    return 0;
+}
+int rt_visibility(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return c ? visibility_host(c, points, n, params, out) : -1; }
+int rt_visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out) { return c ? visibility_device(c, points, n, params, out) : -1; }
+int rt_get_visibility_info(rt_ctx* c, rt_visibility_info* out)
+{
+    if (!c || !out) return -1;
+    *out = c->visibility_info;
     return 0;
 }
 int rt_get_radiance_info(rt_ctx* c, rt_radiance_info* out)
@@ -2673,6 +2791,25 @@ int multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_param
     });
 }
 
+// rt_multi_visibility: multi_query's slices (no params needed, as there); context i's points keep the stream indices they have in the
+// whole batch
+int multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out)
+{
+    rt_visibility_params q;
+    if (visibility_arguments(m->ctx[0], "rt_multi_visibility", points, n, params, out, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
+    if (n == 0) return 0;
+    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
+    const int N = (int)m->ctx.size();
+    const int per = (n + N - 1) / N;
+    const size_t floats = 4 * visibility_out_float4(q.mode);
+    return on_every_context(m, "rt_visibility", [&](int i) {
+        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
+        rt_visibility_params qi = q;
+        qi.firstIndex = q.firstIndex + (uint32_t)first;
+        return visibility_host(m->ctx[i], points + first, cnt, &qi, out + floats * (size_t)first);
+    });
+}
+
 // What the denoiser and the temporal step share behind the handle: every context settled and holding current strips of the image
 // (if `image`) and of both feature planes with a frame in them, then those strips gathered to the first device
 int multi_gather_inputs(rt_multi* m, const char* what, bool image)
@@ -2701,6 +2838,7 @@ int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { 
 int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return m ? multi_query(m, true, rays, n, occluded) : -1; }
 int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return m ? multi_radiance(m, rays, n, params, rgba) : -1; }
 int rt_multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return m ? multi_gather(m, points, n, params, out) : -1; }
+int rt_multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return m ? multi_visibility(m, points, n, params, out) : -1; }
 
 // Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands
 int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)

@@ -441,6 +441,16 @@ class RayTracingManager:
         self.InitFrame()
         return self.backend.gather(points, samples, seed, firstIndex, mode)
 
+    def Visibility(self, points, samples: int = None, seed: int = 0, firstIndex: int = 0, mode: int = 0):
+        """Beyond the reference: how open each point of the scene the next frame traces is, over `samples` directions the device draws —
+        the directions Gather draws for the same seed and index (rt_visibility; None: 64).  points as for Gather, tMax the reach.  mode 0
+        -> float32 (n, 4): bent normal and visibility fraction (ambient occlusion = 1 - it) — a lightmap texel; mode 1 -> float32
+        (n, 12): nine SH coefficients of the visibility, the fraction, 0, 0 — a probe's sky visibility; mode 2 -> float32 (n, 4): mean
+        distance, mean squared distance, hit fraction, 1 — probe placement.  A tensor on the tracer's device takes rt_visibility_device
+        and returns a tensor."""
+        self.InitFrame()
+        return self.backend.visibility(points, samples, seed, firstIndex, mode)
+
     def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
         """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
         the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices

@@ -499,6 +499,24 @@ std::vector<float> RayTracingManager::Gather(rt_multi* m, const std::vector<rt_r
     return out;
 }
 
+static size_t visibility_floats(const rt_visibility_params* params) { return params && params->mode == RT_VIS_SH9 ? 12 : 4; }
+
+std::vector<float> RayTracingManager::Visibility(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_visibility_params* params)
+{
+    InitFrame(ctx);
+    std::vector<float> out(points.size() * visibility_floats(params));
+    check(ctx, rt_visibility(ctx, points.data(), (int)points.size(), params, out.data()), "rt_visibility");
+    return out;
+}
+
+std::vector<float> RayTracingManager::Visibility(rt_multi* m, const std::vector<rt_ray>& points, const rt_visibility_params* params)
+{
+    InitFrame(m);
+    std::vector<float> out(points.size() * visibility_floats(params));
+    mcheck(m, rt_multi_visibility(m, points.data(), (int)points.size(), params, out.data()), "rt_multi_visibility");
+    return out;
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

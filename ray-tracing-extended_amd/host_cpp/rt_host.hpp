@@ -155,6 +155,12 @@ public:
     // RT_GATHER_COSINE).  Returns points.size() * 4 floats (mode 0: mean radiance, 1) or points.size() * 36 (mode 1: nine SH coefficients).
     std::vector<float> Gather(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
     std::vector<float> Gather(rt_multi* multi, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
+    // Beyond the reference: how open each of the caller's points is (rt_ray: origin, the reach in tMax, the NORMAL in direction) over the
+    // directions Gather draws — rt_visibility / rt_multi_visibility (params null = 64 samples, seed 0, firstIndex 0, mode RT_VIS_COSINE).
+    // Returns points.size() * 4 floats (mode 0: bent normal, visibility; mode 2: mean distance, mean squared distance, hit fraction, 1)
+    // or points.size() * 12 (mode 1: nine SH coefficients, visibility, 0, 0).
+    std::vector<float> Visibility(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
+    std::vector<float> Visibility(rt_multi* multi, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

@@ -5,7 +5,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
 import numpy as np
 
-from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array
+from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_host.so")
 _lib = None
@@ -28,6 +28,7 @@ def load_host_library():
         L.rth_render_animated.argtypes = [c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float)]
         L.rth_trace_radiance.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_gather.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
+        L.rth_visibility.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_split_mesh.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]
         L.rth_split_info.argtypes = [c_void_p, c_void_p, c_void_p]
         L.rth_split_triangles.argtypes = [c_void_p]
@@ -144,4 +145,18 @@ class CppScene:
         if self._L.rth_gather(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
                               None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
             raise RtError("Gather: " + self._L.rth_last_error().decode())
+        return out
+
+    def visibility(self, points, samples=None, seed=0, first_index=0, mode=0, devices=(), device: int = 0) -> np.ndarray:
+        """RayTracingManager::Visibility on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: points (a RAY array or float32
+        (n, 8), the normal in the direction field, the reach in tMax) -> float32 (n, 4) in modes 0 and 2, (n, 12) in mode 1; samples
+        None = the library's defaults."""
+        r = _ray_array(points)
+        q = _visibility_params(samples, seed, first_index, mode)
+        out = np.zeros(_visibility_shape(r.shape[0], q), np.float32)
+        devs = list(devices) if devices else [device]
+        arr = (c_int * len(devs))(*devs)
+        if self._L.rth_visibility(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
+                                  None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
+            raise RtError("Visibility: " + self._L.rth_last_error().decode())
         return out

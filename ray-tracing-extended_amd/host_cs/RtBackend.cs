@@ -247,6 +247,24 @@ namespace RtMi355x
             return result;
         }
 
+        // ---- visibility gathers (ambient occlusion, bent normals, sky visibility, distance moments: RtVisibility.cs) --------------------
+        /// How open each point of the scene the next frame traces is, over `samples` directions the device draws (0 = 64, with seed 0):
+        /// the directions Gather draws for the same seed.  A point is an RtRay with the surface NORMAL in its direction and the reach in
+        /// its maxDistance (MakeRay(position, normal, reach)).  mode 0: points.Length * 4 floats, the bent normal (not normalised) and the
+        /// visibility fraction (ambient occlusion = 1 - it); mode 1: points.Length * 12 floats, nine SH coefficients of the visibility,
+        /// the fraction, 0, 0; mode 2: points.Length * 4 floats, mean distance, mean squared distance, hit fraction, 1.
+        public float[] Visibility(RtRay[] points, int samples = 0, uint seed = 0, int mode = 0)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            if (samples <= 0) samples = 64;
+            float[] result = new float[(long)points.Length * (mode == 1 ? 12 : 4)];
+            RtVisibilityParams[] q = new[] { new RtVisibilityParams { samples = samples, seed = seed, mode = mode } };
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_visibility(multi, points, points.Length, q, result), "rt_multi_visibility");
+            else RtNative.Check(ctx, RtNative.rt_visibility(ctx, points, points.Length, q, result), "rt_visibility");
+            return result;
+        }
+
         /// The radiance along one ray (a probe, the light behind a picked pixel).
         public Color Radiance(Vector3 origin, Vector3 direction, float maxDistance, int samples = 0, uint seed = 0)
         {

@@ -263,6 +263,11 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_gather_device(IntPtr ctx, IntPtr points, int n, [In] RtGatherParams[] p, IntPtr result);
         [DllImport(Lib)] public static extern int rt_get_gather_info(IntPtr ctx, out RtGatherInfo info);
         [DllImport(Lib)] public static extern int rt_multi_gather(IntPtr multi, [In] RtRay[] points, int n, [In] RtGatherParams[] p, [Out] float[] result);
+        // visibility gathers (RtVisibilityParams, RtVisibilityInfo: RtVisibility.cs; p: one entry, or null = 64 samples, seed 0, firstIndex 0, mode 0; result: n * 4 or n * 12 floats)
+        [DllImport(Lib)] public static extern int rt_visibility(IntPtr ctx, [In] RtRay[] points, int n, [In] RtVisibilityParams[] p, [Out] float[] result);
+        [DllImport(Lib)] public static extern int rt_visibility_device(IntPtr ctx, IntPtr points, int n, [In] RtVisibilityParams[] p, IntPtr result);
+        [DllImport(Lib)] public static extern int rt_get_visibility_info(IntPtr ctx, out RtVisibilityInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_visibility(IntPtr multi, [In] RtRay[] points, int n, [In] RtVisibilityParams[] p, [Out] float[] result);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -313,6 +318,8 @@ namespace RtMi355x
             Same("rt_radiance_info", Marshal.SizeOf<RtRadianceInfo>());
             Same("rt_gather_params", Marshal.SizeOf<RtGatherParams>());
             Same("rt_gather_info", Marshal.SizeOf<RtGatherInfo>());
+            Same("rt_visibility_params", Marshal.SizeOf<RtVisibilityParams>());
+            Same("rt_visibility_info", Marshal.SizeOf<RtVisibilityInfo>());
         }
     }
 }
