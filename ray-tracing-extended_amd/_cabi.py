@@ -297,9 +297,15 @@ def _radiance_params(samples, seed, first_index):
     return p
 
 
-def _radiance_host(call, handle, rays, params, check, what):
-    r = _ray_array(rays)
-    out = np.zeros((r.shape[0], 4), np.float32)
+def _radiance_shape(n, params):
+    return (n, 4)
+
+
+def _sampled_host(call, handle, items, params, shape, check, what):
+    """A host entry of a sampled family (radiance, gather, visibility; a context's or a MultiTracer's): items as _ray_array takes them,
+    params a record or None -> float32 of shape(n, params)"""
+    r = _ray_array(items)
+    out = np.zeros(shape(r.shape[0], params), np.float32)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
                out.ctypes.data_as(c_void_p)), what)
     return out
@@ -324,14 +330,6 @@ def _gather_shape(n, params):
     return (n, 9, 4) if params is not None and int(params["mode"]) == GATHER_SH9 else (n, 4)
 
 
-def _gather_host(call, handle, points, params, check, what):
-    r = _ray_array(points)
-    out = np.zeros(_gather_shape(r.shape[0], params), np.float32)
-    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
-               out.ctypes.data_as(c_void_p)), what)
-    return out
-
-
 def _visibility_params(samples, seed, first_index, mode):
     """None (the library's defaults: 64 samples, seed 0, firstIndex 0, mode 0) when nothing is given; else a VISIBILITY_PARAMS record,
     samples None standing for the library's default count"""
@@ -346,14 +344,6 @@ def _visibility_params(samples, seed, first_index, mode):
 def _visibility_shape(n, params):
     """(n, 4) in modes 0 and 2, (n, 12) in mode 1"""
     return (n, 12) if params is not None and int(params["mode"]) == VIS_SH9 else (n, 4)
-
-
-def _visibility_host(call, handle, points, params, check, what):
-    r = _ray_array(points)
-    out = np.zeros(_visibility_shape(r.shape[0], params), np.float32)
-    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), None if params is None else params.ctypes.data_as(c_void_p),
-               out.ctypes.data_as(c_void_p)), what)
-    return out
 
 
 def _denoise_params(params: dict):
@@ -533,22 +523,26 @@ class Tracer:
             self._lib.rt_set_stream(self._ctx, c_void_p(getattr(self, "_stream", None) or None))
         self._check(rc, what)
 
+    def _sampled(self, name, items, params, shape):
+        """A sampled family (radiance, gather, visibility): its host entry `name` on arrays, `name`_device on a float32 CUDA tensor (n, 8) of the
+        context's device, ordered with torch's current stream as _query_device describes; -> float32 of shape(n, params) either way"""
+        if not _is_tensor(items):
+            return _sampled_host(getattr(self._lib, name), self._ctx, items, params, shape, self._check, name)
+        import torch
+        items = self._ray_tensor(items)
+        n = int(items.shape[0])
+        out = torch.empty(shape(n, params), dtype=torch.float32, device=items.device)
+        qp = None if params is None else params.ctypes.data_as(c_void_p)
+        call = getattr(self._lib, name + "_device")
+        self._on_torch_stream(items.device, lambda: call(self._ctx, c_void_p(items.data_ptr()), n, qp, c_void_p(out.data_ptr())), name + "_device")
+        return out
+
     # -- radiance queries
     def trace_radiance(self, rays, samples=None, seed=0, first_index=0):
         """rt_trace_radiance: Trace along every ray, averaged over `samples` runs (None: the context's numRaysPerPixel, seed 0, first
         index 0).  rays: a RAY array or float32 (n, 8) -> float32 (n, 4).  A float32 CUDA tensor (n, 8) on the context's device takes the
         device entry, ordered with torch's current stream as trace_rays is, and returns a float32 (n, 4) tensor."""
-        q = _radiance_params(samples, seed, first_index)
-        if not _is_tensor(rays):
-            return _radiance_host(self._lib.rt_trace_radiance, self._ctx, rays, q, self._check, "rt_trace_radiance")
-        import torch
-        rays = self._ray_tensor(rays)
-        n = int(rays.shape[0])
-        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        qp = None if q is None else q.ctypes.data_as(c_void_p)
-        self._on_torch_stream(rays.device, lambda: self._lib.rt_trace_radiance_device(self._ctx, c_void_p(rays.data_ptr()), n, qp, c_void_p(out.data_ptr())),
-                              "rt_trace_radiance_device")
-        return out
+        return self._sampled("rt_trace_radiance", rays, _radiance_params(samples, seed, first_index), _radiance_shape)
 
     def radiance_info(self) -> dict:
         s = np.zeros((), RADIANCE_INFO)
@@ -564,16 +558,7 @@ class Tracer:
         entry, ordered with torch's current stream as trace_rays is, and returns a tensor of that shape.  samples=None with a seed, first
         index or mode (gather(points, mode=GATHER_SH9)) is the numRaysPerPixel of the params set last, as the library's own default is."""
         q = _gather_params(samples, seed, first_index, mode, None if self._params is None else int(self._params["numRaysPerPixel"]))
-        if not _is_tensor(points):
-            return _gather_host(self._lib.rt_gather, self._ctx, points, q, self._check, "rt_gather")
-        import torch
-        points = self._ray_tensor(points)
-        n = int(points.shape[0])
-        out = torch.empty(_gather_shape(n, q), dtype=torch.float32, device=points.device)
-        qp = None if q is None else q.ctypes.data_as(c_void_p)
-        self._on_torch_stream(points.device, lambda: self._lib.rt_gather_device(self._ctx, c_void_p(points.data_ptr()), n, qp, c_void_p(out.data_ptr())),
-                              "rt_gather_device")
-        return out
+        return self._sampled("rt_gather", points, q, _gather_shape)
 
     def gather_info(self) -> dict:
         s = np.zeros((), GATHER_INFO)
@@ -589,17 +574,7 @@ class Tracer:
         VIS_DISTANCE -> float32 (n, 4): mean distance (a miss counts the reach), mean squared distance, hit fraction, 1.  A float32 CUDA
         tensor (n, 8) on the context's device takes the device entry, ordered with torch's current stream as trace_rays is, and returns a
         tensor of that shape."""
-        q = _visibility_params(samples, seed, first_index, mode)
-        if not _is_tensor(points):
-            return _visibility_host(self._lib.rt_visibility, self._ctx, points, q, self._check, "rt_visibility")
-        import torch
-        points = self._ray_tensor(points)
-        n = int(points.shape[0])
-        out = torch.empty(_visibility_shape(n, q), dtype=torch.float32, device=points.device)
-        qp = None if q is None else q.ctypes.data_as(c_void_p)
-        self._on_torch_stream(points.device, lambda: self._lib.rt_visibility_device(self._ctx, c_void_p(points.data_ptr()), n, qp, c_void_p(out.data_ptr())),
-                              "rt_visibility_device")
-        return out
+        return self._sampled("rt_visibility", points, _visibility_params(samples, seed, first_index, mode), _visibility_shape)
 
     visibility_device = visibility          # (a tensor takes rt_visibility_device; the name says so at the call site)
 
@@ -884,19 +859,18 @@ class MultiTracer:
 
     def trace_radiance(self, rays, samples=None, seed=0, first_index=0) -> np.ndarray:
         """rt_multi_trace_radiance: Tracer.trace_radiance over the contexts (host arrays), every ray keeping its stream index."""
-        return _radiance_host(self._lib.rt_multi_trace_radiance, self._m, rays, _radiance_params(samples, seed, first_index), self._check,
-                              "rt_multi_trace_radiance")
+        return _sampled_host(self._lib.rt_multi_trace_radiance, self._m, rays, _radiance_params(samples, seed, first_index), _radiance_shape,
+                             self._check, "rt_multi_trace_radiance")
 
     def gather(self, points, samples=None, seed=0, first_index=0, mode=GATHER_COSINE) -> np.ndarray:
         """rt_multi_gather: Tracer.gather over the contexts (host arrays), every point keeping its stream index."""
         q = _gather_params(samples, seed, first_index, mode, getattr(self, "_rays_per_pixel", None))
-        return _gather_host(self._lib.rt_multi_gather, self._m, points, q, self._check,
-                            "rt_multi_gather")
+        return _sampled_host(self._lib.rt_multi_gather, self._m, points, q, _gather_shape, self._check, "rt_multi_gather")
 
     def visibility(self, points, samples=None, seed=0, first_index=0, mode=VIS_COSINE) -> np.ndarray:
         """rt_multi_visibility: Tracer.visibility over the contexts (host arrays), every point keeping its stream index."""
-        return _visibility_host(self._lib.rt_multi_visibility, self._m, points, _visibility_params(samples, seed, first_index, mode), self._check,
-                                "rt_multi_visibility")
+        return _sampled_host(self._lib.rt_multi_visibility, self._m, points, _visibility_params(samples, seed, first_index, mode), _visibility_shape,
+                             self._check, "rt_multi_visibility")
 
     def render_params(self, first_frame: int, params):
         """rt_multi_render_params: every context renders its bands with the per-frame uniforms params[f], then one gather."""

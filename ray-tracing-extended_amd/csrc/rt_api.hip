@@ -48,8 +48,13 @@ struct ErrOwner { std::string err; };       // what rt_ctx and rt_multi are to f
         if (e_ != hipSuccess) return fail(ctx, -100, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// Device memory that is freed with its owner (the owner makes its device current before it goes: rt_destroy, rt_multi_destroy)
 template <class T> struct DevBuf {
     T* p = nullptr; size_t cap = 0, used = 0;       // used: elements the last ensure() asked for (what clone_scene copies)
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t n)
     {
         used = n;
@@ -196,14 +201,11 @@ struct rt_ctx : ErrOwner {
     int opt_primary_lists = 1;                      // 1: camera rays of a static camera start from their pixel's candidate leaves (k_stream); 0: always from the root
     DevBuf<float> d_park;              // k_stream, Philox mode: parked sub-stream sums
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
-    DevBuf<float4> d_q_rays, d_q_hits; DevBuf<uint8_t> d_q_occ;            // ray queries: staging of the host entries (one slice)
-    DevBuf<unsigned int> d_q_bound;                                         // ... the device entries' origin bound
-    DevBuf<float4> d_q_rgba;                                                // radiance queries: the host entry's results (one slice)
-    rt_radiance_info radiance_info{};
-    DevBuf<float4> d_q_gather;                                              // gather queries: the host entry's results (one slice: 1 or 9 float4 per point)
-    rt_gather_info gather_info{};
-    DevBuf<float4> d_q_vis;                                                 // visibility gathers: the host entry's results (one slice: 1 or 3 float4 per point)
-    rt_visibility_info visibility_info{};
+    // queries (rt_trace_rays ... rt_visibility): staging of the host entries (one slice of rays or points in, one slice of results out,
+    // in bytes), the device entries' origin bound, and the sampled families' info records (QueryFamily indexes them)
+    DevBuf<float4> d_q_rays; DevBuf<uint8_t> d_q_out;
+    DevBuf<unsigned int> d_q_bound;
+    rt_gather_info query_info[3]{};
     int opt_visibility_slice = 1 << 22; // visibility gathers: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_gather_slice = 1 << 20;     // gather queries: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_radiance_slice = 1 << 22;   // radiance queries: rays per launch (and per staging slice of the host entry); the result never depends on it
@@ -1257,55 +1259,6 @@ int query_prepare(rt_ctx* c, float G)
     return cover_origins(c, G);
 }
 
-// n rays (device, 2 float4 each) -> n rt_hit (4 float4 each) or n occlusion bytes, on the context's stream; no synchronisation
-int launch_query(rt_ctx* c, bool any, const float4* rays, int n, void* out)
-{
-    rtk::DeviceScene S{};
-    { int r = fill_scene(c, S); if (r) return r; }
-    rtk::QueryArgs Q{};
-    Q.order = c->d_order.p;
-    Q.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
-    Q.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
-    Q.full_sort = c->opt_full_sort;
-    const bool compact = c->opt_compact_nodes != 0;     // the node form the renderer's kernels traverse (plan_launch)
-    const void* fn = any ? (compact ? (const void*)rtk::k_ray_query<true, true> : (const void*)rtk::k_ray_query<true, false>)
-                         : (compact ? (const void*)rtk::k_ray_query<false, true> : (const void*)rtk::k_ray_query<false, false>);
-    for (int first = 0; first < n; first += kQuerySlice) {
-        const int cnt = std::min(kQuerySlice, n - first);
-        const int grid = (cnt + rtk::kBlock - 1) / rtk::kBlock;
-        LaneStack st;
-        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st); if (r) return r; }
-        Q.stack_cap = st.cap; Q.gstack = st.gstack; Q.gstack_stride = st.stride;
-        Q.rays = rays + 2 * (size_t)first; Q.n = cnt;
-        Q.hits = any ? nullptr : static_cast<float4*>(out) + 4 * (size_t)first;
-        Q.occluded = any ? static_cast<uint8_t*>(out) + first : nullptr;
-        void* args[] = { &S, &Q };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
-    }
-    return 0;
-}
-
-int query_host(rt_ctx* c, bool any, const rt_ray* rays, int n, void* out)
-{
-    RT_SETTLE(c);
-    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, out %p)", any ? "rt_occluded" : "rt_trace_rays", n, (const void*)rays, out);
-    if (n == 0) return 0;
-    { int r = query_prepare(c, query_origin_bound(rays, n)); if (r) return r; }
-    const size_t slice = (size_t)std::min(n, kQuerySlice);
-    RT_HIP(c, c->d_q_rays.ensure(2 * slice));
-    if (any) RT_HIP(c, c->d_q_occ.ensure(slice)); else RT_HIP(c, c->d_q_hits.ensure(4 * slice));
-    const size_t out_size = any ? 1 : sizeof(rt_hit);
-    for (int first = 0; first < n; first += kQuerySlice) {
-        const int cnt = std::min(kQuerySlice, n - first);
-        void* dev_out = any ? (void*)c->d_q_occ.p : (void*)c->d_q_hits.p;
-        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, rays + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        { int r = launch_query(c, any, c->d_q_rays.p, cnt, dev_out); if (r) return r; }
-        RT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + (size_t)first * out_size, dev_out, (size_t)cnt * out_size, hipMemcpyDeviceToHost, c->stream));
-    }
-    RT_HIP(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 // p lies in memory of the context's device (hipMalloc'ed or managed)
 bool on_ctx_device(const rt_ctx* c, const void* p)
 {
@@ -1329,309 +1282,246 @@ int cover_origins_device(rt_ctx* c, const float4* rays, int n)
     return cover_origins(c, u2f(bits));
 }
 
-int query_device(rt_ctx* c, bool any, const void* rays, int n, void* out)
+// ---- the one path of the four query families ----------------------------------------------------------------------------------------
+// Ray queries (rt_trace_rays / rt_occluded, csrc/rt_query.hpp), radiance queries (rt_trace_radiance, csrc/rt_radiance.hpp), gather
+// queries (rt_gather, csrc/rt_gather.hpp) and visibility gathers (rt_visibility, csrc/rt_visibility.hpp) all take n rt_ray (2 float4
+// each) and write a fixed number of bytes per item.  A family supplies a description of the call (QueryCall, built by its *_call once
+// the arguments are known to be good) and a function that fills its kernel's Args for one launch; everything between the exported
+// entry and hipLaunchKernel is below, once.
+enum QueryFamily { kRadiance, kGather, kVisibility, kRays };    // (the first three: the sampled families, indices of rt_ctx::query_info)
+
+// The sampled families' params and info records have one layout: rt_radiance_* keeps reserved words where the other two have `mode`.
+// rt_gather_params / rt_gather_info are the form the path works with.
+#define RT_SAME_FIELD(A, B, a, b) static_assert(offsetof(A, a) == offsetof(B, b), #A "." #a " is not where " #B "." #b " is")
+#define RT_SAME_PARAMS(T, mode_word) static_assert(sizeof(T) == sizeof(rt_gather_params), #T); RT_SAME_FIELD(T, rt_gather_params, samples, samples); \
+    RT_SAME_FIELD(T, rt_gather_params, seed, seed); RT_SAME_FIELD(T, rt_gather_params, firstIndex, firstIndex); static_assert(offsetof(T, mode_word) == offsetof(rt_gather_params, mode), #T)
+#define RT_SAME_INFO(T, mode_word) static_assert(sizeof(T) == sizeof(rt_gather_info), #T); RT_SAME_FIELD(T, rt_gather_info, samples, samples); \
+    RT_SAME_FIELD(T, rt_gather_info, lastSampleLanes, lastSampleLanes); RT_SAME_FIELD(T, rt_gather_info, calls, calls); RT_SAME_FIELD(T, rt_gather_info, mode_word, mode); \
+    RT_SAME_FIELD(T, rt_gather_info, lastKernelMs, lastKernelMs); RT_SAME_FIELD(T, rt_gather_info, totalKernelMs, totalKernelMs)
+RT_SAME_PARAMS(rt_radiance_params, _reserved); RT_SAME_PARAMS(rt_visibility_params, mode);
+RT_SAME_INFO(rt_radiance_info, _reserved); RT_SAME_INFO(rt_visibility_info, mode);
+#undef RT_SAME_FIELD
+#undef RT_SAME_PARAMS
+#undef RT_SAME_INFO
+
+// One launch: `n` items from `in`, results to `out`, item 0 with stream index first_index
+struct QuerySlice { const rtk::DeviceScene* S; const float4* in; void* out; int n; uint32_t first_index; int grid; LaneStack st; };
+
+struct QueryCall {
+    QueryFamily family;
+    const char* what;               // the entry's exported name, for messages
+    const char* in_word, * out_word;    // what the messages call the items and the results
+    int slice;                      // items per launch (and per staging slice of the host entry)
+    size_t out_bytes;               // of result per item
+    bool out_aligned;               // the device entry wants 16-byte aligned results (all but occlusion bytes)
+    const char* refuse_4g_for;      // plan_lane_stack's name for the call; null: ray queries, whose overflow area has no limit
+    hipError_t (*launch)(rt_ctx*, const QueryCall&, const QuerySlice&);     // fills the family's Args and launches its kernel
+    int sample_lanes_log2;          // S = 16 / 4 / 1 lanes share an item's samples (include/rt.h RT_RNG_PHILOX); ray queries: 0
+    rt_gather_params p;             // the sampled families' params, defaults filled in (mode 0 for radiance queries)
+    bool sampled() const { return family != kRays; }
+};
+
+// What every launch function ends with: the fields all four Args share, then the launch on the context's stream
+template <class Args> hipError_t launch_slice(rt_ctx* c, const void* fn, const QuerySlice& s, Args& A)
 {
-    const char* what = any ? "rt_occluded_device" : "rt_trace_rays_device";
-    RT_SETTLE(c);
-    if (n < 0 || (n > 0 && (!rays || !out))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, out %p)", what, n, rays, out);
-    if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    if (!on_ctx_device(c, rays) || !on_ctx_device(c, out))
-        return fail(c, -2, "%s: rays and results must be device memory of the context's device %d", what, c->device);
-    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (!any && (reinterpret_cast<uintptr_t>(out) & 15u)))
-        return fail(c, -2, "%s: rays and hits must be 16-byte aligned", what);
-    { int r = prepare_scene(c); if (r) return r; }
-    { int r = cover_origins_device(c, static_cast<const float4*>(rays), n); if (r) return r; }
-    return launch_query(c, any, static_cast<const float4*>(rays), n, out);
+    A.n = s.n; A.stack_cap = s.st.cap; A.gstack = s.st.gstack; A.gstack_stride = s.st.stride;
+    void* args[] = { const_cast<rtk::DeviceScene*>(s.S), &A };
+    return hipLaunchKernel(fn, dim3(s.grid), dim3(rtk::kBlock), args, s.st.lds, c->stream);
 }
 
-// ---- radiance queries (rt_trace_radiance, csrc/rt_radiance.hpp) -------------------------------------------------------------------
-// The arguments of a call as the kernel takes them; params == NULL: the context's numRaysPerPixel samples, seed 0, firstIndex 0
-int radiance_arguments(rt_ctx* c, const char* what, const void* rays, int n, const rt_radiance_params* params, const void* rgba, rt_radiance_params& q)
-{
-    if (!c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", what);
-    if (n < 0 || (n > 0 && (!rays || !rgba))) return fail(c, -2, "%s: bad arguments (n = %d, rays %p, rgba %p)", what, n, rays, rgba);
-    q = rt_radiance_params{};
-    if (params) q = *params; else q.samples = c->params.numRaysPerPixel;
-    if (q.samples < 1 || q.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", what, q.samples);
-    for (int r : q._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_radiance_params is not 0", what);
-    return 0;
-}
-
-// n rays (device, 2 float4 each) -> n float4, on the context's stream; no synchronisation.  One launch per opt_radiance_slice rays, each
-// with firstIndex advanced by the rays before it.
-int launch_radiance(rt_ctx* c, const float4* rays, int n, const rt_radiance_params& q, float4* rgba)
+// n items in device memory -> n results, on the context's stream; no synchronisation.  One launch per q.slice items, each with the
+// stream index advanced by the items before it (uint32_t: it wraps).
+int launch_slices(rt_ctx* c, const QueryCall& q, const float4* in, void* out, int n, uint32_t first_index)
 {
     rtk::DeviceScene S{};
     { int r = fill_scene(c, S); if (r) return r; }
+    if (q.sampled()) {
+        rt_gather_info& info = c->query_info[q.family];
+        info.samples = q.p.samples; info.lastSampleLanes = 1 << q.sample_lanes_log2; info.mode = q.p.mode;
+    }
+    for (int first = 0; first < n; first += q.slice) {
+        QuerySlice s{};
+        s.S = &S; s.n = std::min(q.slice, n - first);
+        const size_t lanes = (size_t)s.n << q.sample_lanes_log2;        // (a slice is at most 2^22 items: items * S stays below 2^31)
+        s.grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
+        { int r = plan_lane_stack(c, (size_t)s.grid * rtk::kBlock, s.st, q.refuse_4g_for); if (r) return r; }
+        s.in = in + 2 * (size_t)first; s.out = static_cast<char*>(out) + q.out_bytes * (size_t)first;
+        s.first_index = first_index + (uint32_t)first;
+        RT_HIP(c, q.launch(c, q, s));
+    }
+    return 0;
+}
+
+// Host memory in, host memory out: a slice at a time through the context's staging, sized to min(n, slice) items (an SH9 gather slice
+// is 144 B per point).  The sampled families time each slice's launches with the context's one event pair, so they wait for every
+// slice before the next records the events again; ray queries record nothing and wait once, at the end.
+int query_host(rt_ctx* c, const QueryCall& q, const rt_ray* in, int n, void* out)
+{
+    if (n == 0) return 0;
+    { int r = query_prepare(c, query_origin_bound(in, n)); if (r) return r; }
+    const size_t staged = (size_t)std::min(n, q.slice);
+    RT_HIP(c, c->d_q_rays.ensure(2 * staged));
+    RT_HIP(c, c->d_q_out.ensure(q.out_bytes * staged));
+    double ms_sum = 0;
+    for (int first = 0; first < n; first += q.slice) {
+        const int cnt = std::min(q.slice, n - first);
+        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, in + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+        if (q.sampled()) RT_HIP(c, hipEventRecord(c->ev0, c->stream));
+        { int r = launch_slices(c, q, c->d_q_rays.p, c->d_q_out.p, cnt, q.p.firstIndex + (uint32_t)first); if (r) return r; }
+        if (q.sampled()) RT_HIP(c, hipEventRecord(c->ev1, c->stream));
+        RT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + q.out_bytes * (size_t)first, c->d_q_out.p, q.out_bytes * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+        if (!q.sampled()) continue;
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        ms_sum += ms;
+    }
+    if (!q.sampled()) { RT_HIP(c, hipStreamSynchronize(c->stream)); return 0; }
+    rt_gather_info& info = c->query_info[q.family];
+    info.calls++; info.lastKernelMs = ms_sum; info.totalKernelMs += ms_sum;
+    return 0;
+}
+
+// Device memory of the context's GPU in and out, ordered on the context's stream; the info record counts the call and keeps the host
+// entry's times (the call is asynchronous)
+int query_device(rt_ctx* c, const QueryCall& q, const void* in, int n, void* out)
+{
+    if (n == 0) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!on_ctx_device(c, in) || !on_ctx_device(c, out))
+        return fail(c, -2, "%s: %s and results must be device memory of the context's device %d", q.what, q.in_word, c->device);
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (q.out_aligned && (reinterpret_cast<uintptr_t>(out) & 15u)))
+        return fail(c, -2, "%s: %s%s%s must be 16-byte aligned", q.what, q.in_word, q.out_aligned ? " and " : "", q.out_aligned ? q.out_word : "");
+    { int r = prepare_scene(c); if (r) return r; }
+    { int r = cover_origins_device(c, static_cast<const float4*>(in), n); if (r) return r; }
+    { int r = launch_slices(c, q, static_cast<const float4*>(in), out, n, q.p.firstIndex); if (r) return r; }
+    if (q.sampled()) c->query_info[q.family].calls++;
+    return 0;
+}
+
+// ---- the four descriptions --------------------------------------------------------------------------------------------------------
+// A *_call checks the arguments of a call to `what` and describes it; all four have the signature of QueryDescribe (ray queries take
+// no params).  The checks come in one order: params set (where the family needs them), n and the pointers, the defaults of
+// params == NULL, samples, mode, reserved words.
+using QueryDescribe = int (*)(rt_ctx* c, const char* what, const void* in, int n, const void* params, const void* out, QueryCall& q);
+
+int query_pointers(rt_ctx* c, const QueryCall& q, const void* in, int n, const void* out)
+{
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(c, -2, "%s: bad arguments (n = %d, %s %p, %s %p)", q.what, n, q.in_word, in, q.out_word, out);
+    return 0;
+}
+
+// The sampled families' common part.  modes: how many values of `mode` the family has, named by mode_text (radiance queries: one, and
+// the word is a reserved one); params == NULL: default_samples samples, seed 0, firstIndex 0, mode 0.
+int sampled_arguments(rt_ctx* c, QueryCall& q, bool need_params, const void* in, int n, const void* params, int default_samples, const void* out,
+                      int modes, const char* mode_text, const char* params_type)
+{
+    if (need_params && !c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", q.what);
+    { int r = query_pointers(c, q, in, n, out); if (r) return r; }
+    q.p = rt_gather_params{};
+    if (params) std::memcpy(&q.p, params, sizeof q.p); else q.p.samples = default_samples;
+    if (q.p.samples < 1 || q.p.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", q.what, q.p.samples);
+    q.sample_lanes_log2 = q.p.samples >= 16 ? 4 : q.p.samples >= 4 ? 2 : 0;
+    if (mode_text && (q.p.mode < 0 || q.p.mode >= modes)) return fail(c, -2, "%s: mode = %d is %s", q.what, q.p.mode, mode_text);
+    bool reserved = !mode_text && q.p.mode != 0;
+    for (int r : q.p._reserved) reserved = reserved || r != 0;
+    if (reserved) return fail(c, -2, "%s: a reserved word of %s is not 0", q.what, params_type);
+    return 0;
+}
+
+template <bool ANY> hipError_t launch_rays(rt_ctx* c, const QueryCall&, const QuerySlice& s)
+{
+    rtk::QueryArgs Q{};
+    Q.order = c->d_order.p;
+    Q.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
+    Q.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    Q.full_sort = c->opt_full_sort;
+    Q.rays = s.in;
+    Q.hits = ANY ? nullptr : static_cast<float4*>(s.out);
+    Q.occluded = ANY ? static_cast<uint8_t*>(s.out) : nullptr;
+    // (H: the node form the renderer's kernels traverse, plan_launch)
+    return launch_slice(c, c->opt_compact_nodes != 0 ? (const void*)rtk::k_ray_query<ANY, true> : (const void*)rtk::k_ray_query<ANY, false>, s, Q);
+}
+// n rt_hit (4 float4 each) / n occlusion bytes
+int trace_rays_call(rt_ctx* c, const char* what, const void* rays, int n, const void*, const void* hits, QueryCall& q)
+{
+    q = QueryCall{ kRays, what, "rays", "hits", kQuerySlice, sizeof(rt_hit), true, nullptr, launch_rays<false> };
+    return query_pointers(c, q, rays, n, hits);
+}
+int occluded_call(rt_ctx* c, const char* what, const void* rays, int n, const void*, const void* occluded, QueryCall& q)
+{
+    q = QueryCall{ kRays, what, "rays", "occluded", kQuerySlice, 1, false, nullptr, launch_rays<true> };
+    return query_pointers(c, q, rays, n, occluded);
+}
+
+hipError_t launch_radiance(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
+{
     rtk::RadianceArgs A{};
     A.p = c->params;
-    A.samples = q.samples; A.seed = q.seed;
-    A.sample_lanes_log2 = q.samples >= 16 ? 4 : q.samples >= 4 ? 2 : 0;       // S = 16 / 4 / 1 (include/rt.h RT_RNG_PHILOX)
+    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
     A.full_sort = c->opt_full_sort;
-    c->radiance_info.samples = q.samples; c->radiance_info.lastSampleLanes = 1 << A.sample_lanes_log2;
-    const void* fn = c->opt_compact_nodes != 0 ? (const void*)rtk::k_radiance<true> : (const void*)rtk::k_radiance<false>;     // the node form the renderer's kernels traverse
-    const int slice = c->opt_radiance_slice;
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        const size_t lanes = (size_t)cnt << A.sample_lanes_log2;
-        const int grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
-        LaneStack st;
-        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_trace_radiance"); if (r) return r; }
-        A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
-        A.rays = rays + 2 * (size_t)first; A.rgba = rgba + first; A.n = cnt;
-        A.first_index = q.firstIndex + (uint32_t)first;
-        void* args[] = { &S, &A };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
-    }
-    return 0;
+    A.rays = s.in; A.rgba = static_cast<float4*>(s.out);
+    return launch_slice(c, c->opt_compact_nodes != 0 ? (const void*)rtk::k_radiance<true> : (const void*)rtk::k_radiance<false>, s, A);
+}
+// n float4; params == NULL: the context's numRaysPerPixel samples
+int radiance_call(rt_ctx* c, const char* what, const void* rays, int n, const void* params, const void* rgba, QueryCall& q)
+{
+    q = QueryCall{ kRadiance, what, "rays", "rgba", c->opt_radiance_slice, sizeof(float4), true, "rt_trace_radiance", launch_radiance };
+    return sampled_arguments(c, q, true, rays, n, params, c->params.numRaysPerPixel, rgba, 1, nullptr, "rt_radiance_params");
 }
 
-int radiance_host(rt_ctx* c, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba)
+hipError_t launch_gather(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
-    RT_SETTLE(c);
-    rt_radiance_params q;
-    { int r = radiance_arguments(c, "rt_trace_radiance", rays, n, params, rgba, q); if (r) return r; }
-    if (n == 0) return 0;
-    { int r = query_prepare(c, query_origin_bound(rays, n)); if (r) return r; }
-    const int slice = c->opt_radiance_slice;
-    RT_HIP(c, c->d_q_rays.ensure(2 * (size_t)std::min(n, slice)));
-    RT_HIP(c, c->d_q_rgba.ensure((size_t)std::min(n, slice)));
-    double ms_sum = 0;
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        rt_radiance_params qs = q;
-        qs.firstIndex = q.firstIndex + (uint32_t)first;
-        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, rays + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        RT_HIP(c, hipEventRecord(c->ev0, c->stream));
-        { int r = launch_radiance(c, c->d_q_rays.p, cnt, qs, c->d_q_rgba.p); if (r) return r; }
-        RT_HIP(c, hipEventRecord(c->ev1, c->stream));
-        RT_HIP(c, hipMemcpyAsync(rgba + 4 * (size_t)first, c->d_q_rgba.p, (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        RT_HIP(c, hipStreamSynchronize(c->stream));     // (the events are the context's one pair: read before the next slice records them)
-        float ms = 0.f;
-        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        ms_sum += ms;
-    }
-    c->radiance_info.calls++; c->radiance_info.lastKernelMs = ms_sum; c->radiance_info.totalKernelMs += ms_sum;
-    return 0;
-}
-
-int radiance_device(rt_ctx* c, const void* rays, int n, const rt_radiance_params* params, void* rgba)
-{
-    const char* what = "rt_trace_radiance_device";
-    RT_SETTLE(c);
-    rt_radiance_params q;
-    { int r = radiance_arguments(c, what, rays, n, params, rgba, q); if (r) return r; }
-    if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    if (!on_ctx_device(c, rays) || !on_ctx_device(c, rgba))
-        return fail(c, -2, "%s: rays and results must be device memory of the context's device %d", what, c->device);
-    if ((reinterpret_cast<uintptr_t>(rays) & 15u) || (reinterpret_cast<uintptr_t>(rgba) & 15u))
-        return fail(c, -2, "%s: rays and rgba must be 16-byte aligned", what);
-    { int r = prepare_scene(c); if (r) return r; }
-    { int r = cover_origins_device(c, static_cast<const float4*>(rays), n); if (r) return r; }
-    { int r = launch_radiance(c, static_cast<const float4*>(rays), n, q, static_cast<float4*>(rgba)); if (r) return r; }
-    c->radiance_info.calls++;                           // (asynchronous: the times are the host entry's)
-    return 0;
-}
-
-// ---- gather queries (rt_gather, csrc/rt_gather.hpp) -----------------------------------------------------------------------------------
-// The arguments of a call as the kernel takes them; params == NULL: the context's numRaysPerPixel samples, seed 0, firstIndex 0, mode 0
-int gather_arguments(rt_ctx* c, const char* what, const void* points, int n, const rt_gather_params* params, const void* out, rt_gather_params& q)
-{
-    if (!c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", what);
-    if (n < 0 || (n > 0 && (!points || !out))) return fail(c, -2, "%s: bad arguments (n = %d, points %p, out %p)", what, n, points, out);
-    q = rt_gather_params{};
-    if (params) q = *params; else q.samples = c->params.numRaysPerPixel;
-    if (q.samples < 1 || q.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", what, q.samples);
-    if (q.mode != RT_GATHER_COSINE && q.mode != RT_GATHER_SH9) return fail(c, -2, "%s: mode = %d is neither RT_GATHER_COSINE nor RT_GATHER_SH9", what, q.mode);
-    for (int r : q._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_gather_params is not 0", what);
-    return 0;
-}
-inline size_t gather_out_float4(int mode) { return mode == RT_GATHER_SH9 ? 9 : 1; }      // float4 per point
-
-// n points (device, 2 float4 each) -> n or 9 n float4, on the context's stream; no synchronisation.  One launch per opt_gather_slice
-// points, each with firstIndex advanced by the points before it.
-int launch_gather(rt_ctx* c, const float4* points, int n, const rt_gather_params& q, float4* out)
-{
-    rtk::DeviceScene S{};
-    { int r = fill_scene(c, S); if (r) return r; }
     rtk::GatherArgs A{};
     A.p = c->params;
-    A.samples = q.samples; A.seed = q.seed;
-    A.sample_lanes_log2 = q.samples >= 16 ? 4 : q.samples >= 4 ? 2 : 0;       // S = 16 / 4 / 1 (include/rt.h RT_RNG_PHILOX)
+    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
     A.full_sort = c->opt_full_sort;
-    c->gather_info.samples = q.samples; c->gather_info.lastSampleLanes = 1 << A.sample_lanes_log2; c->gather_info.mode = q.mode;
-    const bool compact = c->opt_compact_nodes != 0;     // the node form the renderer's kernels traverse
-    const void* fn = q.mode == RT_GATHER_SH9 ? (compact ? (const void*)rtk::k_gather<RT_GATHER_SH9, true> : (const void*)rtk::k_gather<RT_GATHER_SH9, false>)
-                                             : (compact ? (const void*)rtk::k_gather<RT_GATHER_COSINE, true> : (const void*)rtk::k_gather<RT_GATHER_COSINE, false>);
-    const size_t per = gather_out_float4(q.mode);
-    const int slice = c->opt_gather_slice;
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        const size_t lanes = (size_t)cnt << A.sample_lanes_log2;
-        const int grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
-        LaneStack st;
-        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_gather"); if (r) return r; }
-        A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
-        A.points = points + 2 * (size_t)first; A.out = out + per * (size_t)first; A.n = cnt;
-        A.first_index = q.firstIndex + (uint32_t)first;
-        void* args[] = { &S, &A };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
-    }
+    A.points = s.in; A.out = static_cast<float4*>(s.out);
+    const bool compact = c->opt_compact_nodes != 0;
+    return launch_slice(c, q.p.mode == RT_GATHER_SH9 ? (compact ? (const void*)rtk::k_gather<RT_GATHER_SH9, true> : (const void*)rtk::k_gather<RT_GATHER_SH9, false>)
+                                                     : (compact ? (const void*)rtk::k_gather<RT_GATHER_COSINE, true> : (const void*)rtk::k_gather<RT_GATHER_COSINE, false>), s, A);
+}
+// n or 9 n float4; params == NULL: the context's numRaysPerPixel samples
+int gather_call(rt_ctx* c, const char* what, const void* points, int n, const void* params, const void* out, QueryCall& q)
+{
+    q = QueryCall{ kGather, what, "points", "out", c->opt_gather_slice, 0, true, "rt_gather", launch_gather };
+    { int r = sampled_arguments(c, q, true, points, n, params, c->params.numRaysPerPixel, out, 2, "neither RT_GATHER_COSINE nor RT_GATHER_SH9", "rt_gather_params"); if (r) return r; }
+    q.out_bytes = sizeof(float4) * (q.p.mode == RT_GATHER_SH9 ? 9 : 1);
     return 0;
 }
 
-int gather_host(rt_ctx* c, const rt_ray* points, int n, const rt_gather_params* params, float* out)
+hipError_t launch_visibility(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
-    RT_SETTLE(c);
-    rt_gather_params q;
-    { int r = gather_arguments(c, "rt_gather", points, n, params, out, q); if (r) return r; }
-    if (n == 0) return 0;
-    { int r = query_prepare(c, query_origin_bound(points, n)); if (r) return r; }
-    const size_t per = gather_out_float4(q.mode);
-    const int slice = c->opt_gather_slice;
-    RT_HIP(c, c->d_q_rays.ensure(2 * (size_t)std::min(n, slice)));        // (min(n, slice), not the slice: an SH9 slice is 144 B per point)
-    RT_HIP(c, c->d_q_gather.ensure(per * (size_t)std::min(n, slice)));
-    double ms_sum = 0;
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        rt_gather_params qs = q;
-        qs.firstIndex = q.firstIndex + (uint32_t)first;
-        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, points + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        RT_HIP(c, hipEventRecord(c->ev0, c->stream));
-        { int r = launch_gather(c, c->d_q_rays.p, cnt, qs, c->d_q_gather.p); if (r) return r; }
-        RT_HIP(c, hipEventRecord(c->ev1, c->stream));
-        RT_HIP(c, hipMemcpyAsync(out + 4 * per * (size_t)first, c->d_q_gather.p, per * (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        RT_HIP(c, hipStreamSynchronize(c->stream));     // (the events are the context's one pair: read before the next slice records them)
-        float ms = 0.f;
-        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        ms_sum += ms;
-    }
-    c->gather_info.calls++; c->gather_info.lastKernelMs = ms_sum; c->gather_info.totalKernelMs += ms_sum;
-    return 0;
-}
-
-int gather_device(rt_ctx* c, const void* points, int n, const rt_gather_params* params, void* out)
-{
-    const char* what = "rt_gather_device";
-    RT_SETTLE(c);
-    rt_gather_params q;
-    { int r = gather_arguments(c, what, points, n, params, out, q); if (r) return r; }
-    if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    if (!on_ctx_device(c, points) || !on_ctx_device(c, out))
-        return fail(c, -2, "%s: points and results must be device memory of the context's device %d", what, c->device);
-    if ((reinterpret_cast<uintptr_t>(points) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(c, -2, "%s: points and out must be 16-byte aligned", what);
-    { int r = prepare_scene(c); if (r) return r; }
-    { int r = cover_origins_device(c, static_cast<const float4*>(points), n); if (r) return r; }
-    { int r = launch_gather(c, static_cast<const float4*>(points), n, q, static_cast<float4*>(out)); if (r) return r; }
-    c->gather_info.calls++;                             // (asynchronous: the times are the host entry's)
-    return 0;
-}
-
-// ---- visibility gathers (rt_visibility, csrc/rt_visibility.hpp) -------------------------------------------------------------------
-// The arguments of a call as the kernel takes them; params == NULL: RT_VISIBILITY_DEFAULT_SAMPLES samples, seed 0, firstIndex 0, mode 0.
-// No rt_params are needed: the kernel reads intersectMode alone, as the ray queries do
-int visibility_arguments(rt_ctx* c, const char* what, const void* points, int n, const rt_visibility_params* params, const void* out, rt_visibility_params& q)
-{
-    if (n < 0 || (n > 0 && (!points || !out))) return fail(c, -2, "%s: bad arguments (n = %d, points %p, out %p)", what, n, points, out);
-    q = rt_visibility_params{};
-    if (params) q = *params; else q.samples = RT_VISIBILITY_DEFAULT_SAMPLES;
-    if (q.samples < 1 || q.samples > 65536) return fail(c, -2, "%s: samples = %d outside 1..65536", what, q.samples);
-    if (q.mode < RT_VIS_COSINE || q.mode > RT_VIS_DISTANCE) return fail(c, -2, "%s: mode = %d is none of RT_VIS_COSINE, RT_VIS_SH9, RT_VIS_DISTANCE", what, q.mode);
-    for (int r : q._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_visibility_params is not 0", what);
-    return 0;
-}
-inline size_t visibility_out_float4(int mode) { return mode == RT_VIS_SH9 ? 3 : 1; }      // float4 per point
-
-const void* visibility_kernel(int mode, bool compact)
-{
-    switch (mode) {
-    case RT_VIS_SH9:      return compact ? (const void*)rtk::k_visibility<RT_VIS_SH9, true> : (const void*)rtk::k_visibility<RT_VIS_SH9, false>;
-    case RT_VIS_DISTANCE: return compact ? (const void*)rtk::k_visibility<RT_VIS_DISTANCE, true> : (const void*)rtk::k_visibility<RT_VIS_DISTANCE, false>;
-    default:              return compact ? (const void*)rtk::k_visibility<RT_VIS_COSINE, true> : (const void*)rtk::k_visibility<RT_VIS_COSINE, false>;
-    }
-}
-
-// n points (device, 2 float4 each) -> n or 3 n float4, on the context's stream; no synchronisation.  launch_gather's slices: one launch
-// per opt_visibility_slice points, each with firstIndex advanced by the points before it.
-int launch_visibility(rt_ctx* c, const float4* points, int n, const rt_visibility_params& q, float4* out)
-{
-    rtk::DeviceScene S{};
-    { int r = fill_scene(c, S); if (r) return r; }
     rtk::VisibilityArgs A{};
-    A.samples = q.samples; A.seed = q.seed;
-    A.sample_lanes_log2 = q.samples >= 16 ? 4 : q.samples >= 4 ? 2 : 0;       // S = 16 / 4 / 1 (include/rt.h RT_RNG_PHILOX)
+    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
     A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
     A.full_sort = c->opt_full_sort;
-    c->visibility_info.samples = q.samples; c->visibility_info.lastSampleLanes = 1 << A.sample_lanes_log2; c->visibility_info.mode = q.mode;
-    const void* fn = visibility_kernel(q.mode, c->opt_compact_nodes != 0);     // the node form the renderer's kernels traverse
-    const size_t per = visibility_out_float4(q.mode);
-    const int slice = c->opt_visibility_slice;          // (at most 2^22 points: points * S stays below 2^31)
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        const size_t lanes = (size_t)cnt << A.sample_lanes_log2;
-        const int grid = (int)((lanes + rtk::kBlock - 1) / rtk::kBlock);
-        LaneStack st;
-        { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_visibility"); if (r) return r; }
-        A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
-        A.points = points + 2 * (size_t)first; A.out = out + per * (size_t)first; A.n = cnt;
-        A.first_index = q.firstIndex + (uint32_t)first;
-        void* args[] = { &S, &A };
-        RT_HIP(c, hipLaunchKernel(fn, dim3(grid), dim3(rtk::kBlock), args, st.lds, c->stream));
+    A.points = s.in; A.out = static_cast<float4*>(s.out);
+    const bool compact = c->opt_compact_nodes != 0;
+    switch (q.p.mode) {
+    case RT_VIS_SH9:      return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_SH9, true> : (const void*)rtk::k_visibility<RT_VIS_SH9, false>, s, A);
+    case RT_VIS_DISTANCE: return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_DISTANCE, true> : (const void*)rtk::k_visibility<RT_VIS_DISTANCE, false>, s, A);
+    default:              return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_COSINE, true> : (const void*)rtk::k_visibility<RT_VIS_COSINE, false>, s, A);
     }
+}
+// n or 3 n float4; params == NULL: RT_VISIBILITY_DEFAULT_SAMPLES samples.  No rt_params are needed: the kernel reads intersectMode
+// alone, as the ray queries do
+int visibility_call(rt_ctx* c, const char* what, const void* points, int n, const void* params, const void* out, QueryCall& q)
+{
+    q = QueryCall{ kVisibility, what, "points", "out", c->opt_visibility_slice, 0, true, "rt_visibility", launch_visibility };
+    { int r = sampled_arguments(c, q, false, points, n, params, RT_VISIBILITY_DEFAULT_SAMPLES, out, 3, "none of RT_VIS_COSINE, RT_VIS_SH9, RT_VIS_DISTANCE", "rt_visibility_params"); if (r) return r; }
+    q.out_bytes = sizeof(float4) * (q.p.mode == RT_VIS_SH9 ? 3 : 1);
     return 0;
 }
 
-int visibility_host(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out)
+// Every exported query entry of a context: settle, check and describe, then the host or the device path
+int query_entry(rt_ctx* c, QueryDescribe describe, const char* what, bool device, const void* in, int n, const void* params, void* out)
 {
+    if (!c) return -1;
     RT_SETTLE(c);
-    rt_visibility_params q;
-    { int r = visibility_arguments(c, "rt_visibility", points, n, params, out, q); if (r) return r; }
-    if (n == 0) return 0;
-    { int r = query_prepare(c, query_origin_bound(points, n)); if (r) return r; }
-    const size_t per = visibility_out_float4(q.mode);
-    const int slice = c->opt_visibility_slice;
-    RT_HIP(c, c->d_q_rays.ensure(2 * (size_t)std::min(n, slice)));
-    RT_HIP(c, c->d_q_vis.ensure(per * (size_t)std::min(n, slice)));
-    double ms_sum = 0;
-    for (int first = 0; first < n; first += slice) {
-        const int cnt = std::min(slice, n - first);
-        rt_visibility_params qs = q;
-        qs.firstIndex = q.firstIndex + (uint32_t)first;
-        RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, points + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        RT_HIP(c, hipEventRecord(c->ev0, c->stream));
-        { int r = launch_visibility(c, c->d_q_rays.p, cnt, qs, c->d_q_vis.p); if (r) return r; }
-        RT_HIP(c, hipEventRecord(c->ev1, c->stream));
-        RT_HIP(c, hipMemcpyAsync(out + 4 * per * (size_t)first, c->d_q_vis.p, per * (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-        RT_HIP(c, hipStreamSynchronize(c->stream));     // (the events are the context's one pair: read before the next slice records them)
-        float ms = 0.f;
-        RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        ms_sum += ms;
-    }
-    c->visibility_info.calls++; c->visibility_info.lastKernelMs = ms_sum; c->visibility_info.totalKernelMs += ms_sum;
-    return 0;
-}
-
-int visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out)
-{
-    const char* what = "rt_visibility_device";
-    RT_SETTLE(c);
-    rt_visibility_params q;
-    { int r = visibility_arguments(c, what, points, n, params, out, q); if (r) return r; }
-    if (n == 0) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    if (!on_ctx_device(c, points) || !on_ctx_device(c, out))
-        return fail(c, -2, "%s: points and results must be device memory of the context's device %d", what, c->device);
-    if ((reinterpret_cast<uintptr_t>(points) & 15u) || (reinterpret_cast<uintptr_t>(out) & 15u))
-        return fail(c, -2, "%s: points and out must be 16-byte aligned", what);
-    { int r = prepare_scene(c); if (r) return r; }
-    { int r = cover_origins_device(c, static_cast<const float4*>(points), n); if (r) return r; }
-    { int r = launch_visibility(c, static_cast<const float4*>(points), n, q, static_cast<float4*>(out)); if (r) return r; }
-    c->visibility_info.calls++;                         // (asynchronous: the times are the host entry's)
-    return 0;
+    QueryCall q;
+    { int r = describe(c, what, in, n, params, out, q); if (r) return r; }
+    return device ? query_device(c, q, in, n, out) : query_host(c, q, static_cast<const rt_ray*>(in), n, out);
 }
 
 // ---- feature buffers (rt_render_aov, csrc/rt_aov.hpp) -----------------------------------------------------------------------------
@@ -2005,10 +1895,6 @@ void rt_destroy(rt_ctx* c)
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->d_sph_geom.release(); c->d_sph_mat.release(); c->d_nodes.release(); c->d_nodes_h.release(); c->d_tri_geo.release(); c->d_tri_nrm.release();
-    c->d_chunk_mat.release(); c->d_chunk_box.release(); c->d_raw_tris.release(); c->d_raw_range.release();
-    c->d_primary.release(); c->d_focus.release(); c->d_primary_counts.release();
-    c->d_frame.release(); c->d_accum.release(); c->d_gstack.release(); c->d_park.release(); c->d_display.release(); c->d_batch.release(); c->d_tile_order.release(); c->d_tile_cost.release(); c->d_tile_hist.release();
     if (c->d_tile_counter) (void)hipFree(c->d_tile_counter);
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2019,13 +1905,8 @@ void rt_destroy(rt_ctx* c)
     if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
     if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
     c->bvh_ws.release();
-    c->d_local_tris.release(); c->d_tri_mesh.release(); c->d_tri_chunk.release(); c->d_tri_rank.release(); c->d_order.release(); c->d_xf.release();
-    c->d_q_rays.release(); c->d_q_hits.release(); c->d_q_occ.release(); c->d_q_bound.release();
-    for (DevBuf<float4>& b : c->d_aov) b.release();
-    c->dn.release();
-    c->tp.release();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                           // (every DevBuf frees itself, on the device made current above)
 }
 
 int rt_set_stream(rt_ctx* c, void* hip_stream)
@@ -2345,34 +2226,34 @@ int rt_read_bvh_order(rt_ctx* c, uint32_t* order, size_t n)
     return 0;
 }
 
-int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits) { return c ? query_host(c, false, rays, n, hits) : -1; }
-int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { return c ? query_host(c, true, rays, n, occluded) : -1; }
-int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return c ? query_device(c, false, rays, n, hits) : -1; }
-int rt_occluded_device(rt_ctx* c, const void* rays, int n, void* occluded) { return c ? query_device(c, true, rays, n, occluded) : -1; }
-
-int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return c ? radiance_host(c, rays, n, params, rgba) : -1; }
-int rt_trace_radiance_device(rt_ctx* c, const void* rays, int n, const rt_radiance_params* params, void* rgba) { return c ? radiance_device(c, rays, n, params, rgba) : -1; }
-int rt_gather(rt_ctx* c, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return c ? gather_host(c, points, n, params, out) : -1; }
-int rt_gather_device(rt_ctx* c, const void* points, int n, const rt_gather_params* params, void* out) { return c ? gather_device(c, points, n, params, out) : -1; }
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int n, rt_hit* hits) { return query_entry(c, trace_rays_call, "rt_trace_rays", false, rays, n, nullptr, hits); }
+int rt_occluded(rt_ctx* c, const rt_ray* rays, int n, uint8_t* occluded) { return query_entry(c, occluded_call, "rt_occluded", false, rays, n, nullptr, occluded); }
+int rt_trace_rays_device(rt_ctx* c, const void* rays, int n, void* hits) { return query_entry(c, trace_rays_call, "rt_trace_rays_device", true, rays, n, nullptr, hits); }
+int rt_occluded_device(rt_ctx* c, const void* rays, int n, void* occluded) { return query_entry(c, occluded_call, "rt_occluded_device", true, rays, n, nullptr, occluded); }
+int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return query_entry(c, radiance_call, "rt_trace_radiance", false, rays, n, params, rgba); }
+int rt_trace_radiance_device(rt_ctx* c, const void* rays, int n, const rt_radiance_params* params, void* rgba) { return query_entry(c, radiance_call, "rt_trace_radiance_device", true, rays, n, params, rgba); }
+int rt_gather(rt_ctx* c, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return query_entry(c, gather_call, "rt_gather", false, points, n, params, out); }
+int rt_gather_device(rt_ctx* c, const void* points, int n, const rt_gather_params* params, void* out) { return query_entry(c, gather_call, "rt_gather_device", true, points, n, params, out); }
+int rt_visibility(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return query_entry(c, visibility_call, "rt_visibility", false, points, n, params, out); }
+int rt_visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out) { return query_entry(c, visibility_call, "rt_visibility_device", true, points, n, params, out); }
+// (the three info records are one layout, checked where QueryFamily is declared)
 int rt_get_gather_info(rt_ctx* c, rt_gather_info* out)
 {
     if (!c || !out) return -1;
-    *out = c->gather_info;
+    *out = c->query_info[kGather];
     return 0;
 }
-int rt_visibility(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return c ? visibility_host(c, points, n, params, out) : -1; }
-int rt_visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out) { return c ? visibility_device(c, points, n, params, out) : -1; }
 int rt_get_visibility_info(rt_ctx* c, rt_visibility_info* out)
 {
     if (!c || !out) return -1;
-    *out = c->visibility_info;
+    std::memcpy(out, &c->query_info[kVisibility], sizeof *out);
     return 0;
 }
 int rt_get_radiance_info(rt_ctx* c, rt_radiance_info* out)
 {
     if (!c) return -1;
     if (!out) return fail(c, -2, "null out");
-    *out = c->radiance_info;
+    std::memcpy(out, &c->query_info[kRadiance], sizeof *out);
     return 0;
 }
 
@@ -2588,8 +2469,9 @@ void rt_multi_destroy(rt_multi* m)
     if (!m) return;
     for (size_t i = 0; i < m->ev_strip.size() && i < m->ctx.size(); ++i)
         if (m->ev_strip[i]) { (void)hipSetDevice(m->ctx[i]->device); (void)hipEventDestroy(m->ev_strip[i]); }
-    if (!m->ctx.empty()) { (void)hipSetDevice(m->ctx[0]->device); m->d_image.release(); m->d_staging.release(); m->d_display.release(); m->d_aov_image.release(); m->d_dn_albedo.release(); m->d_dn_guide.release(); m->dn.release(); m->tp.release(); }
+    const int device0 = m->ctx.empty() ? -1 : m->ctx[0]->device;
     for (rt_ctx* c : m->ctx) rt_destroy(c);
+    if (device0 >= 0) (void)hipSetDevice(device0);      // the handle's own planes live on the first context's device
     delete m;
 }
 
@@ -2737,76 +2619,24 @@ int multi_render(rt_multi* m, int first_frame, int n_frames, const rt_params* pa
     return gather_strips(m, m->d_image, m->lastGatherMs, [](rt_ctx* c) { return c->d_accum.p; }, [](rt_ctx* c) { return c->target.rows; });
 }
 
-// rt_multi_trace_rays / rt_multi_occluded: one contiguous slice of the batch per context, traced concurrently, each slice's results
-// written in place
-int multi_query(rt_multi* m, bool any, const rt_ray* rays, int n, void* out)
+// Every query entry of the handle (`what`; host_what: the context entry behind it): one contiguous slice of the batch per context,
+// traced concurrently, each slice's results written in place.  A sampled family's items keep the stream indices they have in the
+// whole batch.
+int multi_query(rt_multi* m, QueryDescribe describe, const char* what, const char* host_what, bool need_params, const rt_ray* in, int n, const void* params, void* out)
 {
-    const char* what = any ? "rt_occluded" : "rt_trace_rays";
-    if (n < 0 || (n > 0 && (!rays || !out))) return fail(m, -2, "rt_multi %s: bad arguments (n = %d)", what, n);
+    if (!m) return -1;
+    if (need_params && !m->have_params) return fail(m, -2, "%s: rt_multi_set_params has not been called", what);
+    QueryCall q;
+    if (describe(m->ctx[0], what, in, n, params, out, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
     if (n == 0) return 0;
     { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
     const int N = (int)m->ctx.size();
     const int per = (n + N - 1) / N;
-    const size_t out_size = any ? 1 : sizeof(rt_hit);
-    return on_every_context(m, what, [&](int i) {
+    return on_every_context(m, host_what, [&](int i) {
         const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-        return query_host(m->ctx[i], any, rays + first, cnt, static_cast<char*>(out) + (size_t)first * out_size);
-    });
-}
-
-// rt_multi_trace_radiance: multi_query's slices; context i's rays keep the stream indices they have in the whole batch
-int multi_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba)
-{
-    if (!m->have_params) return fail(m, -2, "rt_multi_trace_radiance: rt_multi_set_params has not been called");
-    rt_radiance_params q;
-    if (radiance_arguments(m->ctx[0], "rt_multi_trace_radiance", rays, n, params, rgba, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
-    if (n == 0) return 0;
-    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
-    const int N = (int)m->ctx.size();
-    const int per = (n + N - 1) / N;
-    return on_every_context(m, "rt_trace_radiance", [&](int i) {
-        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-        rt_radiance_params qi = q;
-        qi.firstIndex = q.firstIndex + (uint32_t)first;
-        return radiance_host(m->ctx[i], rays + first, cnt, &qi, rgba + 4 * (size_t)first);
-    });
-}
-
-// rt_multi_gather: multi_radiance's slices; context i's points keep the stream indices they have in the whole batch
-int multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out)
-{
-    if (!m->have_params) return fail(m, -2, "rt_multi_gather: rt_multi_set_params has not been called");
-    rt_gather_params q;
-    if (gather_arguments(m->ctx[0], "rt_multi_gather", points, n, params, out, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
-    if (n == 0) return 0;
-    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
-    const int N = (int)m->ctx.size();
-    const int per = (n + N - 1) / N;
-    const size_t floats = 4 * gather_out_float4(q.mode);
-    return on_every_context(m, "rt_gather", [&](int i) {
-        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-        rt_gather_params qi = q;
-        qi.firstIndex = q.firstIndex + (uint32_t)first;
-        return gather_host(m->ctx[i], points + first, cnt, &qi, out + floats * (size_t)first);
-    });
-}
-
-// rt_multi_visibility: multi_query's slices (no params needed, as there); context i's points keep the stream indices they have in the
-// whole batch
-int multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out)
-{
-    rt_visibility_params q;
-    if (visibility_arguments(m->ctx[0], "rt_multi_visibility", points, n, params, out, q)) return fail(m, -2, "%s", rt_last_error(m->ctx[0]));
-    if (n == 0) return 0;
-    { int r = multi_share_scene(m, [&](rt_ctx* root) { RT_SETTLE(root); return query_prepare(root, 0.f); }); if (r) return r; }
-    const int N = (int)m->ctx.size();
-    const int per = (n + N - 1) / N;
-    const size_t floats = 4 * visibility_out_float4(q.mode);
-    return on_every_context(m, "rt_visibility", [&](int i) {
-        const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-        rt_visibility_params qi = q;
-        qi.firstIndex = q.firstIndex + (uint32_t)first;
-        return visibility_host(m->ctx[i], points + first, cnt, &qi, out + floats * (size_t)first);
+        rt_gather_params pi = q.p;              // (ray queries take none)
+        pi.firstIndex = q.p.firstIndex + (uint32_t)first;
+        return query_entry(m->ctx[i], describe, host_what, false, in + first, cnt, q.sampled() ? &pi : nullptr, static_cast<char*>(out) + q.out_bytes * (size_t)first);
     });
 }
 
@@ -2834,11 +2664,11 @@ int multi_gather_inputs(rt_multi* m, const char* what, bool image)
 
 extern "C" {
 
-int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { return m ? multi_query(m, false, rays, n, hits) : -1; }
-int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return m ? multi_query(m, true, rays, n, occluded) : -1; }
-int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return m ? multi_radiance(m, rays, n, params, rgba) : -1; }
-int rt_multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return m ? multi_gather(m, points, n, params, out) : -1; }
-int rt_multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return m ? multi_visibility(m, points, n, params, out) : -1; }
+int rt_multi_trace_rays(rt_multi* m, const rt_ray* rays, int n, rt_hit* hits) { return multi_query(m, trace_rays_call, "rt_multi_trace_rays", "rt_trace_rays", false, rays, n, nullptr, hits); }
+int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded) { return multi_query(m, occluded_call, "rt_multi_occluded", "rt_occluded", false, rays, n, nullptr, occluded); }
+int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return multi_query(m, radiance_call, "rt_multi_trace_radiance", "rt_trace_radiance", true, rays, n, params, rgba); }
+int rt_multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return multi_query(m, gather_call, "rt_multi_gather", "rt_gather", true, points, n, params, out); }
+int rt_multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return multi_query(m, visibility_call, "rt_multi_visibility", "rt_visibility", false, points, n, params, out); }
 
 // Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands
 int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)

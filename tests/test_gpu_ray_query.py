@@ -389,3 +389,41 @@ def test_manager_raycast_with_device_geometry(rtx, shim):
             else:
                 assert comp is None
         assert 2 in kinds
+
+
+def device_free_bytes():
+    """hipMemGetInfo's free figure, from the HIP runtime the library has loaded (found among this process's mappings)"""
+    with open("/proc/self/maps") as maps:
+        paths = {line.split()[-1] for line in maps if "libamdhip64" in line}
+    assert len(paths) == 1, f"expected one HIP runtime in the process, found {sorted(paths)}"
+    hip = ctypes.CDLL(paths.pop())
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+    return free.value
+
+
+def test_destroying_a_context_gives_its_query_staging_back(rtx):
+    """Six contexts in turn each make one host-entry radiance, SH9 gather and SH9 visibility call on 2^18 points and are closed.  Their
+    results are staged in 2^18 * (16 + 144 + 48) B = 54.5 MB a round.  The device's free memory after the sixth close may not lie below
+    the figure after the first by more than that one round; contexts that kept their staging past rt_destroy would be five rounds, 272 MB,
+    down.  (Free memory is device-wide: more rounds, not a wider bound, if other users of the device ever move it by tens of MB.)"""
+    n, rounds = 1 << 18, 6
+    one_round = n * (16 + 144 + 48)
+    mgr = rtx.scenes.mesh_test_scene(64, 48)
+    params, spheres, tris, infos = mgr.build_buffers()
+    rng = np.random.default_rng(11)
+    normals = rng.standard_normal((n, 3)).astype(np.float32)
+    normals /= np.linalg.norm(normals, axis=1, keepdims=True)
+    points = make_rays(rtx, rng.uniform(-4.0, 4.0, (n, 3)).astype(np.float32), normals)
+    free = []
+    for _ in range(rounds):
+        with rtx.Tracer(0) as t:
+            t.set_params(params)
+            t.upload(spheres=spheres, triangles=tris, meshinfo=infos)
+            assert t.trace_radiance(points, samples=1).shape == (n, 4)
+            assert t.gather(points, samples=1, mode=rtx._cabi.GATHER_SH9).shape == (n, 9, 4)
+            assert t.visibility(points, samples=1, mode=rtx._cabi.VIS_SH9).shape == (n, 12)
+        free.append(device_free_bytes())
+    print(f"free after each close: {free}; after round 1 - after round {rounds} = {free[0] - free[-1]} B, bound {one_round} B")
+    assert free[0] - free[-1] <= one_round, (f"free memory fell by {free[0] - free[-1]} B between the first and the last of {rounds} closed contexts "
+                                              f"(bound: one round's staging, {one_round} B): {free}")
