@@ -237,12 +237,16 @@ __device__ __forceinline__ RaySlabT<H> make_slab(v3 o, v3 d)
     RaySlabT<H> r;
     r.inv = rtm::mk(rtm::rcp_(d.x), rtm::rcp_(d.y), rtm::rcp_(d.z));
     r.oinv = rtm::mk(o.x * r.inv.x, o.y * r.inv.y, o.z * r.inv.z);
+    // The near planes follow the sign of 1 / d, not of d: a component of -0.0 has the reciprocal -inf and is not < 0.  Picking the low
+    // plane as its near plane gave far = high * -inf - o * -inf = -inf for an origin below a positive high plane, inside the slab, and
+    // pruned the box (a miss where the reference hits).  With the high plane near, as for +0.0 mirrored, every such term is NaN or the
+    // infinity that the origin's side of the slab calls for, and the fmax / fmin below drop a NaN.
     if constexpr (H) {
-        r.sets = ((d.x < 0.0f ? 16u : 0u) + (d.y < 0.0f ? 32u : 0u)) | (d.z < 0.0f ? 80u << 8 : 64u << 8);
+        r.sets = ((r.inv.x < 0.0f ? 16u : 0u) + (r.inv.y < 0.0f ? 32u : 0u)) | (r.inv.z < 0.0f ? 80u << 8 : 64u << 8);
     } else {
-        r.nx = d.x < 0.0f ? 48u : 0u;
-        r.ny = d.y < 0.0f ? 64u : 16u;
-        r.nz = d.z < 0.0f ? 80u : 32u;
+        r.nx = r.inv.x < 0.0f ? 48u : 0u;
+        r.ny = r.inv.y < 0.0f ? 64u : 16u;
+        r.nz = r.inv.z < 0.0f ? 80u : 32u;
         r.fx = 48u - r.nx; r.fy = 80u - r.ny; r.fz = 112u - r.nz;
     }
     return r;
@@ -484,7 +488,8 @@ __device__ __forceinline__ Hit closest_hit_flat(const DeviceScene& S, int inters
 }
 
 // GetEnvironmentLight — RayTracing.shader:238-251
-__device__ __forceinline__ v3 environment_light(const rt_params& p, v3 d)
+// any_length: d is a caller's direction, used as given (radiance queries), not one the shader normalised
+__device__ __forceinline__ v3 environment_light(const rt_params& p, v3 d, bool any_length = false)
 {
     if (!p.environmentEnabled) return rtm::mk(0.f, 0.f, 0.f);
     float skyGradientT = rtm::pow_(rtm::smoothstep(0.0f, 0.4f, d.y), 0.35f);
@@ -493,7 +498,10 @@ __device__ __forceinline__ v3 environment_light(const rt_params& p, v3 d)
     // sunIntensity == +0 (e.g. Chess.unity:30185): the base max(0, dot) is finite, >= 0 and at most 1 + a few ulp, so for
     // 1 <= sunFocus <= 1e6 pow() is finite and >= 0 and the product is exactly +0; skip the transcendentals, keep the adds.
     float sun = 0.0f;
-    if (!(__float_as_uint(p.sunIntensity) == 0u && p.sunFocus >= 1.0f && p.sunFocus <= 1.0e6f)) {     // (wave-uniform: parameters only)
+    // A direction of any length can have dot > 1, where pow() overflows to +inf and the reference's product inf * 0 is NaN: such a
+    // direction takes the formula as written.
+    if (!(__float_as_uint(p.sunIntensity) == 0u && p.sunFocus >= 1.0f && p.sunFocus <= 1.0e6f) ||     // (wave-uniform: parameters only)
+        (any_length && !(rtm::dot(d, ld3(p.worldSpaceLightPos0)) <= 1.0f))) {
         RT_MARK("begin env_sun");
         sun = rtm::pow_(rtm::fmax_(0.0f, rtm::dot(d, ld3(p.worldSpaceLightPos0))), p.sunFocus) * p.sunIntensity;
         RT_MARK("end env_sun");

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void k_radiance(DeviceScene S, RadianceArgs
                 if (bounce > p.maxBounceCount) path_done = true;                           // loop bound :305
             } else {
                 if (e_bounce < 0) { e_h = h; e_o = o; e_bounce = bounce; }
-                light = light + environment_light(p, d) * rayColour;                       // :346-347
+                light = light + environment_light(p, d, true) * rayColour;                 // :346-347 (d may be the caller's: any length)
                 path_done = true;
             }
             if (path_done) {

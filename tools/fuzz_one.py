@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import rtx_pkg
 import oracle_binding
-from test_gpu_fuzz import random_scene
+from test_gpu_fuzz import draw_knobs, random_scene
 from test_gpu_parity import bits_equal, run_gpu
 
 rtx = rtx_pkg.load()
@@ -19,11 +19,7 @@ over = dict(a.split("=") for a in sys.argv[2:])
 b = random_scene(rtx, seed)
 kernel = (0, 1, 1, 1, 0, 1, -1)[seed % 7]
 rng = np.random.default_rng(seed)
-knobs = {"stream_stack": int(rng.choice([4, 9, 30, 37])), "node_min": int(rng.choice([1, 6, 24, 64])), "tiles_per_fetch": int(rng.choice([1, 2, 5, 40])), "fetch_guide": int(rng.choice([1, 4, 16])),
-         "max_leaf": int(rng.choice([1, 2, 4])), "full_sort": int(rng.integers(0, 2)), "frame_batch": int(rng.choice([0, 1])),
-         "bvh_reinsert": int(rng.choice([0, 0, 2])),
-         "stream_tile": int(rng.choice([0, 2, 4])), "compact_nodes": int(rng.choice([0, 1, 1])), "tile_lpt": int(rng.choice([0, 1, 1])),
-         "device_bvh": int(rng.choice([0, 1])), "bvh_collapse": int(rng.choice([0, 1, 2])), "bvh_radius": int(rng.choice([2, 8, -16, 40])), "bvh_top": int(rng.choice([0, 2, 600, 1024])), "bvh_treelets": int(rng.choice([0, 1, 3, 6]))}
+knobs = draw_knobs(rng)
 nf = int(rng.choice([2, 2, 4, 5]))
 thr = int(rng.choice([1, 24, 48, 64]))
 if "kernel" in over:
