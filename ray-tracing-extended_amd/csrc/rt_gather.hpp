@@ -1,7 +1,7 @@
 // rt_gather.hpp — gather queries: the light that arrives at a POINT, over the cosine lobe about its normal or over the sphere as nine SH
 // coefficients (include/rt.h rt_gather).  What a lightmap texel or a light probe asks; the directions are drawn on the device.
 //
-// Definition (include/rt.h "gather queries"; tests/gather_oracle.c runs the oracle's own random_direction() and trace() for it):
+// Definition (include/rt.h "gather queries"; tests/query_oracle.c runs the oracle's own random_direction() and trace() for it):
 //   stream        point i of a call has the Philox key (firstIndex + i, seed); sample s draws its direction from counter (block, s) with
 //                 blocks 0xFFFFFFFE (words 0..3) and 0xFFFFFFFF (words 0, 1): R = RandomDirection (RayTracing.shader:216-223).  Trace's
 //                 hits use blocks 1 + 2b, 2 + 2b as in a radiance query, so the two never meet

@@ -1,7 +1,7 @@
 // rt_radiance.hpp — radiance queries: Trace (RayTracing.shader:300-352) for rays the caller supplies (include/rt.h rt_trace_radiance):
 // how much light arrives along each ray, averaged over N independent runs of Trace.
 //
-// Definition (include/rt.h "radiance queries"; tests/radiance_oracle.c runs the oracle's own trace() for it):
+// Definition (include/rt.h "radiance queries"; tests/query_oracle.c runs the oracle's own trace() for it):
 //   stream        ray i of a call has the Philox key (firstIndex + i, seed); sample s draws from counter (block, s): the hit at loop index
 //                 b takes blocks 1 + 2b and 2 + 2b, block 0 (a frame's camera ray) is unused — the caller made the ray
 //   first cast    counts only hits with dst < tMax (rt_trace_rays' rule); every later cast is unbounded

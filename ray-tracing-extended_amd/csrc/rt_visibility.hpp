@@ -3,7 +3,7 @@
 // visibility SH9 of a probe, the distance moments that place probes.  Geometry only: no rt_params field but intersectMode is read and
 // nothing is shaded.
 //
-// Definition (include/rt.h "visibility gathers"; tests/visibility_oracle.c runs the oracle's own random_direction() and
+// Definition (include/rt.h "visibility gathers"; tests/query_oracle.c runs the oracle's own random_direction() and
 // calculate_ray_collision() for it):
 //   direction     rt_gather's, bit for bit (gather_direction of rt_gather.hpp is CALLED, not copied: using it here changes nothing in
 //                 k_gather): key (firstIndex + i, seed), counter (block, s), blocks 0xFFFFFFFE / 0xFFFFFFFF.  RT_VIS_COSINE and

@@ -1,15 +1,10 @@
 """The feature-buffer checker: tests/aov_oracle.c compiled with the CFLAGS of oracle/Makefile and bound with ctypes, plus the bitwise
 comparison the feature-buffer tests share.  Test infrastructure only."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from checker_build import compile_checker
 
 _lib = None
 
@@ -17,11 +12,7 @@ _lib = None
 def shim():
     global _lib
     if _lib is None:
-        mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-        cflags = re.search(r"^CFLAGS\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-        so = os.path.join(tempfile.mkdtemp(prefix="aov_oracle_"), "libaov.so")
-        subprocess.check_call(["gcc", *cflags, "-shared", "-o", so, os.path.join(HERE, "aov_oracle.c"), "-lm"])
-        lib = ctypes.CDLL(so)
+        lib = compile_checker("aov_oracle.c")
         vp, ci = ctypes.c_void_p, ctypes.c_int
         lib.aov_frame.argtypes = [vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         lib.aov_frame.restype = ci

@@ -2,15 +2,10 @@
 restatement of the same definition written from the text of include/rt.h (exact 2**x), and the inputs the denoiser tests share.
 Test infrastructure only."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from checker_build import compile_checker
 
 DEFAULTS = dict(iterations=5, demodulate=0, sigmaColour=16.0, sigmaNormal=1.0, sigmaDepth=0.5)      # RT_DENOISE_DEFAULT_* of include/rt.h
 TIGHT = dict(sigmaColour=0.05, sigmaNormal=0.02, sigmaDepth=0.003)
@@ -22,11 +17,7 @@ _lib = None
 def shim():
     global _lib
     if _lib is None:
-        mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-        cflags = re.search(r"^CFLAGS\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-        so = os.path.join(tempfile.mkdtemp(prefix="denoise_oracle_"), "libdenoise.so")
-        subprocess.check_call(["gcc", *cflags, "-shared", "-o", so, os.path.join(HERE, "denoise_oracle.c"), "-lm"])
-        lib = ctypes.CDLL(so)
+        lib = compile_checker("denoise_oracle.c")
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         lib.denoise_image.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, cf, cf, ci, vp]
         lib.denoise_image.restype = ci

@@ -6,10 +6,11 @@ An item is an rt_ray.  The ray families read it as origin / direction / tMax, th
 first-cast bound or reach, so every item is given to every family.  Everything is a pure function of the seed."""
 import numpy as np
 
-import gather_check as gc
-import radiance_check as rc
-import visibility_check as vc
-from ray_query_helpers import load_shim, make_rays, oracle_candidates, oracle_hits
+import query_check as gc
+import query_check as rc
+import query_check as vc
+from query_check import oracle_candidates, oracle_hits
+from ray_query_helpers import load_shim, make_rays
 from test_gpu_fuzz import draw_knobs, random_scene
 
 N_ITEMS = 768

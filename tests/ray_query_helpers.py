@@ -1,67 +1,26 @@
-"""What the ray-query tests share: the oracle's CalculateRayCollision for caller-supplied rays (tests/ray_query_oracle.c compiled with the
-CFLAGS of oracle/Makefile), the ray sets, and the scenes.  Test infrastructure only."""
-import ctypes
+"""What the query tests share besides their checker (tests/query_check.py): its library as a fixture, the ray sets, and the scenes.
+Test infrastructure only."""
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import query_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
 SCENES = ["Balls_Outdoors", "Chess", "Knight", "Reflective_Balls", "Suzanne", "Thumbnail"]
 
 
-_lib = None
-
-
 def load_shim(directory=None):
-    """tests/ray_query_oracle.c compiled with the CFLAGS of oracle/Makefile (once per process; into `directory`, or a temporary one)"""
-    global _lib
-    if _lib is None:
-        mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-        cflags = re.search(r"^CFLAGS\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-        so = os.path.join(directory or tempfile.mkdtemp(prefix="ray_query_oracle_"), "librq.so")
-        subprocess.check_call(["gcc", *cflags, "-shared", "-o", so, os.path.join(HERE, "ray_query_oracle.c"), "-lm"])
-        lib = ctypes.CDLL(so)
-        scene = [ctypes.c_void_p, ctypes.c_int] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-        lib.rq_trace.argtypes = scene + [ctypes.c_int, ctypes.c_void_p]
-        lib.rq_candidates.argtypes = scene + [ctypes.c_void_p]
-        lib.rq_trace.restype = lib.rq_candidates.restype = ctypes.c_int
-        _lib = lib
-    return _lib
+    """the query checkers' library (tests/query_oracle.c; once per process; built into `directory`, or a temporary one)"""
+    return query_check.lib(directory)
 
 
 @pytest.fixture(scope="session")
 def shim(tmp_path_factory):
-    """tests/ray_query_oracle.c compiled with the CFLAGS of oracle/Makefile"""
+    """the query checkers' library (tests/query_oracle.c compiled with the CFLAGS of oracle/Makefile)"""
     return load_shim(str(tmp_path_factory.mktemp("rq")))
-
-
-def _buffers(rtx, spheres, tris, infos, rays):
-    return (np.ascontiguousarray(spheres, rtx.SPHERE), np.ascontiguousarray(tris, rtx.TRIANGLE), np.ascontiguousarray(infos, rtx.MESHINFO),
-            np.ascontiguousarray(rays, rtx.RAY).reshape(-1))
-
-
-def oracle_hits(rtx, shim, spheres, tris, infos, mode, rays, accel=False):
-    """HIT (n,): the closest hit of every ray on the CPU oracle, by its literal loop or (accel) its search tree"""
-    s, t, m, r = _buffers(rtx, spheres, tris, infos, rays)
-    out = np.zeros(len(r), rtx.HIT)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
-    assert shim.rq_trace(p(s), len(s), p(t), len(t), p(m), len(m), int(mode), p(r), len(r), 1 if accel else 0, p(out)) == 0
-    return out
-
-
-def oracle_candidates(rtx, shim, spheres, tris, infos, mode, rays):
-    """int32 (n,): the candidates at the bit-identical dst of every ray's closest hit, the winner included (0: a miss)"""
-    s, t, m, r = _buffers(rtx, spheres, tris, infos, rays)
-    out = np.zeros(len(r), np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
-    assert shim.rq_candidates(p(s), len(s), p(t), len(t), p(m), len(m), int(mode), p(r), len(r), p(out)) == 0
-    return out
 
 
 def make_rays(rtx, origins, directions, t_max=np.inf):

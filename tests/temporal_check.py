@@ -2,15 +2,10 @@
 lock-step driver that holds the checker's own state from call 0, a float64 numpy restatement of the same definition written from the
 text of include/rt.h, and the cameras the temporal tests share.  Test infrastructure only."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from checker_build import compile_checker
 
 DEFAULTS = dict(maxHistory=32, depthTolerance=0.05, normalTolerance=0.5)        # RT_TEMPORAL_DEFAULT_* of include/rt.h
 TIGHT = dict(depthTolerance=0.01, normalTolerance=0.1)
@@ -22,11 +17,7 @@ _lib = None
 def shim():
     global _lib
     if _lib is None:
-        mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-        cflags = re.search(r"^CFLAGS\s*\?=\s*(.*)$", mk, re.M).group(1).split()
-        so = os.path.join(tempfile.mkdtemp(prefix="temporal_oracle_"), "libtemporal.so")
-        subprocess.check_call(["gcc", *cflags, "-shared", "-o", so, os.path.join(HERE, "temporal_oracle.c"), "-lm"])
-        lib = ctypes.CDLL(so)
+        lib = compile_checker("temporal_oracle.c")
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         lib.temporal_step.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, cf, cf, ci, vp, vp, vp, vp]
         lib.temporal_step.restype = ci

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import bvh_audit as A
-from ray_query_helpers import oracle_hits, shim      # noqa: F401 (shim is a fixture)
+from query_check import oracle_hits
+from ray_query_helpers import shim      # noqa: F401 (shim is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ray-tracing-extended_amd", "csrc")

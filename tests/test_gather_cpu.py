@@ -1,4 +1,4 @@
-"""Gather queries without a GPU: the checker (tests/gather_oracle.c: the oracle's own random_direction() and trace() per point and sample)
+"""Gather queries without a GPU: the checker (tests/query_oracle.c: the oracle's own random_direction() and trace() per point and sample)
 is pinned to the oracle's Philox words and intrinsics, to the radiance checker, to its tree and basis restated in numpy and to analytic
 cases, and the ABI is declared, exported and bound.
 
@@ -16,9 +16,10 @@ import re
 import numpy as np
 import pytest
 
-import gather_check as gc
-import radiance_check as rc
-from ray_query_helpers import camera_rays, make_rays, oracle_hits, scene_of, shim  # noqa: F401  (shim: a fixture)
+import query_check as gc
+import query_check as rc
+from query_check import oracle_hits
+from ray_query_helpers import camera_rays, make_rays, scene_of, shim  # noqa: F401  (shim: a fixture)
 from test_camera_batch_cpu import built_library
 from test_csharp_binding_cpu import CS, _cs_structs, _layout
 from test_kernarg_layout_cpu import ROOT, code_objects, kernel_metadata
@@ -98,11 +99,11 @@ def test_sample_equals_the_radiance_checkers_sample_along_the_direction(rtx, shi
         for s in (0, 1, 7):
             d = gc.direction(pts["direction"][i], s, seed, first + i, mode)
             ray = make_rays(rtx, [pts["origin"][i]], [d], pts["tMax"][i])
-            want = rc.oracle_sample(rtx, params, spheres, tris, infos, ray, s, seed=seed, index=first + i)
-            got = gc.oracle_sample(rtx, params, spheres, tris, infos, pts[i:i + 1], s, seed=seed, index=first + i, mode=mode)
+            want = rc.oracle_radiance_sample(rtx, params, spheres, tris, infos, ray, s, seed=seed, index=first + i)
+            got = gc.oracle_gather_sample(rtx, params, spheres, tris, infos, pts[i:i + 1], s, seed=seed, index=first + i, mode=mode)
             gc.assert_same_bits(got, want, f"point {i} sample {s}")
             unbounded = make_rays(rtx, [pts["origin"][i]], [d])
-            differ += int((rc.oracle_sample(rtx, params, spheres, tris, infos, unbounded, s, seed=seed, index=first + i) != want).any())
+            differ += int((rc.oracle_radiance_sample(rtx, params, spheres, tris, infos, unbounded, s, seed=seed, index=first + i) != want).any())
     assert differ > 0                                                                # (the bound changed some samples)
 
 
@@ -117,7 +118,7 @@ def test_the_tree_is_the_written_rule(rtx, shim, n):  # noqa: F811
         got = gc.oracle_gather(rtx, params, spheres, tris, infos, pts, n, seed, first, mode)
         varied = False
         for i in range(len(pts)):
-            L = np.stack([gc.oracle_sample(rtx, params, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode) for s in range(n)])
+            L = np.stack([gc.oracle_gather_sample(rtx, params, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode) for s in range(n)])
             varied = varied or len(np.unique(L, axis=0)) > 1
             if mode == gc.COSINE:
                 gc.assert_same_bits(got[i, :3], gc.tree_sum(L), f"N = {n}, point {i}")
@@ -190,7 +191,7 @@ def test_constant_radiance_inside_an_emitter(rtx):
     got = gc.oracle_gather(rtx, *scene, pt, N, seed=5, mode=gc.COSINE)
     assert got.tolist() == [[0.5, 1.0, 1.5, 1.0]]
     for s in (0, 1, 4095):
-        assert gc.oracle_sample(rtx, *scene, pt, s, seed=5, mode=gc.SH9).tolist() == [0.5, 1.0, 1.5]
+        assert gc.oracle_gather_sample(rtx, *scene, pt, s, seed=5, mode=gc.SH9).tolist() == [0.5, 1.0, 1.5]
 
     # SH9: L with L * Y0 = 1/4 exactly in float32 (see the module docstring), two more channels by exact halving and doubling
     Y0 = f32(0.28209479)

@@ -1,5 +1,5 @@
 """Gather queries on the GPU (rt_gather and its device and rt_multi forms): every float of every result bitwise against the checker
-(tests/gather_oracle.c: the oracle's own random_direction() and trace() per point and sample) and, with no checker in between, against
+(tests/query_oracle.c: the oracle's own random_direction() and trace() per point and sample) and, with no checker in between, against
 the radiance kernel; invisible slicing, rt_multi, a spilling traversal stack, far origins, special values, the device entry; a call
 leaves every other state of the context alone.  The points are the first hits of a scene's 64 x 48 camera rays (rt_trace_rays):
 hitPoint + 1e-3 * normal with the normal, misses kept with n = 0."""
@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-import gather_check as gc
+import query_check as gc
 from ray_query_helpers import camera_rays, make_rays, scene_of
 from test_gpu_radiance import light_manager
 from test_gpu_ray_query import far_rays, loaded_tracer

@@ -14,10 +14,11 @@ import sys
 import numpy as np
 import pytest
 
-import gather_check as gc
+import query_check as gc
 import query_fuzz as qf
-import visibility_check as vc
-from ray_query_helpers import camera_rays, make_rays, oracle_candidates, oracle_hits, shim      # noqa: F401 (shim is a fixture)
+import query_check as vc
+from query_check import oracle_candidates, oracle_hits
+from ray_query_helpers import camera_rays, make_rays, shim      # noqa: F401 (shim is a fixture)
 from test_gpu_ray_query import FLOAT_COLS, check_queries
 
 pytestmark = pytest.mark.gpu

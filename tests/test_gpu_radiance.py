@@ -1,5 +1,5 @@
 """Radiance queries on the GPU (rt_trace_radiance and its device and rt_multi forms): every float of every result bitwise against the
-checker (tests/radiance_oracle.c: the oracle's own trace() per ray and sample) and, with no checker in between, against the frame
+checker (tests/query_oracle.c: the oracle's own trace() per ray and sample) and, with no checker in between, against the frame
 kernel in Philox mode; invisible slicing, rt_multi, a spilling traversal stack, far origins, the device entry; a call leaves every
 other state of the context alone."""
 import ctypes
@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-import radiance_check as rc
+import query_check as rc
 from ray_query_helpers import SCENES, camera_rays, make_rays, random_rays, scene_of
 from test_gpu_ray_query import far_rays, loaded_tracer, local_tracer
 

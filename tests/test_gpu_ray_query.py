@@ -1,5 +1,5 @@
 """Ray queries on the GPU (rt_trace_rays / rt_occluded and their device and rt_multi forms): every field of every rt_hit bitwise against the
-CPU oracle's CalculateRayCollision (tests/ray_query_oracle.c), occlusion against the oracle's dst < tMax, on the reference's scenes and on
+CPU oracle's CalculateRayCollision (tests/query_oracle.c), occlusion against the oracle's dst < tMax, on the reference's scenes and on
 rays made to hit the edges: random origins inside and outside the scene, unnormalised / axis-aligned / tiny / huge directions, rays that
 start on surfaces, NaN / inf origins and zero directions, tMax at the hit distance and one ulp either side, origins far outside the box
 padding, both intersect modes, both BVH builders, moving local meshes, and scenes with no triangles or nothing at all.  A query leaves the
@@ -12,7 +12,8 @@ import sys
 import numpy as np
 import pytest
 
-from ray_query_helpers import SCENES, camera_rays, make_rays, oracle_hits, random_rays, scene_of, shim      # noqa: F401 (shim is a fixture)
+from query_check import oracle_hits
+from ray_query_helpers import SCENES, camera_rays, make_rays, random_rays, scene_of, shim      # noqa: F401 (shim is a fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """Visibility gathers on the GPU (rt_visibility and its device and rt_multi forms): every float of every result bitwise against the checker
-(tests/visibility_oracle.c: the oracle's own random_direction() and calculate_ray_collision() per point and sample) and, with no checker
+(tests/query_oracle.c: the oracle's own random_direction() and calculate_ray_collision() per point and sample) and, with no checker
 in between, against rt_occluded and rt_trace_rays over the same rays; invisible slicing, rt_multi, a spilling traversal stack, the
 device entry; a call needs no rt_params and leaves every other state of the context alone.
 
@@ -14,7 +14,7 @@ import sys
 import numpy as np
 import pytest
 
-import visibility_check as vc
+import query_check as vc
 from ray_query_helpers import camera_rays, scene_of
 from test_gpu_radiance import light_manager
 from test_gpu_ray_query import far_rays, loaded_tracer

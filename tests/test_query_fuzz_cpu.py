@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import query_fuzz as qf
-from radiance_check import assert_same_bits
-from ray_query_helpers import oracle_hits, shim      # noqa: F401 (shim is a fixture)
+from query_check import assert_same_bits, oracle_hits
+from ray_query_helpers import shim      # noqa: F401 (shim is a fixture)
 
 SEEDS = range(24)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,4 @@
-"""Radiance queries without a GPU: the checker (tests/radiance_oracle.c, the oracle's own trace() per ray and sample) is pinned to the
+"""Radiance queries without a GPU: the checker (tests/query_oracle.c, the oracle's own trace() per ray and sample) is pinned to the
 renderer's oracle, to its tree restated in numpy and to analytic cases, and the ABI is declared, exported and bound.
 
 1. rad_trace over rad_camera_rays with samples 1 and seed f is the rgb of orc_render_frame in Philox mode with numRaysPerPixel 1.
@@ -12,7 +12,7 @@ import re
 import numpy as np
 import pytest
 
-import radiance_check as rc
+import query_check as rc
 from ray_query_helpers import camera_rays, make_rays, scene_of
 from test_camera_batch_cpu import built_library
 from test_csharp_binding_cpu import CS, _cs_structs, _layout
@@ -69,7 +69,7 @@ def test_the_tree_is_the_written_rule(rtx, n):
     got = rc.oracle_radiance(rtx, params, spheres, tris, infos, rays, n, seed=seed, first_index=first)
     varied = False
     for i in range(len(rays)):
-        values = np.stack([rc.oracle_sample(rtx, params, spheres, tris, infos, rays[i:i + 1], s, seed=seed, index=first + i) for s in range(n)])
+        values = np.stack([rc.oracle_radiance_sample(rtx, params, spheres, tris, infos, rays[i:i + 1], s, seed=seed, index=first + i) for s in range(n)])
         varied = varied or len(np.unique(values, axis=0)) > 1
         rc.assert_same_bits(got[i, :3], rc.tree_sum(values), f"N = {n}, ray {i}")
         assert got[i, 3] == 1

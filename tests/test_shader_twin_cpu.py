@@ -11,7 +11,8 @@ import pytest
 
 import shader_twin as tw
 import twin_cases as tc
-from ray_query_helpers import GOLDEN, camera_rays, oracle_hits, scene_of, shim      # noqa: F401 (shim is a fixture)
+from query_check import oracle_hits
+from ray_query_helpers import GOLDEN, camera_rays, scene_of, shim      # noqa: F401 (shim is a fixture)
 
 
 # ---- the twin's integer streams ------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Visibility gathers without a GPU: the checker (tests/visibility_oracle.c: the oracle's own random_direction() and
+"""Visibility gathers without a GPU: the checker (tests/query_oracle.c: the oracle's own random_direction() and
 calculate_ray_collision() per point and sample) is pinned to the gather checker's directions, to the ray-query checker, to the tree restated
 in numpy and to exact and statistical cases, and the ABI is declared, exported and bound.
 
@@ -14,9 +14,10 @@ import re
 import numpy as np
 import pytest
 
-import gather_check as gc
-import visibility_check as vc
-from ray_query_helpers import camera_rays, make_rays, oracle_hits, shim  # noqa: F401  (shim: a fixture)
+import query_check as gc
+import query_check as vc
+from query_check import oracle_hits
+from ray_query_helpers import camera_rays, make_rays, shim  # noqa: F401  (shim: a fixture)
 from test_camera_batch_cpu import built_library
 from test_csharp_binding_cpu import CS, _cs_structs, _layout
 from test_gather_cpu import inward_box, triangle_scene
@@ -69,7 +70,7 @@ def test_samples_are_the_ray_query_checkers_answers(rtx, shim, batch, intersect)
         free = oracle_hits(rtx, shim, spheres, tris, infos, intersect, make_rays(rtx, rays["origin"], rays["direction"])).reshape(len(pts), N)
         for i in range(len(pts)):
             for s in range(N):
-                got = vc.oracle_sample(rtx, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode, intersect)
+                got = vc.oracle_visibility_sample(rtx, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode, intersect)
                 occ = hits["kind"][i, s] != 0
                 seen.add((mode, bool(occ)))
                 seen.add(("bounded away", bool(free["kind"][i, s] != 0 and not occ)))
@@ -102,7 +103,7 @@ def test_the_tree_is_the_written_rule(rtx, batch, n):
         got = vc.oracle_visibility(rtx, spheres, tris, infos, pts, n, seed, first, mode)
         varied = False
         for i in range(len(pts)):
-            ch = np.stack([vc.oracle_sample(rtx, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode) for s in range(n)])
+            ch = np.stack([vc.oracle_visibility_sample(rtx, spheres, tris, infos, pts[i:i + 1], s, seed, first + i, mode) for s in range(n)])
             varied = varied or len(np.unique(ch, axis=0)) > 1
             vc.assert_same_bits(got[i], vc.finish(vc.tree_sum(ch), mode), f"N = {n}, mode {mode}, point {i}")
             count = ch[:, -1].astype(np.float64).sum()                               # the 0 / 1 channel: count / N whatever the tree

@@ -4,7 +4,7 @@ one Philox-mode image frame (rt_render_frame, rt_stats.lastKernelMs) of the same
 the two alternate and each is timed by the library's own HIP events.  Both are printed as rays of CalculateRayCollision per second.  The
 frame's casts are the library's own count (rt_stats.rays).  The query has no work counters: its casts are what the DEFINITION casts
 (every sample's first cast included — the kernel makes fewer, it re-enters a ray's first hit), counted on the CPU by the checker
-(tests/radiance_oracle.c) on a sub-grid of the pixels and scaled to the image; --count-step 0 skips the count and says so.
+(tests/query_oracle.c) on a sub-grid of the pixels and scaled to the image; --count-step 0 skips the count and says so.
 
     python tools/bench_radiance.py --config 3 --repeats 5
 """
@@ -56,9 +56,9 @@ def main(argv=None):
     casts_per_ray = None
     if args.count_step > 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import radiance_check
+        import query_check
         sub = rays.reshape(h, w)[args.count_step // 2::args.count_step, args.count_step // 2::args.count_step].reshape(-1)
-        _, casts = radiance_check.oracle_radiance(rtx, params, spheres, tris, infos, sub, args.samples, count_casts=True)
+        _, casts = query_check.oracle_radiance(rtx, params, spheres, tris, infos, sub, args.samples, count_casts=True)
         casts_per_ray = casts / len(sub)
 
     frame_ms, query_ms = [], []

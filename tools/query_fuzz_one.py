@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import rtx_pkg
 import query_fuzz as qf
-from ray_query_helpers import load_shim, oracle_hits
+from query_check import oracle_hits
+from ray_query_helpers import load_shim
 
 rtx = rtx_pkg.load()
 seed = int(sys.argv[1])
