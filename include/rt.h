@@ -773,6 +773,71 @@ int rt_read_temporal_display(rt_ctx* ctx, uint32_t* rgba8, size_t n_pixels);
 int rt_get_temporal_info(rt_ctx* ctx, rt_temporal_info* out);
 int rt_denoise_temporal(rt_ctx* ctx, const rt_denoise_params* params);
 
+/* ---- variance-guided denoiser: an A-trous filter whose colour edge-stop follows the noise ---------------------------------
+ * rt_denoise_variance is a second filter beside rt_denoise: the spatial half of SVGF (Schied et al., HPG 2017, 4.2-4.4).  It estimates
+ * a per-pixel luminance variance from the image it is given, scales its luminance edge-stop by the square root of that variance and
+ * carries the variance through its passes.  It keeps no temporal moments and no state across calls beside its planes.  The definition
+ * is frozen to the bit.  All arithmetic follows the denoiser's rules: IEEE float32 without FMA contraction, every '/' and sqrt
+ * correctly rounded, exp2_ = rtm::exp2_, operations in the order written.  C is resultTexture (source == 0) or the temporal plane T
+ * (source == 1, what rt_denoise_temporal reads); A and G are the feature planes.  Per pixel p:
+ *
+ *   prep          d and e0.rgb exactly as rt_denoise's demodulate step (d = 1 and e0 = C.rgb with demodulate == 0).
+ *   lum           l(e) = (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z
+ *   constants     kn, kz and the per-pixel zs exactly as rt_denoise.
+ *   estimate      once, on e0: the taps q = p + (dx, dy), dy = -3..3 outer, dx = -3..3 inner; a tap outside the image is skipped.
+ *                     g = exp2_(-(dn2*kn + (dz*dz)*zs))       dn2 and dz as in rt_denoise; there is no spatial kernel
+ *                 in tap order sg = sg + g, m1 = m1 + g*l_q, m2 = m2 + g*(l_q*l_q) with l_q = l(e0(q)); then mu = m1 / sg,
+ *                 v = m2 / sg - mu*mu and var_0(p) = v > 0 ? v : 0 (a select: NaN gives 0).  The centre tap has g = 1.
+ *   pass i        for i = 0 .. iterations - 1, with s = 1 << i.
+ *                 prefilter: the 3 x 3 taps q = p + (dx, dy) at spacing 1 (whatever s), dy = -1..1 outer, dx inner, that lie inside the
+ *                 image, k3 = {1/4, 1/2, 1/4}: pn = pn + (k3[dy+1]*k3[dx+1]) * var_i(q), pd = pd + k3[dy+1]*k3[dx+1]; gv = pn / pd.
+ *                 sigma: kl = 1.0f / (sigmaLuminance * sqrt(gv) + 1e-6f).
+ *                 taps: rt_denoise's 25 taps at spacing s, in its order, with its skipping rule:
+ *                     x = (dn2*kn + (dz*dz)*zs) + fabs(l(e_i(p)) - l(e_i(q))) * kl
+ *                     w = (h[dy+2] * h[dx+2]) * exp2_(-x)
+ *                 sw = sw + w, s.ch = s.ch + w * e_i(q).ch, sv = sv + (w*w) * var_i(q); then e_{i+1}(p).ch = s.ch / sw and
+ *                 var_{i+1}(p) = sv / (sw*sw).  The colour sigma does not halve per pass: the propagated variance shrinks it.
+ *   output        out.ch = e_last.ch * d.ch, out.a = C.a, written to the denoised plane: the plane rt_read_denoised,
+ *                 rt_copy_denoised_to_device and rt_read_denoised_display read (a read after only this call succeeds).  var_0 is kept in
+ *                 the variance plane, height*width floats.
+ *
+ * Non-finite inputs give whatever this arithmetic gives; the call does not fault on them.
+ * rt_denoise_variance settles the queue, runs on the context's stream (rt_set_stream) and moves only the denoised plane, the variance
+ * plane, the work planes it shares with rt_denoise (either call rewrites them whole) and rt_vdenoise_info: resultTexture, T and its
+ * history, the feature planes, rt_aov_info, rt_denoise_info, rt_temporal_info and every rt_stats field stay.  (The planes are created
+ * at first use and again when the image size changes; a re-creation by either filter call restarts rt_denoise_info.totalKernelMs and
+ * rt_vdenoise_info.totalKernelMs, the sums over the calls on the planes that exist.)  It needs the whole image in one context (else use
+ * rt_multi_denoise_variance).  params == NULL means source 0 and RT_VDENOISE_DEFAULT_* (chosen by the sweep of
+ * profiles/vdenoise_defaults.txt).
+ * Errors: null handle -1; no params set, no feature frame accumulated, source == 1 before any rt_temporal (or at another image size),
+ * a context holding part of the image, iterations outside 1..6, demodulate or source neither 0 nor 1, a sigma that is <= 0 or not
+ * finite, a non-zero reserved word, a wrong n_floats, a null buffer, rt_read_variance before any rt_denoise_variance: -2 with a
+ * message, and nothing changed.                                                                                                    */
+typedef struct rt_vdenoise_params {     /* 32 B */
+    int32_t iterations;                 /* 1..6; pass i uses tap spacing 2^i                                                */
+    int32_t demodulate;                 /* 0 / 1                                                                            */
+    int32_t source;                     /* 0 = resultTexture, 1 = the temporal plane                                        */
+    float   sigmaLuminance, sigmaNormal, sigmaDepth;   /* each finite and > 0                                               */
+    int32_t _reserved[2];               /* must be 0                                                                        */
+} rt_vdenoise_params;
+#define RT_VDENOISE_DEFAULT_ITERATIONS      3
+#define RT_VDENOISE_DEFAULT_DEMODULATE      1
+#define RT_VDENOISE_DEFAULT_SIGMA_LUMINANCE 8.0f
+#define RT_VDENOISE_DEFAULT_SIGMA_NORMAL    0.25f
+#define RT_VDENOISE_DEFAULT_SIGMA_DEPTH     0.5f
+typedef struct rt_vdenoise_info {       /* 32 B */
+    int32_t iterations;                 /* of the last call                                                                 */
+    int32_t source;                     /* of the last call                                                                 */
+    int32_t width, height;
+    double  lastKernelMs;               /* HIP-event time of the last call's launches                                       */
+    double  totalKernelMs;
+} rt_vdenoise_info;
+int rt_denoise_variance(rt_ctx* ctx, const rt_vdenoise_params* params);
+/* var_0 of the last call: height*width floats, row 0 = bottom (rt_read_accum's row order) */
+int rt_read_variance(rt_ctx* ctx, float* var, size_t n_floats);
+int rt_copy_variance_to_device(rt_ctx* ctx, void* dst_device_ptr, size_t n_floats);
+int rt_get_vdenoise_info(rt_ctx* ctx, rt_vdenoise_info* out);
+
 /* ---- several GPUs of one node behind one handle ---------------------------------------------------------------------
  * The reference renders on one GPU; its path shards into independent pixels (seed = global pixel index + Frame * 719393,
  * RayTracing.shader:360-362; Accumulate.shader is per pixel), so the frame tiles across devices by rows.  An rt_multi owns one
@@ -862,10 +927,15 @@ int rt_multi_read_temporal        (rt_multi* m, float* rgba, size_t n_floats);
 int rt_multi_read_temporal_history(rt_multi* m, float* n, size_t n_floats);
 int rt_multi_read_temporal_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels);
 int rt_multi_denoise_temporal     (rt_multi* m, const rt_denoise_params* params);
+/* The variance-guided denoiser behind the handle: the gather of rt_multi_denoise (source == 0) or of rt_multi_denoise_temporal (source ==
+ * 1: C = the handle's T) and rt_denoise_variance's filter on the first device — bitwise the single-context result; the denoised plane is
+ * read with rt_multi_read_denoised*, var_0 with rt_multi_read_variance.                                                            */
+int rt_multi_denoise_variance     (rt_multi* m, const rt_vdenoise_params* params);
+int rt_multi_read_variance        (rt_multi* m, float* var, size_t n_floats);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_vdenoise_params" | "rt_vdenoise_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" */
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,12 @@ TEMPORAL_PARAMS = np.dtype([("maxHistory", "<i4"), ("depthTolerance", "<f4"), ("
 TEMPORAL_INFO = np.dtype([("calls", "<i4"), ("width", "<i4"), ("height", "<i4"), ("_reserved", "<i4"),
                           ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert TEMPORAL_PARAMS.itemsize == 32 and TEMPORAL_INFO.itemsize == 32
+# variance-guided denoiser (rt_denoise_variance): the parameters of a call and the state of the last one
+VDENOISE_PARAMS = np.dtype([("iterations", "<i4"), ("demodulate", "<i4"), ("source", "<i4"), ("sigmaLuminance", "<f4"), ("sigmaNormal", "<f4"),
+                            ("sigmaDepth", "<f4"), ("_reserved", "<i4", 2)])
+VDENOISE_INFO = np.dtype([("iterations", "<i4"), ("source", "<i4"), ("width", "<i4"), ("height", "<i4"),
+                          ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
+assert VDENOISE_PARAMS.itemsize == 32 and VDENOISE_INFO.itemsize == 32
 # radiance queries (rt_trace_radiance): the parameters of a call and the state of the last one
 RADIANCE_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex", "<u4"), ("_reserved", "<i4", 5)])
 RADIANCE_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("_reserved", "<i4"),
@@ -94,6 +100,8 @@ assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize =
 DENOISE_DEFAULTS = {"iterations": 5, "demodulate": 0, "sigmaColour": 16.0, "sigmaNormal": 1.0, "sigmaDepth": 0.5}
 # RT_TEMPORAL_DEFAULT_* of include/rt.h (what a null rt_temporal_params means)
 TEMPORAL_DEFAULTS = {"maxHistory": 32, "depthTolerance": 0.05, "normalTolerance": 0.5}
+# RT_VDENOISE_DEFAULT_* of include/rt.h (what a null rt_vdenoise_params means; source 0)
+VDENOISE_DEFAULTS = {"iterations": 3, "demodulate": 1, "source": 0, "sigmaLuminance": 8.0, "sigmaNormal": 0.25, "sigmaDepth": 0.5}
 
 RT_INTERSECT_FLAT_CHUNKS = 0
 RT_INTERSECT_BRUTE = 1
@@ -119,6 +127,8 @@ SYMBOLS = [
     "rt_read_temporal_display", "rt_get_temporal_info", "rt_denoise_temporal",
     "rt_multi_temporal", "rt_multi_reset_temporal", "rt_multi_read_temporal", "rt_multi_read_temporal_history", "rt_multi_read_temporal_display",
     "rt_multi_denoise_temporal",
+    "rt_denoise_variance", "rt_read_variance", "rt_copy_variance_to_device", "rt_get_vdenoise_info",
+    "rt_multi_denoise_variance", "rt_multi_read_variance",
     "rt_trace_radiance", "rt_trace_radiance_device", "rt_get_radiance_info", "rt_multi_trace_radiance",
     "rt_gather", "rt_gather_device", "rt_get_gather_info", "rt_multi_gather",
     "rt_visibility", "rt_visibility_device", "rt_get_visibility_info", "rt_multi_visibility",
@@ -230,6 +240,12 @@ def load_library() -> ctypes.CDLL:
     lib.rt_multi_read_temporal_history.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     lib.rt_multi_read_temporal_display.argtypes = [c_void_p, c_void_p, c_size_t]
     lib.rt_multi_denoise_temporal.argtypes = [c_void_p, c_void_p]
+    lib.rt_denoise_variance.argtypes = [c_void_p, c_void_p]
+    lib.rt_read_variance.argtypes = [c_void_p, POINTER(c_float), c_size_t]
+    lib.rt_copy_variance_to_device.argtypes = [c_void_p, c_void_p, c_size_t]
+    lib.rt_get_vdenoise_info.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_denoise_variance.argtypes = [c_void_p, c_void_p]
+    lib.rt_multi_read_variance.argtypes = [c_void_p, POINTER(c_float), c_size_t]
     for n in ("rt_trace_radiance", "rt_trace_radiance_device", "rt_multi_trace_radiance"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.rt_get_radiance_info.argtypes = [c_void_p, c_void_p]
@@ -251,6 +267,7 @@ def load_library() -> ctypes.CDLL:
                      ("rt_ray", RAY), ("rt_hit", HIT), ("rt_aov_info", AOV_INFO),
                      ("rt_denoise_params", DENOISE_PARAMS), ("rt_denoise_info", DENOISE_INFO),
                      ("rt_temporal_params", TEMPORAL_PARAMS), ("rt_temporal_info", TEMPORAL_INFO),
+                     ("rt_vdenoise_params", VDENOISE_PARAMS), ("rt_vdenoise_info", VDENOISE_INFO),
                      ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO),
                      ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO),
                      ("rt_visibility_params", VISIBILITY_PARAMS), ("rt_visibility_info", VISIBILITY_INFO)):
@@ -357,6 +374,21 @@ def _denoise_params(params: dict):
     for k, v in params.items():
         if k not in DENOISE_DEFAULTS:
             raise TypeError(f"denoise: unknown parameter {k!r} (one of {sorted(DENOISE_DEFAULTS)})")
+        p[k] = v
+    return p
+
+
+def _vdenoise_params(params: dict):
+    """None (the library's defaults) when no field is given; else a VDENOISE_PARAMS record: the defaults of include/rt.h with the given
+    fields (iterations, demodulate, source, sigmaLuminance, sigmaNormal, sigmaDepth) replaced"""
+    if not params:
+        return None
+    p = np.zeros((), VDENOISE_PARAMS)
+    for k, v in VDENOISE_DEFAULTS.items():
+        p[k] = v
+    for k, v in params.items():
+        if k not in VDENOISE_DEFAULTS:
+            raise TypeError(f"denoise_variance: unknown parameter {k!r} (one of {sorted(VDENOISE_DEFAULTS)})")
         p[k] = v
     return p
 
@@ -764,6 +796,29 @@ class Tracer:
         p = _denoise_params(params)
         self._check(self._lib.rt_denoise_temporal(self._ctx, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_denoise_temporal")
 
+    # -- variance-guided denoiser
+    def denoise_variance(self, **params):
+        """rt_denoise_variance: the variance-guided filter of resultTexture (source 0) or the temporal colour (source 1) into the denoised
+        plane; read with read_denoised*, var_0 with read_variance.  Keywords: iterations, demodulate, source, sigmaLuminance,
+        sigmaNormal, sigmaDepth; none = the library's defaults."""
+        p = _vdenoise_params(params)
+        self._check(self._lib.rt_denoise_variance(self._ctx, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_denoise_variance")
+
+    def read_variance(self) -> np.ndarray:
+        """var_0 of the last denoise_variance(), shape (H, W)"""
+        H, W = self._image_shape()
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.rt_read_variance(self._ctx, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_read_variance")
+        return out
+
+    def copy_variance_to_device(self, device_ptr: int, n_floats: int):
+        self._check(self._lib.rt_copy_variance_to_device(self._ctx, c_void_p(device_ptr), n_floats), "rt_copy_variance_to_device")
+
+    def vdenoise_info(self) -> dict:
+        s = np.zeros((), VDENOISE_INFO)
+        self._check(self._lib.rt_get_vdenoise_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_vdenoise_info")
+        return {k: s[k].item() for k in VDENOISE_INFO.names}
+
     def stats(self) -> dict:
         s = np.zeros((), STATS)
         self._check(self._lib.rt_get_stats(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_stats")
@@ -977,6 +1032,18 @@ class MultiTracer:
         p = _denoise_params(params)
         self._check(self._lib.rt_multi_denoise_temporal(self._m, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_multi_denoise_temporal")
         self._denoise_last = dict(DENOISE_DEFAULTS, **params)
+
+    # -- variance-guided denoiser
+    def denoise_variance(self, **params):
+        """rt_multi_denoise_variance: the gather of denoise() or denoise_temporal(), Tracer.denoise_variance's filter on the first device"""
+        p = _vdenoise_params(params)
+        self._check(self._lib.rt_multi_denoise_variance(self._m, p.ctypes.data_as(c_void_p) if p is not None else None), "rt_multi_denoise_variance")
+
+    def read_variance(self) -> np.ndarray:
+        H, W = self._shape
+        out = np.empty((H, W), np.float32)
+        self._check(self._lib.rt_multi_read_variance(self._m, out.ctypes.data_as(POINTER(c_float)), out.size), "rt_multi_read_variance")
+        return out
 
     def stats(self) -> dict:
         s = np.zeros((), STATS)

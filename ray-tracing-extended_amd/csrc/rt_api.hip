@@ -36,6 +36,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
+#include "rt_vdenoise.hpp"
 
 namespace {
 
@@ -74,6 +75,14 @@ struct DenoisePlanes {
     bool filled = false;            // `out` holds the result of a call
     rt_denoise_info info{};
     void release() { e[0].release(); e[1].release(); d.release(); out.release(); w = h = 0; filled = false; }
+};
+
+// what rt_denoise_variance keeps beside the denoiser's planes (csrc/rt_vdenoise.hpp): var_0 of the last call
+struct VariancePlane {
+    DevBuf<float> var;
+    int w = 0, h = 0;
+    bool filled = false;
+    rt_vdenoise_info info{};
 };
 
 // the state of temporal reprojection for one image size (rt_temporal, csrc/rt_temporal.hpp): T, N and the guide G' as ping-pong pairs
@@ -215,6 +224,7 @@ struct rt_ctx : ErrOwner {
     rt_aov_info aov_info{};
     DenoisePlanes dn;                   // rt_denoise
     TemporalPlanes tp;                  // rt_temporal
+    VariancePlane vd;                   // rt_denoise_variance
     hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
     rt_stats stats{};
 
@@ -1617,15 +1627,22 @@ const char* denoise_params(const rt_denoise_params* in, rt_denoise_params& P)
 
 // The filter: C (resultTexture), A and G (the feature planes), all W x H float4 on the current device -> D.out, on `stream`, timed by
 // ev0 / ev1 and waited for.  Shared by rt_denoise and rt_multi_denoise; P has passed denoise_params.
+// the denoiser's planes at W x H: created at first use and again when the size changes (both filter calls)
+hipError_t ensure_denoise_planes(DenoisePlanes& D, int W, int H)
+{
+    if (D.w == W && D.h == H && D.out.p) return hipSuccess;
+    hipError_t e;
+    for (DevBuf<float4>* b : { &D.e[0], &D.e[1], &D.d, &D.out }) if ((e = b->ensure((size_t)W * H)) != hipSuccess) return e;
+    D.w = W; D.h = H; D.filled = false; D.info.totalKernelMs = 0;
+    return hipSuccess;
+}
+
 hipError_t run_denoise(DenoisePlanes& D, const float4* C, const float4* A, const float4* G, int W, int H, const rt_denoise_params& P,
                        hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
 {
     const size_t px = (size_t)W * H;
     hipError_t e;
-    if (D.w != W || D.h != H || !D.out.p) {
-        for (DevBuf<float4>* b : { &D.e[0], &D.e[1], &D.d, &D.out }) if ((e = b->ensure(px)) != hipSuccess) return e;
-        D.w = W; D.h = H; D.filled = false; D.info.totalKernelMs = 0;
-    }
+    if ((e = ensure_denoise_planes(D, W, H)) != hipSuccess) return e;
     float ms = 0.f;
     if (px) {
         const float kn = 1.0f / (P.sigmaNormal * P.sigmaNormal), kz = 1.0f / (P.sigmaDepth * P.sigmaDepth);
@@ -1822,6 +1839,103 @@ int read_temporal(rt_ctx* c, bool history, void* dst, size_t n_floats, bool to_d
     return 0;
 }
 
+// ---- variance-guided denoiser (rt_denoise_variance, csrc/rt_vdenoise.hpp) -----------------------------------------------------------
+static_assert(sizeof(rt_vdenoise_params) == 32 && sizeof(rt_vdenoise_info) == 32, "variance-guided denoiser ABI");
+
+const char* vdenoise_params(const rt_vdenoise_params* in, rt_vdenoise_params& P)
+{
+    if (in) P = *in;
+    else {
+        P = rt_vdenoise_params{};
+        P.iterations = RT_VDENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_VDENOISE_DEFAULT_DEMODULATE;
+        P.sigmaLuminance = RT_VDENOISE_DEFAULT_SIGMA_LUMINANCE; P.sigmaNormal = RT_VDENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_VDENOISE_DEFAULT_SIGMA_DEPTH;
+    }
+    if (P.iterations < 1 || P.iterations > 6) return "iterations outside 1..6";
+    if (P.demodulate != 0 && P.demodulate != 1) return "demodulate is neither 0 nor 1";
+    if (P.source != 0 && P.source != 1) return "source is neither 0 nor 1";
+    for (float sg : { P.sigmaLuminance, P.sigmaNormal, P.sigmaDepth })
+        if (!std::isfinite(sg) || !(sg > 0.0f)) return "a sigma is not finite or not > 0";
+    if (P._reserved[0] != 0 || P._reserved[1] != 0) return "a reserved word is not 0";
+    return nullptr;
+}
+
+// The filter: C (resultTexture or T), A and G, all W x H float4 on the current device -> D.out and V.var, through D's work planes, on
+// `stream`, timed by ev0 / ev1 and waited for.  Shared by rt_denoise_variance and rt_multi_denoise_variance; P has passed vdenoise_params.
+hipError_t run_vdenoise(DenoisePlanes& D, VariancePlane& V, const float4* C, const float4* A, const float4* G, int W, int H,
+                        const rt_vdenoise_params& P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+{
+    const size_t px = (size_t)W * H;
+    hipError_t e;
+    if ((e = ensure_denoise_planes(D, W, H)) != hipSuccess) return e;
+    if (V.w != W || V.h != H || !V.var.p) {
+        if ((e = V.var.ensure(px)) != hipSuccess) return e;
+        V.w = W; V.h = H; V.filled = false; V.info.totalKernelMs = 0;
+    }
+    float ms = 0.f;
+    if (px) {
+        const float kn = 1.0f / (P.sigmaNormal * P.sigmaNormal), kz = 1.0f / (P.sigmaDepth * P.sigmaDepth);
+        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
+        hipLaunchKernelGGL(rtk::k_denoise_prep, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, C, A, D.e[0].p, D.d.p, px, P.demodulate);
+        const dim3 grid((W + rtk::kDenoiseTileW - 1) / rtk::kDenoiseTileW, (H + rtk::kDenoiseTileH - 1) / rtk::kDenoiseTileH);
+        rtk::VarEstimateArgs v{};
+        v.e0 = D.e[0].p; v.guide = G; v.e_out = D.e[1].p; v.var = V.var.p; v.W = W; v.H = H; v.kn = kn; v.kz = kz;
+        hipLaunchKernelGGL(rtk::k_variance_estimate, grid, dim3(256), 0, stream, v);
+        for (int i = 0; i < P.iterations; ++i) {            // (e_0, var_0) is in e[1]: pass i reads e[(i + 1) & 1]
+            const bool last = i == P.iterations - 1;
+            rtk::VarAtrousArgs a{};
+            a.e_in = D.e[(i + 1) & 1].p; a.guide = G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[i & 1].p;
+            a.W = W; a.H = H; a.step = 1 << i;
+            a.kn = kn; a.kz = kz; a.sl = P.sigmaLuminance;
+            if (last) hipLaunchKernelGGL(rtk::k_var_atrous<true>, grid, dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL(rtk::k_var_atrous<false>, grid, dim3(256), 0, stream, a);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
+    }
+    D.filled = true; V.filled = true;
+    V.info.iterations = P.iterations; V.info.source = P.source; V.info.width = W; V.info.height = H;
+    V.info.lastKernelMs = ms; V.info.totalKernelMs += ms;
+    return hipSuccess;
+}
+
+int denoise_variance(rt_ctx* c, const rt_vdenoise_params* in)
+{
+    RT_SETTLE(c);
+    if (!c->have_params) return fail(c, -2, "rt_denoise_variance: rt_set_params has not been called");
+    rt_vdenoise_params P;
+    if (const char* why = vdenoise_params(in, P)) return fail(c, -2, "rt_denoise_variance: %s", why);
+    StripLayout L;
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
+        return fail(c, -2, "rt_denoise_variance: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise_variance", L.rows, L.h);
+    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "rt_denoise_variance: no feature frame accumulated (call rt_render_aov first)");
+    if (P.source == 1) {
+        if (!c->tp.filled) return fail(c, -2, "rt_denoise_variance: source 1, and rt_temporal has not been called");
+        if (c->tp.w != L.w || c->tp.h != L.h) return fail(c, -2, "rt_denoise_variance: the temporal image is %d x %d, the context's image %d x %d", c->tp.w, c->tp.h, L.w, L.h);
+    }
+    RT_HIP(c, hipSetDevice(c->device));
+    if (P.source == 0) { int r = ensure_targets(c); if (r) return r; }         // (as in rt_denoise)
+    RT_HIP(c, run_vdenoise(c->dn, c->vd, P.source ? c->tp.t[c->tp.cur].p : c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p,
+                           L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
+    return 0;
+}
+
+int read_variance(rt_ctx* c, void* dst, size_t n_floats, bool to_device)
+{
+    RT_SETTLE(c);
+    if (!c->vd.filled) return fail(c, -2, "rt_denoise_variance has not been called");
+    if (!dst) return fail(c, -2, "null destination");
+    const size_t px = (size_t)c->vd.w * c->vd.h;
+    if (n_floats != px) return fail(c, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, hipMemcpyAsync(dst, c->vd.var.p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1847,6 +1961,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_denoise_info")) return (int)sizeof(rt_denoise_info);
     if (!std::strcmp(name, "rt_temporal_params")) return (int)sizeof(rt_temporal_params);
     if (!std::strcmp(name, "rt_temporal_info")) return (int)sizeof(rt_temporal_info);
+    if (!std::strcmp(name, "rt_vdenoise_params")) return (int)sizeof(rt_vdenoise_params);
+    if (!std::strcmp(name, "rt_vdenoise_info")) return (int)sizeof(rt_vdenoise_info);
     if (!std::strcmp(name, "rt_radiance_params")) return (int)sizeof(rt_radiance_params);
     if (!std::strcmp(name, "rt_radiance_info")) return (int)sizeof(rt_radiance_info);
     if (!std::strcmp(name, "rt_gather_params")) return (int)sizeof(rt_gather_params);
@@ -2306,6 +2422,18 @@ int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out)
     return 0;
 }
 
+int rt_denoise_variance(rt_ctx* c, const rt_vdenoise_params* params) { return c ? denoise_variance(c, params) : -1; }
+int rt_read_variance(rt_ctx* c, float* var, size_t n) { return c ? read_variance(c, var, n, false) : -1; }
+int rt_copy_variance_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_variance(c, dst, n, true) : -1; }
+int rt_get_vdenoise_info(rt_ctx* c, rt_vdenoise_info* out)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    if (!out) return fail(c, -2, "null info");
+    *out = c->vd.info;
+    return 0;
+}
+
 int rt_temporal(rt_ctx* c, const rt_temporal_params* params) { return c ? temporal(c, params) : -1; }
 int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* params) { return c ? denoise_temporal(c, params) : -1; }
 int rt_reset_temporal(rt_ctx* c)
@@ -2365,6 +2493,7 @@ struct rt_multi : ErrOwner {
     DevBuf<float4> d_aov_image;                 // ... the assembled feature plane of the last rt_multi_read_aov
     DevBuf<float4> d_dn_albedo, d_dn_guide;     // ... both assembled feature planes of the last rt_multi_denoise
     DenoisePlanes dn;                           // ... its work planes and the denoised plane
+    VariancePlane vd;                           // ... var_0 of the last rt_multi_denoise_variance
     TemporalPlanes tp;                          // ... the state of rt_multi_temporal
     std::vector<hipEvent_t> ev_strip;           // per context: its strip has arrived on the first device (recorded on the SOURCE context's stream)
     int max_rows = 0;
@@ -2781,6 +2910,38 @@ int rt_multi_denoise_temporal(rt_multi* m, const rt_denoise_params* params)
     rt_ctx* root = m->ctx[0];
     RT_HIP(m, hipSetDevice(root->device));
     RT_HIP(m, run_denoise(m->dn, m->tp.t[m->tp.cur].p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
+    return 0;
+}
+
+// The variance-guided denoiser behind the handle: the same gathers, rt_denoise_variance's filter on the first device.
+int rt_multi_denoise_variance(rt_multi* m, const rt_vdenoise_params* params)
+{
+    if (!m) return -1;
+    if (!m->have_params) return fail(m, -2, "rt_multi_denoise_variance: rt_multi_set_params has not been called");
+    rt_vdenoise_params P;
+    if (const char* why = vdenoise_params(params, P)) return fail(m, -2, "rt_multi_denoise_variance: %s", why);
+    if (P.source == 1) {
+        if (!m->tp.filled) return fail(m, -2, "rt_multi_denoise_variance: source 1, and rt_multi_temporal has not been called");
+        if (m->tp.w != m->width || m->tp.h != m->height) return fail(m, -2, "rt_multi_denoise_variance: the temporal image is %d x %d, the handle's image %d x %d", m->tp.w, m->tp.h, m->width, m->height);
+    }
+    { int r = multi_gather_inputs(m, "rt_multi_denoise_variance", P.source == 0); if (r) return r; }
+    rt_ctx* root = m->ctx[0];
+    RT_HIP(m, hipSetDevice(root->device));
+    RT_HIP(m, run_vdenoise(m->dn, m->vd, P.source ? m->tp.t[m->tp.cur].p : m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P,
+                           root->stream, root->ev_dn0, root->ev_dn1));
+    return 0;
+}
+
+int rt_multi_read_variance(rt_multi* m, float* var, size_t n_floats)
+{
+    if (!m) return -1;
+    if (!m->vd.filled) return fail(m, -2, "rt_multi_denoise_variance has not been called");
+    if (!var) return fail(m, -2, "null destination");
+    const size_t px = (size_t)m->vd.w * m->vd.h;
+    if (n_floats != px) return fail(m, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
+    if (!n_floats) return 0;
+    RT_HIP(m, hipSetDevice(m->ctx[0]->device));
+    RT_HIP(m, hipMemcpy(var, m->vd.var.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -467,6 +467,14 @@ class RayTracingManager:
         self.backend.denoise(**params)
         return self.backend.read_denoised()
 
+    def DenoiseVariance(self, **params):
+        """Beyond the reference: the variance-guided filter (rt_denoise_variance) of the accumulated image, or of the temporal colour with
+        source=1, guided by the planes RenderFeatures accumulated: a per-pixel luminance variance estimated from the image scales the
+        colour edge-stop.  Keywords as Tracer.denoise_variance (none = the library's defaults).  Returns (the denoised image (H, W, 4),
+        the estimated variance (H, W)); the image, the planes and numRenderedFrames are left alone."""
+        self.backend.denoise_variance(**params)
+        return self.backend.read_denoised(), self.backend.read_variance()
+
     def Temporal(self, **params):
         """Beyond the reference: the step in front of Denoise for a moving camera (rt_temporal).  After a frame rendered from a fresh
         accumulation at the current pose and RenderFeatures at that pose, the previous result is reprojected into the new view and the

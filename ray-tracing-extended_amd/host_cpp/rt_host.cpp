@@ -447,6 +447,32 @@ void RayTracingManager::Denoise(rt_multi* m, const rt_denoise_params* params, st
     }
 }
 
+void RayTracingManager::DenoiseVariance(rt_ctx* ctx, const rt_vdenoise_params* params, std::vector<float>* denoised, std::vector<float>* variance)
+{
+    check(ctx, rt_denoise_variance(ctx, params), "rt_denoise_variance");
+    if (denoised) {
+        denoised->resize((size_t)width * height * 4);
+        check(ctx, rt_read_denoised(ctx, denoised->data(), denoised->size()), "rt_read_denoised");
+    }
+    if (variance) {
+        variance->resize((size_t)width * height);
+        check(ctx, rt_read_variance(ctx, variance->data(), variance->size()), "rt_read_variance");
+    }
+}
+
+void RayTracingManager::DenoiseVariance(rt_multi* m, const rt_vdenoise_params* params, std::vector<float>* denoised, std::vector<float>* variance)
+{
+    mcheck(m, rt_multi_denoise_variance(m, params), "rt_multi_denoise_variance");
+    if (denoised) {
+        denoised->resize((size_t)width * height * 4);
+        mcheck(m, rt_multi_read_denoised(m, denoised->data(), denoised->size()), "rt_multi_read_denoised");
+    }
+    if (variance) {
+        variance->resize((size_t)width * height);
+        mcheck(m, rt_multi_read_variance(m, variance->data(), variance->size()), "rt_multi_read_variance");
+    }
+}
+
 void RayTracingManager::Temporal(rt_ctx* ctx, const rt_temporal_params* params, std::vector<float>* temporal)
 {
     check(ctx, rt_temporal(ctx, params), "rt_temporal");

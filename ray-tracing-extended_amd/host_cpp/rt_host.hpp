@@ -139,6 +139,10 @@ public:
     // the planes RenderFeatures accumulated; the plane (width * height * 4 floats) is read back when asked for.
     void Denoise(rt_ctx* ctx, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
     void Denoise(rt_multi* multi, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
+    // Beyond the reference: the variance-guided filter (rt_denoise_variance; params null = the library's defaults, source 0) into the same
+    // denoised plane; `denoised` (width*height*4) and `variance` (var_0, width*height) are filled if asked for.
+    void DenoiseVariance(rt_ctx* ctx, const rt_vdenoise_params* params = nullptr, std::vector<float>* denoised = nullptr, std::vector<float>* variance = nullptr);
+    void DenoiseVariance(rt_multi* multi, const rt_vdenoise_params* params = nullptr, std::vector<float>* denoised = nullptr, std::vector<float>* variance = nullptr);
     // Beyond the reference: the step in front of Denoise for a moving camera (rt_temporal; params null = the library's defaults): the
     // previous temporal colour reprojected into the current camera's view, the accumulated image blended in.  Call it after a frame
     // rendered from a fresh accumulation and RenderFeatures at the new pose; the colour (width * height * 4 floats) is read back when

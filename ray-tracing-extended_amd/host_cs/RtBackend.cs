@@ -304,6 +304,25 @@ namespace RtMi355x
         }
         public void Denoise() { Denoise(RtDenoiseParams.Defaults); }
 
+        /// The variance-guided filter (rt_denoise_variance) of the accumulated image (p.source 0) or the temporal colour (p.source 1) into
+        /// the denoised plane; read the result with ReadDenoised / ReadDenoisedDisplay, the estimated variance with ReadVariance.
+        public void DenoiseVariance(RtVDenoiseParams p)
+        {
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_denoise_variance(multi, ref p), "rt_multi_denoise_variance");
+            else RtNative.Check(ctx, RtNative.rt_denoise_variance(ctx, ref p), "rt_denoise_variance");
+        }
+        public void DenoiseVariance() { DenoiseVariance(RtVDenoiseParams.Defaults); }
+
+        /// var_0 of the last DenoiseVariance, width * height floats, row 0 = bottom.
+        public float[] ReadVariance()
+        {
+            var v = new float[(long)width * height];
+            var n = (UIntPtr)(ulong)v.LongLength;
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_read_variance(multi, v, n), "rt_multi_read_variance");
+            else RtNative.Check(ctx, RtNative.rt_read_variance(ctx, v, n), "rt_read_variance");
+            return v;
+        }
+
         /// The denoised plane, width * height * 4 floats, row 0 = bottom.
         public float[] ReadDenoised()
         {

@@ -238,6 +238,13 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_multi_denoise(IntPtr multi, ref RtDenoiseParams p);
         [DllImport(Lib)] public static extern int rt_multi_read_denoised(IntPtr multi, [Out] float[] rgba, UIntPtr nFloats);
         [DllImport(Lib)] public static extern int rt_multi_read_denoised_display(IntPtr multi, [Out] uint[] rgba8, UIntPtr nPixels);
+        // variance-guided denoiser (RtVDenoiseParams, RtVDenoiseInfo: RtDenoise.cs); its image is read with rt_read_denoised*
+        [DllImport(Lib)] public static extern int rt_denoise_variance(IntPtr ctx, ref RtVDenoiseParams p);
+        [DllImport(Lib)] public static extern int rt_read_variance(IntPtr ctx, [Out] float[] var, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_copy_variance_to_device(IntPtr ctx, IntPtr dstDevicePtr, UIntPtr nFloats);
+        [DllImport(Lib)] public static extern int rt_get_vdenoise_info(IntPtr ctx, out RtVDenoiseInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_denoise_variance(IntPtr multi, ref RtVDenoiseParams p);
+        [DllImport(Lib)] public static extern int rt_multi_read_variance(IntPtr multi, [Out] float[] var, UIntPtr nFloats);
         // temporal reprojection (RtTemporalParams, RtTemporalInfo: RtTemporal.cs; RtTemporalParams.Defaults = what a null pointer means in C)
         [DllImport(Lib)] public static extern int rt_temporal(IntPtr ctx, ref RtTemporalParams p);
         [DllImport(Lib)] public static extern int rt_reset_temporal(IntPtr ctx);
@@ -314,6 +321,8 @@ namespace RtMi355x
             Same("rt_aov_info", Marshal.SizeOf<RtAovInfo>());
             Same("rt_denoise_params", Marshal.SizeOf<RtDenoiseParams>());
             Same("rt_denoise_info", Marshal.SizeOf<RtDenoiseInfo>());
+            Same("rt_vdenoise_params", Marshal.SizeOf<RtVDenoiseParams>());
+            Same("rt_vdenoise_info", Marshal.SizeOf<RtVDenoiseInfo>());
             Same("rt_radiance_params", Marshal.SizeOf<RtRadianceParams>());
             Same("rt_radiance_info", Marshal.SizeOf<RtRadianceInfo>());
             Same("rt_gather_params", Marshal.SizeOf<RtGatherParams>());

@@ -29,9 +29,10 @@ def main(argv=None):
     ap.add_argument("--aov", metavar="PREFIX", help="also accumulate the feature buffers over the same frames (rt_render_aov) and write PREFIX.albedo "
                     "(albedo, alpha = coverage), PREFIX.normal (mean shading normal, alpha = coverage) and PREFIX.depth (mean depth in every "
                     "channel, alpha = coverage), as .exr, or as .pfm when --pfm is given and --exr is not")
-    ap.add_argument("--denoise", action="store_true", help="after the frames (and the feature frames: accumulated over the same frames even without --aov) "
-                    "run rt_denoise with the library's defaults and write the denoised image beside the noisy one: NAME.denoised.EXT for "
-                    "every --png / --exr / --pfm given")
+    ap.add_argument("--denoise", nargs="?", const="atrous", choices=("atrous", "variance"), help="after the frames (and the feature frames: accumulated "
+                    "over the same frames even without --aov) run rt_denoise (--denoise or --denoise atrous) or the variance-guided "
+                    "rt_denoise_variance (--denoise variance) with the library's defaults and write the denoised image beside the noisy one: "
+                    "NAME.denoised.EXT for every --png / --exr / --pfm given")
     ap.add_argument("--temporal", type=int, default=0, metavar="POSES", help="after the image: a camera path of POSES poses, each --temporal-step "
                     "world units further along the camera's right axis; at every pose a fresh accumulation of --temporal-frames frames, fresh "
                     "feature frames, rt_temporal and rt_denoise_temporal with the library's defaults.  Writes, for the last pose, "
@@ -80,8 +81,12 @@ def main(argv=None):
     if args.denoise:
         if not args.aov:
             mgr.RenderFeatures(frames=args.frames, firstFrame=0)
-        denoised = mgr.Denoise()
-        info = tracer.denoise_info()
+        if args.denoise == "variance":
+            denoised, _ = mgr.DenoiseVariance()
+            info = tracer.vdenoise_info()
+        else:
+            denoised = mgr.Denoise()
+            info = tracer.denoise_info()
 
         def beside(path):
             stem, ext = os.path.splitext(path)
