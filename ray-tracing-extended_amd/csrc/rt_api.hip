@@ -68,33 +68,53 @@ template <class T> struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; used = 0; }
 };
 
-// the denoiser's planes for one image size (rt_denoise, csrc/rt_denoise.hpp): e_i ping and pong, (d.rgb, C.a), the denoised plane
-struct DenoisePlanes {
-    DevBuf<float4> e[2], d, out;
+// What the image filters keep between calls (DESIGN.md "The image filters' one host path"): planes made for one image size, and whether
+// they hold the result of a call
+struct FilterPlanes {
     int w = 0, h = 0;
-    bool filled = false;            // `out` holds the result of a call
+    bool filled = false;
+    size_t pixels() const { return (size_t)w * h; }
+};
+
+// THE rule of those planes: `bufs` at W x H are kept while S has that size; else they are re-created, S holds no result and S.new_size()
+// resets what S counted over calls
+template <class Planes, class... Bufs> hipError_t planes_at(Planes& S, int W, int H, Bufs&... bufs)
+{
+    if (S.w == W && S.h == H && (... && bufs.p)) return hipSuccess;
+    hipError_t e = hipSuccess;
+    (void)(... && ((e = bufs.ensure((size_t)W * H)) == hipSuccess));
+    if (e != hipSuccess) return e;
+    S.w = W; S.h = H; S.filled = false; S.new_size();
+    return hipSuccess;
+}
+
+// the denoiser's planes (rt_denoise, csrc/rt_denoise.hpp): e_i ping and pong, (d.rgb, C.a), the denoised plane `out` (filled: of a call)
+struct DenoisePlanes : FilterPlanes {
+    DevBuf<float4> e[2], d, out;
     rt_denoise_info info{};
-    void release() { e[0].release(); e[1].release(); d.release(); out.release(); w = h = 0; filled = false; }
+    hipError_t at(int W, int H) { return planes_at(*this, W, H, e[0], e[1], d, out); }
+    void new_size() { info.totalKernelMs = 0; }
 };
 
 // what rt_denoise_variance keeps beside the denoiser's planes (csrc/rt_vdenoise.hpp): var_0 of the last call
-struct VariancePlane {
+struct VariancePlane : FilterPlanes {
     DevBuf<float> var;
-    int w = 0, h = 0;
-    bool filled = false;
     rt_vdenoise_info info{};
+    hipError_t at(int W, int H) { return planes_at(*this, W, H, var); }
+    void new_size() { info.totalKernelMs = 0; }
 };
 
-// the state of temporal reprojection for one image size (rt_temporal, csrc/rt_temporal.hpp): T, N and the guide G' as ping-pong pairs
-// (`cur` is the pair the last call wrote) and the camera of the last call
-struct TemporalPlanes {
+// the state of temporal reprojection (rt_temporal, csrc/rt_temporal.hpp): T, N and the guide G' as ping-pong pairs (`cur` is the pair the
+// last call wrote; filled: t[cur], n[cur] and g[cur] hold the result of a call) and that call's camera
+struct TemporalPlanes : FilterPlanes {
     DevBuf<float4> t[2], g[2];
     DevBuf<float> n[2];
-    int w = 0, h = 0, cur = 0;
-    bool filled = false;            // t[cur], n[cur] and g[cur] hold the result of a call; `cam` is that call's camera
+    int cur = 0;
     rt_params cam{};                // (its camera fields)
     rt_temporal_info info{};
-    void release() { for (int i = 0; i < 2; ++i) { t[i].release(); g[i].release(); n[i].release(); } w = h = 0; filled = false; info = rt_temporal_info{}; }
+    hipError_t at(int W, int H) { return planes_at(*this, W, H, t[0], t[1], g[0], g[1], n[0], n[1]); }
+    void new_size() { info = rt_temporal_info{}; }
+    void reset() { filled = false; info.calls = 0; info.lastKernelMs = 0; info.totalKernelMs = 0; }      // rt_reset_temporal: the history is dropped
 };
 
 // The rows of the image a context renders (rt_set_rows / rt_set_bands) and so the layout of the planes that hold them: local row ly is
@@ -1164,15 +1184,16 @@ int launch_frames(rt_ctx* c, int first_frame, int n_frames, Variant var, const r
     return 0;
 }
 
-// The end of every read of a plane: n_floats must be the plane's expect_floats (`shape`: what the message calls its rows), then one copy
-// on the context's stream, waited for.  What a null destination means is the entry point's own rule, checked before.
-int copy_plane(rt_ctx* c, const float4* src, size_t expect_floats, const char* shape, void* dst, size_t n_floats, bool to_device)
+// The end of every read of a plane: n_floats must be the plane's expect_floats (`shape`: what the message calls that product), then one
+// copy on the stream of `on` — the context that holds the plane: o itself, or the first context of the handle o — waited for.  What a
+// null destination means is the entry point's own rule, checked before.
+int copy_plane(ErrOwner* o, const rt_ctx* on, const void* src, size_t expect_floats, const char* shape, void* dst, size_t n_floats, bool to_device)
 {
-    if (n_floats != expect_floats) return fail(c, -2, "expected %zu floats (%s*width*4), got %zu", expect_floats, shape, n_floats);
+    if (n_floats != expect_floats) return fail(o, -2, "expected %zu floats (%s), got %zu", expect_floats, shape, n_floats);
     if (!n_floats) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(dst, src, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
+    RT_HIP(o, hipSetDevice(on->device));
+    RT_HIP(o, hipMemcpyAsync(dst, src, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on->stream));
+    RT_HIP(o, hipStreamSynchronize(on->stream));
     return 0;
 }
 
@@ -1181,7 +1202,7 @@ int read_target(rt_ctx* c, bool accum, float* dst, size_t n_floats, bool to_devi
     if (!c) return -1;
     if (!dst && n_floats) return fail(c, -2, "null destination");
     if (c->have_params) { int r = ensure_targets(c); if (r) return r; }
-    return copy_plane(c, accum ? c->d_accum.p : c->d_frame.p, c->target.pixels() * 4, "rows", dst, n_floats, to_device);
+    return copy_plane(c, c, accum ? c->d_accum.p : c->d_frame.p, c->target.pixels() * 4, "rows*width*4", dst, n_floats, to_device);
 }
 
 // Frames first .. first + n - 1 with the uniforms params[f] (all with the settings of c->params).  One camera for all: today's path
@@ -1603,97 +1624,102 @@ int read_aov(rt_ctx* c, int which, void* dst, size_t n_floats, bool to_device)
     if (!dst) return fail(c, -2, "null destination");
     RT_HIP(c, hipSetDevice(c->device));
     { int r = ensure_aov(c); if (r) return r; }
-    return copy_plane(c, c->d_aov[which].p, c->aov.pixels() * 4, "rows", dst, n_floats, to_device);
+    return copy_plane(c, c, c->d_aov[which].p, c->aov.pixels() * 4, "rows*width*4", dst, n_floats, to_device);
 }
 
-// ---- denoiser (rt_denoise, csrc/rt_denoise.hpp) -----------------------------------------------------------------------------------
-static_assert(sizeof(rt_denoise_params) == 32 && sizeof(rt_denoise_info) == 32, "denoiser ABI");
+// ---- the image filters' one host path -----------------------------------------------------------------------------------
+// rt_denoise, rt_temporal, rt_denoise_temporal, rt_denoise_variance and their rt_multi_ forms are each: begin_filter, the filter's
+// validator, filter_inputs, the filter's run_*.  A context and a handle differ in the two overloads of begin_filter and filter_inputs (and
+// in the order of their checks); everything else below is written once.
 
-// the parameters of a call: the caller's, or the defaults; nullptr (and a message) when they are out of range
-const char* denoise_params(const rt_denoise_params* in, rt_denoise_params& P)
-{
-    if (in) P = *in;
-    else {
-        P = rt_denoise_params{};
-        P.iterations = RT_DENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_DENOISE_DEFAULT_DEMODULATE;
-        P.sigmaColour = RT_DENOISE_DEFAULT_SIGMA_COLOUR; P.sigmaNormal = RT_DENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_DENOISE_DEFAULT_SIGMA_DEPTH;
-    }
-    if (P.iterations < 1 || P.iterations > 6) return "iterations outside 1..6";
-    if (P.demodulate != 0 && P.demodulate != 1) return "demodulate is neither 0 nor 1";
-    for (float sg : { P.sigmaColour, P.sigmaNormal, P.sigmaDepth })
-        if (!std::isfinite(sg) || !(sg > 0.0f)) return "a sigma is not finite or not > 0";
-    return nullptr;
-}
+// What a call is called and what its refusals say: `use_instead` is the call a context that holds rows of the image is sent to, `lead`
+// what goes before "<rt_temporal> has not been called" when the temporal colour is the source and missing
+struct FilterCall { const char* what; const char* use_instead; const char* lead = ""; };
 
-// The filter: C (resultTexture), A and G (the feature planes), all W x H float4 on the current device -> D.out, on `stream`, timed by
-// ev0 / ev1 and waited for.  Shared by rt_denoise and rt_multi_denoise; P has passed denoise_params.
-// the denoiser's planes at W x H: created at first use and again when the size changes (both filter calls)
-hipError_t ensure_denoise_planes(DenoisePlanes& D, int W, int H)
-{
-    if (D.w == W && D.h == H && D.out.p) return hipSuccess;
-    hipError_t e;
-    for (DevBuf<float4>* b : { &D.e[0], &D.e[1], &D.d, &D.out }) if ((e = b->ensure((size_t)W * H)) != hipSuccess) return e;
-    D.w = W; D.h = H; D.filled = false; D.info.totalKernelMs = 0;
-    return hipSuccess;
-}
+// What a filter runs on: source colour C, albedo A and guide G, all W x H float4 on the current device, the camera `cam` of that image,
+// the stream of the launches and the two events that time them
+struct FilterInputs {
+    const float4* C = nullptr; const float4* A = nullptr; const float4* G = nullptr;
+    int W = 0, H = 0;
+    const rt_params* cam = nullptr;
+    hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    size_t pixels() const { return (size_t)W * H; }
+};
 
-hipError_t run_denoise(DenoisePlanes& D, const float4* C, const float4* A, const float4* G, int W, int H, const rt_denoise_params& P,
-                       hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+// The temporal colour as a filter's source: T exists and has the image's size.  `temporal` is the call that makes T and `whose` the
+// owner of the image in the messages ("context's" / "handle's")
+int temporal_source(ErrOwner* o, const TemporalPlanes& T, int W, int H, const FilterCall& k, const char* temporal, const char* whose)
 {
-    const size_t px = (size_t)W * H;
-    hipError_t e;
-    if ((e = ensure_denoise_planes(D, W, H)) != hipSuccess) return e;
-    float ms = 0.f;
-    if (px) {
-        const float kn = 1.0f / (P.sigmaNormal * P.sigmaNormal), kz = 1.0f / (P.sigmaDepth * P.sigmaDepth);
-        const float kc0 = 1.0f / (P.sigmaColour * P.sigmaColour);
-        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(rtk::k_denoise_prep, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, C, A, D.e[0].p, D.d.p, px, P.demodulate);
-        const dim3 grid((W + rtk::kDenoiseTileW - 1) / rtk::kDenoiseTileW, (H + rtk::kDenoiseTileH - 1) / rtk::kDenoiseTileH);
-        for (int i = 0; i < P.iterations; ++i) {
-            const bool last = i == P.iterations - 1;
-            rtk::AtrousArgs a{};
-            a.e_in = D.e[i & 1].p; a.guide = G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[(i + 1) & 1].p;
-            a.W = W; a.H = H; a.step = 1 << i;
-            a.kn = kn; a.kz = kz; a.kc = kc0 * (float)(1 << (2 * i));
-            if (last) hipLaunchKernelGGL(rtk::k_atrous<true>, grid, dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL(rtk::k_atrous<false>, grid, dim3(256), 0, stream, a);
-        }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
-    }
-    D.filled = true;
-    D.info.iterations = P.iterations; D.info.demodulate = P.demodulate; D.info.width = W; D.info.height = H;
-    D.info.lastKernelMs = ms; D.info.totalKernelMs += ms;
-    return hipSuccess;
-}
-
-int denoise(rt_ctx* c, const rt_denoise_params* in)
-{
-    RT_SETTLE(c);
-    if (!c->have_params) return fail(c, -2, "rt_denoise: rt_set_params has not been called");
-    rt_denoise_params P;
-    if (const char* why = denoise_params(in, P)) return fail(c, -2, "rt_denoise: %s", why);
-    StripLayout L;
-    { int r = strip_layout(c, L); if (r) return r; }
-    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
-        return fail(c, -2, "rt_denoise: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise", L.rows, L.h);
-    // the feature planes of THIS image layout, with at least one frame in them (planes of another layout would be re-created, zeroed)
-    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "rt_denoise: no feature frame accumulated (call rt_render_aov first)");
-    RT_HIP(c, hipSetDevice(c->device));
-    { int r = ensure_targets(c); if (r) return r; }             // (a no-op unless the image was never created at this size: then it is a cleared image)
-    RT_HIP(c, run_denoise(c->dn, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
+    if (!T.filled) return fail(o, -2, "%s: %s%s has not been called", k.what, k.lead, temporal);
+    if (T.w != W || T.h != H) return fail(o, -2, "%s: the temporal image is %d x %d, the %s image %d x %d", k.what, T.w, T.h, whose, W, H);
     return 0;
 }
 
-int read_denoised(rt_ctx* c, void* dst, size_t n_floats, bool to_device)
+// A context may run the call: settled, with params ...
+int begin_filter(rt_ctx* c, const char* what)
 {
     RT_SETTLE(c);
-    if (!c->dn.filled) return fail(c, -2, "rt_denoise has not been called");
-    if (!dst) return fail(c, -2, "null destination");
-    return copy_plane(c, c->dn.out.p, (size_t)c->dn.w * c->dn.h * 4, "height", dst, n_floats, to_device);
+    return c->have_params ? 0 : fail(c, -2, "%s: rt_set_params has not been called", what);
+}
+// ... and it holds the whole image and current feature planes with a frame in them (planes of another layout would be re-created,
+// zeroed); then T, if that is the source (from_T) and not the image; then the inputs on its device (the image is a cleared one if it was
+// never created at this size)
+int filter_inputs(rt_ctx* c, const FilterCall& k, bool from_T, FilterInputs& I)
+{
+    StripLayout L;
+    { int r = strip_layout(c, L); if (r) return r; }
+    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
+        return fail(c, -2, "%s: the context holds rows of the image, not the whole image (%d of %d rows); use %s", k.what, L.rows, L.h, k.use_instead);
+    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "%s: no feature frame accumulated (call rt_render_aov first)", k.what);
+    if (from_T) { int r = temporal_source(c, c->tp, L.w, L.h, k, "rt_temporal", "context's"); if (r) return r; }
+    RT_HIP(c, hipSetDevice(c->device));
+    if (!from_T) { int r = ensure_targets(c); if (r) return r; }
+    I.C = from_T ? c->tp.t[c->tp.cur].p : c->d_accum.p; I.A = c->d_aov[RT_AOV_ALBEDO].p; I.G = c->d_aov[RT_AOV_NORMAL_DEPTH].p;
+    I.W = L.w; I.H = L.h; I.cam = &c->params;
+    I.stream = c->stream; I.ev0 = c->ev_dn0; I.ev1 = c->ev_dn1;
+    return 0;
+}
+// (the handle's two are defined with the handle, below)
+int begin_filter(rt_multi* m, const char* what);
+int filter_inputs(rt_multi* m, const FilterCall& k, bool from_T, FilterInputs& I);
+
+// `launches` on `stream` between ev0 and ev1, waited for -> their time
+template <class Fn> hipError_t timed(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, float& ms, Fn launches)
+{
+    hipError_t e;
+    if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
+    launches();
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    return hipEventElapsedTime(&ms, ev0, ev1);
+}
+
+// The pieces the validators are made of.  A validator gives P the caller's parameters or the defaults, and returns nullptr, or why they
+// are out of range
+bool is_flag(int v) { return v == 0 || v == 1; }
+bool finite_and_positive(std::initializer_list<float> values)
+{
+    for (float v : values) if (!std::isfinite(v) || !(v > 0.0f)) return false;
+    return true;
+}
+const char* atrous_params(int iterations, int demodulate)           // what both A-trous filters take
+{
+    if (iterations < 1 || iterations > 6) return "iterations outside 1..6";
+    return is_flag(demodulate) ? nullptr : "demodulate is neither 0 nor 1";
+}
+
+// The readers of a filter's plane S (`call`: the call that fills it), for the owner o whose plane it is, on the context `on` that holds
+// it (copy_plane).  `per` floats per pixel: 4 or 1
+int readable(ErrOwner* o, const FilterPlanes& S, const char* call, const void* dst)
+{
+    if (!S.filled) return fail(o, -2, "%s has not been called", call);
+    return dst ? 0 : fail(o, -2, "null destination");
+}
+int read_filter_plane(ErrOwner* o, const rt_ctx* on, const FilterPlanes& S, const char* call, const void* src, int per, void* dst, size_t n_floats, bool to_device)
+{
+    { int r = readable(o, S, call, dst); if (r) return r; }
+    return copy_plane(o, on, src, S.pixels() * per, per == 4 ? "height*width*4" : "height*width", dst, n_floats, to_device);
 }
 
 // The display step: linear -> sRGB8 of a plane of n_pixels > 0 on c's device (already current), through `display` there, on c's stream;
@@ -1712,50 +1738,144 @@ hipError_t display_plane(rt_ctx* c, const float4* plane, DevBuf<uint32_t>& displ
     return kernel_ms ? hipEventElapsedTime(kernel_ms, c->evg0, c->evg1) : hipSuccess;
 }
 
+// The end of every read of a whole-image plane as sRGB8: n_pixels must be its `pixels`, then the display step on `on` (as copy_plane).
+// A plane that is still null is the handle's image before the first render
+int read_srgb8(ErrOwner* o, rt_ctx* on, const float4* plane, size_t pixels, DevBuf<uint32_t>& display, uint32_t* rgba8, size_t n_pixels)
+{
+    if (n_pixels != pixels) return fail(o, -2, "expected %zu pixels (height*width), got %zu", pixels, n_pixels);
+    if (!n_pixels) return 0;
+    if (!plane) return fail(o, -2, "nothing rendered yet");
+    RT_HIP(o, hipSetDevice(on->device));
+    RT_HIP(o, display_plane(on, plane, display, rgba8, n_pixels));
+    return 0;
+}
+int read_filter_display(ErrOwner* o, rt_ctx* on, const FilterPlanes& S, const char* call, const float4* plane, DevBuf<uint32_t>& display, uint32_t* rgba8, size_t n_pixels)
+{
+    { int r = readable(o, S, call, rgba8); if (r) return r; }
+    return read_srgb8(o, on, plane, S.pixels(), display, rgba8, n_pixels);
+}
+
+// a context's reads of its own filter planes (the queue settled first)
+enum class OwnPlane { Denoised, Temporal, History, Variance };
+int read_own(rt_ctx* c, OwnPlane which, void* dst, size_t n_floats, bool to_device)
+{
+    if (!c) return -1;
+    RT_SETTLE(c);
+    switch (which) {
+    case OwnPlane::Denoised: return read_filter_plane(c, c, c->dn, "rt_denoise", c->dn.out.p, 4, dst, n_floats, to_device);
+    case OwnPlane::Temporal: return read_filter_plane(c, c, c->tp, "rt_temporal", c->tp.t[c->tp.cur].p, 4, dst, n_floats, to_device);
+    case OwnPlane::History:  return read_filter_plane(c, c, c->tp, "rt_temporal", c->tp.n[c->tp.cur].p, 1, dst, n_floats, to_device);
+    default:                 return read_filter_plane(c, c, c->vd, "rt_denoise_variance", c->vd.var.p, 1, dst, n_floats, to_device);
+    }
+}
+
+// a context's info record (the queue settled first)
+template <class Info> int read_info(rt_ctx* c, const Info& info, Info* out)
+{
+    RT_SETTLE(c);
+    if (!out) return fail(c, -2, "null info");
+    *out = info;
+    return 0;
+}
+
+// ---- denoiser (rt_denoise, csrc/rt_denoise.hpp) -----------------------------------------------------------------------------------
+static_assert(sizeof(rt_denoise_params) == 32 && sizeof(rt_denoise_info) == 32, "denoiser ABI");
+
+const char* denoise_params(const rt_denoise_params* in, rt_denoise_params& P)
+{
+    P = rt_denoise_params{};
+    P.iterations = RT_DENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_DENOISE_DEFAULT_DEMODULATE;
+    P.sigmaColour = RT_DENOISE_DEFAULT_SIGMA_COLOUR; P.sigmaNormal = RT_DENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_DENOISE_DEFAULT_SIGMA_DEPTH;
+    if (in) P = *in;
+    if (const char* why = atrous_params(P.iterations, P.demodulate)) return why;
+    return finite_and_positive({ P.sigmaColour, P.sigmaNormal, P.sigmaDepth }) ? nullptr : "a sigma is not finite or not > 0";
+}
+
+// What both A-trous filters start with (inside their timed launches): e_0 and d from C and A, then the passes' tile grid and the
+// guide weights' factors
+struct AtrousStart { dim3 grid; float kn, kz; };
+AtrousStart atrous_start(DenoisePlanes& D, const FilterInputs& I, int demodulate, float sigmaNormal, float sigmaDepth)
+{
+    const size_t px = I.pixels();
+    hipLaunchKernelGGL(rtk::k_denoise_prep, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, I.stream, I.C, I.A, D.e[0].p, D.d.p, px, demodulate);
+    return { dim3((I.W + rtk::kDenoiseTileW - 1) / rtk::kDenoiseTileW, (I.H + rtk::kDenoiseTileH - 1) / rtk::kDenoiseTileH),
+             1.0f / (sigmaNormal * sigmaNormal), 1.0f / (sigmaDepth * sigmaDepth) };
+}
+
+// The filter: I -> D.out; P has passed denoise_params
+hipError_t run_denoise(DenoisePlanes& D, const FilterInputs& I, const rt_denoise_params& P)
+{
+    hipError_t e = D.at(I.W, I.H);
+    if (e != hipSuccess) return e;
+    float ms = 0.f;
+    if (I.pixels()) e = timed(I.stream, I.ev0, I.ev1, ms, [&] {
+        const AtrousStart s = atrous_start(D, I, P.demodulate, P.sigmaNormal, P.sigmaDepth);
+        const float kc0 = 1.0f / (P.sigmaColour * P.sigmaColour);
+        for (int i = 0; i < P.iterations; ++i) {
+            const bool last = i == P.iterations - 1;
+            rtk::AtrousArgs a{};
+            a.e_in = D.e[i & 1].p; a.guide = I.G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[(i + 1) & 1].p;
+            a.W = I.W; a.H = I.H; a.step = 1 << i;
+            a.kn = s.kn; a.kz = s.kz; a.kc = kc0 * (float)(1 << (2 * i));
+            if (last) hipLaunchKernelGGL(rtk::k_atrous<true>, s.grid, dim3(256), 0, I.stream, a);
+            else hipLaunchKernelGGL(rtk::k_atrous<false>, s.grid, dim3(256), 0, I.stream, a);
+        }
+    });
+    if (e != hipSuccess) return e;
+    D.filled = true;
+    D.info.iterations = P.iterations; D.info.demodulate = P.demodulate; D.info.width = I.W; D.info.height = I.H;
+    D.info.lastKernelMs = ms; D.info.totalKernelMs += ms;
+    return hipSuccess;
+}
+
+// rt_denoise, rt_denoise_temporal (from_T) and their rt_multi_ forms
+template <class Owner> int denoise_call(Owner* o, const FilterCall& k, bool from_T, const rt_denoise_params* in)
+{
+    if (!o) return -1;
+    { int r = begin_filter(o, k.what); if (r) return r; }
+    rt_denoise_params P;
+    if (const char* why = denoise_params(in, P)) return fail(o, -2, "%s: %s", k.what, why);
+    FilterInputs I;
+    { int r = filter_inputs(o, k, from_T, I); if (r) return r; }
+    RT_HIP(o, run_denoise(o->dn, I, P));
+    return 0;
+}
+
 // ---- temporal reprojection (rt_temporal, csrc/rt_temporal.hpp) --------------------------------------------------------------------
 static_assert(sizeof(rt_temporal_params) == 32 && sizeof(rt_temporal_info) == 32, "temporal ABI");
 
 const char* temporal_params(const rt_temporal_params* in, rt_temporal_params& P)
 {
+    P = rt_temporal_params{};
+    P.maxHistory = RT_TEMPORAL_DEFAULT_MAX_HISTORY;
+    P.depthTolerance = RT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE; P.normalTolerance = RT_TEMPORAL_DEFAULT_NORMAL_TOLERANCE;
     if (in) P = *in;
-    else {
-        P = rt_temporal_params{};
-        P.maxHistory = RT_TEMPORAL_DEFAULT_MAX_HISTORY;
-        P.depthTolerance = RT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE; P.normalTolerance = RT_TEMPORAL_DEFAULT_NORMAL_TOLERANCE;
-    }
     if (P.maxHistory < 1 || P.maxHistory > 4096) return "maxHistory outside 1..4096";
-    for (float tol : { P.depthTolerance, P.normalTolerance })
-        if (!std::isfinite(tol) || !(tol > 0.0f)) return "a tolerance is not finite or not > 0";
-    return nullptr;
+    return finite_and_positive({ P.depthTolerance, P.normalTolerance }) ? nullptr : "a tolerance is not finite or not > 0";
 }
 
-// The step: C (resultTexture), A and G (the feature planes), all W x H float4 on the current device, and the camera fields of `cam`
-// -> the other pair of S's planes, on `stream`, timed by ev0 / ev1 and waited for.  Shared by rt_temporal and rt_multi_temporal; P has
-// passed temporal_params.  Without history (call 0) N' is zeroed, so no tap counts, and the previous camera is this call's.
-hipError_t run_temporal(TemporalPlanes& S, const float4* C, const float4* A, const float4* G, int W, int H, const rt_params& cam,
-                        const rt_temporal_params& P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+// The step: I (and its camera) -> the other pair of S's planes; P has passed temporal_params.  Without history (call 0) N' is zeroed, so
+// no tap counts, and the previous camera is this call's.
+hipError_t run_temporal(TemporalPlanes& S, const FilterInputs& I, const rt_temporal_params& P)
 {
-    const size_t px = (size_t)W * H;
-    hipError_t e;
-    if (S.w != W || S.h != H || !S.t[0].p) {
-        for (int i = 0; i < 2; ++i)
-            if ((e = S.t[i].ensure(px)) != hipSuccess || (e = S.g[i].ensure(px)) != hipSuccess || (e = S.n[i].ensure(px)) != hipSuccess) return e;
-        S.w = W; S.h = H; S.filled = false; S.info = rt_temporal_info{};
-    }
+    const size_t px = I.pixels();
+    const rt_params& cam = *I.cam;
+    hipError_t e = S.at(I.W, I.H);
+    if (e != hipSuccess) return e;
     const int prev = S.cur, next = S.cur ^ 1;
     float ms = 0.f;
     if (px) {
         if (!S.filled) {            // no history: T', N' and G' read as zero
-            if ((e = hipMemsetAsync(S.t[prev].p, 0, px * sizeof(float4), stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(S.g[prev].p, 0, px * sizeof(float4), stream)) != hipSuccess) return e;
-            if ((e = hipMemsetAsync(S.n[prev].p, 0, px * sizeof(float), stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(S.t[prev].p, 0, px * sizeof(float4), I.stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(S.g[prev].p, 0, px * sizeof(float4), I.stream)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(S.n[prev].p, 0, px * sizeof(float), I.stream)) != hipSuccess) return e;
         }
         const rt_params& pc = S.filled ? S.cam : cam;
         rtk::TemporalArgs a{};
-        a.C = C; a.A = A; a.G = G;
+        a.C = I.C; a.A = I.A; a.G = I.G;
         a.Tp = S.t[prev].p; a.Np = S.n[prev].p; a.Gp = S.g[prev].p;
         a.T = S.t[next].p; a.N = S.n[next].p; a.Gn = S.g[next].p;
-        a.W = W; a.H = H;
+        a.W = I.W; a.H = I.H;
         for (int i = 0; i < 12; ++i) a.M[i] = cam.camLocalToWorld[i];
         const float* Mp = pc.camLocalToWorld;
         for (int i = 0; i < 3; ++i) {
@@ -1767,75 +1887,25 @@ hipError_t run_temporal(TemporalPlanes& S, const float4* C, const float4* A, con
             a.pcc[i] = (cx * cx + cy * cy) + cz * cz;
         }
         a.depthTol = P.depthTolerance; a.normalTol2 = P.normalTolerance * P.normalTolerance; a.maxHistory = (float)P.maxHistory;
-        const dim3 grid((W + rtk::kTemporalTileW - 1) / rtk::kTemporalTileW, (H + rtk::kTemporalTileH - 1) / rtk::kTemporalTileH);
-        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(rtk::k_temporal, grid, dim3(256), 0, stream, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
+        const dim3 grid((I.W + rtk::kTemporalTileW - 1) / rtk::kTemporalTileW, (I.H + rtk::kTemporalTileH - 1) / rtk::kTemporalTileH);
+        if ((e = timed(I.stream, I.ev0, I.ev1, ms, [&] { hipLaunchKernelGGL(rtk::k_temporal, grid, dim3(256), 0, I.stream, a); })) != hipSuccess) return e;
     }
     S.cur = next; S.filled = true; S.cam = cam;
-    S.info.calls += 1; S.info.width = W; S.info.height = H;
+    S.info.calls += 1; S.info.width = I.W; S.info.height = I.H;
     S.info.lastKernelMs = ms; S.info.totalKernelMs += ms;
     return hipSuccess;
 }
 
-// what rt_temporal and rt_denoise_temporal ask of a context before they run: params, the whole image, current feature planes with a
-// frame in them
-int whole_image_with_features(rt_ctx* c, const char* what, StripLayout& L)
+// rt_temporal and rt_multi_temporal
+template <class Owner> int temporal_call(Owner* o, const FilterCall& k, const rt_temporal_params* in)
 {
-    if (!c->have_params) return fail(c, -2, "%s: rt_set_params has not been called", what);
-    { int r = strip_layout(c, L); if (r) return r; }
-    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
-        return fail(c, -2, "%s: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_temporal", what, L.rows, L.h);
-    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "%s: no feature frame accumulated (call rt_render_aov first)", what);
-    return 0;
-}
-
-int temporal(rt_ctx* c, const rt_temporal_params* in)
-{
-    RT_SETTLE(c);
-    if (!c->have_params) return fail(c, -2, "rt_temporal: rt_set_params has not been called");
+    if (!o) return -1;
+    { int r = begin_filter(o, k.what); if (r) return r; }
     rt_temporal_params P;
-    if (const char* why = temporal_params(in, P)) return fail(c, -2, "rt_temporal: %s", why);
-    StripLayout L;
-    { int r = whole_image_with_features(c, "rt_temporal", L); if (r) return r; }
-    RT_HIP(c, hipSetDevice(c->device));
-    { int r = ensure_targets(c); if (r) return r; }             // (as in rt_denoise)
-    RT_HIP(c, run_temporal(c->tp, c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, c->params, P,
-                           c->stream, c->ev_dn0, c->ev_dn1));
-    return 0;
-}
-
-int denoise_temporal(rt_ctx* c, const rt_denoise_params* in)
-{
-    RT_SETTLE(c);
-    if (!c->have_params) return fail(c, -2, "rt_denoise_temporal: rt_set_params has not been called");
-    rt_denoise_params P;
-    if (const char* why = denoise_params(in, P)) return fail(c, -2, "rt_denoise_temporal: %s", why);
-    StripLayout L;
-    { int r = whole_image_with_features(c, "rt_denoise_temporal", L); if (r) return r; }
-    if (!c->tp.filled) return fail(c, -2, "rt_denoise_temporal: rt_temporal has not been called");
-    if (c->tp.w != L.w || c->tp.h != L.h) return fail(c, -2, "rt_denoise_temporal: the temporal image is %d x %d, the context's image %d x %d", c->tp.w, c->tp.h, L.w, L.h);
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, run_denoise(c->dn, c->tp.t[c->tp.cur].p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p, L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
-    return 0;
-}
-
-// T (history false: height*width*4 floats) or N (history true: height*width floats) of the last call
-int read_temporal(rt_ctx* c, bool history, void* dst, size_t n_floats, bool to_device)
-{
-    RT_SETTLE(c);
-    if (!c->tp.filled) return fail(c, -2, "rt_temporal has not been called");
-    if (!dst) return fail(c, -2, "null destination");
-    const size_t px = (size_t)c->tp.w * c->tp.h;
-    if (!history) return copy_plane(c, c->tp.t[c->tp.cur].p, px * 4, "height", dst, n_floats, to_device);
-    if (n_floats != px) return fail(c, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(dst, c->tp.n[c->tp.cur].p, n_floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (const char* why = temporal_params(in, P)) return fail(o, -2, "%s: %s", k.what, why);
+    FilterInputs I;
+    { int r = filter_inputs(o, k, false, I); if (r) return r; }
+    RT_HIP(o, run_temporal(o->tp, I, P));
     return 0;
 }
 
@@ -1844,95 +1914,54 @@ static_assert(sizeof(rt_vdenoise_params) == 32 && sizeof(rt_vdenoise_info) == 32
 
 const char* vdenoise_params(const rt_vdenoise_params* in, rt_vdenoise_params& P)
 {
+    P = rt_vdenoise_params{};
+    P.iterations = RT_VDENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_VDENOISE_DEFAULT_DEMODULATE;
+    P.sigmaLuminance = RT_VDENOISE_DEFAULT_SIGMA_LUMINANCE; P.sigmaNormal = RT_VDENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_VDENOISE_DEFAULT_SIGMA_DEPTH;
     if (in) P = *in;
-    else {
-        P = rt_vdenoise_params{};
-        P.iterations = RT_VDENOISE_DEFAULT_ITERATIONS; P.demodulate = RT_VDENOISE_DEFAULT_DEMODULATE;
-        P.sigmaLuminance = RT_VDENOISE_DEFAULT_SIGMA_LUMINANCE; P.sigmaNormal = RT_VDENOISE_DEFAULT_SIGMA_NORMAL; P.sigmaDepth = RT_VDENOISE_DEFAULT_SIGMA_DEPTH;
-    }
-    if (P.iterations < 1 || P.iterations > 6) return "iterations outside 1..6";
-    if (P.demodulate != 0 && P.demodulate != 1) return "demodulate is neither 0 nor 1";
-    if (P.source != 0 && P.source != 1) return "source is neither 0 nor 1";
-    for (float sg : { P.sigmaLuminance, P.sigmaNormal, P.sigmaDepth })
-        if (!std::isfinite(sg) || !(sg > 0.0f)) return "a sigma is not finite or not > 0";
-    if (P._reserved[0] != 0 || P._reserved[1] != 0) return "a reserved word is not 0";
-    return nullptr;
+    if (const char* why = atrous_params(P.iterations, P.demodulate)) return why;
+    if (!is_flag(P.source)) return "source is neither 0 nor 1";
+    if (!finite_and_positive({ P.sigmaLuminance, P.sigmaNormal, P.sigmaDepth })) return "a sigma is not finite or not > 0";
+    return P._reserved[0] == 0 && P._reserved[1] == 0 ? nullptr : "a reserved word is not 0";
 }
 
-// The filter: C (resultTexture or T), A and G, all W x H float4 on the current device -> D.out and V.var, through D's work planes, on
-// `stream`, timed by ev0 / ev1 and waited for.  Shared by rt_denoise_variance and rt_multi_denoise_variance; P has passed vdenoise_params.
-hipError_t run_vdenoise(DenoisePlanes& D, VariancePlane& V, const float4* C, const float4* A, const float4* G, int W, int H,
-                        const rt_vdenoise_params& P, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1)
+// The filter: I -> D.out and V.var, through D's work planes; P has passed vdenoise_params
+hipError_t run_vdenoise(DenoisePlanes& D, VariancePlane& V, const FilterInputs& I, const rt_vdenoise_params& P)
 {
-    const size_t px = (size_t)W * H;
     hipError_t e;
-    if ((e = ensure_denoise_planes(D, W, H)) != hipSuccess) return e;
-    if (V.w != W || V.h != H || !V.var.p) {
-        if ((e = V.var.ensure(px)) != hipSuccess) return e;
-        V.w = W; V.h = H; V.filled = false; V.info.totalKernelMs = 0;
-    }
+    if ((e = D.at(I.W, I.H)) != hipSuccess || (e = V.at(I.W, I.H)) != hipSuccess) return e;
     float ms = 0.f;
-    if (px) {
-        const float kn = 1.0f / (P.sigmaNormal * P.sigmaNormal), kz = 1.0f / (P.sigmaDepth * P.sigmaDepth);
-        if ((e = hipEventRecord(ev0, stream)) != hipSuccess) return e;
-        hipLaunchKernelGGL(rtk::k_denoise_prep, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, C, A, D.e[0].p, D.d.p, px, P.demodulate);
-        const dim3 grid((W + rtk::kDenoiseTileW - 1) / rtk::kDenoiseTileW, (H + rtk::kDenoiseTileH - 1) / rtk::kDenoiseTileH);
+    if (I.pixels()) e = timed(I.stream, I.ev0, I.ev1, ms, [&] {
+        const AtrousStart s = atrous_start(D, I, P.demodulate, P.sigmaNormal, P.sigmaDepth);
         rtk::VarEstimateArgs v{};
-        v.e0 = D.e[0].p; v.guide = G; v.e_out = D.e[1].p; v.var = V.var.p; v.W = W; v.H = H; v.kn = kn; v.kz = kz;
-        hipLaunchKernelGGL(rtk::k_variance_estimate, grid, dim3(256), 0, stream, v);
+        v.e0 = D.e[0].p; v.guide = I.G; v.e_out = D.e[1].p; v.var = V.var.p; v.W = I.W; v.H = I.H; v.kn = s.kn; v.kz = s.kz;
+        hipLaunchKernelGGL(rtk::k_variance_estimate, s.grid, dim3(256), 0, I.stream, v);
         for (int i = 0; i < P.iterations; ++i) {            // (e_0, var_0) is in e[1]: pass i reads e[(i + 1) & 1]
             const bool last = i == P.iterations - 1;
             rtk::VarAtrousArgs a{};
-            a.e_in = D.e[(i + 1) & 1].p; a.guide = G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[i & 1].p;
-            a.W = W; a.H = H; a.step = 1 << i;
-            a.kn = kn; a.kz = kz; a.sl = P.sigmaLuminance;
-            if (last) hipLaunchKernelGGL(rtk::k_var_atrous<true>, grid, dim3(256), 0, stream, a);
-            else hipLaunchKernelGGL(rtk::k_var_atrous<false>, grid, dim3(256), 0, stream, a);
+            a.e_in = D.e[(i + 1) & 1].p; a.guide = I.G; a.d = D.d.p; a.e_out = last ? D.out.p : D.e[i & 1].p;
+            a.W = I.W; a.H = I.H; a.step = 1 << i;
+            a.kn = s.kn; a.kz = s.kz; a.sl = P.sigmaLuminance;
+            if (last) hipLaunchKernelGGL(rtk::k_var_atrous<true>, s.grid, dim3(256), 0, I.stream, a);
+            else hipLaunchKernelGGL(rtk::k_var_atrous<false>, s.grid, dim3(256), 0, I.stream, a);
         }
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ev1, stream)) != hipSuccess) return e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if ((e = hipEventElapsedTime(&ms, ev0, ev1)) != hipSuccess) return e;
-    }
+    });
+    if (e != hipSuccess) return e;
     D.filled = true; V.filled = true;
-    V.info.iterations = P.iterations; V.info.source = P.source; V.info.width = W; V.info.height = H;
+    V.info.iterations = P.iterations; V.info.source = P.source; V.info.width = I.W; V.info.height = I.H;
     V.info.lastKernelMs = ms; V.info.totalKernelMs += ms;
     return hipSuccess;
 }
 
-int denoise_variance(rt_ctx* c, const rt_vdenoise_params* in)
+// rt_denoise_variance and rt_multi_denoise_variance (source 1: the temporal colour)
+template <class Owner> int denoise_variance_call(Owner* o, const FilterCall& k, const rt_vdenoise_params* in)
 {
-    RT_SETTLE(c);
-    if (!c->have_params) return fail(c, -2, "rt_denoise_variance: rt_set_params has not been called");
+    if (!o) return -1;
+    { int r = begin_filter(o, k.what); if (r) return r; }
     rt_vdenoise_params P;
-    if (const char* why = vdenoise_params(in, P)) return fail(c, -2, "rt_denoise_variance: %s", why);
-    StripLayout L;
-    { int r = strip_layout(c, L); if (r) return r; }
-    if (c->band_stride > 1 || L.row0 != 0 || L.rows != L.h)
-        return fail(c, -2, "rt_denoise_variance: the context holds rows of the image, not the whole image (%d of %d rows); use rt_multi_denoise_variance", L.rows, L.h);
-    if (!aov_current(c, L) || c->aov_info.framesAccumulated == 0) return fail(c, -2, "rt_denoise_variance: no feature frame accumulated (call rt_render_aov first)");
-    if (P.source == 1) {
-        if (!c->tp.filled) return fail(c, -2, "rt_denoise_variance: source 1, and rt_temporal has not been called");
-        if (c->tp.w != L.w || c->tp.h != L.h) return fail(c, -2, "rt_denoise_variance: the temporal image is %d x %d, the context's image %d x %d", c->tp.w, c->tp.h, L.w, L.h);
-    }
-    RT_HIP(c, hipSetDevice(c->device));
-    if (P.source == 0) { int r = ensure_targets(c); if (r) return r; }         // (as in rt_denoise)
-    RT_HIP(c, run_vdenoise(c->dn, c->vd, P.source ? c->tp.t[c->tp.cur].p : c->d_accum.p, c->d_aov[RT_AOV_ALBEDO].p, c->d_aov[RT_AOV_NORMAL_DEPTH].p,
-                           L.w, L.h, P, c->stream, c->ev_dn0, c->ev_dn1));
-    return 0;
-}
-
-int read_variance(rt_ctx* c, void* dst, size_t n_floats, bool to_device)
-{
-    RT_SETTLE(c);
-    if (!c->vd.filled) return fail(c, -2, "rt_denoise_variance has not been called");
-    if (!dst) return fail(c, -2, "null destination");
-    const size_t px = (size_t)c->vd.w * c->vd.h;
-    if (n_floats != px) return fail(c, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, hipMemcpyAsync(dst, c->vd.var.p, n_floats * sizeof(float), to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(c, hipStreamSynchronize(c->stream));
+    if (const char* why = vdenoise_params(in, P)) return fail(o, -2, "%s: %s", k.what, why);
+    FilterInputs I;
+    { int r = filter_inputs(o, k, P.source == 1, I); if (r) return r; }
+    RT_HIP(o, run_vdenoise(o->dn, o->vd, I, P));
     return 0;
 }
 
@@ -2388,85 +2417,49 @@ int rt_reset_aov(rt_ctx* c)
     c->aov_info.framesAccumulated = 0; c->aov_info.totalKernelMs = 0;
     return 0;
 }
-int rt_get_aov_info(rt_ctx* c, rt_aov_info* out)
-{
-    if (!c) return -1;
-    RT_SETTLE(c);
-    if (!out) return fail(c, -2, "null info");
-    *out = c->aov_info;
-    return 0;
-}
+int rt_get_aov_info(rt_ctx* c, rt_aov_info* out) { return c ? read_info(c, c->aov_info, out) : -1; }
 
-int rt_denoise(rt_ctx* c, const rt_denoise_params* params) { return c ? denoise(c, params) : -1; }
-int rt_read_denoised(rt_ctx* c, float* rgba, size_t n) { return c ? read_denoised(c, rgba, n, false) : -1; }
-int rt_copy_denoised_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_denoised(c, dst, n, true) : -1; }
+int rt_denoise(rt_ctx* c, const rt_denoise_params* params) { return denoise_call(c, { "rt_denoise", "rt_multi_denoise" }, false, params); }
+int rt_read_denoised(rt_ctx* c, float* rgba, size_t n) { return read_own(c, OwnPlane::Denoised, rgba, n, false); }
+int rt_copy_denoised_to_device(rt_ctx* c, void* dst, size_t n) { return read_own(c, OwnPlane::Denoised, dst, n, true); }
 int rt_read_denoised_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
 {
     if (!c) return -1;
     RT_SETTLE(c);
-    if (!c->dn.filled) return fail(c, -2, "rt_denoise has not been called");
-    if (!rgba8) return fail(c, -2, "null destination");
-    const size_t px = (size_t)c->dn.w * c->dn.h;
-    if (n_pixels != px) return fail(c, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
-    if (!n_pixels) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, display_plane(c, c->dn.out.p, c->d_display, rgba8, n_pixels));
-    return 0;
+    return read_filter_display(c, c, c->dn, "rt_denoise", c->dn.out.p, c->d_display, rgba8, n_pixels);
 }
-int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out)
-{
-    if (!c) return -1;
-    RT_SETTLE(c);
-    if (!out) return fail(c, -2, "null info");
-    *out = c->dn.info;
-    return 0;
-}
+int rt_get_denoise_info(rt_ctx* c, rt_denoise_info* out) { return c ? read_info(c, c->dn.info, out) : -1; }
 
-int rt_denoise_variance(rt_ctx* c, const rt_vdenoise_params* params) { return c ? denoise_variance(c, params) : -1; }
-int rt_read_variance(rt_ctx* c, float* var, size_t n) { return c ? read_variance(c, var, n, false) : -1; }
-int rt_copy_variance_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_variance(c, dst, n, true) : -1; }
-int rt_get_vdenoise_info(rt_ctx* c, rt_vdenoise_info* out)
+int rt_denoise_variance(rt_ctx* c, const rt_vdenoise_params* params)
 {
-    if (!c) return -1;
-    RT_SETTLE(c);
-    if (!out) return fail(c, -2, "null info");
-    *out = c->vd.info;
-    return 0;
+    return denoise_variance_call(c, { "rt_denoise_variance", "rt_multi_denoise_variance", "source 1, and " }, params);
 }
+int rt_read_variance(rt_ctx* c, float* var, size_t n) { return read_own(c, OwnPlane::Variance, var, n, false); }
+int rt_copy_variance_to_device(rt_ctx* c, void* dst, size_t n) { return read_own(c, OwnPlane::Variance, dst, n, true); }
+int rt_get_vdenoise_info(rt_ctx* c, rt_vdenoise_info* out) { return c ? read_info(c, c->vd.info, out) : -1; }
 
-int rt_temporal(rt_ctx* c, const rt_temporal_params* params) { return c ? temporal(c, params) : -1; }
-int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* params) { return c ? denoise_temporal(c, params) : -1; }
+int rt_temporal(rt_ctx* c, const rt_temporal_params* params) { return temporal_call(c, { "rt_temporal", "rt_multi_temporal" }, params); }
+int rt_denoise_temporal(rt_ctx* c, const rt_denoise_params* params)
+{
+    return denoise_call(c, { "rt_denoise_temporal", "rt_multi_temporal" }, true, params);
+}
 int rt_reset_temporal(rt_ctx* c)
 {
     if (!c) return -1;
     RT_SETTLE(c);
-    c->tp.filled = false; c->tp.info.calls = 0; c->tp.info.lastKernelMs = 0; c->tp.info.totalKernelMs = 0;
+    c->tp.reset();
     return 0;
 }
-int rt_read_temporal(rt_ctx* c, float* rgba, size_t n) { return c ? read_temporal(c, false, rgba, n, false) : -1; }
-int rt_read_temporal_history(rt_ctx* c, float* hist, size_t n) { return c ? read_temporal(c, true, hist, n, false) : -1; }
-int rt_copy_temporal_to_device(rt_ctx* c, void* dst, size_t n) { return c ? read_temporal(c, false, dst, n, true) : -1; }
+int rt_read_temporal(rt_ctx* c, float* rgba, size_t n) { return read_own(c, OwnPlane::Temporal, rgba, n, false); }
+int rt_read_temporal_history(rt_ctx* c, float* hist, size_t n) { return read_own(c, OwnPlane::History, hist, n, false); }
+int rt_copy_temporal_to_device(rt_ctx* c, void* dst, size_t n) { return read_own(c, OwnPlane::Temporal, dst, n, true); }
 int rt_read_temporal_display(rt_ctx* c, uint32_t* rgba8, size_t n_pixels)
 {
     if (!c) return -1;
     RT_SETTLE(c);
-    if (!c->tp.filled) return fail(c, -2, "rt_temporal has not been called");
-    if (!rgba8) return fail(c, -2, "null destination");
-    const size_t px = (size_t)c->tp.w * c->tp.h;
-    if (n_pixels != px) return fail(c, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
-    if (!n_pixels) return 0;
-    RT_HIP(c, hipSetDevice(c->device));
-    RT_HIP(c, display_plane(c, c->tp.t[c->tp.cur].p, c->d_display, rgba8, n_pixels));
-    return 0;
+    return read_filter_display(c, c, c->tp, "rt_temporal", c->tp.t[c->tp.cur].p, c->d_display, rgba8, n_pixels);
 }
-int rt_get_temporal_info(rt_ctx* c, rt_temporal_info* out)
-{
-    if (!c) return -1;
-    RT_SETTLE(c);
-    if (!out) return fail(c, -2, "null info");
-    *out = c->tp.info;
-    return 0;
-}
+int rt_get_temporal_info(rt_ctx* c, rt_temporal_info* out) { return c ? read_info(c, c->tp.info, out) : -1; }
 
 int rt_get_stats(rt_ctx* c, rt_stats* out)
 {
@@ -2529,8 +2522,9 @@ template <class Fn> int on_every_context(rt_multi* m, const char* what, Fn fn)
     return 0;
 }
 
-// copy_plane's counterpart for the handle: a whole-image plane on the first device -> the host.  source(src) says where the plane is,
-// assembling it first if need be; it runs once the size is known to be right and not zero
+// copy_plane's counterpart for the handle's planes that are assembled on demand (rt_multi_read_aov, rt_multi_read_accum): a whole-image
+// plane on the first device -> the host.  source(src) says where the plane is, assembling it first if need be; it runs once the size is
+// known to be right and not zero
 template <class Source> int read_image(rt_multi* m, size_t expect_floats, float* dst, size_t n_floats, Source source)
 {
     if (n_floats != expect_floats) return fail(m, -2, "expected %zu floats (height*width*4), got %zu", expect_floats, n_floats);
@@ -2789,6 +2783,24 @@ int multi_gather_inputs(rt_multi* m, const char* what, bool image)
     { int r = gather_strips(m, m->d_dn_guide, gather_ms, [](rt_ctx* c) { return c->d_aov[RT_AOV_NORMAL_DEPTH].p; }, [](rt_ctx* c) { return c->aov.rows; }); if (r) return r; }
     return 0;
 }
+
+// The handle's half of the filters' host path (begin_filter / filter_inputs of a context, above): T first, if that is the source, then
+// the gather to the first device, whose stream and events run the filter
+int begin_filter(rt_multi* m, const char* what)
+{
+    return m->have_params ? 0 : fail(m, -2, "%s: rt_multi_set_params has not been called", what);
+}
+int filter_inputs(rt_multi* m, const FilterCall& k, bool from_T, FilterInputs& I)
+{
+    if (from_T) { int r = temporal_source(m, m->tp, m->width, m->height, k, "rt_multi_temporal", "handle's"); if (r) return r; }
+    { int r = multi_gather_inputs(m, k.what, !from_T); if (r) return r; }
+    rt_ctx* root = m->ctx[0];
+    RT_HIP(m, hipSetDevice(root->device));
+    I.C = from_T ? m->tp.t[m->tp.cur].p : m->d_image.p; I.A = m->d_dn_albedo.p; I.G = m->d_dn_guide.p;
+    I.W = m->width; I.H = m->height; I.cam = &root->params;
+    I.stream = root->stream; I.ev0 = root->ev_dn0; I.ev1 = root->ev_dn1;
+    return 0;
+}
 } // namespace
 
 extern "C" {
@@ -2828,143 +2840,50 @@ int rt_multi_read_aov(rt_multi* m, int which, float* rgba, size_t n_floats)
 
 int rt_multi_reset_aov(rt_multi* m) { return m ? for_each_ctx(m, "rt_reset_aov", [&](rt_ctx* c) { return rt_reset_aov(c); }) : -1; }
 
-// The denoiser behind the handle: image and both feature planes gathered to the first device, rt_denoise's filter there.
-int rt_multi_denoise(rt_multi* m, const rt_denoise_params* params)
+// The image filters behind the handle: image and both feature planes gathered to the first device, the context's filter there, the
+// planes and the temporal state on the handle.  Its reads take the first context's stream (every producer has waited before it returned)
+int rt_multi_denoise(rt_multi* m, const rt_denoise_params* params) { return denoise_call(m, { "rt_multi_denoise", nullptr }, false, params); }
+int rt_multi_temporal(rt_multi* m, const rt_temporal_params* params) { return temporal_call(m, { "rt_multi_temporal", nullptr }, params); }
+int rt_multi_denoise_temporal(rt_multi* m, const rt_denoise_params* params)
 {
-    if (!m) return -1;
-    if (!m->have_params) return fail(m, -2, "rt_multi_denoise: rt_multi_set_params has not been called");
-    rt_denoise_params P;
-    if (const char* why = denoise_params(params, P)) return fail(m, -2, "rt_multi_denoise: %s", why);
-    { int r = multi_gather_inputs(m, "rt_multi_denoise", true); if (r) return r; }
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, run_denoise(m->dn, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
-    return 0;
+    return denoise_call(m, { "rt_multi_denoise_temporal", nullptr }, true, params);
 }
-
-// Temporal reprojection behind the handle: the same gather, rt_temporal's step on the first device, the state on the handle.
-int rt_multi_temporal(rt_multi* m, const rt_temporal_params* params)
+int rt_multi_denoise_variance(rt_multi* m, const rt_vdenoise_params* params)
 {
-    if (!m) return -1;
-    if (!m->have_params) return fail(m, -2, "rt_multi_temporal: rt_multi_set_params has not been called");
-    rt_temporal_params P;
-    if (const char* why = temporal_params(params, P)) return fail(m, -2, "rt_multi_temporal: %s", why);
-    { int r = multi_gather_inputs(m, "rt_multi_temporal", true); if (r) return r; }
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, run_temporal(m->tp, m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, root->params, P, root->stream, root->ev_dn0, root->ev_dn1));
-    return 0;
+    return denoise_variance_call(m, { "rt_multi_denoise_variance", nullptr, "source 1, and " }, params);
 }
 
 int rt_multi_reset_temporal(rt_multi* m)
 {
     if (!m) return -1;
-    m->tp.filled = false; m->tp.info.calls = 0; m->tp.info.lastKernelMs = 0; m->tp.info.totalKernelMs = 0;
+    m->tp.reset();
     return 0;
 }
 
-int rt_multi_read_temporal(rt_multi* m, float* rgba, size_t n_floats)
+int rt_multi_read_temporal(rt_multi* m, float* rgba, size_t n)
 {
-    if (!m) return -1;
-    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
-    if (!rgba) return fail(m, -2, "null destination");
-    return read_image(m, (size_t)m->tp.w * m->tp.h * 4, rgba, n_floats, [&](const float4*& src) { src = m->tp.t[m->tp.cur].p; return 0; });
+    return m ? read_filter_plane(m, m->ctx[0], m->tp, "rt_multi_temporal", m->tp.t[m->tp.cur].p, 4, rgba, n, false) : -1;
 }
-
-int rt_multi_read_temporal_history(rt_multi* m, float* hist, size_t n_floats)
+int rt_multi_read_temporal_history(rt_multi* m, float* hist, size_t n)
 {
-    if (!m) return -1;
-    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
-    if (!hist) return fail(m, -2, "null destination");
-    const size_t px = (size_t)m->tp.w * m->tp.h;
-    if (n_floats != px) return fail(m, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(m, hipSetDevice(m->ctx[0]->device));
-    RT_HIP(m, hipMemcpy(hist, m->tp.n[m->tp.cur].p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return m ? read_filter_plane(m, m->ctx[0], m->tp, "rt_multi_temporal", m->tp.n[m->tp.cur].p, 1, hist, n, false) : -1;
 }
-
 int rt_multi_read_temporal_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 {
-    if (!m) return -1;
-    if (!m->tp.filled) return fail(m, -2, "rt_multi_temporal has not been called");
-    if (!rgba8) return fail(m, -2, "null destination");
-    const size_t px = (size_t)m->tp.w * m->tp.h;
-    if (n_pixels != px) return fail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
-    if (!n_pixels) return 0;
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, display_plane(root, m->tp.t[m->tp.cur].p, m->d_display, rgba8, n_pixels));
-    return 0;
+    return m ? read_filter_display(m, m->ctx[0], m->tp, "rt_multi_temporal", m->tp.t[m->tp.cur].p, m->d_display, rgba8, n_pixels) : -1;
 }
-
-int rt_multi_denoise_temporal(rt_multi* m, const rt_denoise_params* params)
+int rt_multi_read_variance(rt_multi* m, float* var, size_t n)
 {
-    if (!m) return -1;
-    if (!m->have_params) return fail(m, -2, "rt_multi_denoise_temporal: rt_multi_set_params has not been called");
-    rt_denoise_params P;
-    if (const char* why = denoise_params(params, P)) return fail(m, -2, "rt_multi_denoise_temporal: %s", why);
-    if (!m->tp.filled) return fail(m, -2, "rt_multi_denoise_temporal: rt_multi_temporal has not been called");
-    if (m->tp.w != m->width || m->tp.h != m->height) return fail(m, -2, "rt_multi_denoise_temporal: the temporal image is %d x %d, the handle's image %d x %d", m->tp.w, m->tp.h, m->width, m->height);
-    { int r = multi_gather_inputs(m, "rt_multi_denoise_temporal", false); if (r) return r; }
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, run_denoise(m->dn, m->tp.t[m->tp.cur].p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P, root->stream, root->ev_dn0, root->ev_dn1));
-    return 0;
+    return m ? read_filter_plane(m, m->ctx[0], m->vd, "rt_multi_denoise_variance", m->vd.var.p, 1, var, n, false) : -1;
 }
-
-// The variance-guided denoiser behind the handle: the same gathers, rt_denoise_variance's filter on the first device.
-int rt_multi_denoise_variance(rt_multi* m, const rt_vdenoise_params* params)
+// (whichever filter filled the denoised plane, the message names rt_multi_denoise)
+int rt_multi_read_denoised(rt_multi* m, float* rgba, size_t n)
 {
-    if (!m) return -1;
-    if (!m->have_params) return fail(m, -2, "rt_multi_denoise_variance: rt_multi_set_params has not been called");
-    rt_vdenoise_params P;
-    if (const char* why = vdenoise_params(params, P)) return fail(m, -2, "rt_multi_denoise_variance: %s", why);
-    if (P.source == 1) {
-        if (!m->tp.filled) return fail(m, -2, "rt_multi_denoise_variance: source 1, and rt_multi_temporal has not been called");
-        if (m->tp.w != m->width || m->tp.h != m->height) return fail(m, -2, "rt_multi_denoise_variance: the temporal image is %d x %d, the handle's image %d x %d", m->tp.w, m->tp.h, m->width, m->height);
-    }
-    { int r = multi_gather_inputs(m, "rt_multi_denoise_variance", P.source == 0); if (r) return r; }
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, run_vdenoise(m->dn, m->vd, P.source ? m->tp.t[m->tp.cur].p : m->d_image.p, m->d_dn_albedo.p, m->d_dn_guide.p, m->width, m->height, P,
-                           root->stream, root->ev_dn0, root->ev_dn1));
-    return 0;
+    return m ? read_filter_plane(m, m->ctx[0], m->dn, "rt_multi_denoise", m->dn.out.p, 4, rgba, n, false) : -1;
 }
-
-int rt_multi_read_variance(rt_multi* m, float* var, size_t n_floats)
-{
-    if (!m) return -1;
-    if (!m->vd.filled) return fail(m, -2, "rt_multi_denoise_variance has not been called");
-    if (!var) return fail(m, -2, "null destination");
-    const size_t px = (size_t)m->vd.w * m->vd.h;
-    if (n_floats != px) return fail(m, -2, "expected %zu floats (height*width), got %zu", px, n_floats);
-    if (!n_floats) return 0;
-    RT_HIP(m, hipSetDevice(m->ctx[0]->device));
-    RT_HIP(m, hipMemcpy(var, m->vd.var.p, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int rt_multi_read_denoised(rt_multi* m, float* rgba, size_t n_floats)
-{
-    if (!m) return -1;
-    if (!m->dn.filled) return fail(m, -2, "rt_multi_denoise has not been called");
-    if (!rgba) return fail(m, -2, "null destination");
-    return read_image(m, (size_t)m->dn.w * m->dn.h * 4, rgba, n_floats, [&](const float4*& src) { src = m->dn.out.p; return 0; });
-}
-
 int rt_multi_read_denoised_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 {
-    if (!m) return -1;
-    if (!m->dn.filled) return fail(m, -2, "rt_multi_denoise has not been called");
-    if (!rgba8) return fail(m, -2, "null destination");
-    const size_t px = (size_t)m->dn.w * m->dn.h;
-    if (n_pixels != px) return fail(m, -2, "expected %zu pixels (height*width), got %zu", px, n_pixels);
-    if (!n_pixels) return 0;
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, display_plane(root, m->dn.out.p, m->d_display, rgba8, n_pixels));
-    return 0;
+    return m ? read_filter_display(m, m->ctx[0], m->dn, "rt_multi_denoise", m->dn.out.p, m->d_display, rgba8, n_pixels) : -1;
 }
 
 int rt_multi_render(rt_multi* m, int first_frame, int n_frames)
@@ -2989,13 +2908,7 @@ int rt_multi_read_display(rt_multi* m, uint32_t* rgba8, size_t n_pixels)
 {
     if (!m) return -1;
     if (!rgba8 && n_pixels) return fail(m, -2, "null destination");
-    if (n_pixels != (size_t)m->width * m->height) return fail(m, -2, "expected %zu pixels (height*width), got %zu", (size_t)m->width * m->height, n_pixels);
-    if (!n_pixels) return 0;
-    if (!m->d_image.p) return fail(m, -2, "nothing rendered yet");
-    rt_ctx* root = m->ctx[0];
-    RT_HIP(m, hipSetDevice(root->device));
-    RT_HIP(m, display_plane(root, m->d_image.p, m->d_display, rgba8, n_pixels));
-    return 0;
+    return read_srgb8(m, m->ctx[0], m->d_image.p, (size_t)m->width * m->height, m->d_display, rgba8, n_pixels);
 }
 
 // Restore a saved accumulation state (rt_write_accum's twin): the whole image goes in, every context takes the rows of its bands.
