@@ -246,6 +246,10 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     the result never depends on it
  *   "visibility_slice" rt_visibility: points per launch and per staging slice, 1..4194304 (default 4194304, the ray queries' slice);
  *                     the result never depends on it
+ *   "closest_slice"   rt_closest_points: points per launch and per staging slice, 1..4194304 (default 4194304); the result never
+ *                     depends on it
+ *   "closest_count"   rt_closest_points: 1 = the counting build of the kernel, which fills rt_closest_info.lastNodeSteps / lastPrimTests
+ *                     (default 0: those stay 0); the results are the same bits
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -592,6 +596,83 @@ int rt_visibility        (rt_ctx* ctx, const rt_ray* points, int n, const rt_vis
 int rt_visibility_device (rt_ctx* ctx, const void* points, int n, const rt_visibility_params* params, void* out);
 int rt_get_visibility_info(rt_ctx* ctx, rt_visibility_info* out);
 
+/* ---- closest-point queries: the nearest surface to a point, its distance, and the side the point lies on ------------------------------
+ * The one question of this group that is about a POINT, not a ray: which sphere or triangle is nearest to p, where on it, how far, and
+ * on which side.  Signed-distance baking, pushing a probe out of a wall, snapping a picked position to geometry, proximity tests, the
+ * offset a gather point needs.  The reference has no such function; the definition below is this library's own, in float32 with every
+ * product and sum rounded on its own (no FMA), and the answer is the same bits whatever the tree, the builder, the leaf size or the
+ * order of the visit.  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; cross, +, -, * on vectors are component-wise as in the shader;
+ * / and sqrtf are IEEE.
+ *
+ *   input         an rt_ray: origin = the point p, tMax = the search radius R (+inf: unbounded).  direction and the reserved word are
+ *                 never read.
+ *   candidates    every uploaded sphere, and every triangle of the tree: the ones rt_read_bvh_order lists, those a ray query can hit.
+ *                 intersectMode plays no part and no rt_params are needed.
+ *   sphere        m = p - c; len = sqrtf(dot(m, m)); ds = fabsf(len - r); key k = ds * ds; dst = ds; point = c + m * (r / len);
+ *                 side = len >= r ? +1 : -1; normal = normalize(point - c).  p on the centre: whatever this arithmetic gives.
+ *   triangle      A = posA, eAB = posB - posA, eAC = posC - posA (the floats RayTriangle forms), ap = p - A.  The seven-region test
+ *                 (Ericson, Real-Time Collision Detection 5.1.5) on these alone:
+ *                   d1 = dot(eAB, ap); d2 = dot(eAC, ap); bp = ap - eAB; d3 = dot(eAB, bp); d4 = dot(eAC, bp);
+ *                   cp = ap - eAC; d5 = dot(eAB, cp); d6 = dot(eAC, cp);
+ *                   vc = d1 * d4 - d3 * d2; vb = d5 * d2 - d1 * d6; va = d3 * d6 - d5 * d4; d43 = d4 - d3; d56 = d5 - d6;
+ *                 the first of these that holds decides (u, v):
+ *                   d1 <= 0 && d2 <= 0                      vertex A   u = 0, v = 0
+ *                   d3 >= 0 && d4 <= d3                     vertex B   u = 1, v = 0
+ *                   vc <= 0 && d1 >= 0 && d3 <= 0           edge AB    u = d1 / (d1 - d3), v = 0
+ *                   d6 >= 0 && d5 <= d6                     vertex C   u = 0, v = 1
+ *                   vb <= 0 && d2 >= 0 && d6 <= 0           edge AC    u = 0, v = d2 / (d2 - d6)
+ *                   va <= 0 && d43 >= 0 && d56 >= 0         edge BC    v = d43 / (d43 + d56), u = 1 - v
+ *                   otherwise                               interior   den = (va + vb) + vc; u = vb / den; v = vc / den; then
+ *                                                                      u = u < 0 ? 0 : u; u = u > 1 ? 1 : u; v = v < 0 ? 0 : v;
+ *                                                                      v = v > 1 - u ? 1 - u : v   (rounding in va, vb, vc can leave the
+ *                                                                      quotients just outside the triangle; a NaN stays a NaN)
+ *                 q = (A + eAB * u) + eAC * v; e = p - q; key k = dot(e, e); dst = sqrtf(k); point = q;
+ *                 s = dot(e, cross(eAB, eAC)); side = s > 0 ? +1 : s < 0 ? -1 : 0 (0 also for NaN); normal = rt_hit's: the normalised
+ *                 interpolation of the vertex normals at (u, v).  A degenerate triangle falls into a vertex or edge region; if it
+ *                 reaches the interior its denominator is 0 and the NaN key never wins.
+ *   acceptance    a candidate counts when k < R * R (the product a float, the comparison strict; a NaN k never counts).  The winner is
+ *                 the smallest (k, kind, primitive): at equal k a sphere comes before a triangle, then the lower uploaded index wins.
+ *                 Ties are the normal case for a point over a shared edge or vertex.
+ *   not searched  R <= 0 or NaN: the miss record, nothing is read.  A point with a NaN or infinite component has no candidate (every
+ *                 key it forms is +inf or NaN): the miss record.
+ *   side          +1 in front of a triangle (the side its winding's normal cross(eAB, eAC) points to) or outside a sphere, -1 behind /
+ *                 inside.  As the sign of a distance field it is reliable for closed, consistently wound meshes away from creases: where
+ *                 the closest point lies on an edge or vertex the sign is that of ONE of the faces that meet there (the lowest index), which
+ *                 at a sharp crease can differ from the inside / outside of the solid.
+ *   scene, state  as for ray queries: the queue is settled, the scene made current, the box padding widened for the largest finite
+ *                 |coordinate| among points with R > 0.  Nothing else moves — not the image, feature, filter or other query state, and no
+ *                 rt_stats field except bvhBuilds / bvhRebuilds / bvhRepads.  The library's slices ("closest_slice") and rt_multi are
+ *                 invisible; a batch cut anywhere into two calls gives the bits of one.
+ *   errors        a null handle -1; n == 0 returns 0; n < 0, a null buffer with n > 0, and for the device entry a pointer of another
+ *                 device or one not 16-byte aligned: -2 with a message, and nothing changes.                                         */
+typedef struct rt_closest {             /* 64 B; nothing within reach: dst = +inf, point = normal = 0, kind = RT_HIT_NONE, indices -1, u = v = 0, side = 0 */
+    float   dst;                        /* unsigned distance from the query point to `point`                                            */
+    float   point[3];                   /* the closest point of the closest primitive                                                   */
+    float   normal[3];                  /* the shading normal there, as rt_hit.normal defines it                                        */
+    int32_t kind;                       /* RT_HIT_*                                                                                     */
+    int32_t primitive;                  /* exactly as in rt_hit                                                                         */
+    int32_t chunk;
+    int32_t mesh;
+    float   u, v;                       /* triangle: point = A + (B - A) * u + (C - A) * v, rt_hit's convention; else 0                 */
+    int32_t side;                       /* +1 / -1 / 0, see above                                                                       */
+    int32_t _reserved[2];
+} rt_closest;
+typedef struct rt_closest_info {        /* 40 B */
+    int32_t  calls;                     /* calls so far                                                                                 */
+    int32_t  _reserved;
+    double   lastKernelMs, totalKernelMs;   /* HIP-event time of the launches of the last host-entry call / summed                      */
+    uint64_t lastNodeSteps, lastPrimTests;  /* option "closest_count" = 1: node steps and primitive tests (spheres and triangles) of all
+                                               points of the last call; else 0                                                          */
+} rt_closest_info;
+/* Host memory; returns when the results are in out.  The points go through device buffers of the context in slices of "closest_slice"
+ * points, sized to min(n, slice).                                                                                                */
+int rt_closest_points       (rt_ctx* ctx, const rt_ray* points, int n, rt_closest* out);
+/* Device memory of the context's GPU (points: n rt_ray, out: n rt_closest, both 16-byte aligned), ordered on the context's stream as
+ * rt_trace_rays_device is, with its one synchronisation for the origin bound; rt_closest_info counts the call and keeps the host
+ * entry's times.  After a counting call rt_get_closest_info waits for the stream once to fetch the counts.                        */
+int rt_closest_points_device(rt_ctx* ctx, const void* points, int n, void* out);
+int rt_get_closest_info     (rt_ctx* ctx, rt_closest_info* out);
+
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
  * target is the colour of RayTracing.shader:388); the definition below is this library's, built from the reference's own steps.
@@ -905,6 +986,8 @@ int rt_multi_gather          (rt_multi* m, const rt_ray* points, int n, const rt
 /* Visibility gathers behind the handle: the same slices, context i's points keeping their stream indices — bitwise the single-context
  * result.                                                                                                                        */
 int rt_multi_visibility      (rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out);
+/* Closest-point queries behind the handle: the same slices — bitwise the single-context result.                                   */
+int rt_multi_closest_points  (rt_multi* m, const rt_ray* points, int n, rt_closest* out);
 /* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
  * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
  * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
@@ -935,7 +1018,7 @@ int rt_multi_read_variance        (rt_multi* m, float* var, size_t n_floats);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_vdenoise_params" | "rt_vdenoise_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_vdenoise_params" | "rt_vdenoise_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" | "rt_closest" | "rt_closest_info" */
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,12 @@ VISIBILITY_PARAMS = np.dtype([("samples", "<i4"), ("seed", "<u4"), ("firstIndex"
 VISIBILITY_INFO = np.dtype([("samples", "<i4"), ("lastSampleLanes", "<i4"), ("calls", "<i4"), ("mode", "<i4"),
                             ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8")])
 assert VISIBILITY_PARAMS.itemsize == 32 and VISIBILITY_INFO.itemsize == 32
+# closest-point queries (rt_closest_points): the record of a point's nearest surface and the state of the last call
+CLOSEST = np.dtype([("dst", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("kind", "<i4"), ("primitive", "<i4"), ("chunk", "<i4"),
+                    ("mesh", "<i4"), ("u", "<f4"), ("v", "<f4"), ("side", "<i4"), ("_reserved", "<i4", 2)])
+CLOSEST_INFO = np.dtype([("calls", "<i4"), ("_reserved", "<i4"), ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8"),
+                         ("lastNodeSteps", "<u8"), ("lastPrimTests", "<u8")])
+assert CLOSEST.itemsize == 64 and CLOSEST_INFO.itemsize == 40
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
@@ -132,6 +138,7 @@ SYMBOLS = [
     "rt_trace_radiance", "rt_trace_radiance_device", "rt_get_radiance_info", "rt_multi_trace_radiance",
     "rt_gather", "rt_gather_device", "rt_get_gather_info", "rt_multi_gather",
     "rt_visibility", "rt_visibility_device", "rt_get_visibility_info", "rt_multi_visibility",
+    "rt_closest_points", "rt_closest_points_device", "rt_get_closest_info", "rt_multi_closest_points",
 ]
 
 _lib = None
@@ -255,6 +262,9 @@ def load_library() -> ctypes.CDLL:
     for n in ("rt_visibility", "rt_visibility_device", "rt_multi_visibility"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.rt_get_visibility_info.argtypes = [c_void_p, c_void_p]
+    for n in ("rt_closest_points", "rt_closest_points_device", "rt_multi_closest_points"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.rt_get_closest_info.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -270,7 +280,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_vdenoise_params", VDENOISE_PARAMS), ("rt_vdenoise_info", VDENOISE_INFO),
                      ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO),
                      ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO),
-                     ("rt_visibility_params", VISIBILITY_PARAMS), ("rt_visibility_info", VISIBILITY_INFO)):
+                     ("rt_visibility_params", VISIBILITY_PARAMS), ("rt_visibility_info", VISIBILITY_INFO),
+                     ("rt_closest", CLOSEST), ("rt_closest_info", CLOSEST_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -298,6 +309,13 @@ def _ray_array(rays) -> np.ndarray:
 def _query_host(call, handle, rays, any_hit: bool, check, what):
     r = _ray_array(rays)
     out = np.zeros(r.shape[0], np.uint8) if any_hit else np.zeros(r.shape[0], HIT)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
+def _closest_host(call, handle, points, check, what):
+    r = _ray_array(points)
+    out = np.zeros(r.shape[0], CLOSEST)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
     return out
 
@@ -615,6 +633,29 @@ class Tracer:
         self._check(self._lib.rt_get_visibility_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_visibility_info")
         return {k: s[k].item() for k in VISIBILITY_INFO.names}
 
+    # -- closest-point queries
+    def closest_points(self, points):
+        """rt_closest_points: the nearest sphere or triangle to every point, where on it, how far and on which side.  points: a RAY array
+        or float32 (n, 8) — the point, the search radius in tMax (inf: unbounded), the rest unread -> a CLOSEST array.  No params are
+        needed.  A float32 CUDA tensor (n, 8) on the context's device takes the device entry, ordered with torch's current stream as
+        trace_rays is, and returns a float32 (n, 16) tensor (the CLOSEST records)."""
+        if not _is_tensor(points):
+            return _closest_host(self._lib.rt_closest_points, self._ctx, points, self._check, "rt_closest_points")
+        import torch
+        points = self._ray_tensor(points)
+        n = int(points.shape[0])
+        out = torch.empty((n, 16), dtype=torch.float32, device=points.device)
+        self._on_torch_stream(points.device, lambda: self._lib.rt_closest_points_device(self._ctx, c_void_p(points.data_ptr()), n, c_void_p(out.data_ptr())),
+                              "rt_closest_points_device")
+        return out
+
+    closest_points_device = closest_points  # (a tensor takes rt_closest_points_device; the name says so at the call site)
+
+    def closest_info(self) -> dict:
+        s = np.zeros((), CLOSEST_INFO)
+        self._check(self._lib.rt_get_closest_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_closest_info")
+        return {k: s[k].item() for k in CLOSEST_INFO.names if k != "_reserved"}
+
     # -- rendering
     def render_frame(self, frame: int):
         self._check(self._lib.rt_render_frame(self._ctx, frame), "rt_render_frame")
@@ -911,6 +952,10 @@ class MultiTracer:
     def occluded(self, rays) -> np.ndarray:
         """rt_multi_occluded: Tracer.occluded over the contexts (host arrays)."""
         return _query_host(self._lib.rt_multi_occluded, self._m, rays, True, self._check, "rt_multi_occluded")
+
+    def closest_points(self, points) -> np.ndarray:
+        """rt_multi_closest_points: Tracer.closest_points over the contexts (host arrays), one contiguous slice of the batch each."""
+        return _closest_host(self._lib.rt_multi_closest_points, self._m, points, self._check, "rt_multi_closest_points")
 
     def trace_radiance(self, rays, samples=None, seed=0, first_index=0) -> np.ndarray:
         """rt_multi_trace_radiance: Tracer.trace_radiance over the contexts (host arrays), every ray keeping its stream index."""

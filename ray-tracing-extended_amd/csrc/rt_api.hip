@@ -33,6 +33,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_radiance.hpp"
 #include "rt_gather.hpp"
 #include "rt_visibility.hpp"
+#include "rt_closest.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -230,11 +231,18 @@ struct rt_ctx : ErrOwner {
     int opt_primary_lists = 1;                      // 1: camera rays of a static camera start from their pixel's candidate leaves (k_stream); 0: always from the root
     DevBuf<float> d_park;              // k_stream, Philox mode: parked sub-stream sums
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
-    // queries (rt_trace_rays ... rt_visibility): staging of the host entries (one slice of rays or points in, one slice of results out,
-    // in bytes), the device entries' origin bound, and the sampled families' info records (QueryFamily indexes them)
+    // queries (rt_trace_rays ... rt_closest_points): staging of the host entries (one slice of rays or points in, one slice of results
+    // out, in bytes), the device entries' origin bound, and the timed families' info records (QueryFamily indexes them; closest-point
+    // queries use calls and the two times of theirs)
     DevBuf<float4> d_q_rays; DevBuf<uint8_t> d_q_out;
     DevBuf<unsigned int> d_q_bound;
-    rt_gather_info query_info[3]{};
+    rt_gather_info query_info[4]{};
+    // closest-point queries: points per launch; 1 = the counting kernel (node steps and primitive tests of a call, summed on the device
+    // and fetched by rt_get_closest_info when counts_pending says the last call left some there)
+    int opt_closest_slice = 1 << 22, opt_closest_count = 0;
+    DevBuf<unsigned long long> d_closest_counts;
+    bool closest_counts_pending = false;
+    unsigned long long closest_counts[2]{};
     int opt_visibility_slice = 1 << 22; // visibility gathers: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_gather_slice = 1 << 20;     // gather queries: points per launch (and per staging slice of the host entry); the result never depends on it
     int opt_radiance_slice = 1 << 22;   // radiance queries: rays per launch (and per staging slice of the host entry); the result never depends on it
@@ -1313,13 +1321,13 @@ int cover_origins_device(rt_ctx* c, const float4* rays, int n)
     return cover_origins(c, u2f(bits));
 }
 
-// ---- the one path of the four query families ----------------------------------------------------------------------------------------
+// ---- the one path of the five query families ----------------------------------------------------------------------------------------
 // Ray queries (rt_trace_rays / rt_occluded, csrc/rt_query.hpp), radiance queries (rt_trace_radiance, csrc/rt_radiance.hpp), gather
-// queries (rt_gather, csrc/rt_gather.hpp) and visibility gathers (rt_visibility, csrc/rt_visibility.hpp) all take n rt_ray (2 float4
-// each) and write a fixed number of bytes per item.  A family supplies a description of the call (QueryCall, built by its *_call once
+// queries (rt_gather, csrc/rt_gather.hpp), visibility gathers (rt_visibility, csrc/rt_visibility.hpp) and closest-point queries
+// (rt_closest_points, csrc/rt_closest.hpp) all take n rt_ray (2 float4 each) and write a fixed number of bytes per item.  A family supplies a description of the call (QueryCall, built by its *_call once
 // the arguments are known to be good) and a function that fills its kernel's Args for one launch; everything between the exported
 // entry and hipLaunchKernel is below, once.
-enum QueryFamily { kRadiance, kGather, kVisibility, kRays };    // (the first three: the sampled families, indices of rt_ctx::query_info)
+enum QueryFamily { kRadiance, kGather, kVisibility, kClosest, kRays };  // (the first three: the sampled families; the first four are timed and index rt_ctx::query_info)
 
 // The sampled families' params and info records have one layout: rt_radiance_* keeps reserved words where the other two have `mode`.
 // rt_gather_params / rt_gather_info are the form the path works with.
@@ -1349,7 +1357,9 @@ struct QueryCall {
     hipError_t (*launch)(rt_ctx*, const QueryCall&, const QuerySlice&);     // fills the family's Args and launches its kernel
     int sample_lanes_log2;          // S = 16 / 4 / 1 lanes share an item's samples (include/rt.h RT_RNG_PHILOX); ray queries: 0
     rt_gather_params p;             // the sampled families' params, defaults filled in (mode 0 for radiance queries)
-    bool sampled() const { return family != kRays; }
+    int (*begin)(rt_ctx*);          // what the family does once per call, after the scene is current and before the first launch; may be null
+    bool sampled() const { return family < kClosest; }      // takes params and draws samples
+    bool timed() const { return family != kRays; }          // has an info record with calls and kernel times
 };
 
 // What every launch function ends with: the fields all four Args share, then the launch on the context's stream
@@ -1384,12 +1394,13 @@ int launch_slices(rt_ctx* c, const QueryCall& q, const float4* in, void* out, in
 }
 
 // Host memory in, host memory out: a slice at a time through the context's staging, sized to min(n, slice) items (an SH9 gather slice
-// is 144 B per point).  The sampled families time each slice's launches with the context's one event pair, so they wait for every
+// is 144 B per point).  The timed families time each slice's launches with the context's one event pair, so they wait for every
 // slice before the next records the events again; ray queries record nothing and wait once, at the end.
 int query_host(rt_ctx* c, const QueryCall& q, const rt_ray* in, int n, void* out)
 {
     if (n == 0) return 0;
     { int r = query_prepare(c, query_origin_bound(in, n)); if (r) return r; }
+    if (q.begin) { int r = q.begin(c); if (r) return r; }
     const size_t staged = (size_t)std::min(n, q.slice);
     RT_HIP(c, c->d_q_rays.ensure(2 * staged));
     RT_HIP(c, c->d_q_out.ensure(q.out_bytes * staged));
@@ -1397,17 +1408,17 @@ int query_host(rt_ctx* c, const QueryCall& q, const rt_ray* in, int n, void* out
     for (int first = 0; first < n; first += q.slice) {
         const int cnt = std::min(q.slice, n - first);
         RT_HIP(c, hipMemcpyAsync(c->d_q_rays.p, in + first, (size_t)cnt * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        if (q.sampled()) RT_HIP(c, hipEventRecord(c->ev0, c->stream));
+        if (q.timed()) RT_HIP(c, hipEventRecord(c->ev0, c->stream));
         { int r = launch_slices(c, q, c->d_q_rays.p, c->d_q_out.p, cnt, q.p.firstIndex + (uint32_t)first); if (r) return r; }
-        if (q.sampled()) RT_HIP(c, hipEventRecord(c->ev1, c->stream));
+        if (q.timed()) RT_HIP(c, hipEventRecord(c->ev1, c->stream));
         RT_HIP(c, hipMemcpyAsync(static_cast<char*>(out) + q.out_bytes * (size_t)first, c->d_q_out.p, q.out_bytes * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
-        if (!q.sampled()) continue;
+        if (!q.timed()) continue;
         RT_HIP(c, hipStreamSynchronize(c->stream));
         float ms = 0.f;
         RT_HIP(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
         ms_sum += ms;
     }
-    if (!q.sampled()) { RT_HIP(c, hipStreamSynchronize(c->stream)); return 0; }
+    if (!q.timed()) { RT_HIP(c, hipStreamSynchronize(c->stream)); return 0; }
     rt_gather_info& info = c->query_info[q.family];
     info.calls++; info.lastKernelMs = ms_sum; info.totalKernelMs += ms_sum;
     return 0;
@@ -1425,14 +1436,15 @@ int query_device(rt_ctx* c, const QueryCall& q, const void* in, int n, void* out
         return fail(c, -2, "%s: %s%s%s must be 16-byte aligned", q.what, q.in_word, q.out_aligned ? " and " : "", q.out_aligned ? q.out_word : "");
     { int r = prepare_scene(c); if (r) return r; }
     { int r = cover_origins_device(c, static_cast<const float4*>(in), n); if (r) return r; }
+    if (q.begin) { int r = q.begin(c); if (r) return r; }
     { int r = launch_slices(c, q, static_cast<const float4*>(in), out, n, q.p.firstIndex); if (r) return r; }
-    if (q.sampled()) c->query_info[q.family].calls++;
+    if (q.timed()) c->query_info[q.family].calls++;
     return 0;
 }
 
-// ---- the four descriptions --------------------------------------------------------------------------------------------------------
-// A *_call checks the arguments of a call to `what` and describes it; all four have the signature of QueryDescribe (ray queries take
-// no params).  The checks come in one order: params set (where the family needs them), n and the pointers, the defaults of
+// ---- the five descriptions --------------------------------------------------------------------------------------------------------
+// A *_call checks the arguments of a call to `what` and describes it; all have the signature of QueryDescribe (ray queries and
+// closest-point queries take no params).  The checks come in one order: params set (where the family needs them), n and the pointers, the defaults of
 // params == NULL, samples, mode, reserved words.
 using QueryDescribe = int (*)(rt_ctx* c, const char* what, const void* in, int n, const void* params, const void* out, QueryCall& q);
 
@@ -1543,6 +1555,38 @@ int visibility_call(rt_ctx* c, const char* what, const void* points, int n, cons
     { int r = sampled_arguments(c, q, false, points, n, params, RT_VISIBILITY_DEFAULT_SAMPLES, out, 3, "none of RT_VIS_COSINE, RT_VIS_SH9, RT_VIS_DISTANCE", "rt_visibility_params"); if (r) return r; }
     q.out_bytes = sizeof(float4) * (q.p.mode == RT_VIS_SH9 ? 3 : 1);
     return 0;
+}
+
+// Counting calls start from zero; the sums stay on the device until rt_get_closest_info asks for them (the device entry does not wait)
+int begin_closest(rt_ctx* c)
+{
+    c->closest_counts[0] = c->closest_counts[1] = 0;
+    c->closest_counts_pending = false;
+    if (!c->opt_closest_count) return 0;
+    RT_HIP(c, c->d_closest_counts.ensure(2));
+    RT_HIP(c, hipMemsetAsync(c->d_closest_counts.p, 0, 2 * sizeof(unsigned long long), c->stream));
+    c->closest_counts_pending = true;
+    return 0;
+}
+hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
+{
+    rtk::ClosestArgs A{};
+    A.order = c->d_order.p;
+    A.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
+    A.points = s.in; A.out = static_cast<float4*>(s.out);
+    const bool compact = c->opt_compact_nodes != 0;
+    if (c->opt_closest_count) {
+        A.counters = c->d_closest_counts.p;
+        return launch_slice(c, compact ? (const void*)rtk::k_closest<true, true> : (const void*)rtk::k_closest<false, true>, s, A);
+    }
+    return launch_slice(c, compact ? (const void*)rtk::k_closest<true, false> : (const void*)rtk::k_closest<false, false>, s, A);
+}
+// n rt_closest (4 float4 each); no params of either kind
+int closest_call(rt_ctx* c, const char* what, const void* points, int n, const void*, const void* out, QueryCall& q)
+{
+    q = QueryCall{ kClosest, what, "points", "out", c->opt_closest_slice, sizeof(rt_closest), true, nullptr, launch_closest };
+    q.begin = begin_closest;
+    return query_pointers(c, q, points, n, out);
 }
 
 // Every exported query entry of a context: settle, check and describe, then the host or the device path
@@ -1998,6 +2042,8 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_gather_info")) return (int)sizeof(rt_gather_info);
     if (!std::strcmp(name, "rt_visibility_params")) return (int)sizeof(rt_visibility_params);
     if (!std::strcmp(name, "rt_visibility_info")) return (int)sizeof(rt_visibility_info);
+    if (!std::strcmp(name, "rt_closest")) return (int)sizeof(rt_closest);
+    if (!std::strcmp(name, "rt_closest_info")) return (int)sizeof(rt_closest_info);
     return -1;
 }
 
@@ -2215,6 +2261,8 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "queue_linger_us")) { if (value < 0 || value > 1000000) return fail(c, -2, "queue_linger_us must be in [0,1000000]"); c->opt_queue_linger_us = value; }
     else if (!std::strcmp(name, "gather_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "gather_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_gather_slice = value; }
     else if (!std::strcmp(name, "visibility_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "visibility_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_visibility_slice = value; }
+    else if (!std::strcmp(name, "closest_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "closest_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_closest_slice = value; }
+    else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
     else return fail(c, -2, "unknown option '%s'", name);
@@ -2381,6 +2429,24 @@ int rt_gather(rt_ctx* c, const rt_ray* points, int n, const rt_gather_params* pa
 int rt_gather_device(rt_ctx* c, const void* points, int n, const rt_gather_params* params, void* out) { return query_entry(c, gather_call, "rt_gather_device", true, points, n, params, out); }
 int rt_visibility(rt_ctx* c, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return query_entry(c, visibility_call, "rt_visibility", false, points, n, params, out); }
 int rt_visibility_device(rt_ctx* c, const void* points, int n, const rt_visibility_params* params, void* out) { return query_entry(c, visibility_call, "rt_visibility_device", true, points, n, params, out); }
+int rt_closest_points(rt_ctx* c, const rt_ray* points, int n, rt_closest* out) { return query_entry(c, closest_call, "rt_closest_points", false, points, n, nullptr, out); }
+int rt_closest_points_device(rt_ctx* c, const void* points, int n, void* out) { return query_entry(c, closest_call, "rt_closest_points_device", true, points, n, nullptr, out); }
+// The counts of a counting call are fetched here, once: the call's one wait when it came through the device entry
+int rt_get_closest_info(rt_ctx* c, rt_closest_info* out)
+{
+    if (!c || !out) return -1;
+    if (c->closest_counts_pending) {
+        RT_HIP(c, hipSetDevice(c->device));
+        RT_HIP(c, hipMemcpyAsync(c->closest_counts, c->d_closest_counts.p, sizeof c->closest_counts, hipMemcpyDeviceToHost, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));
+        c->closest_counts_pending = false;
+    }
+    const rt_gather_info& g = c->query_info[kClosest];
+    *out = rt_closest_info{};
+    out->calls = g.calls; out->lastKernelMs = g.lastKernelMs; out->totalKernelMs = g.totalKernelMs;
+    out->lastNodeSteps = c->closest_counts[0]; out->lastPrimTests = c->closest_counts[1];
+    return 0;
+}
 // (the three info records are one layout, checked where QueryFamily is declared)
 int rt_get_gather_info(rt_ctx* c, rt_gather_info* out)
 {
@@ -2810,6 +2876,7 @@ int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded)
 int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return multi_query(m, radiance_call, "rt_multi_trace_radiance", "rt_trace_radiance", true, rays, n, params, rgba); }
 int rt_multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return multi_query(m, gather_call, "rt_multi_gather", "rt_gather", true, points, n, params, out); }
 int rt_multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return multi_query(m, visibility_call, "rt_multi_visibility", "rt_visibility", false, points, n, params, out); }
+int rt_multi_closest_points(rt_multi* m, const rt_ray* points, int n, rt_closest* out) { return multi_query(m, closest_call, "rt_multi_closest_points", "rt_closest_points", false, points, n, nullptr, out); }
 
 // Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands
 int rt_multi_render_aov(rt_multi* m, int first_frame, int n_frames)

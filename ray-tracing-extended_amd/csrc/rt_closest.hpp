@@ -1,0 +1,270 @@
+// rt_closest.hpp — closest-point queries: the nearest surface to a POINT the caller supplies, how far away it is and on which side of
+// it the point lies (include/rt.h rt_closest, rt_closest_points).  Signed-distance baking, probe placement, snapping, proximity tests.
+// Geometry only: no rt_params field is read and nothing is shaded.
+//
+// Definition (include/rt.h "closest-point queries"; tests/closest_oracle.c restates it as a brute-force loop): every sphere and every
+// triangle of the tree gets a float32 key k, its squared distance, every product and sum rounded on its own; a candidate counts when
+// k < R * R and the smallest (k, kind, uploaded index) wins — whatever the tree, the builder, the leaf size or the visiting order.
+//
+// k_ray_query's launch: one point per lane, 256-thread blocks, one launch per slice, lane_stack's LDS stack with the global overflow.
+// The traversal is ordered by distance, not by a slab test: a node step computes, for each of the four children,
+//     lb2 = sum over the axes of max(lo - p, p - hi, 0)^2
+// visits the nearest child next and pushes the others, farthest first.  A child is skipped only when lb2 > kb * (1 + 2^-19), kb the
+// best key so far (R * R at the start): DESIGN.md "Closest-point queries" derives that this never skips a triangle whose key could
+// count, equal keys included (a tie can still win on its index).  Entries already on the stack are not culled again when they are
+// popped: a stale internal node costs one node step whose children are all skipped, a stale leaf its triangle tests.
+#pragma once
+#include "rt_query.hpp"
+
+namespace rtk {
+
+static_assert(sizeof(rt_closest) == 64, "a closest-point record is four float4 stores");
+
+struct ClosestArgs {
+    const float4* points;       // [n*2]  rt_ray: (p, R) (-, -)
+    float4* out;                // [n*4]  rt_closest
+    const uint32_t* order;      // BVH order -> uploaded triangle (d_order)
+    const uint32_t* tri_mesh;   // uploaded triangle -> mesh (local uploads); null = world-space upload
+    unsigned long long* counters;   // counting build: [0] node steps, [1] primitive tests (spheres and triangles) of the call so far
+    uint32_t* gstack; unsigned int gstack_stride;   // as QueryArgs
+    int n;
+    int stack_cap;
+};
+
+// kb * kCullSlack is the largest lower bound that is still visited; never below kCullFloor, so that no square that matters to the
+// comparison is a denormal
+constexpr float kCullSlack = 1.0f + 0x1p-19f;
+constexpr float kCullFloor = 0x1p-100f;
+
+// The closest point of triangle (A, A + ab, A + ac) to p as (u, v), point = A + ab * u + ac * v: the seven-region test (Ericson,
+// Real-Time Collision Detection 5.1.5) on A, ab, ac and ap = p - A alone, in the operation order include/rt.h freezes.  The regions are
+// tested in the order A, B, AB, C, AC, BC, interior; here the first that holds is picked by selects, and ONE quotient per coordinate is
+// taken from the numerator and denominator that region names (a vertex: 0 / 1 or 1 / 1, exact).  Every comparison with a NaN is false,
+// so a NaN anywhere ends in the interior formula and a NaN key, which never counts.
+__device__ __forceinline__ void closest_on_triangle(v3 p, v3 A, v3 ab, v3 ac, float& k, float& u, float& v)
+{
+    const v3 ap = p - A;
+    const float d1 = rtm::dot(ab, ap), d2 = rtm::dot(ac, ap);
+    const v3 bp = ap - ab;
+    const float d3 = rtm::dot(ab, bp), d4 = rtm::dot(ac, bp);
+    const v3 cp = ap - ac;
+    const float d5 = rtm::dot(ab, cp), d6 = rtm::dot(ac, cp);
+    const float vc = d1 * d4 - d3 * d2;
+    const float vb = d5 * d2 - d1 * d6;
+    const float va = d3 * d6 - d5 * d4;
+    const float d43 = d4 - d3, d56 = d5 - d6;
+    const float den = (va + vb) + vc;
+    const bool rA = d1 <= 0.0f && d2 <= 0.0f;
+    const bool rB = d3 >= 0.0f && d4 <= d3;
+    const bool rAB = vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f;
+    const bool rC = d6 >= 0.0f && d5 <= d6;
+    const bool rAC = vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f;
+    const bool rBC = va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f;
+    // lowest priority first, each earlier region overriding the later ones
+    float un = vb, ud = den, vn = vc, vd = den;                             // interior
+    if (rBC) { un = 0.0f; ud = 1.0f; vn = d43; vd = d43 + d56; }            // (u = 1 - v below)
+    if (rAC) { un = 0.0f; ud = 1.0f; vn = d2; vd = d2 - d6; }
+    if (rC)  { un = 0.0f; ud = 1.0f; vn = 1.0f; vd = 1.0f; }
+    if (rAB) { un = d1; ud = d1 - d3; vn = 0.0f; vd = 1.0f; }
+    if (rB)  { un = 1.0f; ud = 1.0f; vn = 0.0f; vd = 1.0f; }
+    if (rA)  { un = 0.0f; ud = 1.0f; vn = 0.0f; vd = 1.0f; }
+    const bool edge_bc = rBC && !(rA || rB || rAB || rC || rAC);
+    const bool interior = !(rA || rB || rAB || rC || rAC || rBC);
+    u = un / ud;
+    v = vn / vd;
+    if (edge_bc) u = 1.0f - v;
+    if (interior) {
+        // rounding in va, vb, vc can leave the quotients just outside the triangle: bring them back (selects: a NaN stays a NaN)
+        u = u < 0.0f ? 0.0f : u;
+        u = u > 1.0f ? 1.0f : u;
+        v = v < 0.0f ? 0.0f : v;
+        const float room = 1.0f - u;
+        v = v > room ? room : v;
+    }
+    const v3 q = (A + ab * u) + ac * v;
+    const v3 e = p - q;
+    k = rtm::dot(e, e);
+}
+
+// The four children of node `cur`: their squared lower bounds sorted ascending with their references; a child that is empty or whose
+// bound exceeds thr carries kNone (and +inf).
+template <bool H>
+__device__ __forceinline__ void closest_node_step(const float4* __restrict__ nodes, uint32_t cur, v3 p, float thr,
+                                                  float& l0, float& l1, float& l2, float& l3,
+                                                  uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
+{
+    const char* nb = reinterpret_cast<const char*>(nodes);
+    const uint32_t base = cur << 7;                                         // (the host refuses BVHs of 2^25 nodes or more)
+    const float INF = __builtin_inff();
+#define RT_LB(LOX, HIX, LOY, HIY, LOZ, HIZ, LK)                                                                          \
+    {                                                                                                                    \
+        const float dx_ = __builtin_fmaxf(__builtin_fmaxf((LOX) - p.x, p.x - (HIX)), 0.0f);                              \
+        const float dy_ = __builtin_fmaxf(__builtin_fmaxf((LOY) - p.y, p.y - (HIY)), 0.0f);                              \
+        const float dz_ = __builtin_fmaxf(__builtin_fmaxf((LOZ) - p.z, p.z - (HIZ)), 0.0f);                              \
+        LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
+    }
+    if constexpr (H) {
+        // Node4h (bvh.hpp): plane set 0 = (minx, miny), set 3 = (maxx, maxy), the first z quad = (minz, maxz), children, origin: five
+        // loads.  plane = origin + offset is one rounding of a sum whose exact value lies outside the f32 box (the offsets were rounded
+        // outwards from it), and rounding is monotone: the plane used here is outside the f32 box's as well
+        const uint4 lo = *reinterpret_cast<const uint4*>(nb + base), hi = *reinterpret_cast<const uint4*>(nb + (base + 48u));
+        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + 64u));
+        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
+        const float4 og = *reinterpret_cast<const float4*>(nb + (base + 112u));
+        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
+#define RT_LBH(XW, YW, ZLW, ZHW, E, LK)                                                                                   \
+        RT_LB(og.x + (float)as_half2(lo.XW).E, og.x + (float)as_half2(hi.XW).E, og.y + (float)as_half2(lo.YW).E,         \
+              og.y + (float)as_half2(hi.YW).E, og.z + (float)as_half2(zz.ZLW).E, og.z + (float)as_half2(zz.ZHW).E, LK)
+        RT_LBH(x, z, x, z, x, l0) RT_LBH(x, z, x, z, y, l1) RT_LBH(y, w, y, w, x, l2) RT_LBH(y, w, y, w, y, l3)
+#undef RT_LBH
+    } else {
+        const float4 mnx = *reinterpret_cast<const float4*>(nb + base), mny = *reinterpret_cast<const float4*>(nb + (base + 16u));
+        const float4 mnz = *reinterpret_cast<const float4*>(nb + (base + 32u)), mxx = *reinterpret_cast<const float4*>(nb + (base + 48u));
+        const float4 mxy = *reinterpret_cast<const float4*>(nb + (base + 64u)), mxz = *reinterpret_cast<const float4*>(nb + (base + 80u));
+        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
+        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
+        RT_LB(mnx.x, mxx.x, mny.x, mxy.x, mnz.x, mxz.x, l0) RT_LB(mnx.y, mxx.y, mny.y, mxy.y, mnz.y, mxz.y, l1)
+        RT_LB(mnx.z, mxx.z, mny.z, mxy.z, mnz.z, mxz.z, l2) RT_LB(mnx.w, mxx.w, mny.w, mxy.w, mnz.w, mxz.w, l3)
+    }
+#undef RT_LB
+    // an empty slot holds a (+inf, -inf) box: its bound is +inf, which is not above a threshold of +inf — it is dropped by its reference
+    if (c0 == kNone || l0 > thr) { c0 = kNone; l0 = INF; }
+    if (c1 == kNone || l1 > thr) { c1 = kNone; l1 = INF; }
+    if (c2 == kNone || l2 > thr) { c2 = kNone; l2 = INF; }
+    if (c3 == kNone || l3 > thr) { c3 = kNone; l3 = INF; }
+    // sorted by (bound, dropped last): a kept child can have a bound of +inf too (thr = +inf, a point so far away that the squares
+    // overflow), so the reference breaks the tie
+#define RT_CSWAP(LA, CA, LB, CB) { const bool s_ = LB < LA || (LB == LA && CA == kNone); const float lt_ = s_ ? LB : LA, lu_ = s_ ? LA : LB; \
+                                   const uint32_t ct_ = s_ ? CB : CA, cu_ = s_ ? CA : CB; LA = lt_; LB = lu_; CA = ct_; CB = cu_; }
+    RT_CSWAP(l0, c0, l1, c1) RT_CSWAP(l2, c2, l3, c3) RT_CSWAP(l0, c0, l2, c2) RT_CSWAP(l1, c1, l3, c3) RT_CSWAP(l1, c1, l2, c2)
+#undef RT_CSWAP
+}
+
+template <bool H, bool COUNT>
+__global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q)
+{
+    extern __shared__ uint32_t lds_stack[];
+    const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
+    const bool present = i < (unsigned)Q.n;
+    if (!COUNT && !present) return;                                     // (the counting build keeps every lane for the wave's sums)
+    const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
+    const float INF = __builtin_inff(), FMAX = 3.4028235e38f;
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (present) r0 = Q.points[2 * (size_t)i];
+    const v3 p = rtm::mk(r0.x, r0.y, r0.z);
+    const float R = r0.w;
+    // R <= 0 or NaN: not searched.  A point with a component that is not finite has no candidate either — every key it forms is +inf
+    // or NaN, and neither is below R * R — so it is answered without a search (its bounds would be +inf or NaN at every node)
+    const bool searched = present && R > 0.0f && __builtin_fabsf(p.x) <= FMAX && __builtin_fabsf(p.y) <= FMAX && __builtin_fabsf(p.z) <= FMAX;
+    float kb = R * R;                                                   // the best key so far; before the first candidate, the bound
+    uint32_t best = kNone;                                              // kNone | sphere index | kTriBit + triangle in BVH order
+    float bu = 0.0f, bv = 0.0f;
+    uint32_t n_nodes = 0, n_prims = 0;
+
+    if (searched) {
+        for (int s = 0; s < S.ns; ++s) {
+            const float4 sp = S.sph_geom[s];
+            const v3 m = p - rtm::mk(sp.x, sp.y, sp.z);
+            const float len = rtm::sqrt_(rtm::dot(m, m));
+            const float ds = __builtin_fabsf(len - sp.w);
+            const float k = ds * ds;
+            if (COUNT) ++n_prims;
+            if (k < kb) { kb = k; best = (uint32_t)s; }                // strict: the lower index keeps a tie
+        }
+        if (S.nn > 0) {
+            const float4* nodes = H ? S.nodes_h : S.nodes;
+            int sp = 0;
+            uint32_t cur = 0;                                           // root
+            uint32_t top = kNone;                                       // the top of the stack in a register, as in closest_hit
+#define RT_PUSH(X) { if (top != kNone) stk.push(sp, top); top = (X); }
+#define RT_POP()   { cur = top; top = (sp > 0) ? stk.pop(sp) : kNone; }
+            while (cur != kNone) {
+                while ((int)cur >= 0) {
+                    if (COUNT) ++n_nodes;
+                    float l0, l1, l2, l3;
+                    uint32_t c0, c1, c2, c3;
+                    closest_node_step<H>(nodes, cur, p, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
+                    if (c3 != kNone) RT_PUSH(c3)
+                    if (c2 != kNone) RT_PUSH(c2)
+                    if (c1 != kNone) RT_PUSH(c1)
+                    if (c0 != kNone) cur = c0;
+                    else RT_POP()
+                }
+                if (cur != kNone) {
+                    const uint32_t first = (cur & 0x7FFFFFFFu) >> 2, count = (cur & 3u) + 1u;
+                    for (uint32_t j = 0; j < count; ++j) {
+                        const uint32_t ti = first + j;
+                        float4 g0, g1, g2;
+                        load_tri(S.tri_geo, ti, g0, g1, g2);
+                        float k, u, v;
+                        closest_on_triangle(p, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), k, u, v);
+                        if (COUNT) ++n_prims;
+                        if (k <= kb) {
+                            bool take = k < kb;
+                            // equal keys: a sphere keeps the tie (and so does the bound R * R while nothing has been found); between
+                            // triangles the lower uploaded index wins
+                            if (!take && best != kNone && (best & kTriBit)) take = Q.order[ti] < Q.order[best & ~kTriBit];
+                            if (take) { kb = k; best = kTriBit | ti; bu = u; bv = v; }
+                        }
+                    }
+                    RT_POP()
+                }
+            }
+#undef RT_PUSH
+#undef RT_POP
+        }
+    }
+
+    if (present) {
+        float4 w0, w1, w2, w3;
+        const float NEG1 = __int_as_float(-1);
+        if (best == kNone) {
+            w0 = make_float4(INF, 0.f, 0.f, 0.f);
+            w1 = make_float4(0.f, 0.f, 0.f, __int_as_float(RT_HIT_NONE));
+            w2 = make_float4(NEG1, NEG1, NEG1, 0.f);
+            w3 = make_float4(0.f, __int_as_float(0), 0.f, 0.f);
+        } else {
+            Hit h; h.id = best; h.t = 0.0f; h.u = bu; h.v = bv;
+            v3 point, normal; const float4* mat;
+            float dst; int side;
+            if (best & kTriBit) {
+                // the winner's point again from its (u, v): the same operations as in the search, the same bits
+                const uint32_t ti = best & ~kTriBit;
+                float4 g0, g1, g2;
+                load_tri(S.tri_geo, ti, g0, g1, g2);
+                point = (rtm::mk(g0.x, g0.y, g0.z) + rtm::mk(g0.w, g1.x, g1.y) * bu) + rtm::mk(g1.z, g1.w, g2.x) * bv;
+                const float s = rtm::dot(p - point, rtm::mk(g2.y, g2.z, g2.w));    // (n = cross(eAB, eAC), formed at the upload)
+                side = s > 0.0f ? 1 : s < 0.0f ? -1 : 0;
+                dst = rtm::sqrt_(kb);
+                surface_of(S, h, point, normal, mat);
+                const uint32_t prim = Q.order[ti];
+                const int mesh = Q.tri_mesh ? (int)Q.tri_mesh[prim] : -1;
+                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_TRIANGLE));
+                w2 = make_float4(__uint_as_float(prim), S.tri_nrm[(size_t)ti * 3].w, __int_as_float(mesh), bu);     // (.w: the chunk index's bits)
+                w3 = make_float4(bv, __int_as_float(side), 0.f, 0.f);
+            } else {
+                const float4 sp = S.sph_geom[best];
+                const v3 c = rtm::mk(sp.x, sp.y, sp.z), m = p - c;
+                const float len = rtm::sqrt_(rtm::dot(m, m));
+                dst = __builtin_fabsf(len - sp.w);
+                point = c + m * (sp.w / len);
+                side = len >= sp.w ? 1 : -1;
+                surface_of(S, h, point, normal, mat);
+                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_SPHERE));
+                w2 = make_float4(__uint_as_float(best), NEG1, NEG1, 0.f);
+                w3 = make_float4(0.f, __int_as_float(side), 0.f, 0.f);
+            }
+            w0 = make_float4(dst, point.x, point.y, point.z);
+        }
+        float4* out = Q.out + 4 * (size_t)i;
+        out[0] = w0; out[1] = w1; out[2] = w2; out[3] = w3;
+    }
+
+    if (COUNT) {
+        unsigned long long a = n_nodes, b = n_prims;
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
+        if ((threadIdx.x & 63) == 0) { atomicAdd(&Q.counters[0], a); atomicAdd(&Q.counters[1], b); }
+    }
+}
+
+} // namespace rtk

@@ -451,6 +451,14 @@ class RayTracingManager:
         self.InitFrame()
         return self.backend.visibility(points, samples, seed, firstIndex, mode)
 
+    def ClosestPoints(self, points):
+        """Beyond the reference: the nearest surface of the scene the next frame traces to each point (rt_closest_points) — which sphere
+        or triangle, where on it, how far and on which side (+1 in front / outside, -1 behind / inside): signed-distance baking, pushing a
+        probe out of a wall, snapping.  points: a RAY array or float32 (n, 8) with the point in origin and the search radius in tMax ->
+        a CLOSEST array.  A tensor on the tracer's device takes rt_closest_points_device and returns a float32 (n, 16) tensor."""
+        self.InitFrame()
+        return self.backend.closest_points(points)
+
     def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
         """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
         the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices

@@ -543,6 +543,22 @@ std::vector<float> RayTracingManager::Visibility(rt_multi* m, const std::vector<
     return out;
 }
 
+std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points)
+{
+    InitFrame(ctx);
+    std::vector<rt_closest> out(points.size());
+    check(ctx, rt_closest_points(ctx, points.data(), (int)points.size(), out.data()), "rt_closest_points");
+    return out;
+}
+
+std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_multi* m, const std::vector<rt_ray>& points)
+{
+    InitFrame(m);
+    std::vector<rt_closest> out(points.size());
+    mcheck(m, rt_multi_closest_points(m, points.data(), (int)points.size(), out.data()), "rt_multi_closest_points");
+    return out;
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

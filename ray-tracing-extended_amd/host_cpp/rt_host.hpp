@@ -165,6 +165,10 @@ public:
     // or points.size() * 12 (mode 1: nine SH coefficients, visibility, 0, 0).
     std::vector<float> Visibility(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
     std::vector<float> Visibility(rt_multi* multi, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
+    // Beyond the reference: the nearest surface to each of the caller's points (rt_ray: the point in origin, the search radius in tMax) —
+    // rt_closest_points / rt_multi_closest_points: which sphere or triangle, where on it, how far and on which side.
+    std::vector<rt_closest> ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points);
+    std::vector<rt_closest> ClosestPoints(rt_multi* multi, const std::vector<rt_ray>& points);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

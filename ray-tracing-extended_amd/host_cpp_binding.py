@@ -5,7 +5,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
 import numpy as np
 
-from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape
+from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape, CLOSEST
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_host.so")
 _lib = None
@@ -29,6 +29,7 @@ def load_host_library():
         L.rth_trace_radiance.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_gather.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_visibility.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
+        L.rth_closest_points.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p]
         L.rth_split_mesh.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]
         L.rth_split_info.argtypes = [c_void_p, c_void_p, c_void_p]
         L.rth_split_triangles.argtypes = [c_void_p]
@@ -159,4 +160,15 @@ class CppScene:
         if self._L.rth_visibility(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
                                   None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
             raise RtError("Visibility: " + self._L.rth_last_error().decode())
+        return out
+
+    def closest_points(self, points, devices=(), device: int = 0) -> np.ndarray:
+        """RayTracingManager::ClosestPoints on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: points (a RAY array or float32
+        (n, 8), the point in origin and the search radius in tMax) -> a CLOSEST array."""
+        r = _ray_array(points)
+        out = np.zeros(r.shape[0], CLOSEST)
+        devs = list(devices) if devices else [device]
+        arr = (c_int * len(devs))(*devs)
+        if self._L.rth_closest_points(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)):
+            raise RtError("ClosestPoints: " + self._L.rth_last_error().decode())
         return out

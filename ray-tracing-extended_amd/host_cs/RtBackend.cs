@@ -265,6 +265,20 @@ namespace RtMi355x
             return result;
         }
 
+        // ---- closest-point queries (signed-distance baking, probe placement, snapping: RtClosest.cs) ------------------------------------
+        /// The nearest surface of the scene the next frame traces to each point: which sphere or triangle, where on it, how far and on
+        /// which side (+1 in front / outside, -1 behind / inside).  A point is an RtRay with the position in its origin and the search
+        /// radius in its tMax (MakeRay(position, Vector3.zero, radius); float.PositiveInfinity = unbounded).
+        public RtClosest[] ClosestPoints(RtRay[] points)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            RtClosest[] result = new RtClosest[points.Length];
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_closest_points(multi, points, points.Length, result), "rt_multi_closest_points");
+            else RtNative.Check(ctx, RtNative.rt_closest_points(ctx, points, points.Length, result), "rt_closest_points");
+            return result;
+        }
+
         /// The radiance along one ray (a probe, the light behind a picked pixel).
         public Color Radiance(Vector3 origin, Vector3 direction, float maxDistance, int samples = 0, uint seed = 0)
         {

@@ -275,6 +275,11 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_visibility_device(IntPtr ctx, IntPtr points, int n, [In] RtVisibilityParams[] p, IntPtr result);
         [DllImport(Lib)] public static extern int rt_get_visibility_info(IntPtr ctx, out RtVisibilityInfo info);
         [DllImport(Lib)] public static extern int rt_multi_visibility(IntPtr multi, [In] RtRay[] points, int n, [In] RtVisibilityParams[] p, [Out] float[] result);
+        // closest-point queries (RtClosest, RtClosestInfo: RtClosest.cs; a point is an RtRay with the point in origin and the search radius in tMax)
+        [DllImport(Lib)] public static extern int rt_closest_points(IntPtr ctx, [In] RtRay[] points, int n, [Out] RtClosest[] result);
+        [DllImport(Lib)] public static extern int rt_closest_points_device(IntPtr ctx, IntPtr points, int n, IntPtr result);
+        [DllImport(Lib)] public static extern int rt_get_closest_info(IntPtr ctx, out RtClosestInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_closest_points(IntPtr multi, [In] RtRay[] points, int n, [Out] RtClosest[] result);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -329,6 +334,8 @@ namespace RtMi355x
             Same("rt_gather_info", Marshal.SizeOf<RtGatherInfo>());
             Same("rt_visibility_params", Marshal.SizeOf<RtVisibilityParams>());
             Same("rt_visibility_info", Marshal.SizeOf<RtVisibilityInfo>());
+            Same("rt_closest", Marshal.SizeOf<RtClosest>());
+            Same("rt_closest_info", Marshal.SizeOf<RtClosestInfo>());
         }
     }
 }
