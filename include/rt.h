@@ -250,6 +250,8 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     depends on it
  *   "closest_count"   rt_closest_points: 1 = the counting build of the kernel, which fills rt_closest_info.lastNodeSteps / lastPrimTests
  *                     (default 0: those stay 0); the results are the same bits
+ *   "hits_slice"      rt_trace_hits: rays per launch and per staging slice, 1..4194304 (default 262144: at most 128 MiB of staged records
+ *                     at maxHits = 8); the result never depends on it
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -673,6 +675,84 @@ int rt_closest_points       (rt_ctx* ctx, const rt_ray* points, int n, rt_closes
 int rt_closest_points_device(rt_ctx* ctx, const void* points, int n, void* out);
 int rt_get_closest_info     (rt_ctx* ctx, rt_closest_info* out);
 
+/* ---- multi-hit ray queries: the first K surfaces along a ray, in order -----------------------------------------------------------------
+ * Beside closest hit (rt_trace_rays) and any hit (rt_occluded): EVERYTHING a ray passes through, nearest first — Unity's
+ * Physics.RaycastAll.  Layered picking, layer counts, the thickness of a solid along a ray (entry / exit pairs), point-in-solid by
+ * parity, transparency and decal stacks.  The reference's RayTriangle is one-sided (det >= 1E-6) and its RaySphere reports the near root
+ * only, so RT_HITS_BOTH defines a two-sided mode from the reference's own expressions.  All of it in float32, every product and sum
+ * rounded on its own (no FMA); / and sqrtf are IEEE; the answer is the same bits whatever the tree, the builder, the leaf size, the
+ * node form or the order of the visit.
+ *
+ *   candidates    every uploaded sphere, and every triangle CalculateRayCollision can reach: those a chunk addresses.  The context's
+ *                 intersectMode applies as for ray queries (RT_INTERSECT_FLAT_CHUNKS when rt_set_params was never called: a query
+ *                 needs no params): in FLAT_CHUNKS mode a triangle counts only if its chunk's RayBoundingBox passes (:279).
+ *   triangle      front hit: RayTriangle (:150-174) accepts it — det >= 1e-6f && dst >= 0 && u >= 0 && v >= 0 && w >= 0; side = +1.
+ *                 back hit (RT_HITS_BOTH only): the same det, inv = 1.0f / det, dst, u, v, w = 1 - u - v that RayTriangle computes,
+ *                 accepted when det <= -1e-6f && dst >= 0 && u >= 0 && v >= 0 && w >= 0; side = -1.  u, v, w keep their meaning (the
+ *                 weights of B, C and A of the uploaded triangle), so hitPoint and normal are rt_hit's expressions unchanged.  The
+ *                 normal is the normalised interpolation of the vertex normals and is NOT flipped for a back hit: it points to the
+ *                 triangle's front side, away from the ray's origin side.
+ *   sphere        with RaySphere's (:120-146) oc, a, b, c, disc: entry = (-b - sqrtf(disc)) / (2a), accepted when disc >= 0 and the
+ *                 quotient >= 0 (RaySphere itself); side = +1.  Exit (RT_HITS_BOTH only) = (-b + sqrtf(disc)) / (2a) from the same b,
+ *                 disc and a, accepted when disc >= 0 and the quotient >= 0; side = -1.  normal = normalize(hitPoint - centre) for
+ *                 both (it points outwards).  An origin inside a sphere sees its exit alone.
+ *   bound         a hit counts when dst < tMax (strict).  tMax <= 0 or NaN: nothing is traced, K empty records, hitCount = 0.  An
+ *                 accepted dst is finite and >= 0; -0.0f is possible.
+ *   order         ascending (dst, kind, primitive, side): dst compares as a float (-0.0f == 0.0f); at equal dst a sphere comes before
+ *                 a triangle, then the lower uploaded index, then front (+1) before back (-1).  Record 0 therefore equals
+ *                 rt_trace_rays' hit, with ONE difference: where several candidates share the closest dst bit for bit, the reference
+ *                 keeps the first in its visiting order (spheres in buffer order, then chunk by chunk) and this call keeps the lowest
+ *                 (kind, primitive) — the same candidate unless chunks are listed out of the order of their triangles.
+ *   output        out holds n * K records, ray-major: records 0 .. min(total, K) - 1 of a ray are its first hits in order, the rest
+ *                 are empty: dst = +inf, indices -1, kind = RT_HIT_NONE, side = 0, all else 0 (hitCount apart).
+ *   hitCount      the same value in all K records of a ray.  countAll == 0: min(total, K), so hitCount == K means "there may be
+ *                 more".  countAll == 1: the number of ALL accepted hits with dst < tMax; the traversal is then bounded by tMax
+ *                 alone and cannot stop early.  In RT_HITS_FRONT mode hitCount > 0 exactly when rt_occluded says 1.
+ *   defaults      params == NULL: maxHits = RT_HITS_DEFAULT_MAX, RT_HITS_FRONT, countAll 0.
+ *   scene, state  as for ray queries: the queue is settled, the scene made current, the box padding widened for the largest finite
+ *                 |origin coordinate| among rays with tMax > 0 (the device entry: one small reduction and one synchronisation first).
+ *                 Nothing else moves — not the image, feature, filter or other query state, and no rt_stats field except bvhBuilds /
+ *                 bvhRebuilds / bvhRepads.  The library's slices ("hits_slice") and rt_multi are invisible; a batch cut anywhere into
+ *                 two calls gives the bits of one.
+ *   errors        a null handle -1; n == 0 returns 0; maxHits outside 1..RT_HITS_MAX, an unknown mode, countAll neither 0 nor 1, a
+ *                 reserved word of params that is not 0, n < 0, a null buffer with n > 0, and for the device entry a pointer of another
+ *                 device or one not 16-byte aligned: -2 with a message, and nothing changes.                                         */
+enum { RT_HITS_FRONT = 0, RT_HITS_BOTH = 1 };
+#define RT_HITS_MAX          8
+#define RT_HITS_DEFAULT_MAX  4
+typedef struct rt_hits_params {         /* 32 B */
+    int32_t maxHits;                    /* K, 1..RT_HITS_MAX: the records per ray                                                       */
+    int32_t mode;                       /* RT_HITS_FRONT / RT_HITS_BOTH                                                                 */
+    int32_t countAll;                   /* 0 / 1, see hitCount                                                                          */
+    int32_t _reserved[5];               /* must be 0                                                                                    */
+} rt_hits_params;
+typedef struct rt_multihit {            /* 64 B; an empty record: dst = +inf, hitPoint = normal = 0, kind = RT_HIT_NONE, indices -1, u = v = 0, side = 0 */
+    float   dst;
+    float   hitPoint[3];                /* origin + direction * dst                                                                     */
+    float   normal[3];                  /* as rt_hit.normal; not flipped for a back hit                                                 */
+    int32_t kind;                       /* RT_HIT_*                                                                                     */
+    int32_t primitive;                  /* exactly as in rt_hit                                                                         */
+    int32_t chunk;
+    int32_t mesh;
+    float   u, v;                       /* triangle: RayTriangle's u, v; else 0                                                         */
+    int32_t side;                       /* +1 front face / sphere entry, -1 back face / sphere exit, 0 in an empty record               */
+    int32_t hitCount;                   /* see above; the same value in all K records of a ray                                          */
+    int32_t _reserved;
+} rt_multihit;
+typedef struct rt_hits_info {           /* 32 B */
+    int32_t calls;                      /* calls so far                                                                                 */
+    int32_t lastMaxHits, lastMode, lastCountAll;    /* the params of the last call, defaults filled in                                  */
+    double  lastKernelMs, totalKernelMs;    /* HIP-event time of the launches of the last host-entry call / summed                      */
+} rt_hits_info;
+/* Host memory; returns when the results are in out (n * K records).  The rays go through device buffers of the context in slices of
+ * "hits_slice" rays, sized to min(n, slice) rays and min(n, slice) * K records.                                                   */
+int rt_trace_hits       (rt_ctx* ctx, const rt_ray* rays, int n, const rt_hits_params* params, rt_multihit* out);
+/* Device memory of the context's GPU (rays: n rt_ray, out: n * K rt_multihit, both 16-byte aligned), ordered on the context's stream
+ * as rt_trace_rays_device is, with its one synchronisation for the origin bound; rt_hits_info counts the call and keeps the host
+ * entry's times.                                                                                                                 */
+int rt_trace_hits_device(rt_ctx* ctx, const void* rays, int n, const rt_hits_params* params, void* out);
+int rt_get_hits_info    (rt_ctx* ctx, rt_hits_info* out);
+
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only
  * target is the colour of RayTracing.shader:388); the definition below is this library's, built from the reference's own steps.
@@ -988,6 +1068,8 @@ int rt_multi_gather          (rt_multi* m, const rt_ray* points, int n, const rt
 int rt_multi_visibility      (rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out);
 /* Closest-point queries behind the handle: the same slices — bitwise the single-context result.                                   */
 int rt_multi_closest_points  (rt_multi* m, const rt_ray* points, int n, rt_closest* out);
+/* Multi-hit ray queries behind the handle: the same slices — bitwise the single-context result.                                   */
+int rt_multi_trace_hits      (rt_multi* m, const rt_ray* rays, int n, const rt_hits_params* params, rt_multihit* out);
 /* Feature buffers behind the handle: every context renders the feature frames of its bands, concurrently; rt_multi_read_aov gathers the
  * strips of one plane to the first device (the gather of rt_multi_render) and returns the assembled plane, height*width*4 floats, row
  * 0 = bottom — bitwise the single-context plane.  rt_multi_reset_aov zeroes the planes of every context.                          */
@@ -1018,7 +1100,7 @@ int rt_multi_read_variance        (rt_multi* m, float* var, size_t n_floats);
 
 /* ABI self-description for binding generators / tests. */
 int rt_abi_version(void);
-int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_vdenoise_params" | "rt_vdenoise_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" | "rt_closest" | "rt_closest_info" */
+int rt_sizeof(const char* struct_name);   /* "rt_material" | "rt_sphere" | "rt_triangle" | "rt_meshinfo" | "rt_params" | "rt_stats" | "rt_mesh_transform" | "rt_local_chunk" | "rt_multi_info" | "rt_ray" | "rt_hit" | "rt_aov_info" | "rt_denoise_params" | "rt_denoise_info" | "rt_temporal_params" | "rt_temporal_info" | "rt_vdenoise_params" | "rt_vdenoise_info" | "rt_radiance_params" | "rt_radiance_info" | "rt_gather_params" | "rt_gather_info" | "rt_visibility_params" | "rt_visibility_info" | "rt_closest" | "rt_closest_info" | "rt_hits_params" | "rt_multihit" | "rt_hits_info" */
 
 #ifdef __cplusplus
 }

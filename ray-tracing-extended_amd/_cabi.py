@@ -100,6 +100,14 @@ CLOSEST = np.dtype([("dst", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), (
 CLOSEST_INFO = np.dtype([("calls", "<i4"), ("_reserved", "<i4"), ("lastKernelMs", "<f8"), ("totalKernelMs", "<f8"),
                          ("lastNodeSteps", "<u8"), ("lastPrimTests", "<u8")])
 assert CLOSEST.itemsize == 64 and CLOSEST_INFO.itemsize == 40
+# multi-hit ray queries (rt_trace_hits): the params of a call, one of a ray's K records, and the state of the last call
+HITS_PARAMS = np.dtype([("maxHits", "<i4"), ("mode", "<i4"), ("countAll", "<i4"), ("_reserved", "<i4", 5)])
+MULTIHIT = np.dtype([("dst", "<f4"), ("hitPoint", "<f4", 3), ("normal", "<f4", 3), ("kind", "<i4"), ("primitive", "<i4"), ("chunk", "<i4"),
+                     ("mesh", "<i4"), ("u", "<f4"), ("v", "<f4"), ("side", "<i4"), ("hitCount", "<i4"), ("_reserved", "<i4")])
+HITS_INFO = np.dtype([("calls", "<i4"), ("lastMaxHits", "<i4"), ("lastMode", "<i4"), ("lastCountAll", "<i4"), ("lastKernelMs", "<f8"),
+                      ("totalKernelMs", "<f8")])
+assert HITS_PARAMS.itemsize == 32 and MULTIHIT.itemsize == 64 and HITS_INFO.itemsize == 32
+HITS_FRONT, HITS_BOTH, HITS_MAX, HITS_DEFAULT_MAX = 0, 1, 8, 4      # RT_HITS_* of include/rt.h
 assert MATERIAL.itemsize == 64 and SPHERE.itemsize == 80 and TRIANGLE.itemsize == 72 and MESHINFO.itemsize == 96
 
 # RT_DENOISE_DEFAULT_* of include/rt.h (what a null rt_denoise_params means)
@@ -139,6 +147,7 @@ SYMBOLS = [
     "rt_gather", "rt_gather_device", "rt_get_gather_info", "rt_multi_gather",
     "rt_visibility", "rt_visibility_device", "rt_get_visibility_info", "rt_multi_visibility",
     "rt_closest_points", "rt_closest_points_device", "rt_get_closest_info", "rt_multi_closest_points",
+    "rt_trace_hits", "rt_trace_hits_device", "rt_get_hits_info", "rt_multi_trace_hits",
 ]
 
 _lib = None
@@ -265,6 +274,9 @@ def load_library() -> ctypes.CDLL:
     for n in ("rt_closest_points", "rt_closest_points_device", "rt_multi_closest_points"):
         getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.rt_get_closest_info.argtypes = [c_void_p, c_void_p]
+    for n in ("rt_trace_hits", "rt_trace_hits_device", "rt_multi_trace_hits"):
+        getattr(lib, n).argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.rt_get_hits_info.argtypes = [c_void_p, c_void_p]
     for n in SYMBOLS:
         f = getattr(lib, n)
         if f.restype is None or n in ("rt_create", "rt_last_error", "rt_destroy", "rt_multi_create", "rt_multi_destroy", "rt_multi_last_error",
@@ -281,7 +293,8 @@ def load_library() -> ctypes.CDLL:
                      ("rt_radiance_params", RADIANCE_PARAMS), ("rt_radiance_info", RADIANCE_INFO),
                      ("rt_gather_params", GATHER_PARAMS), ("rt_gather_info", GATHER_INFO),
                      ("rt_visibility_params", VISIBILITY_PARAMS), ("rt_visibility_info", VISIBILITY_INFO),
-                     ("rt_closest", CLOSEST), ("rt_closest_info", CLOSEST_INFO)):
+                     ("rt_closest", CLOSEST), ("rt_closest_info", CLOSEST_INFO),
+                     ("rt_hits_params", HITS_PARAMS), ("rt_multihit", MULTIHIT), ("rt_hits_info", HITS_INFO)):
         got = lib.rt_sizeof(name.encode())
         if got != dt.itemsize:
             raise RtError(f"ABI mismatch: sizeof({name}) = {got} in the library, {dt.itemsize} in the binding")
@@ -310,6 +323,23 @@ def _query_host(call, handle, rays, any_hit: bool, check, what):
     r = _ray_array(rays)
     out = np.zeros(r.shape[0], np.uint8) if any_hit else np.zeros(r.shape[0], HIT)
     check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)), what)
+    return out
+
+
+def _hits_params(max_hits, both_sides, count_all):
+    """a HITS_PARAMS record"""
+    p = np.zeros((), HITS_PARAMS)
+    p["maxHits"], p["mode"], p["countAll"] = int(max_hits), HITS_BOTH if both_sides else HITS_FRONT, int(bool(count_all))
+    return p
+
+
+def _hits_host(call, handle, rays, params, check, what):
+    r = _ray_array(rays)
+    K = int(params["maxHits"])
+    if not 1 <= K <= HITS_MAX:
+        raise RtError(f"{what}: max_hits = {K} outside 1..{HITS_MAX}")
+    out = np.zeros((r.shape[0], K), MULTIHIT)
+    check(call(handle, r.ctypes.data_as(c_void_p), int(r.shape[0]), params.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)), what)
     return out
 
 
@@ -656,6 +686,33 @@ class Tracer:
         self._check(self._lib.rt_get_closest_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_closest_info")
         return {k: s[k].item() for k in CLOSEST_INFO.names if k != "_reserved"}
 
+    # -- multi-hit ray queries
+    def trace_hits(self, rays, max_hits=HITS_DEFAULT_MAX, both_sides=False, count_all=False):
+        """rt_trace_hits: the first max_hits (1..8) surfaces along every ray, nearest first.  rays: a RAY array or float32 (n, 8) -> a
+        MULTIHIT array (n, max_hits); records past a ray's last hit are empty (kind 0, dst inf).  both_sides: back faces of triangles
+        and the exit points of spheres count too (side = -1).  count_all: hitCount is the number of all hits below tMax instead of
+        min(hits, max_hits).  No params are needed.  A float32 CUDA tensor (n, 8) on the context's device takes the device entry,
+        ordered with torch's current stream as trace_rays is, and returns a float32 (n, max_hits, 16) tensor (the MULTIHIT records)."""
+        p = _hits_params(max_hits, both_sides, count_all)
+        if not _is_tensor(rays):
+            return _hits_host(self._lib.rt_trace_hits, self._ctx, rays, p, self._check, "rt_trace_hits")
+        import torch
+        rays = self._ray_tensor(rays)
+        n, K = int(rays.shape[0]), int(p["maxHits"])
+        if not 1 <= K <= HITS_MAX:
+            raise RtError(f"rt_trace_hits_device: max_hits = {K} outside 1..{HITS_MAX}")
+        out = torch.empty((n, K, 16), dtype=torch.float32, device=rays.device)
+        self._on_torch_stream(rays.device, lambda: self._lib.rt_trace_hits_device(self._ctx, c_void_p(rays.data_ptr()), n, p.ctypes.data_as(c_void_p),
+                                                                                  c_void_p(out.data_ptr())), "rt_trace_hits_device")
+        return out
+
+    trace_hits_device = trace_hits  # (a tensor takes rt_trace_hits_device; the name says so at the call site)
+
+    def hits_info(self) -> dict:
+        s = np.zeros((), HITS_INFO)
+        self._check(self._lib.rt_get_hits_info(self._ctx, s.ctypes.data_as(c_void_p)), "rt_get_hits_info")
+        return {k: s[k].item() for k in HITS_INFO.names}
+
     # -- rendering
     def render_frame(self, frame: int):
         self._check(self._lib.rt_render_frame(self._ctx, frame), "rt_render_frame")
@@ -952,6 +1009,10 @@ class MultiTracer:
     def occluded(self, rays) -> np.ndarray:
         """rt_multi_occluded: Tracer.occluded over the contexts (host arrays)."""
         return _query_host(self._lib.rt_multi_occluded, self._m, rays, True, self._check, "rt_multi_occluded")
+
+    def trace_hits(self, rays, max_hits=HITS_DEFAULT_MAX, both_sides=False, count_all=False) -> np.ndarray:
+        """rt_multi_trace_hits: Tracer.trace_hits over the contexts (host arrays), one contiguous slice of the batch each."""
+        return _hits_host(self._lib.rt_multi_trace_hits, self._m, rays, _hits_params(max_hits, both_sides, count_all), self._check, "rt_multi_trace_hits")
 
     def closest_points(self, points) -> np.ndarray:
         """rt_multi_closest_points: Tracer.closest_points over the contexts (host arrays), one contiguous slice of the batch each."""

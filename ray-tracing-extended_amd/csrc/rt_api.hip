@@ -34,6 +34,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_gather.hpp"
 #include "rt_visibility.hpp"
 #include "rt_closest.hpp"
+#include "rt_multihit.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -231,12 +232,16 @@ struct rt_ctx : ErrOwner {
     int opt_primary_lists = 1;                      // 1: camera rays of a static camera start from their pixel's candidate leaves (k_stream); 0: always from the root
     DevBuf<float> d_park;              // k_stream, Philox mode: parked sub-stream sums
     std::vector<rtk::CamRecord> h_cams; DevBuf<rtk::CamRecord> d_cams;     // k_cam_stream: the camera table of the last launch (rt_render_params)
-    // queries (rt_trace_rays ... rt_closest_points): staging of the host entries (one slice of rays or points in, one slice of results
+    // queries (rt_trace_rays ... rt_trace_hits): staging of the host entries (one slice of rays or points in, one slice of results
     // out, in bytes), the device entries' origin bound, and the timed families' info records (QueryFamily indexes them; closest-point
-    // queries use calls and the two times of theirs)
+    // queries and
+    // multi-hit queries use calls and the two times of theirs)
     DevBuf<float4> d_q_rays; DevBuf<uint8_t> d_q_out;
     DevBuf<unsigned int> d_q_bound;
-    rt_gather_info query_info[4]{};
+    rt_gather_info query_info[5]{};
+    // multi-hit ray queries: rays per launch (a slice stages maxHits * 64 B of records per ray), and the params of the last call
+    int opt_hits_slice = 1 << 18;
+    rt_hits_params hits_last{};
     // closest-point queries: points per launch; 1 = the counting kernel (node steps and primitive tests of a call, summed on the device
     // and fetched by rt_get_closest_info when counts_pending says the last call left some there)
     int opt_closest_slice = 1 << 22, opt_closest_count = 0;
@@ -1321,13 +1326,13 @@ int cover_origins_device(rt_ctx* c, const float4* rays, int n)
     return cover_origins(c, u2f(bits));
 }
 
-// ---- the one path of the five query families ----------------------------------------------------------------------------------------
+// ---- the one path of the six query families ----------------------------------------------------------------------------------------
 // Ray queries (rt_trace_rays / rt_occluded, csrc/rt_query.hpp), radiance queries (rt_trace_radiance, csrc/rt_radiance.hpp), gather
-// queries (rt_gather, csrc/rt_gather.hpp), visibility gathers (rt_visibility, csrc/rt_visibility.hpp) and closest-point queries
-// (rt_closest_points, csrc/rt_closest.hpp) all take n rt_ray (2 float4 each) and write a fixed number of bytes per item.  A family supplies a description of the call (QueryCall, built by its *_call once
+// queries (rt_gather, csrc/rt_gather.hpp), visibility gathers (rt_visibility, csrc/rt_visibility.hpp), closest-point queries
+// (rt_closest_points, csrc/rt_closest.hpp) and multi-hit ray queries (rt_trace_hits, csrc/rt_multihit.hpp) all take n rt_ray (2 float4 each) and write a fixed number of bytes per item.  A family supplies a description of the call (QueryCall, built by its *_call once
 // the arguments are known to be good) and a function that fills its kernel's Args for one launch; everything between the exported
 // entry and hipLaunchKernel is below, once.
-enum QueryFamily { kRadiance, kGather, kVisibility, kClosest, kRays };  // (the first three: the sampled families; the first four are timed and index rt_ctx::query_info)
+enum QueryFamily { kRadiance, kGather, kVisibility, kClosest, kHits, kRays };    // (the first three: the sampled families; the first five are timed and index rt_ctx::query_info)
 
 // The sampled families' params and info records have one layout: rt_radiance_* keeps reserved words where the other two have `mode`.
 // rt_gather_params / rt_gather_info are the form the path works with.
@@ -1358,6 +1363,7 @@ struct QueryCall {
     int sample_lanes_log2;          // S = 16 / 4 / 1 lanes share an item's samples (include/rt.h RT_RNG_PHILOX); ray queries: 0
     rt_gather_params p;             // the sampled families' params, defaults filled in (mode 0 for radiance queries)
     int (*begin)(rt_ctx*);          // what the family does once per call, after the scene is current and before the first launch; may be null
+    rt_hits_params h;               // multi-hit queries: their params, defaults filled in
     bool sampled() const { return family < kClosest; }      // takes params and draws samples
     bool timed() const { return family != kRays; }          // has an info record with calls and kernel times
 };
@@ -1442,9 +1448,9 @@ int query_device(rt_ctx* c, const QueryCall& q, const void* in, int n, void* out
     return 0;
 }
 
-// ---- the five descriptions --------------------------------------------------------------------------------------------------------
+// ---- the six descriptions --------------------------------------------------------------------------------------------------------
 // A *_call checks the arguments of a call to `what` and describes it; all have the signature of QueryDescribe (ray queries and
-// closest-point queries take no params).  The checks come in one order: params set (where the family needs them), n and the pointers, the defaults of
+// closest-point queries take no params; multi-hit queries take their own, which are not the sampled families').  The checks come in one order: params set (where the family needs them), n and the pointers, the defaults of
 // params == NULL, samples, mode, reserved words.
 using QueryDescribe = int (*)(rt_ctx* c, const char* what, const void* in, int n, const void* params, const void* out, QueryCall& q);
 
@@ -1587,6 +1593,34 @@ int closest_call(rt_ctx* c, const char* what, const void* points, int n, const v
     q = QueryCall{ kClosest, what, "points", "out", c->opt_closest_slice, sizeof(rt_closest), true, nullptr, launch_closest };
     q.begin = begin_closest;
     return query_pointers(c, q, points, n, out);
+}
+
+hipError_t launch_hits(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
+{
+    rtk::MultihitArgs A{};
+    A.order = c->d_order.p;
+    A.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
+    A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    A.max_hits = q.h.maxHits; A.count_all = q.h.countAll;
+    A.rays = s.in; A.out = static_cast<float4*>(s.out);
+    c->hits_last = q.h;
+    const bool compact = c->opt_compact_nodes != 0;
+    if (q.h.mode == RT_HITS_BOTH) return launch_slice(c, compact ? (const void*)rtk::k_multihit<true, true> : (const void*)rtk::k_multihit<false, true>, s, A);
+    return launch_slice(c, compact ? (const void*)rtk::k_multihit<true, false> : (const void*)rtk::k_multihit<false, false>, s, A);
+}
+// n * K rt_multihit (4 float4 each); params == NULL: RT_HITS_DEFAULT_MAX records per ray, front faces, hitCount capped at K.  No
+// rt_params are needed: the kernel reads intersectMode alone, as the ray queries do
+int hits_call(rt_ctx* c, const char* what, const void* rays, int n, const void* params, const void* out, QueryCall& q)
+{
+    q = QueryCall{ kHits, what, "rays", "out", c->opt_hits_slice, 0, true, nullptr, launch_hits };
+    { int r = query_pointers(c, q, rays, n, out); if (r) return r; }
+    if (params) std::memcpy(&q.h, params, sizeof q.h); else q.h.maxHits = RT_HITS_DEFAULT_MAX;
+    if (q.h.maxHits < 1 || q.h.maxHits > RT_HITS_MAX) return fail(c, -2, "%s: maxHits = %d outside 1..%d", what, q.h.maxHits, RT_HITS_MAX);
+    if (q.h.mode != RT_HITS_FRONT && q.h.mode != RT_HITS_BOTH) return fail(c, -2, "%s: mode = %d is neither RT_HITS_FRONT nor RT_HITS_BOTH", what, q.h.mode);
+    if (q.h.countAll != 0 && q.h.countAll != 1) return fail(c, -2, "%s: countAll = %d is neither 0 nor 1", what, q.h.countAll);
+    for (int r : q.h._reserved) if (r != 0) return fail(c, -2, "%s: a reserved word of rt_hits_params is not 0", what);
+    q.out_bytes = sizeof(rt_multihit) * (size_t)q.h.maxHits;
+    return 0;
 }
 
 // Every exported query entry of a context: settle, check and describe, then the host or the device path
@@ -2044,6 +2078,9 @@ int rt_sizeof(const char* name)
     if (!std::strcmp(name, "rt_visibility_info")) return (int)sizeof(rt_visibility_info);
     if (!std::strcmp(name, "rt_closest")) return (int)sizeof(rt_closest);
     if (!std::strcmp(name, "rt_closest_info")) return (int)sizeof(rt_closest_info);
+    if (!std::strcmp(name, "rt_hits_params")) return (int)sizeof(rt_hits_params);
+    if (!std::strcmp(name, "rt_multihit")) return (int)sizeof(rt_multihit);
+    if (!std::strcmp(name, "rt_hits_info")) return (int)sizeof(rt_hits_info);
     return -1;
 }
 
@@ -2262,6 +2299,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "gather_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "gather_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_gather_slice = value; }
     else if (!std::strcmp(name, "visibility_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "visibility_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_visibility_slice = value; }
     else if (!std::strcmp(name, "closest_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "closest_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_closest_slice = value; }
+    else if (!std::strcmp(name, "hits_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "hits_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_hits_slice = value; }
     else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
@@ -2445,6 +2483,17 @@ int rt_get_closest_info(rt_ctx* c, rt_closest_info* out)
     *out = rt_closest_info{};
     out->calls = g.calls; out->lastKernelMs = g.lastKernelMs; out->totalKernelMs = g.totalKernelMs;
     out->lastNodeSteps = c->closest_counts[0]; out->lastPrimTests = c->closest_counts[1];
+    return 0;
+}
+int rt_trace_hits(rt_ctx* c, const rt_ray* rays, int n, const rt_hits_params* params, rt_multihit* out) { return query_entry(c, hits_call, "rt_trace_hits", false, rays, n, params, out); }
+int rt_trace_hits_device(rt_ctx* c, const void* rays, int n, const rt_hits_params* params, void* out) { return query_entry(c, hits_call, "rt_trace_hits_device", true, rays, n, params, out); }
+int rt_get_hits_info(rt_ctx* c, rt_hits_info* out)
+{
+    if (!c || !out) return -1;
+    const rt_gather_info& g = c->query_info[kHits];
+    *out = rt_hits_info{};
+    out->calls = g.calls; out->lastKernelMs = g.lastKernelMs; out->totalKernelMs = g.totalKernelMs;
+    out->lastMaxHits = c->hits_last.maxHits; out->lastMode = c->hits_last.mode; out->lastCountAll = c->hits_last.countAll;
     return 0;
 }
 // (the three info records are one layout, checked where QueryFamily is declared)
@@ -2823,9 +2872,9 @@ int multi_query(rt_multi* m, QueryDescribe describe, const char* what, const cha
     const int per = (n + N - 1) / N;
     return on_every_context(m, host_what, [&](int i) {
         const int first = std::min(n, i * per), cnt = std::min(n, first + per) - first;
-        rt_gather_params pi = q.p;              // (ray queries take none)
+        rt_gather_params pi = q.p;              // (ray queries take none; the others' params go through as they came)
         pi.firstIndex = q.p.firstIndex + (uint32_t)first;
-        return query_entry(m->ctx[i], describe, host_what, false, in + first, cnt, q.sampled() ? &pi : nullptr, static_cast<char*>(out) + q.out_bytes * (size_t)first);
+        return query_entry(m->ctx[i], describe, host_what, false, in + first, cnt, q.sampled() ? &pi : params, static_cast<char*>(out) + q.out_bytes * (size_t)first);
     });
 }
 
@@ -2876,6 +2925,7 @@ int rt_multi_occluded(rt_multi* m, const rt_ray* rays, int n, uint8_t* occluded)
 int rt_multi_trace_radiance(rt_multi* m, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba) { return multi_query(m, radiance_call, "rt_multi_trace_radiance", "rt_trace_radiance", true, rays, n, params, rgba); }
 int rt_multi_gather(rt_multi* m, const rt_ray* points, int n, const rt_gather_params* params, float* out) { return multi_query(m, gather_call, "rt_multi_gather", "rt_gather", true, points, n, params, out); }
 int rt_multi_visibility(rt_multi* m, const rt_ray* points, int n, const rt_visibility_params* params, float* out) { return multi_query(m, visibility_call, "rt_multi_visibility", "rt_visibility", false, points, n, params, out); }
+int rt_multi_trace_hits(rt_multi* m, const rt_ray* rays, int n, const rt_hits_params* params, rt_multihit* out) { return multi_query(m, hits_call, "rt_multi_trace_hits", "rt_trace_hits", false, rays, n, params, out); }
 int rt_multi_closest_points(rt_multi* m, const rt_ray* points, int n, rt_closest* out) { return multi_query(m, closest_call, "rt_multi_closest_points", "rt_closest_points", false, points, n, nullptr, out); }
 
 // Feature buffers behind the handle: the scene is shared as for a render, every context renders the feature frames of its bands

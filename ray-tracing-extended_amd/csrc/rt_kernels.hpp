@@ -172,6 +172,17 @@ __device__ __forceinline__ SphereA sphere_a(float a)
     s.rden = rtm::rcp_mid(s.den);
     return s;
 }
+// num / (2a), the IEEE quotient: a root of RaySphere's quadratic from its numerator (-b - sqrt(disc); the multi-hit queries' exit root
+// takes -b + sqrt(disc) through the same lines)
+__device__ __forceinline__ float sphere_quotient(const SphereA& sa, float num)
+{
+    const float an = __builtin_fabsf(num);
+    const float q0 = num * sa.rden;
+    float q = __builtin_fmaf(__builtin_fmaf(-q0, sa.den, num), sa.rden, q0);
+    q = (num == 0.0f) ? q0 : q;                                   // a zero numerator keeps its sign through the product
+    if (!(sa.den_ok && (num == 0.0f || (an >= 0x1p-60f && an <= 0x1p60f)))) { RT_COLD_PATH(); q = num / sa.den; }
+    return q;
+}
 __device__ __forceinline__ bool ray_sphere(v3 o, v3 d, const SphereA& sa, v3 centre, float radius, float& dst)
 {
     v3 oc = o - centre;
@@ -179,13 +190,7 @@ __device__ __forceinline__ bool ray_sphere(v3 o, v3 d, const SphereA& sa, v3 cen
     float c = rtm::dot(oc, oc) - radius * radius;
     float disc = b * b - 4.0f * sa.a * c;
     if (disc >= 0.0f) {
-        const float num = -b - rtm::sqrt_(disc);
-        const float an = __builtin_fabsf(num);
-        const float q0 = num * sa.rden;
-        float q = __builtin_fmaf(__builtin_fmaf(-q0, sa.den, num), sa.rden, q0);
-        q = (num == 0.0f) ? q0 : q;                               // a zero numerator keeps its sign through the product
-        if (!(sa.den_ok && (num == 0.0f || (an >= 0x1p-60f && an <= 0x1p60f)))) { RT_COLD_PATH(); q = num / sa.den; }
-        dst = q;
+        dst = sphere_quotient(sa, -b - rtm::sqrt_(disc));
         return dst >= 0.0f;
     }
     return false;

@@ -417,6 +417,17 @@ class RayTracingManager:
             return hit, self.meshes[mesh]
         return hit, None
 
+    def RaycastAll(self, origin, direction, maxDistance: float = math.inf, maxHits: int = 8, bothSides: bool = False):
+        """Physics.RaycastAll for the traced scene: everything the ray origin + t * direction (t < maxDistance) passes through in the
+        scene the next frame traces, nearest first, at most maxHits (1..8) surfaces — rt_trace_hits.  bothSides: the back faces of
+        triangles and the exit points of spheres count too (side = -1).  Returns the non-empty MULTIHIT records in order; hitCount ==
+        maxHits in them means there may be more."""
+        self.InitFrame()
+        ray = np.zeros(1, RAY)
+        ray["origin"], ray["direction"], ray["tMax"] = _v3(origin), _v3(direction), f32(maxDistance)
+        hits = self.backend.trace_hits(ray, maxHits, bothSides)[0]
+        return hits[hits["kind"] != 0]
+
     def TraceRadiance(self, rays, samples: int = None, seed: int = 0, firstIndex: int = 0):
         """Beyond the reference: how much light arrives along each ray in the scene the next frame traces — Trace (RayTracing.shader:300-352)
         through rt_trace_radiance, averaged over `samples` runs (None: numRaysPerPixel): light probes, lightmap texels, a camera the

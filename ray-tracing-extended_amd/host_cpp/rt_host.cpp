@@ -559,6 +559,49 @@ std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_multi* m, const std:
     return out;
 }
 
+namespace {
+rt_ray one_ray(const float origin[3], const float direction[3], float maxDistance)
+{
+    rt_ray r{};
+    for (int k = 0; k < 3; ++k) { r.origin[k] = origin[k]; r.direction[k] = direction[k]; }
+    r.tMax = maxDistance;
+    return r;
+}
+rt_hits_params hits_params(int maxHits, bool bothSides)
+{
+    rt_hits_params p{};
+    p.maxHits = maxHits; p.mode = bothSides ? RT_HITS_BOTH : RT_HITS_FRONT;
+    return p;
+}
+std::vector<rt_multihit> hits_found(std::vector<rt_multihit> all)
+{
+    size_t n = 0;
+    while (n < all.size() && all[n].kind != RT_HIT_NONE) ++n;
+    all.resize(n);
+    return all;
+}
+} // namespace
+
+std::vector<rt_multihit> RayTracingManager::RaycastAll(rt_ctx* ctx, const float origin[3], const float direction[3], float maxDistance, int maxHits, bool bothSides)
+{
+    InitFrame(ctx);
+    const rt_ray r = one_ray(origin, direction, maxDistance);
+    const rt_hits_params p = hits_params(maxHits, bothSides);
+    std::vector<rt_multihit> all((size_t)std::max(maxHits, 1));
+    check(ctx, rt_trace_hits(ctx, &r, 1, &p, all.data()), "rt_trace_hits");
+    return hits_found(std::move(all));
+}
+
+std::vector<rt_multihit> RayTracingManager::RaycastAll(rt_multi* m, const float origin[3], const float direction[3], float maxDistance, int maxHits, bool bothSides)
+{
+    InitFrame(m);
+    const rt_ray r = one_ray(origin, direction, maxDistance);
+    const rt_hits_params p = hits_params(maxHits, bothSides);
+    std::vector<rt_multihit> all((size_t)std::max(maxHits, 1));
+    mcheck(m, rt_multi_trace_hits(m, &r, 1, &p, all.data()), "rt_multi_trace_hits");
+    return hits_found(std::move(all));
+}
+
 void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
 
 void RayTracingManager::Start(rt_multi* m)

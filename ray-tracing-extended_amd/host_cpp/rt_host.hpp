@@ -169,6 +169,11 @@ public:
     // rt_closest_points / rt_multi_closest_points: which sphere or triangle, where on it, how far and on which side.
     std::vector<rt_closest> ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points);
     std::vector<rt_closest> ClosestPoints(rt_multi* multi, const std::vector<rt_ray>& points);
+    // Physics.RaycastAll for the traced scene (rt_trace_hits / rt_multi_trace_hits): everything origin + t * direction passes through for
+    // t < maxDistance, nearest first, at most maxHits (1..RT_HITS_MAX) surfaces; bothSides: back faces and sphere exits count too
+    // (side = -1).  Returns the non-empty records; hitCount == maxHits in them means there may be more.
+    std::vector<rt_multihit> RaycastAll(rt_ctx* ctx, const float origin[3], const float direction[3], float maxDistance, int maxHits = RT_HITS_MAX, bool bothSides = false);
+    std::vector<rt_multihit> RaycastAll(rt_multi* multi, const float origin[3], const float direction[3], float maxDistance, int maxHits = RT_HITS_MAX, bool bothSides = false);
     // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
     // gather at the end of the call); resultTexture is the assembled full image.
     void InitFrame(rt_multi* multi);

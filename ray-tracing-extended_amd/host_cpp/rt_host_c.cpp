@@ -172,6 +172,30 @@ int rth_closest_points(void* hp, const int* devices, int n_contexts, const rt_ra
     return rc;
 }
 
+// RayTracingManager::RaycastAll of the loaded scene for one ray, on a fresh rt_ctx or an rt_multi as rth_gather; out holds max_hits
+// rt_multihit; returns the number of hits written (0 .. max_hits), -1 on an error.
+int rth_raycast_all(void* hp, const int* devices, int n_contexts, const float* origin, const float* direction, float max_distance, int max_hits,
+                    int both_sides, rt_multihit* out)
+{
+    auto* h = static_cast<Handle*>(hp);
+    if (!h || !origin || !direction || !out || max_hits < 1 || max_hits > RT_HITS_MAX) { g_err = "rth_raycast_all: bad arguments"; return -1; }
+    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
+    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
+    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
+    int rc = 0;
+    try {
+        rthost::RayTracingManager mgr = h->mgr;
+        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
+        const std::vector<rt_multihit> res = m ? mgr.RaycastAll(m, origin, direction, max_distance, max_hits, both_sides != 0)
+                                               : mgr.RaycastAll(ctx, origin, direction, max_distance, max_hits, both_sides != 0);
+        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(rt_multihit));
+        rc = (int)res.size();
+    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
+    if (m) rt_multi_destroy(m);
+    if (ctx) rt_destroy(ctx);
+    return rc;
+}
+
 // Animated scene through the compiled manager: `steps` times { every mesh is turned by the quaternion q4 (x, y, z, w: rotation = q * rotation)
 // and mesh i moves by shift3 * (i + 1); Start; OnRenderImage(frames_per_step) }, through one rt_ctx (n_contexts = 0) or an rt_multi of
 // n_contexts contexts, with or without the on-device geometry pipeline.  rgba = the last step's resultTexture.  What the reference does

@@ -5,7 +5,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
 import numpy as np
 
-from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape, CLOSEST
+from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape, CLOSEST, MULTIHIT
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_host.so")
 _lib = None
@@ -30,6 +30,7 @@ def load_host_library():
         L.rth_gather.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_visibility.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_closest_points.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p]
+        L.rth_raycast_all.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p]
         L.rth_split_mesh.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]
         L.rth_split_info.argtypes = [c_void_p, c_void_p, c_void_p]
         L.rth_split_triangles.argtypes = [c_void_p]
@@ -172,3 +173,16 @@ class CppScene:
         if self._L.rth_closest_points(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)):
             raise RtError("ClosestPoints: " + self._L.rth_last_error().decode())
         return out
+
+    def raycast_all(self, origin, direction, max_distance=np.inf, max_hits=8, both_sides=False, devices=(), device: int = 0) -> np.ndarray:
+        """RayTracingManager::RaycastAll on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: the non-empty MULTIHIT records of
+        one ray, nearest first."""
+        o, d = np.ascontiguousarray(origin, np.float32).reshape(3), np.ascontiguousarray(direction, np.float32).reshape(3)
+        out = np.zeros(max(int(max_hits), 1), MULTIHIT)
+        devs = list(devices) if devices else [device]
+        arr = (c_int * len(devs))(*devs)
+        n = self._L.rth_raycast_all(self._h, arr, len(devices), o.ctypes.data_as(c_void_p), d.ctypes.data_as(c_void_p), float(max_distance),
+                                    int(max_hits), int(bool(both_sides)), out.ctypes.data_as(c_void_p))
+        if n < 0:
+            raise RtError("RaycastAll: " + self._L.rth_last_error().decode())
+        return out[:n]

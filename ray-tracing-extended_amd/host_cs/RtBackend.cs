@@ -215,6 +215,25 @@ namespace RtMi355x
             return occ[0] != 0;
         }
 
+        /// Physics.RaycastAll for the traced scene: everything origin + t * direction passes through for t < maxDistance, nearest first,
+        /// at most maxHits (1..8) surfaces (RtHits.cs).  bothSides: back faces of triangles and exit points of spheres count too
+        /// (side = -1).  Returns the hits in order; hitCount == maxHits in them means there may be more.
+        public RtMultiHit[] RaycastAll(Vector3 origin, Vector3 direction, float maxDistance = float.PositiveInfinity, int maxHits = 8, bool bothSides = false)
+        {
+            EnsureContexts();
+            Push(ctx, multi);
+            RtRay[] rays = { MakeRay(origin, direction, maxDistance) };
+            RtHitsParams[] p = { new RtHitsParams { maxHits = maxHits, mode = bothSides ? 1 : 0 } };
+            RtMultiHit[] all = new RtMultiHit[Math.Max(maxHits, 1)];
+            if (multi != IntPtr.Zero) RtNative.CheckMulti(multi, RtNative.rt_multi_trace_hits(multi, rays, 1, p, all), "rt_multi_trace_hits");
+            else RtNative.Check(ctx, RtNative.rt_trace_hits(ctx, rays, 1, p, all), "rt_trace_hits");
+            int n = 0;
+            while (n < all.Length && all[n].kind != 0) n++;
+            RtMultiHit[] result = new RtMultiHit[n];
+            Array.Copy(all, result, n);
+            return result;
+        }
+
         // ---- radiance queries (light probes, lightmap texels, cameras the reference does not have: RtRadiance.cs) -------------------
         /// How much light arrives along each ray in the scene the next frame traces: Trace (RayTracing.shader:300-352) averaged over
         /// `samples` runs per ray (0 = numRaysPerPixel, with seed 0).  Returns rays.Length * 4 floats, (r, g, b, 1) per ray; a ray with

@@ -280,6 +280,11 @@ namespace RtMi355x
         [DllImport(Lib)] public static extern int rt_closest_points_device(IntPtr ctx, IntPtr points, int n, IntPtr result);
         [DllImport(Lib)] public static extern int rt_get_closest_info(IntPtr ctx, out RtClosestInfo info);
         [DllImport(Lib)] public static extern int rt_multi_closest_points(IntPtr multi, [In] RtRay[] points, int n, [Out] RtClosest[] result);
+        // multi-hit ray queries (RtHitsParams, RtMultiHit, RtHitsInfo: RtHits.cs; result holds n * maxHits records, ray-major)
+        [DllImport(Lib)] public static extern int rt_trace_hits(IntPtr ctx, [In] RtRay[] rays, int n, [In] RtHitsParams[] p, [Out] RtMultiHit[] result);
+        [DllImport(Lib)] public static extern int rt_trace_hits_device(IntPtr ctx, IntPtr rays, int n, [In] RtHitsParams[] p, IntPtr result);
+        [DllImport(Lib)] public static extern int rt_get_hits_info(IntPtr ctx, out RtHitsInfo info);
+        [DllImport(Lib)] public static extern int rt_multi_trace_hits(IntPtr multi, [In] RtRay[] rays, int n, [In] RtHitsParams[] p, [Out] RtMultiHit[] result);
 
         // ---- helpers --------------------------------------------------------------------------------------------------
         public static string LastError(IntPtr ctx) { return Marshal.PtrToStringAnsi(rt_last_error(ctx)) ?? ""; }
@@ -336,6 +341,9 @@ namespace RtMi355x
             Same("rt_visibility_info", Marshal.SizeOf<RtVisibilityInfo>());
             Same("rt_closest", Marshal.SizeOf<RtClosest>());
             Same("rt_closest_info", Marshal.SizeOf<RtClosestInfo>());
+            Same("rt_hits_params", Marshal.SizeOf<RtHitsParams>());
+            Same("rt_multihit", Marshal.SizeOf<RtMultiHit>());
+            Same("rt_hits_info", Marshal.SizeOf<RtHitsInfo>());
         }
     }
 }
