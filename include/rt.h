@@ -204,7 +204,8 @@ int rt_set_params(rt_ctx* ctx, const rt_params* params);
 /* Buffer upload = copy (caller may free immediately); n == 0 is legal.  Replaces
  * ShaderHelper.CreateStructuredBuffer + Material.SetBuffer/SetInt
  * (RayTracingManager.cs:159-163 "Triangles"/"AllMeshInfo"/"NumMeshes", :184-186 "Spheres"/"NumSpheres").
- * The library re-lays-out triangles and builds its BVH lazily at the next render.                      */
+ * The library re-lays-out triangles and builds its BVH lazily at the next render.
+ * With option "device_geometry" = 1 (rt_set_option) `tris` may lie in device memory: see the option.   */
 int rt_upload_spheres  (rt_ctx* ctx, const rt_sphere*   spheres,  int n);
 int rt_upload_triangles(rt_ctx* ctx, const rt_triangle* tris,     int n);
 int rt_upload_meshinfo (rt_ctx* ctx, const rt_meshinfo* meshinfo, int n);
@@ -268,7 +269,22 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     4-wide nodes: 100k triangles in 2.5 ms, 1M in 5.4 ms, traced within about 1 % / within -4 .. +2 % of the host tree), 0 = the
  *                     host's binned-SAH builder (50 ms / 600 ms), -1 (default) = device for rt_upload_local_meshes (meshes that move) and
  *                     for a world-space scene that is uploaded again within 16 traced frames of its last build (the reference's way of
- *                     animating: everything re-sent every frame), host for the first build of a world-space scene
+ *                     animating: everything re-sent every frame), host for the first build of a world-space scene.  Triangles uploaded from
+ *                     device memory ("device_geometry") are always built on the device, whatever this says: the host builder has no
+ *                     positions to read
+ *   "device_geometry" 0 (default) = rt_upload_triangles / rt_multi_upload_triangles read `tris` as host memory, as ever (no pointer query);
+ *                     1 = `tris` may also lie in memory of the context's device (hipMalloc'ed or managed; the first context's for rt_multi).  The
+ *                     call then copies n * 72 bytes device to device into the context's own buffer, on the context's stream (rt_set_stream),
+ *                     at call time: the caller's writes to `tris` must be ordered before the call (the same stream, or synchronised), and the
+ *                     caller may overwrite `tris` in work it orders after that stream.  No copy of the triangles is kept on the host.  A host
+ *                     pointer takes the usual path.  Refused with -2, nothing changed: n < 0, a device pointer that is not 4-byte aligned,
+ *                     memory of another device (n > 2^28: -3).  Such a scene is always built by the device builder.  An upload of the same
+ *                     number of triangles over a tree built this way — no rt_upload_meshinfo, rt_upload_spheres or builder option since — is a
+ *                     DEFORMATION: the next frame or query rewrites the tracer's triangle records in place (k_deform_update), refits the
+ *                     boxes, and rebuilds on the device only under "rebuild_percent"'s rule (rt_stats.bvhRebuilds; lastGeometryMs is the
+ *                     update's time).  Anything else is a new scene with a full device build.  rt_upload_meshinfo stays a host upload, and its
+ *                     boundsMin / boundsMax stay the caller's, as in the reference: a caller who deforms keeps them current (a min / max over
+ *                     the corners) or uses RT_INTERSECT_BRUTE.  Spheres, local meshes and transforms are host uploads
  *   "bvh_treelets"    device builder: number of sweep-SAH passes over the clustering's tree (default 6; 0 = none).  Pass k rebuilds, one wave
  *                     each, every maximal subtree of <= 64 * 8^k triangles over its subtrees of <= 8^k triangles (pass 0: over the triangles
  *                     themselves) with an exact sweep SAH — all three axes, every split position, large-box isolation — in the node slots the

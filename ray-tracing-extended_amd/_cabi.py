@@ -466,6 +466,31 @@ def _is_tensor(x) -> bool:
     return t.__module__.startswith("torch") and t.__name__ == "Tensor" and getattr(x, "is_cuda", False)
 
 
+def _device_triangles(tris, n):
+    """(device pointer, count, torch device or None) of upload_triangles_device's arguments"""
+    if _is_tensor(tris):
+        import torch
+        if tris.dtype != torch.float32 or tris.dim() != 2 or tris.shape[1] != 18 or not tris.is_contiguous():
+            raise ValueError(f"triangles: a contiguous float32 (n, 18) CUDA tensor, not {tris.dtype} {tuple(tris.shape)}")
+        if n is not None and int(n) != int(tris.shape[0]):
+            raise ValueError(f"n = {n} for a tensor of {int(tris.shape[0])} triangles")
+        return int(tris.data_ptr()), int(tris.shape[0]), tris.device
+    if isinstance(tris, (int, np.integer)) and not isinstance(tris, bool):
+        if n is None:
+            raise ValueError("a device pointer needs n")
+        return int(tris), int(n), None
+    raise ValueError("triangles: a float32 (n, 18) CUDA tensor, or an int device pointer and n")
+
+
+def _arm_device_geometry(tracer):
+    """option "device_geometry" for an upload from device memory: set to 1 unless set_option has set it; set to 0 it refuses here"""
+    state = getattr(tracer, "_device_geometry", None)
+    if state is None:
+        tracer.set_option("device_geometry", 1)
+    elif state == 0:
+        raise RtError("upload_triangles_device: option device_geometry is 0 (a device pointer would be read as host memory)")
+
+
 class Tracer:
     """One rt_ctx.  Thin, exception-raising wrapper; semantics are those documented in include/rt.h."""
 
@@ -514,6 +539,21 @@ class Tracer:
             a, ptr, n = _as_buffer(meshinfo, MESHINFO)
             self._check(self._lib.rt_upload_meshinfo(self._ctx, ptr, n), "rt_upload_meshinfo")
 
+    def upload_triangles_device(self, tris, n=None):
+        """rt_upload_triangles from device memory (option "device_geometry", which this sets to 1 unless set_option has set it): a
+        contiguous float32 CUDA tensor (n, 18) on the context's device — the copy is ordered with torch's current stream as trace_rays'
+        device entry is, so the tensor may be overwritten on that stream right after the call — or an int device pointer and n, copied on
+        the context's stream.  With the option set to 0 this raises before anything is called: a device pointer never reaches the host
+        path."""
+        tensor = _is_tensor(tris)
+        ptr, n, device = _device_triangles(tris, n)
+        _arm_device_geometry(self)
+        call = lambda: self._lib.rt_upload_triangles(self._ctx, c_void_p(ptr), n)      # noqa: E731
+        if tensor:
+            self._on_torch_stream(device, call, "rt_upload_triangles")
+        else:
+            self._check(call(), "rt_upload_triangles")
+
     # -- on-device geometry pipeline
     def upload_local_meshes(self, local_tris, chunks, n_meshes: int):
         t, tp, nt = _as_buffer(local_tris, TRIANGLE)
@@ -543,6 +583,8 @@ class Tracer:
 
     def set_option(self, name: str, value: int):
         self._check(self._lib.rt_set_option(self._ctx, name.encode(), int(value)), f"rt_set_option({name})")
+        if name == "device_geometry":
+            self._device_geometry = int(value)
 
     def set_stream(self, stream_ptr):
         self._check(self._lib.rt_set_stream(self._ctx, c_void_p(stream_ptr)), "rt_set_stream")
@@ -995,6 +1037,23 @@ class MultiTracer:
 
     def set_option(self, name: str, value: int):
         self._check(self._lib.rt_multi_set_option(self._m, name.encode(), int(value)), f"rt_multi_set_option({name})")
+        if name == "device_geometry":
+            self._device_geometry = int(value)
+
+    def upload_triangles_device(self, tris, n=None):
+        """rt_multi_upload_triangles from device memory of the first context's device: Tracer.upload_triangles_device's arguments.  The
+        handle has no stream of the caller's, so a tensor's upload is fenced: torch's current stream is synchronised before the call and
+        the device after it (the tensor may be overwritten at once)."""
+        tensor = _is_tensor(tris)
+        ptr, n, device = _device_triangles(tris, n)
+        _arm_device_geometry(self)
+        if tensor:
+            import torch
+            torch.cuda.current_stream(device).synchronize()
+        rc = self._lib.rt_multi_upload_triangles(self._m, c_void_p(ptr), n)
+        if tensor:
+            torch.cuda.synchronize(device)
+        self._check(rc, "rt_multi_upload_triangles")
 
     def reset_accum(self):
         self._check(self._lib.rt_multi_reset_accum(self._m), "rt_multi_reset_accum")

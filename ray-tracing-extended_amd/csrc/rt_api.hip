@@ -143,6 +143,12 @@ struct rt_ctx : ErrOwner {
     std::vector<rt_triangle> h_tris;
     std::vector<rt_meshinfo> h_mesh;
     bool scene_dirty = true;
+    // option "device_geometry" (rt_upload_triangles from device memory, DESIGN.md "Device-resident triangles")
+    int opt_device_geometry = 0;
+    bool tris_resident = false;         // the uploaded triangles live in d_raw_tris only (h_tris is empty); n_resident of them
+    size_t n_resident = 0;
+    bool tree_resident = false;         // the current tree was built from device-resident triangles
+    bool deform_pending = false;        // d_raw_tris holds new corners for that tree: prepare_scene updates it in place
     size_t n_tris = 0, n_chunks = 0, n_spheres = 0;     // of the scene on the device (set by build_scene / build_scene_local / clone_scene)
     float sphere_mag = 0.f;                             // largest |coordinate| of a sphere surface point of that scene
     // on-device geometry pipeline (rt_upload_local_meshes / rt_set_mesh_transforms)
@@ -434,11 +440,14 @@ int upload_spheres_and_materials(rt_ctx* c)
     return 0;
 }
 
+// Triangles of the world-space upload: in h_tris, or in d_raw_tris alone after an upload from device memory
+size_t world_tri_count(const rt_ctx* c) { return c->tris_resident ? c->n_resident : c->h_tris.size(); }
+
 // The end of a build: the scene's figures and the counts the launches read.  A new scene starts without a tile order; a rebuild of
 // meshes that moved keeps the last one as a predictor, re-measured by the next launch.
 void finish_build(rt_ctx* c, bool rebuild = false)
 {
-    const size_t nt = c->geom_local ? c->h_local_tris.size() : c->h_tris.size(), nm = c->geom_local ? c->h_lchunks.size() : c->h_mesh.size();
+    const size_t nt = c->geom_local ? c->h_local_tris.size() : world_tri_count(c), nm = c->geom_local ? c->h_lchunks.size() : c->h_mesh.size();
     c->stats.numSpheres = (int)c->h_spheres.size(); c->stats.numTriangles = (int)nt; c->stats.numMeshChunks = (int)nm;
     c->stats.numBvhNodes = (int)c->n_nodes; c->stats.bvhMaxStack = c->bvh.maxStack; c->stats.bvhInternalArea = c->area_at_build;
     c->n_spheres = c->h_spheres.size(); c->n_tris = nt; c->n_chunks = nm; c->sphere_mag = sphere_magnitude(c);
@@ -450,7 +459,7 @@ void finish_build(rt_ctx* c, bool rebuild = false)
 // Re-layout of the uploaded buffers + BVH build.
 int build_scene(rt_ctx* c)
 {
-    const size_t nt = c->h_tris.size(), nm = c->h_mesh.size();
+    const size_t nt = world_tri_count(c), nm = c->h_mesh.size();
     if (nt > (1u << 28)) return fail(c, -3, "too many triangles (%zu)", nt);
     // triangle -> chunk map; every triangle the shader can reach belongs to exactly the chunk ranges given.  Equal-distance hits: the
     // reference keeps the triangle its loops reach first — chunks in AllMeshInfo order, triangles in order inside the chunk
@@ -484,8 +493,11 @@ int build_scene(rt_ctx* c)
         range[2 * m] = mi.firstTriangleIndex; range[2 * m + 1] = mi.numTriangles;
     }
     RT_HIP(c, upload(c, c->d_chunk_mat, cm)); RT_HIP(c, upload(c, c->d_chunk_box, cb)); RT_HIP(c, upload(c, c->d_raw_range, range));
-    RT_HIP(c, c->d_raw_tris.ensure(nt * 18));
-    if (nt) RT_HIP(c, hipMemcpyAsync(c->d_raw_tris.p, c->h_tris.data(), nt * sizeof(rt_triangle), hipMemcpyHostToDevice, c->stream));
+    // (resident triangles are in d_raw_tris already: rt_upload_triangles copied them there, device to device)
+    if (!c->tris_resident) {
+        RT_HIP(c, c->d_raw_tris.ensure(nt * 18));
+        if (nt) RT_HIP(c, hipMemcpyAsync(c->d_raw_tris.p, c->h_tris.data(), nt * sizeof(rt_triangle), hipMemcpyHostToDevice, c->stream));
+    }
     RT_HIP(c, upload(c, c->d_tri_chunk, chunk_of)); RT_HIP(c, upload(c, c->d_tri_rank, visit_rank));     // (what k_relayout reads)
     // headroom: the boxes are padded for ray origins up to twice as far out as the camera and the spheres are now (the term is
     // 2e-6 * G), so a camera that drifts away from the geometry widens the padding (repad_boxes) once per doubling, not per frame
@@ -497,7 +509,9 @@ int build_scene(rt_ctx* c)
     const bool moving = c->opt_device_bvh == -1 && c->frames_at_world_build != ~0ull && c->frames_traced - c->frames_at_world_build <= 16;
     c->frames_at_world_build = c->frames_traced;
     int r;
-    if ((c->opt_device_bvh == 1 || moving) && nt > 0) {
+    c->deform_pending = false; c->tree_resident = c->tris_resident && nt > 0;
+    // resident triangles: the host builder has no positions to read, so the tree is the device builder's whatever device_bvh says
+    if ((c->opt_device_bvh == 1 || moving || c->tris_resident) && nt > 0) {
         // the device builder takes every uploaded triangle; one that belongs to no chunk gets NaN records (k_relayout) and can never be hit
         r = device_build(c, (uint32_t)nt, origin_mag);
     } else {
@@ -534,6 +548,45 @@ int repad_boxes(rt_ctx* c, float G)
     if (c->n_nodes && c->bvh.levelStart.size() >= 2) { int r = refit_tree(c, G); if (r) return r; }
     c->bvh.magnitude = G;
     c->stats.bvhRepads++; c->scene_version++;
+    return 0;
+}
+
+// Device-resident triangles that deformed (rt_upload_triangles put new corners for the current tree into d_raw_tris): the tracer's
+// records are rewritten in BVH order (k_deform_update), the boxes refitted level by level for the padding the tree has, and the
+// refitted tree's internal area decides, by the local meshes' rule, whether the device builder replaces it.
+int deform_update(rt_ctx* c)
+{
+    const uint32_t nt = (uint32_t)c->n_tris;
+    c->deform_pending = false;
+    RT_HIP(c, c->d_q_bound.ensure(1));
+    RT_HIP(c, hipEventRecord(c->evg0, c->stream));
+    RT_HIP(c, hipMemsetAsync(c->d_q_bound.p, 0, sizeof(unsigned int), c->stream));
+    hipLaunchKernelGGL(rtg::k_deform_update, dim3((nt + 255) / 256), dim3(256), 0, c->stream,
+                       c->d_raw_tris.p, c->d_order.p, c->d_tri_geo.p, c->d_tri_nrm.p, nt, c->d_q_bound.p);
+    RT_HIP(c, hipGetLastError());
+    // bounce rays start on the triangles: the padding's magnitude covers the new corners as a build's would (4 bytes back, one wait)
+    unsigned int mag_bits = 0;
+    RT_HIP(c, hipMemcpyAsync(&mag_bits, c->d_q_bound.p, sizeof mag_bits, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    c->bvh.magnitude = std::max(c->bvh.magnitude, u2f(mag_bits));
+    { int r = refit_tree(c, c->bvh.magnitude); if (r) return r; }
+    const bool check_area = c->opt_rebuild_percent > 0 && c->area_at_build > 0.f;
+    if (check_area) RT_HIP(c, rtgb::internal_area_async(c->stream, reinterpret_cast<const rtbvh::Node4*>(c->d_nodes.p), (uint32_t)c->n_nodes, c->bvh_ws, &c->area_after_refit));
+    RT_HIP(c, hipEventRecord(c->evg1, c->stream));
+    RT_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&ms, c->evg0, c->evg1));
+    c->stats.lastGeometryMs = ms; c->scene_version++;
+    if (check_area) {
+        const float area = c->area_after_refit;
+        c->stats.refitAreaRatio = area / c->area_at_build;
+        if (area > c->area_at_build * (float)c->opt_rebuild_percent / 100.0f) {
+            int r = device_build(c, nt, std::max(c->bvh.magnitude, 2.0f * std::max(camera_magnitude(c->params), c->sphere_mag))); if (r) return r;
+            RT_HIP(c, hipStreamSynchronize(c->stream));
+            c->stats.bvhRebuilds++;
+            finish_build(c, true);
+        }
+    }
     return 0;
 }
 
@@ -650,6 +703,7 @@ int prepare_scene(rt_ctx* c)
         return 0;
     }
     if (c->scene_dirty) return build_scene(c);
+    if (c->deform_pending) { int r = deform_update(c); if (r) return r; }
     const float om = std::max(camera_magnitude(c->params), c->sphere_mag);
     return om > c->bvh.magnitude ? repad_boxes(c, 2.0f * om) : 0;     // widen the box padding, keep the tree
 }
@@ -686,6 +740,7 @@ int clone_scene(rt_ctx* dst, rt_ctx* src)
 #undef RT_CLONE
     RT_HIP(dst, hipStreamSynchronize(dst->stream));
     dst->h_spheres.clear(); dst->h_tris.clear(); dst->h_mesh.clear(); dst->geom_local = false;
+    dst->tris_resident = false; dst->n_resident = 0; dst->tree_resident = false; dst->deform_pending = false;   // (a received scene is nobody's upload)
     dst->bvh.nodes.clear(); dst->bvh.order.clear();
     dst->bvh.levelStart = src->bvh.levelStart; dst->bvh.maxStack = src->bvh.maxStack; dst->bvh.depth = src->bvh.depth; dst->bvh.magnitude = src->bvh.magnitude;
     dst->n_nodes = src->n_nodes; dst->area_at_build = src->area_at_build;
@@ -1309,6 +1364,14 @@ bool on_ctx_device(const rt_ctx* c, const void* p)
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged) && a.device == c->device;
+}
+
+// the device in whose memory p lies (hipMalloc'ed or managed), -1: host memory (a plain host pointer makes the query fail)
+int device_of_ptr(const void* p)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged || a.isManaged) ? a.device : -1;
 }
 
 // cover_origins for rays in device memory: the origin bound of the batch is measured on the device — one small kernel and a 4-byte
@@ -2182,7 +2245,27 @@ int rt_upload_triangles(rt_ctx* c, const rt_triangle* t, int n)
     if (!c) return -1;
     RT_SETTLE(c);
     if (n < 0 || (n > 0 && !t)) return fail(c, -2, "bad triangle upload (n=%d)", n);
+    // option "device_geometry": tris may lie in device memory.  Everything is checked before anything changes
+    const int dev = (c->opt_device_geometry && n > 0) ? device_of_ptr(t) : -1;
+    if (dev >= 0) {
+        if (n > (1 << 28)) return fail(c, -3, "too many triangles (%d)", n);
+        if (dev != c->device) return fail(c, -2, "rt_upload_triangles: tris lies in memory of device %d, the context is on device %d", dev, c->device);
+        if ((uintptr_t)t % 4 != 0) return fail(c, -2, "rt_upload_triangles: the device pointer is not 4-byte aligned");
+        RT_HIP(c, hipSetDevice(c->device));
+        // new corners for the tree that stands (same count, built from resident triangles, nothing else uploaded or set since): it is
+        // updated in place by the next frame or query.  Anything else is a new scene
+        const bool deformation = !c->scene_dirty && !c->geom_local && c->tree_resident && (size_t)n == c->n_tris;
+        if (!deformation && c->d_raw_tris.cap < (size_t)n * 18) RT_HIP(c, hipStreamSynchronize(c->stream));   // (the buffer is replaced: nothing may still read it)
+        RT_HIP(c, c->d_raw_tris.ensure((size_t)n * 18));
+        RT_HIP(c, hipMemcpyAsync(c->d_raw_tris.p, t, (size_t)n * sizeof(rt_triangle), hipMemcpyDeviceToDevice, c->stream));
+        c->h_tris.clear(); c->h_tris.shrink_to_fit();
+        c->tris_resident = true; c->n_resident = (size_t)n; c->geom_local = false;
+        if (deformation) c->deform_pending = true;
+        else c->scene_dirty = true;
+        return 0;
+    }
     c->h_tris.assign(t, t + n); c->scene_dirty = true; c->geom_local = false;
+    c->tris_resident = false; c->n_resident = 0; c->deform_pending = false;
     return 0;
 }
 int rt_upload_meshinfo(rt_ctx* c, const rt_meshinfo* m, int n)
@@ -2219,6 +2302,7 @@ int rt_upload_local_meshes(rt_ctx* c, const rt_triangle* tris, int n_tris, const
     c->h_local_tris.assign(tris, tris + n_tris); c->h_lchunks.assign(chunks, chunks + n_chunks);
     c->mesh_radius = radius; c->n_meshes = n_meshes;
     c->geom_local = true; c->scene_dirty = true;
+    c->tris_resident = false; c->n_resident = 0; c->tree_resident = false; c->deform_pending = false;     // (d_raw_tris becomes this pipeline's output)
     return 0;
 }
 
@@ -2284,6 +2368,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "compact_nodes")) c->opt_compact_nodes = value ? 1 : 0;
     else if (!std::strcmp(name, "device_bvh")) { if (value < -1 || value > 1) return fail(c, -2, "device_bvh must be -1 (automatic), 0 or 1"); if (value != c->opt_device_bvh) c->scene_dirty = true; c->opt_device_bvh = value; }
     else if (!std::strcmp(name, "bvh_radius")) { if (value == 0 || value < -rtgb::kMaxRadius || value > rtgb::kMaxRadius) return fail(c, -2, "bvh_radius must be in [1,64] (negative: the same radius in every round)"); if (value != c->opt_bvh_radius) c->scene_dirty = true; c->opt_bvh_radius = value; }
+    else if (!std::strcmp(name, "device_geometry")) { if (value != 0 && value != 1) return fail(c, -2, "device_geometry must be 0 or 1"); c->opt_device_geometry = value; }
     else if (!std::strcmp(name, "peer_copies")) { if (value != 0 && value != 1) return fail(c, -2, "peer_copies must be 0 or 1"); c->opt_peer_copies = value; }
     else if (!std::strcmp(name, "bvh_treelet_ratio")) { if (value < 2 || value > 64) return fail(c, -2, "bvh_treelet_ratio must be in [2,64]"); if (value != c->opt_bvh_treelet_ratio) c->scene_dirty = true; c->opt_bvh_treelet_ratio = value; }
     else if (!std::strcmp(name, "bvh_treelet_isolate")) { if (value < 0 || value > 1) return fail(c, -2, "bvh_treelet_isolate must be 0 or 1"); if (value != c->opt_bvh_treelet_isolate) c->scene_dirty = true; c->opt_bvh_treelet_isolate = value; }

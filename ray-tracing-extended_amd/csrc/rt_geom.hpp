@@ -107,6 +107,68 @@ __global__ __launch_bounds__(256) void k_relayout(const float* __restrict__ worl
     tri_nrm[3 * (size_t)i + 2] = make_float4(t[15], t[16], t[17], 0.f);
 }
 
+// Deformation update (option "device_geometry", DESIGN.md "Device-resident triangles"): the triangles of a tree that stays have new
+// corners and normals in world_tris.  One thread per triangle in BVH order rewrites the tracer's records — the bits k_relayout would
+// write.  A triangle record is 72 B, so it starts on a 16-byte boundary when its index is even and 8 bytes past one when it is odd: four
+// 16-byte loads and one 8-byte load either way.  Chunk and visiting rank do not change with the corners: they come from the record
+// itself (two loads in BVH order, next to the stores) instead of two more gathers through `order`.  72 B + 12 B in, 96 B out.
+// The corners are in registers anyway, so the pass also finds what the refit's padding needs: the largest finite |coordinate| of a
+// corner (the device builder's k_tri_bounds rule), reduced per wave and merged into *mag_bits — a non-negative float's bits order as
+// an unsigned integer — by one atomic per wave.
+__global__ __launch_bounds__(256) void k_deform_update(const float* __restrict__ world_tris, const uint32_t* __restrict__ order,
+                                                       float4* __restrict__ tri_geo, float4* __restrict__ tri_nrm, uint32_t nl,
+                                                       unsigned int* __restrict__ mag_bits)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    float mag = 0.f;
+    if (i < nl) {
+    const uint32_t orig = order[i];
+    const float* s = world_tris + (size_t)orig * 18;
+    float t[18];
+    if (orig & 1u) {
+        const float2 h = *reinterpret_cast<const float2*>(s);
+        t[0] = h.x; t[1] = h.y;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *reinterpret_cast<const float4*>(s + 2 + 4 * q);
+            t[2 + 4 * q] = v.x; t[3 + 4 * q] = v.y; t[4 + 4 * q] = v.z; t[5 + 4 * q] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 v = *reinterpret_cast<const float4*>(s + 4 * q);
+            t[4 * q] = v.x; t[4 * q + 1] = v.y; t[4 * q + 2] = v.z; t[4 * q + 3] = v.w;
+        }
+        const float2 h = *reinterpret_cast<const float2*>(s + 16);
+        t[16] = h.x; t[17] = h.y;
+    }
+    const uint32_t* old = reinterpret_cast<const uint32_t*>(tri_nrm + 3 * (size_t)i);
+    const uint32_t chunk = old[3], rank = old[7];
+    const float ex = t[3] - t[0], ey = t[4] - t[1], ez = t[5] - t[2];          // RayTriangle :152-154
+    const float fx = t[6] - t[0], fy = t[7] - t[1], fz = t[8] - t[2];
+    const float nx = ey * fz - ez * fy, ny = ez * fx - ex * fz, nz = ex * fy - ey * fx;
+    if (chunk == 0xFFFFFFFFu) {
+        const float q = __uint_as_float(0x7FC00000u);                           // in no chunk: never hit (k_relayout)
+        tri_geo[3 * (size_t)i + 0] = tri_geo[3 * (size_t)i + 1] = tri_geo[3 * (size_t)i + 2] = make_float4(q, q, q, q);
+    } else {
+        tri_geo[3 * (size_t)i + 0] = make_float4(t[0], t[1], t[2], ex);
+        tri_geo[3 * (size_t)i + 1] = make_float4(ey, ez, fx, fy);
+        tri_geo[3 * (size_t)i + 2] = make_float4(fz, nx, ny, nz);
+    }
+    tri_nrm[3 * (size_t)i + 0] = make_float4(t[9], t[10], t[11], __uint_as_float(chunk));
+    tri_nrm[3 * (size_t)i + 1] = make_float4(t[12], t[13], t[14], __uint_as_float(rank));
+    tri_nrm[3 * (size_t)i + 2] = make_float4(t[15], t[16], t[17], 0.f);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {       // (min / max first, as tri_box does: a NaN corner leaves the others' extent)
+        const float lo = __builtin_fminf(__builtin_fminf(t[a], t[3 + a]), t[6 + a]), hi = __builtin_fmaxf(__builtin_fmaxf(t[a], t[3 + a]), t[6 + a]);
+        const float m = __builtin_fmaxf(__builtin_fabsf(lo), __builtin_fabsf(hi));
+        if (m < 3.0e38f) mag = __builtin_fmaxf(mag, m);
+    }
+    }
+    for (int off = 32; off > 0; off >>= 1) mag = __builtin_fmaxf(mag, __shfl_down(mag, off, 64));
+    if ((threadIdx.x & 63) == 0 && mag > 0.f) atomicMax(mag_bits, __float_as_uint(mag));
+}
+
 // Refit one level of the BVH4 (nodes [n0, n1)), one thread per (node, slot); deeper levels must be done already.
 // Leaf slots: padded bounds of their triangles (same padding as bvh.cpp pad_box); internal slots: union of the child
 // node's four slot boxes.

@@ -276,6 +276,8 @@ class RayTracingManager:
         self.intersectMode = RT_INTERSECT_FLAT_CHUNKS
         self.backend = backend
         self.deviceGeometry = False                       # True: transform / bounds / BVH refit on the GPU (rt_upload_local_meshes)
+        self.deviceTriangles = None                       # a float32 (n, 18) CUDA tensor of world-space triangles, or a callable that returns
+                                                          # this frame's: the caller deforms on the device, no CPU transform (InitFrame)
         self._dirty = True
 
     # -- RayTracingManager.cs:196-203
@@ -383,6 +385,23 @@ class RayTracingManager:
     def InitFrame(self):
         if self.backend is None:
             raise RuntimeError("RayTracingManager has no backend (HIP Tracer); there is no CPU path")
+        if self.deviceTriangles is not None:
+            # the caller holds the world-space triangles on the device (skinning, cloth, a simulation): the chunks' ranges, materials and
+            # boxes go up once — the boxes are the first pose's, so a caller whose mesh leaves them sets intersectMode to
+            # RT_INTERSECT_BRUTE or uploads new ones — and every frame hands over the tensor (Tracer.upload_triangles_device: updated in
+            # place while the count stays)
+            params = np.zeros((), PARAMS)
+            params["width"], params["height"] = self.width, self.height
+            params["intersectMode"] = self.intersectMode
+            self.UpdateCameraParams(params)
+            self.SetShaderParams(params)
+            self.backend.set_params(params)
+            if self._dirty:
+                self.backend.upload(spheres=self.CreateSpheres(), meshinfo=self.CreateMeshes()[1])
+                self._dirty = False
+            tris = self.deviceTriangles() if callable(self.deviceTriangles) else self.deviceTriangles
+            self.backend.upload_triangles_device(tris)
+            return
         if self.deviceGeometry:
             params = np.zeros((), PARAMS)
             params["width"], params["height"] = self.width, self.height
