@@ -1431,7 +1431,22 @@ struct QueryCall {
     bool timed() const { return family != kRays; }          // has an info record with calls and kernel times
 };
 
-// What every launch function ends with: the fields all four Args share, then the launch on the context's stream
+// A kernel's instantiation for the node form the renderer's kernels traverse (plan_launch): k<..., true> for compact nodes
+template <class K> const void* pick_nodes(const rt_ctx* c, K* compact, K* plain)
+{
+    return c->opt_compact_nodes != 0 ? (const void*)compact : (const void*)plain;
+}
+
+// What the kernels that answer with a record start from (rtk::QueryHead's fields; QueryArgs has them under the same names)
+template <class Args> void fill_head(const rt_ctx* c, const QuerySlice& s, Args& A)
+{
+    A.in = s.in;
+    A.order = c->d_order.p;
+    A.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
+    A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS; k_closest does not read it)
+}
+
+// What every launch function ends with: the fields all the Args share, then the launch on the context's stream
 template <class Args> hipError_t launch_slice(rt_ctx* c, const void* fn, const QuerySlice& s, Args& A)
 {
     A.n = s.n; A.stack_cap = s.st.cap; A.gstack = s.st.gstack; A.gstack_stride = s.st.stride;
@@ -1544,15 +1559,11 @@ int sampled_arguments(rt_ctx* c, QueryCall& q, bool need_params, const void* in,
 template <bool ANY> hipError_t launch_rays(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
     rtk::QueryArgs Q{};
-    Q.order = c->d_order.p;
-    Q.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
-    Q.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    fill_head(c, s, Q);
     Q.full_sort = c->opt_full_sort;
-    Q.rays = s.in;
     Q.hits = ANY ? nullptr : static_cast<float4*>(s.out);
     Q.occluded = ANY ? static_cast<uint8_t*>(s.out) : nullptr;
-    // (H: the node form the renderer's kernels traverse, plan_launch)
-    return launch_slice(c, c->opt_compact_nodes != 0 ? (const void*)rtk::k_ray_query<ANY, true> : (const void*)rtk::k_ray_query<ANY, false>, s, Q);
+    return launch_slice(c, pick_nodes(c, rtk::k_ray_query<ANY, true>, rtk::k_ray_query<ANY, false>), s, Q);
 }
 // n rt_hit (4 float4 each) / n occlusion bytes
 int trace_rays_call(rt_ctx* c, const char* what, const void* rays, int n, const void*, const void* hits, QueryCall& q)
@@ -1573,7 +1584,7 @@ hipError_t launch_radiance(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
     A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
     A.full_sort = c->opt_full_sort;
     A.rays = s.in; A.rgba = static_cast<float4*>(s.out);
-    return launch_slice(c, c->opt_compact_nodes != 0 ? (const void*)rtk::k_radiance<true> : (const void*)rtk::k_radiance<false>, s, A);
+    return launch_slice(c, pick_nodes(c, rtk::k_radiance<true>, rtk::k_radiance<false>), s, A);
 }
 // n float4; params == NULL: the context's numRaysPerPixel samples
 int radiance_call(rt_ctx* c, const char* what, const void* rays, int n, const void* params, const void* rgba, QueryCall& q)
@@ -1589,9 +1600,8 @@ hipError_t launch_gather(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
     A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
     A.full_sort = c->opt_full_sort;
     A.points = s.in; A.out = static_cast<float4*>(s.out);
-    const bool compact = c->opt_compact_nodes != 0;
-    return launch_slice(c, q.p.mode == RT_GATHER_SH9 ? (compact ? (const void*)rtk::k_gather<RT_GATHER_SH9, true> : (const void*)rtk::k_gather<RT_GATHER_SH9, false>)
-                                                     : (compact ? (const void*)rtk::k_gather<RT_GATHER_COSINE, true> : (const void*)rtk::k_gather<RT_GATHER_COSINE, false>), s, A);
+    return launch_slice(c, q.p.mode == RT_GATHER_SH9 ? pick_nodes(c, rtk::k_gather<RT_GATHER_SH9, true>, rtk::k_gather<RT_GATHER_SH9, false>)
+                                                     : pick_nodes(c, rtk::k_gather<RT_GATHER_COSINE, true>, rtk::k_gather<RT_GATHER_COSINE, false>), s, A);
 }
 // n or 9 n float4; params == NULL: the context's numRaysPerPixel samples
 int gather_call(rt_ctx* c, const char* what, const void* points, int n, const void* params, const void* out, QueryCall& q)
@@ -1609,11 +1619,10 @@ hipError_t launch_visibility(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
     A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
     A.full_sort = c->opt_full_sort;
     A.points = s.in; A.out = static_cast<float4*>(s.out);
-    const bool compact = c->opt_compact_nodes != 0;
     switch (q.p.mode) {
-    case RT_VIS_SH9:      return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_SH9, true> : (const void*)rtk::k_visibility<RT_VIS_SH9, false>, s, A);
-    case RT_VIS_DISTANCE: return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_DISTANCE, true> : (const void*)rtk::k_visibility<RT_VIS_DISTANCE, false>, s, A);
-    default:              return launch_slice(c, compact ? (const void*)rtk::k_visibility<RT_VIS_COSINE, true> : (const void*)rtk::k_visibility<RT_VIS_COSINE, false>, s, A);
+    case RT_VIS_SH9:      return launch_slice(c, pick_nodes(c, rtk::k_visibility<RT_VIS_SH9, true>, rtk::k_visibility<RT_VIS_SH9, false>), s, A);
+    case RT_VIS_DISTANCE: return launch_slice(c, pick_nodes(c, rtk::k_visibility<RT_VIS_DISTANCE, true>, rtk::k_visibility<RT_VIS_DISTANCE, false>), s, A);
+    default:              return launch_slice(c, pick_nodes(c, rtk::k_visibility<RT_VIS_COSINE, true>, rtk::k_visibility<RT_VIS_COSINE, false>), s, A);
     }
 }
 // n or 3 n float4; params == NULL: RT_VISIBILITY_DEFAULT_SAMPLES samples.  No rt_params are needed: the kernel reads intersectMode
@@ -1640,15 +1649,13 @@ int begin_closest(rt_ctx* c)
 hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
     rtk::ClosestArgs A{};
-    A.order = c->d_order.p;
-    A.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
-    A.points = s.in; A.out = static_cast<float4*>(s.out);
-    const bool compact = c->opt_compact_nodes != 0;
+    fill_head(c, s, A);
+    A.out = static_cast<float4*>(s.out);
     if (c->opt_closest_count) {
         A.counters = c->d_closest_counts.p;
-        return launch_slice(c, compact ? (const void*)rtk::k_closest<true, true> : (const void*)rtk::k_closest<false, true>, s, A);
+        return launch_slice(c, pick_nodes(c, rtk::k_closest<true, true>, rtk::k_closest<false, true>), s, A);
     }
-    return launch_slice(c, compact ? (const void*)rtk::k_closest<true, false> : (const void*)rtk::k_closest<false, false>, s, A);
+    return launch_slice(c, pick_nodes(c, rtk::k_closest<true, false>, rtk::k_closest<false, false>), s, A);
 }
 // n rt_closest (4 float4 each); no params of either kind
 int closest_call(rt_ctx* c, const char* what, const void* points, int n, const void*, const void* out, QueryCall& q)
@@ -1661,15 +1668,12 @@ int closest_call(rt_ctx* c, const char* what, const void* points, int n, const v
 hipError_t launch_hits(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
     rtk::MultihitArgs A{};
-    A.order = c->d_order.p;
-    A.tri_mesh = c->geom_local ? c->d_tri_mesh.p : nullptr;
-    A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
+    fill_head(c, s, A);
     A.max_hits = q.h.maxHits; A.count_all = q.h.countAll;
-    A.rays = s.in; A.out = static_cast<float4*>(s.out);
+    A.out = static_cast<float4*>(s.out);
     c->hits_last = q.h;
-    const bool compact = c->opt_compact_nodes != 0;
-    if (q.h.mode == RT_HITS_BOTH) return launch_slice(c, compact ? (const void*)rtk::k_multihit<true, true> : (const void*)rtk::k_multihit<false, true>, s, A);
-    return launch_slice(c, compact ? (const void*)rtk::k_multihit<true, false> : (const void*)rtk::k_multihit<false, false>, s, A);
+    if (q.h.mode == RT_HITS_BOTH) return launch_slice(c, pick_nodes(c, rtk::k_multihit<true, true>, rtk::k_multihit<false, true>), s, A);
+    return launch_slice(c, pick_nodes(c, rtk::k_multihit<true, false>, rtk::k_multihit<false, false>), s, A);
 }
 // n * K rt_multihit (4 float4 each); params == NULL: RT_HITS_DEFAULT_MAX records per ray, front faces, hitCount capped at K.  No
 // rt_params are needed: the kernel reads intersectMode alone, as the ray queries do
@@ -1742,7 +1746,7 @@ int render_aov(rt_ctx* c, int first_frame, int n_frames)
     LaneStack st;
     { int r = plan_lane_stack(c, (size_t)grid * rtk::kBlock, st, "rt_render_aov"); if (r) return r; }
     A.stack_cap = st.cap; A.gstack = st.gstack; A.gstack_stride = st.stride;
-    const void* fn = c->opt_compact_nodes != 0 ? (const void*)rtk::k_aov<true> : (const void*)rtk::k_aov<false>;     // the node form the renderer's kernels traverse
+    const void* fn = pick_nodes(c, rtk::k_aov<true>, rtk::k_aov<false>);
     RT_HIP(c, hipEventRecord(c->ev0, c->stream));
     for (int f = 0; f < n_frames; ++f) {
         A.frame = first_frame + f; A.accumulated = c->aov_info.framesAccumulated + f;

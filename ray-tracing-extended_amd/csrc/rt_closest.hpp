@@ -20,15 +20,9 @@ namespace rtk {
 
 static_assert(sizeof(rt_closest) == 64, "a closest-point record is four float4 stores");
 
-struct ClosestArgs {
-    const float4* points;       // [n*2]  rt_ray: (p, R) (-, -)
+struct ClosestArgs : QueryHead {        // (intersect_mode is not read: the chunk filter is a ray's)
     float4* out;                // [n*4]  rt_closest
-    const uint32_t* order;      // BVH order -> uploaded triangle (d_order)
-    const uint32_t* tri_mesh;   // uploaded triangle -> mesh (local uploads); null = world-space upload
     unsigned long long* counters;   // counting build: [0] node steps, [1] primitive tests (spheres and triangles) of the call so far
-    uint32_t* gstack; unsigned int gstack_stride;   // as QueryArgs
-    int n;
-    int stack_cap;
 };
 
 // kb * kCullSlack is the largest lower bound that is still visited; never below kCullFloor, so that no square that matters to the
@@ -150,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
     const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
     const float INF = __builtin_inff(), FMAX = 3.4028235e38f;
     float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (present) r0 = Q.points[2 * (size_t)i];
+    if (present) r0 = Q.in[2 * (size_t)i];
     const v3 p = rtm::mk(r0.x, r0.y, r0.z);
     const float R = r0.w;
     // R <= 0 or NaN: not searched.  A point with a component that is not finite has no candidate either — every key it forms is +inf
@@ -173,60 +167,33 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
         }
         if (S.nn > 0) {
             const float4* nodes = H ? S.nodes_h : S.nodes;
-            int sp = 0;
-            uint32_t cur = 0;                                           // root
-            uint32_t top = kNone;                                       // the top of the stack in a register, as in closest_hit
-#define RT_PUSH(X) { if (top != kNone) stk.push(sp, top); top = (X); }
-#define RT_POP()   { cur = top; top = (sp > 0) ? stk.pop(sp) : kNone; }
-            while (cur != kNone) {
-                while ((int)cur >= 0) {
-                    if (COUNT) ++n_nodes;
-                    float l0, l1, l2, l3;
-                    uint32_t c0, c1, c2, c3;
-                    closest_node_step<H>(nodes, cur, p, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
-                    if (c3 != kNone) RT_PUSH(c3)
-                    if (c2 != kNone) RT_PUSH(c2)
-                    if (c1 != kNone) RT_PUSH(c1)
-                    if (c0 != kNone) cur = c0;
-                    else RT_POP()
+            RT_WALK_NODE(stk, 0u)                                       // from the root
+                if (COUNT) ++n_nodes;
+                float l0, l1, l2, l3;
+                uint32_t c0, c1, c2, c3;
+                closest_node_step<H>(nodes, node, p, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
+            RT_WALK_TRIANGLE(S.tri_geo, c0 != kNone, c1 != kNone, c2 != kNone, c3 != kNone)
+                float k, u, v;
+                closest_on_triangle(p, tri_A, tri_AB, tri_AC, k, u, v);
+                if (COUNT) ++n_prims;
+                if (k <= kb) {
+                    bool take = k < kb;
+                    // equal keys: a sphere keeps the tie (and so does the bound R * R while nothing has been found); between
+                    // triangles the lower uploaded index wins
+                    if (!take && best != kNone && (best & kTriBit)) take = Q.order[ti] < Q.order[best & ~kTriBit];
+                    if (take) { kb = k; best = kTriBit | ti; bu = u; bv = v; }
                 }
-                if (cur != kNone) {
-                    const uint32_t first = (cur & 0x7FFFFFFFu) >> 2, count = (cur & 3u) + 1u;
-                    for (uint32_t j = 0; j < count; ++j) {
-                        const uint32_t ti = first + j;
-                        float4 g0, g1, g2;
-                        load_tri(S.tri_geo, ti, g0, g1, g2);
-                        float k, u, v;
-                        closest_on_triangle(p, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), k, u, v);
-                        if (COUNT) ++n_prims;
-                        if (k <= kb) {
-                            bool take = k < kb;
-                            // equal keys: a sphere keeps the tie (and so does the bound R * R while nothing has been found); between
-                            // triangles the lower uploaded index wins
-                            if (!take && best != kNone && (best & kTriBit)) take = Q.order[ti] < Q.order[best & ~kTriBit];
-                            if (take) { kb = k; best = kTriBit | ti; bu = u; bv = v; }
-                        }
-                    }
-                    RT_POP()
-                }
-            }
-#undef RT_PUSH
-#undef RT_POP
+            RT_WALK_END(false)
         }
     }
 
     if (present) {
-        float4 w0, w1, w2, w3;
-        const float NEG1 = __int_as_float(-1);
-        if (best == kNone) {
-            w0 = make_float4(INF, 0.f, 0.f, 0.f);
-            w1 = make_float4(0.f, 0.f, 0.f, __int_as_float(RT_HIT_NONE));
-            w2 = make_float4(NEG1, NEG1, NEG1, 0.f);
-            w3 = make_float4(0.f, __int_as_float(0), 0.f, 0.f);
-        } else {
+        HitRecord rec;
+        if (best == kNone) rec.miss(0);
+        else {
             Hit h; h.id = best; h.t = 0.0f; h.u = bu; h.v = bv;
             v3 point, normal; const float4* mat;
-            float dst; int side;
+            float dst;
             if (best & kTriBit) {
                 // the winner's point again from its (u, v): the same operations as in the search, the same bits
                 const uint32_t ti = best & ~kTriBit;
@@ -234,30 +201,21 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
                 load_tri(S.tri_geo, ti, g0, g1, g2);
                 point = (rtm::mk(g0.x, g0.y, g0.z) + rtm::mk(g0.w, g1.x, g1.y) * bu) + rtm::mk(g1.z, g1.w, g2.x) * bv;
                 const float s = rtm::dot(p - point, rtm::mk(g2.y, g2.z, g2.w));    // (n = cross(eAB, eAC), formed at the upload)
-                side = s > 0.0f ? 1 : s < 0.0f ? -1 : 0;
                 dst = rtm::sqrt_(kb);
                 surface_of(S, h, point, normal, mat);
-                const uint32_t prim = Q.order[ti];
-                const int mesh = Q.tri_mesh ? (int)Q.tri_mesh[prim] : -1;
-                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_TRIANGLE));
-                w2 = make_float4(__uint_as_float(prim), S.tri_nrm[(size_t)ti * 3].w, __int_as_float(mesh), bu);     // (.w: the chunk index's bits)
-                w3 = make_float4(bv, __int_as_float(side), 0.f, 0.f);
+                rec.triangle(S, Q, ti, normal, bu, bv, s > 0.0f ? 1 : s < 0.0f ? -1 : 0, 0);
             } else {
                 const float4 sp = S.sph_geom[best];
                 const v3 c = rtm::mk(sp.x, sp.y, sp.z), m = p - c;
                 const float len = rtm::sqrt_(rtm::dot(m, m));
                 dst = __builtin_fabsf(len - sp.w);
                 point = c + m * (sp.w / len);
-                side = len >= sp.w ? 1 : -1;
                 surface_of(S, h, point, normal, mat);
-                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_SPHERE));
-                w2 = make_float4(__uint_as_float(best), NEG1, NEG1, 0.f);
-                w3 = make_float4(0.f, __int_as_float(side), 0.f, 0.f);
+                rec.sphere(best, normal, len >= sp.w ? 1 : -1, 0);
             }
-            w0 = make_float4(dst, point.x, point.y, point.z);
+            rec.at(dst, point);
         }
-        float4* out = Q.out + 4 * (size_t)i;
-        out[0] = w0; out[1] = w1; out[2] = w2; out[3] = w3;
+        rec.store(Q.out + 4 * (size_t)i);
     }
 
     if (COUNT) {

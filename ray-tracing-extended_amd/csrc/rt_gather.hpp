@@ -24,7 +24,7 @@
 //
 // The tree is four xor-exchanges per channel at lane distances 1, 2, 4, 8; every lane of the wave takes part, lanes without a point
 // carry zeros, and the sub-stream-0 lane stores one or nine float4.  Hit or miss is carried as h.id, a value, never as a bool across
-// the traversal (rt_query.hpp any_hit records why).
+// the traversal (rt_kernels.hpp, the per-lane walk, records why).
 #pragma once
 #include "rt_kernels.hpp"
 

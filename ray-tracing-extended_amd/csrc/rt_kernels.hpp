@@ -361,6 +361,72 @@ __device__ __forceinline__ bool ray_traceable(v3 o, v3 d, float dd)
     return o.x == o.x && o.y == o.y && o.z == o.z && dd == dd && !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
 }
 
+// ---- the per-lane walk ------------------------------------------------------------------------------------
+// One lane walks the BVH4 for its own query with a stack of its own (TravStack), "while-while" shaped: it descends internal nodes
+// until it holds a leaf, tests the leaf's triangles, pops.  The walk is written once, as three macros around the two pieces of code
+// a user supplies (DESIGN.md "The per-lane walk"; k_stream's bursts are a different, wave-cooperative structure, rt_stream_body.hpp):
+//
+//     RT_WALK_NODE(stk, start)                         start: the root, 0, or kNone for a walk that is over before it begins
+//         ... the node step of internal node `node`: declares c0 .. c3, the children nearest first, and whatever says which are kept
+//     RT_WALK_TRIANGLE(tri_geo, kept0, kept1, kept2, kept3)
+//         ... one triangle of a leaf: its BVH-order index `ti`, its record as tri_A, tri_AB, tri_AC, tri_n (load_tri)
+//     RT_WALK_END(done)                                done: after a leaf, the walk ends early (occlusion); false: it never does
+//
+// kept0 .. kept3 are the user's rule for each child, not the walk's: a ray keeps a child whose entry distance is finite (t < INF),
+// a point query one whose reference survived (c != kNone) — its kept children can have a bound of +inf (rt_closest.hpp).
+//
+// Macros and not a function that takes closures, for what the compiler made of those:
+//   * a lambda that captured a lane's state by reference (the multi-hit list) kept that state in scratch;
+//   * a verdict that crosses the walk must be a VGPR value — a float or an int compared after the loops merge — never a bool: the
+//     build leaves uniform regions unstructurized (-structurizecfg-skip-uniform-regions), and a bool computed in the divergent loop,
+//     carried across a uniform branch nested in it and merged after them came back as the lane mask of the inner branch's lanes
+//     only (k_ray_query's occlusion answer: rays whose spheres had answered read 0).  `done` is such a comparison, made on the spot.
+// The top of the stack lives in a register: a pop hands it out at once and refills it from LDS, so the LDS read's latency falls
+// before the *next* pop instead of in front of the next node's address.
+#define RT_WALK_PUSH_(X) { if (walk_top_ != kNone) walk_stk_.push(walk_sp_, walk_top_); walk_top_ = (X); }
+#define RT_WALK_POP_()   { walk_cur_ = walk_top_; walk_top_ = (walk_sp_ > 0) ? walk_stk_.pop(walk_sp_) : kNone; }
+// RT_WALK_NODE gives the user's code `node`; that code must declare uint32_t c0, c1, c2, c3 (RT_WALK_TRIANGLE pushes them by name)
+#define RT_WALK_NODE(STK, START)                                                                                         \
+    {                                                                                                                    \
+        const TravStack& walk_stk_ = (STK);                                                                              \
+        int walk_sp_ = 0;                                                                                                \
+        uint32_t walk_cur_ = (START), walk_top_ = kNone;                                                                 \
+        while (walk_cur_ != kNone) {                                                                                     \
+            while ((int)walk_cur_ >= 0) {               /* descend internal nodes until this lane holds a leaf (or ran dry) */ \
+                const uint32_t node = walk_cur_;
+// RT_WALK_TRIANGLE gives the user's code `ti`, `tri_A`, `tri_AB`, `tri_AC`, `tri_n`; every other name of the walk's ends in `_`
+#define RT_WALK_TRIANGLE(TRI_GEO, KEPT0, KEPT1, KEPT2, KEPT3)                                                            \
+                if (KEPT3) RT_WALK_PUSH_(c3)                                                                             \
+                if (KEPT2) RT_WALK_PUSH_(c2)                                                                             \
+                if (KEPT1) RT_WALK_PUSH_(c1)                                                                             \
+                if (KEPT0) walk_cur_ = c0;                                                                               \
+                else RT_WALK_POP_()                                                                                      \
+            }                                                                                                            \
+            if (walk_cur_ != kNone) {                   /* a leaf: (first triangle << 2 | count - 1) under the sign bit */ \
+                const uint32_t walk_first_ = (walk_cur_ & 0x7FFFFFFFu) >> 2, walk_count_ = (walk_cur_ & 3u) + 1u;        \
+                for (uint32_t walk_j_ = 0; walk_j_ < walk_count_; ++walk_j_) {                                           \
+                    const uint32_t ti = walk_first_ + walk_j_;                                                           \
+                    float4 walk_g0_, walk_g1_, walk_g2_;                                                                 \
+                    load_tri((TRI_GEO), ti, walk_g0_, walk_g1_, walk_g2_);                                               \
+                    const v3 tri_A = rtm::mk(walk_g0_.x, walk_g0_.y, walk_g0_.z), tri_AB = rtm::mk(walk_g0_.w, walk_g1_.x, walk_g1_.y); \
+                    const v3 tri_AC = rtm::mk(walk_g1_.z, walk_g1_.w, walk_g2_.x), tri_n = rtm::mk(walk_g2_.y, walk_g2_.z, walk_g2_.w);
+#define RT_WALK_END(DONE)                                                                                                \
+                }                                                                                                        \
+                if (DONE) walk_cur_ = kNone;                                                                             \
+                else RT_WALK_POP_()                                                                                      \
+            }                                                                                                            \
+        }                                                                                                                \
+    }
+
+// The reference only reaches a triangle if its chunk's box test passes (RayTracing.shader:279): RT_INTERSECT_FLAT_CHUNKS' filter on
+// BVH-order triangle `ti`, RayBoundingBox with the ray's inv = 1 / d.  (A bool, for a caller that consumes it where it stands.)
+__device__ __forceinline__ bool chunk_passes(const DeviceScene& S, uint32_t ti, v3 o, v3 inv)
+{
+    const uint32_t chunk = __float_as_uint(S.tri_nrm[(size_t)ti * 3].w);
+    const float4 bmn = S.chunk_box[(size_t)chunk * 2], bmx = S.chunk_box[(size_t)chunk * 2 + 1];
+    return ray_bounding_box(o, inv, rtm::mk(bmn.x, bmn.y, bmn.z), rtm::mk(bmx.x, bmx.y, bmx.z));
+}
+
 // ---- closest hit: spheres, then BVH ---------------------------------------------------------------------
 // t_max: only hits with dst < t_max count (ray queries, rt_trace_rays); the renderer's rays are unbounded
 template <bool COUNT, bool H = false>
@@ -394,63 +460,30 @@ __device__ __forceinline__ Hit closest_hit(const DeviceScene& S, int intersect_m
 
     if (S.nn > 0 && ray_traceable(o, d, a)) {
         const RaySlabT<H> slab = make_slab<H>(o, d);
-        const v3 inv = slab.inv;                                        // RayBoundingBox :179
-        int sp = 0;
-        uint32_t cur = 0;                                               // root
-        // The top of the stack lives in a register: a pop hands it out at once and refills it from LDS, so the LDS read's
-        // latency falls before the *next* pop instead of in front of the next node's address.
-        uint32_t top = kNone;
-#define RT_PUSH(X) { if (top != kNone) stk.push(sp, top); top = (X); }
-#define RT_POP()   { cur = top; top = (sp > 0) ? stk.pop(sp) : kNone; }
-        while (cur != kNone) {
-            // ---- descend internal nodes until this lane holds a leaf (or ran dry)
-            while ((int)cur >= 0) {
-                if (COUNT) cnt.nodes++;
-                phase_tick<COUNT>(cnt, 0);
-                float t0, t1, t2, t3;
-                uint32_t c0, c1, c2, c3;
-                node_step<H>(H ? S.nodes_h : S.nodes, cur, slab, best.t, full_sort, t0, t1, t2, t3, c0, c1, c2, c3);
-                const float INF = __builtin_inff();
-                if (t3 < INF) RT_PUSH(c3)
-                if (t2 < INF) RT_PUSH(c2)
-                if (t1 < INF) RT_PUSH(c1)
-                if (t0 < INF) cur = c0;
-                else RT_POP()
-            }
-            // ---- leaf
-            if (cur != kNone) {
-                const uint32_t first = (cur & 0x7FFFFFFFu) >> 2, count = (cur & 3u) + 1u;
-                for (uint32_t j = 0; j < count; ++j) {
-                    const uint32_t ti = first + j;
-                    float4 g0, g1, g2;
-                    load_tri(S.tri_geo, ti, g0, g1, g2);
-                    float dst, u, v;
-                    if (COUNT) cnt.tris++;
-                    phase_tick<COUNT>(cnt, 1);
-                    bool hit = ray_triangle(o, d, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y),
-                                            rtm::mk(g1.z, g1.w, g2.x), rtm::mk(g2.y, g2.z, g2.w), dst, u, v);
-                    if (hit && dst <= best.t) {
-                        bool take = dst < best.t;
-                        if (!take && (best.id & kTriBit) && best.id != kNone) {
-                            // equal dst: the reference keeps the triangle that comes first in the buffer
-                            uint32_t oc = __float_as_uint(S.tri_nrm[(size_t)ti * 3 + 1].w);
-                            uint32_t ob = __float_as_uint(S.tri_nrm[(size_t)(best.id & ~kTriBit) * 3 + 1].w);
-                            take = oc < ob;
-                        }
-                        if (take && intersect_mode == RT_INTERSECT_FLAT_CHUNKS) {
-                            // the reference only reaches this triangle if its chunk's box test passes (:279)
-                            uint32_t chunk = __float_as_uint(S.tri_nrm[(size_t)ti * 3].w);
-                            float4 bmn = S.chunk_box[(size_t)chunk * 2], bmx = S.chunk_box[(size_t)chunk * 2 + 1];
-                            take = ray_bounding_box(o, inv, rtm::mk(bmn.x, bmn.y, bmn.z), rtm::mk(bmx.x, bmx.y, bmx.z));
-                        }
-                        if (take) { best.t = dst; best.id = kTriBit | ti; best.u = u; best.v = v; }
-                    }
+        const float INF = __builtin_inff();
+        RT_WALK_NODE(stk, 0u)                                            // from the root
+            if (COUNT) cnt.nodes++;
+            phase_tick<COUNT>(cnt, 0);
+            float t0, t1, t2, t3;
+            uint32_t c0, c1, c2, c3;
+            node_step<H>(H ? S.nodes_h : S.nodes, node, slab, best.t, full_sort, t0, t1, t2, t3, c0, c1, c2, c3);
+        RT_WALK_TRIANGLE(S.tri_geo, t0 < INF, t1 < INF, t2 < INF, t3 < INF)
+            float dst, u, v;
+            if (COUNT) cnt.tris++;
+            phase_tick<COUNT>(cnt, 1);
+            bool hit = ray_triangle(o, d, tri_A, tri_AB, tri_AC, tri_n, dst, u, v);
+            if (hit && dst <= best.t) {
+                bool take = dst < best.t;
+                if (!take && (best.id & kTriBit) && best.id != kNone) {
+                    // equal dst: the reference keeps the triangle that comes first in the buffer
+                    uint32_t oc = __float_as_uint(S.tri_nrm[(size_t)ti * 3 + 1].w);
+                    uint32_t ob = __float_as_uint(S.tri_nrm[(size_t)(best.id & ~kTriBit) * 3 + 1].w);
+                    take = oc < ob;
                 }
-                RT_POP()
+                if (take && intersect_mode == RT_INTERSECT_FLAT_CHUNKS) take = chunk_passes(S, ti, o, slab.inv);
+                if (take) { best.t = dst; best.id = kTriBit | ti; best.u = u; best.v = v; }
             }
-        }
-#undef RT_PUSH
-#undef RT_POP
+        RT_WALK_END(false)
     }
     if (COUNT && best.id != kNone) cnt.hits++;
     return best;

@@ -7,7 +7,7 @@
 // (dst, kind, uploaded index, side) — whatever the tree, the builder, the leaf size or the visiting order.
 //
 // k_ray_query's launch: one ray per lane, 256-thread blocks, one launch per slice, lane_stack's LDS stack with the global overflow,
-// any_hit's traversal loop.  What is new is the per-lane list: eight (dst, id) pairs in registers, sorted, indexed at compile time
+// the per-lane walk (rt_kernels.hpp).  What is new is the per-lane list: eight (dst, id) pairs in registers, sorted, indexed at compile time
 // only (K is a run-time value, but a run-time-indexed private array would live in scratch).  An accepted candidate is carried through
 // the eight slots by compare-and-exchange, so slots 0 .. K-1 always hold the K smallest keys seen; slots K .. 7 hold whatever fell out
 // of them and are never read.  Only keys are kept: the epilogue runs the primitive test again on the <= K winners (it is deterministic:
@@ -23,15 +23,8 @@ namespace rtk {
 
 static_assert(sizeof(rt_multihit) == 64 && sizeof(rt_hits_params) == 32 && RT_HITS_MAX == 8, "a record is four float4 stores, the list has eight slots");
 
-struct MultihitArgs {
-    const float4* rays;         // [n*2]    rt_ray: (origin, tMax) (direction, -)
+struct MultihitArgs : QueryHead {
     float4* out;                // [n*K*4]  rt_multihit, ray-major
-    const uint32_t* order;      // BVH order -> uploaded triangle (d_order)
-    const uint32_t* tri_mesh;   // uploaded triangle -> mesh (local uploads); null = world-space upload
-    uint32_t* gstack; unsigned int gstack_stride;   // as QueryArgs
-    int n;
-    int intersect_mode;
-    int stack_cap;
     int max_hits;               // K, 1..8
     int count_all;              // 1: hitCount = every accepted hit below tMax, and no pruning by the K-th distance
 };
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void k_multihit(DeviceScene S, MultihitArgs
     const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= (unsigned)Q.n) return;
     const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float4 r0 = Q.rays[2 * (size_t)i], r1 = Q.rays[2 * (size_t)i + 1];
+    const float4 r0 = Q.in[2 * (size_t)i], r1 = Q.in[2 * (size_t)i + 1];
     const v3 o = rtm::mk(r0.x, r0.y, r0.z), d = rtm::mk(r1.x, r1.y, r1.z);
     const float t_max = r0.w;
     const int K = Q.max_hits;
@@ -160,66 +153,33 @@ __global__ __launch_bounds__(kBlock) void k_multihit(DeviceScene S, MultihitArgs
         }
         if (S.nn > 0 && ray_traceable(o, d, a)) {
             const RaySlabT<H> slab = make_slab<H>(o, d);
-            int sp = 0;
-            uint32_t cur = 0;                                           // root
-            uint32_t top = kNone;                                       // the top of the stack in a register, as in closest_hit
-#define RT_PUSH(X) { if (top != kNone) stk.push(sp, top); top = (X); }
-#define RT_POP()   { cur = top; top = (sp > 0) ? stk.pop(sp) : kNone; }
-            while (cur != kNone) {
-                while ((int)cur >= 0) {
-                    float t0, t1, t2, t3;
-                    uint32_t c0, c1, c2, c3;
-                    const float bound = count_all ? t_max : __builtin_fminf(t_max, kth);
-                    node_step<H>(H ? S.nodes_h : S.nodes, cur, slab, bound, false, t0, t1, t2, t3, c0, c1, c2, c3);
-                    if (t3 < INF) RT_PUSH(c3)
-                    if (t2 < INF) RT_PUSH(c2)
-                    if (t1 < INF) RT_PUSH(c1)
-                    if (t0 < INF) cur = c0;
-                    else RT_POP()
+            RT_WALK_NODE(stk, 0u)                                       // from the root
+                float t0, t1, t2, t3;
+                uint32_t c0, c1, c2, c3;
+                const float bound = count_all ? t_max : __builtin_fminf(t_max, kth);
+                node_step<H>(H ? S.nodes_h : S.nodes, node, slab, bound, false, t0, t1, t2, t3, c0, c1, c2, c3);
+            RT_WALK_TRIANGLE(S.tri_geo, t0 < INF, t1 < INF, t2 < INF, t3 < INF)
+                float dst, u, v;
+                const int side = ray_triangle_sided<BOTH>(o, d, tri_A, tri_AB, tri_AC, tri_n, dst, u, v);
+                if (side != 0 && dst < t_max && (count_all || dst <= kth)) {
+                    // the chunk filter's verdict is carried in dst, a float (rt_kernels.hpp, the per-lane walk)
+                    if (Q.intersect_mode == RT_INTERSECT_FLAT_CHUNKS && !chunk_passes(S, ti, o, slab.inv)) dst = INF;
+                    if (dst < INF) RT_OFFER(dst, kTriBit | (ti << 1) | (side < 0 ? 1u : 0u))
                 }
-                if (cur != kNone) {
-                    const uint32_t first = (cur & 0x7FFFFFFFu) >> 2, count = (cur & 3u) + 1u;
-                    for (uint32_t j = 0; j < count; ++j) {
-                        const uint32_t ti = first + j;
-                        float4 g0, g1, g2;
-                        load_tri(S.tri_geo, ti, g0, g1, g2);
-                        float dst, u, v;
-                        const int side = ray_triangle_sided<BOTH>(o, d, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x),
-                                                                  rtm::mk(g2.y, g2.z, g2.w), dst, u, v);
-                        if (side != 0 && dst < t_max && (count_all || dst <= kth)) {
-                            if (Q.intersect_mode == RT_INTERSECT_FLAT_CHUNKS) {
-                                // the reference only reaches this triangle if its chunk's box test passes (:279); the verdict is
-                                // carried in dst, a float (the build's flags: a bool merged after a uniform branch can lose lanes)
-                                const uint32_t chunk = __float_as_uint(S.tri_nrm[(size_t)ti * 3].w);
-                                const float4 bmn = S.chunk_box[(size_t)chunk * 2], bmx = S.chunk_box[(size_t)chunk * 2 + 1];
-                                if (!ray_bounding_box(o, slab.inv, rtm::mk(bmn.x, bmn.y, bmn.z), rtm::mk(bmx.x, bmx.y, bmx.z))) dst = INF;
-                            }
-                            if (dst < INF) RT_OFFER(dst, kTriBit | (ti << 1) | (side < 0 ? 1u : 0u))
-                        }
-                    }
-                    RT_POP()
-                }
-            }
-#undef RT_PUSH
-#undef RT_POP
+            RT_WALK_END(false)
         }
     }
 #undef RT_OFFER
 
-    // ---- the records: the winners' tests again, then k_ray_query's expressions
+    // ---- the records: the winners' tests again (their u, v), then k_ray_query's record with side and count
     const int hit_count = count_all ? total : L.filled(K);
-    const float NEG1 = __int_as_float(-1);
     float4* out = Q.out + 4 * ((size_t)i * (size_t)K);
     for (int j = 0; j < K; ++j) {
         float dst; uint32_t id;
         L.pop_front(dst, id);
-        float4 w0, w1, w2, w3;
-        if (id == kNone) {
-            w0 = make_float4(INF, 0.f, 0.f, 0.f);
-            w1 = make_float4(0.f, 0.f, 0.f, __int_as_float(RT_HIT_NONE));
-            w2 = make_float4(NEG1, NEG1, NEG1, 0.f);
-            w3 = make_float4(0.f, __int_as_float(0), __int_as_float(hit_count), 0.f);
-        } else {
+        HitRecord R;
+        if (id == kNone) R.miss(hit_count);
+        else {
             const v3 hitPoint = o + d * dst;
             const int side = (id & 1u) ? -1 : 1;
             v3 normal; const float4* mat;
@@ -233,21 +193,15 @@ __global__ __launch_bounds__(kBlock) void k_multihit(DeviceScene S, MultihitArgs
                                          rtm::mk(g2.y, g2.z, g2.w), t_again, h.u, h.v);
                 h.id = kTriBit | ti;
                 surface_of(S, h, hitPoint, normal, mat);
-                const uint32_t prim = Q.order[ti];
-                const int mesh = Q.tri_mesh ? (int)Q.tri_mesh[prim] : -1;
-                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_TRIANGLE));
-                w2 = make_float4(__uint_as_float(prim), S.tri_nrm[(size_t)ti * 3].w, __int_as_float(mesh), h.u);     // (.w: the chunk index's bits)
+                R.triangle(S, Q, ti, normal, h.u, h.v, side, hit_count);
             } else {
                 h.id = id >> 1;
                 surface_of(S, h, hitPoint, normal, mat);
-                w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_SPHERE));
-                w2 = make_float4(__uint_as_float(h.id), NEG1, NEG1, 0.f);
+                R.sphere(h.id, normal, side, hit_count);
             }
-            w0 = make_float4(dst, hitPoint.x, hitPoint.y, hitPoint.z);
-            w3 = make_float4(h.v, __int_as_float(side), __int_as_float(hit_count), 0.f);
+            R.at(dst, hitPoint);
         }
-        float4* rec = out + 4 * (size_t)j;
-        rec[0] = w0; rec[1] = w1; rec[2] = w2; rec[3] = w3;
+        R.store(out + 4 * (size_t)j);
     }
 }
 

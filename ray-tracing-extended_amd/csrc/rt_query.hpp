@@ -15,10 +15,9 @@ namespace rtk {
 
 static_assert(sizeof(rt_ray) == 32 && sizeof(rt_hit) == 64, "a ray is two float4 loads, a hit four float4 stores");
 
-struct QueryArgs {
-    const float4* rays;         // [n*2]  rt_ray: (origin, tMax) (direction, -)
-    float4* hits;               // [n*4]  rt_hit (closest hit)
-    uint8_t* occluded;          // [n]    (occlusion)
+// What the kernels that answer with a HitRecord take, first: k_multihit (rt_multihit.hpp), k_closest (rt_closest.hpp)
+struct QueryHead {
+    const float4* in;           // [n*2]  rt_ray: (origin, tMax) (direction, -); closest-point queries: (p, R) (-, -)
     const uint32_t* order;      // BVH order -> uploaded triangle (d_order)
     const uint32_t* tri_mesh;   // uploaded triangle -> mesh (local uploads); null = world-space upload
     uint32_t* gstack;           // overflow of the traversal stack beyond stack_cap ([entry][lane of the launch]); may be null
@@ -26,15 +25,29 @@ struct QueryArgs {
     int n;
     int intersect_mode;
     int stack_cap;              // LDS stack entries per lane
+};
+
+// k_ray_query's: the head's fields under the head's names, in the order this kernel was measured with — with QueryHead first and its
+// record written by HitRecord the closest-hit form ran 1 % slower (profiles/walk_refactor_timing.txt), so it keeps both as they were
+struct QueryArgs {
+    const float4* in;           // [n*2]  rt_ray
+    float4* hits;               // [n*4]  rt_hit (closest hit)
+    uint8_t* occluded;          // [n]    (occlusion)
+    const uint32_t* order;
+    const uint32_t* tri_mesh;
+    uint32_t* gstack;
+    unsigned int gstack_stride;
+    int n;
+    int intersect_mode;
+    int stack_cap;
     int full_sort;
 };
 
 // CalculateRayCollision with `dst < t_max` reduced to "is there a hit": every sphere first (no order matters for a yes / no), then the
 // BVH with the slab test bounded by t_max.  A triangle counts when RayTriangle accepts it with dst < t_max and, in FLAT_CHUNKS mode, its
 // chunk's RayBoundingBox passes (:279) — exactly the candidates closest_hit could take, so the answer is closest_hit's hit / miss.
-// Returns the dst of the first accepted candidate (finite: it is < t_max), +inf when there is none.  (The answer is carried as that float,
-// shaped like closest_hit — uniform scene test outside, divergent lane tests inside: a bool carried across the traversal became a lane
-// mask that the uniform-region flags of the build merged wrongly, and lanes whose spheres had answered lost their yes.)
+// Returns the dst of the first accepted candidate (finite: it is < t_max), +inf when there is none: the answer crosses the walk as
+// that float, never as a bool (rt_kernels.hpp, the per-lane walk).
 template <bool H>
 __device__ __forceinline__ float any_hit(const DeviceScene& S, int intersect_mode, v3 o, v3 d, float t_max, const TravStack& stk)
 {
@@ -49,50 +62,55 @@ __device__ __forceinline__ float any_hit(const DeviceScene& S, int intersect_mod
     }
     if (S.nn > 0 && ray_traceable(o, d, a)) {
         const RaySlabT<H> slab = make_slab<H>(o, d);
-        int sp = 0;
-        uint32_t cur = hit_t < INF ? kNone : 0u;                    // root, unless a sphere answered
-        uint32_t top = kNone;                                       // the top of the stack in a register, as in closest_hit
-#define RT_PUSH(X) { if (top != kNone) stk.push(sp, top); top = (X); }
-#define RT_POP()   { cur = top; top = (sp > 0) ? stk.pop(sp) : kNone; }
-        while (cur != kNone) {
-            while ((int)cur >= 0) {
-                float t0, t1, t2, t3;
-                uint32_t c0, c1, c2, c3;
-                node_step<H>(H ? S.nodes_h : S.nodes, cur, slab, t_max, false, t0, t1, t2, t3, c0, c1, c2, c3);
-                if (t3 < INF) RT_PUSH(c3)
-                if (t2 < INF) RT_PUSH(c2)
-                if (t1 < INF) RT_PUSH(c1)
-                if (t0 < INF) cur = c0;
-                else RT_POP()
+        RT_WALK_NODE(stk, hit_t < INF ? kNone : 0u)                     // from the root, unless a sphere answered
+            float t0, t1, t2, t3;
+            uint32_t c0, c1, c2, c3;
+            node_step<H>(H ? S.nodes_h : S.nodes, node, slab, t_max, false, t0, t1, t2, t3, c0, c1, c2, c3);
+        RT_WALK_TRIANGLE(S.tri_geo, t0 < INF, t1 < INF, t2 < INF, t3 < INF)
+            float dst, u, v;
+            if (ray_triangle(o, d, tri_A, tri_AB, tri_AC, tri_n, dst, u, v) && dst < t_max) {
+                bool take = true;
+                if (intersect_mode == RT_INTERSECT_FLAT_CHUNKS) take = chunk_passes(S, ti, o, slab.inv);
+                if (take) hit_t = dst;
             }
-            if (cur != kNone) {
-                const uint32_t first = (cur & 0x7FFFFFFFu) >> 2, count = (cur & 3u) + 1u;
-                for (uint32_t j = 0; j < count; ++j) {
-                    const uint32_t ti = first + j;
-                    float4 g0, g1, g2;
-                    load_tri(S.tri_geo, ti, g0, g1, g2);
-                    float dst, u, v;
-                    if (ray_triangle(o, d, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), rtm::mk(g2.y, g2.z, g2.w),
-                                     dst, u, v) && dst < t_max) {
-                        bool take = true;
-                        if (intersect_mode == RT_INTERSECT_FLAT_CHUNKS) {
-                            // the reference only reaches this triangle if its chunk's box test passes (:279)
-                            const uint32_t chunk = __float_as_uint(S.tri_nrm[(size_t)ti * 3].w);
-                            const float4 bmn = S.chunk_box[(size_t)chunk * 2], bmx = S.chunk_box[(size_t)chunk * 2 + 1];
-                            take = ray_bounding_box(o, slab.inv, rtm::mk(bmn.x, bmn.y, bmn.z), rtm::mk(bmx.x, bmx.y, bmx.z));
-                        }
-                        if (take) hit_t = dst;
-                    }
-                }
-                if (hit_t < INF) cur = kNone;                       // the first accepted hit ends the query
-                else RT_POP()
-            }
-        }
-#undef RT_PUSH
-#undef RT_POP
+        RT_WALK_END(hit_t < INF)                                        // the first accepted hit ends the query
     }
     return hit_t;
 }
+
+// The record rt_hit, rt_multihit and rt_closest share, four float4 stores: w0 = dst + point, w1 = normal + kind, w2 = primitive / chunk
+// index's bits / mesh / u, w3 = v / side / count / 0.  One of the three forms fills it, then store() writes it.  normal is Trace's
+// (surface_of).  k_multihit and k_closest write theirs with it; k_ray_query's epilogue is its own (QueryArgs).
+struct HitRecord {
+    float4 w0, w1, w2, w3;
+    __device__ __forceinline__ void miss(int count)
+    {
+        const float NEG1 = __int_as_float(-1);
+        w0 = make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
+        w1 = make_float4(0.f, 0.f, 0.f, __int_as_float(RT_HIT_NONE));
+        w2 = make_float4(NEG1, NEG1, NEG1, 0.f);
+        w3 = make_float4(0.f, __int_as_float(0), __int_as_float(count), 0.f);
+    }
+    // (a sphere or a triangle: w1 .. w3 here, w0 by at())
+    __device__ __forceinline__ void sphere(uint32_t index, v3 normal, int side, int count)
+    {
+        const float NEG1 = __int_as_float(-1);
+        w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_SPHERE));
+        w2 = make_float4(__uint_as_float(index), NEG1, NEG1, 0.f);
+        w3 = make_float4(0.f, __int_as_float(side), __int_as_float(count), 0.f);
+    }
+    // BVH-order triangle ti: back to the uploaded one through the build's order map and, for local meshes, to its mesh
+    __device__ __forceinline__ void triangle(const DeviceScene& S, const QueryHead& Q, uint32_t ti, v3 normal, float u, float v, int side, int count)
+    {
+        const uint32_t prim = Q.order[ti];
+        const int mesh = Q.tri_mesh ? (int)Q.tri_mesh[prim] : -1;
+        w1 = make_float4(normal.x, normal.y, normal.z, __int_as_float(RT_HIT_TRIANGLE));
+        w2 = make_float4(__uint_as_float(prim), S.tri_nrm[(size_t)ti * 3].w, __int_as_float(mesh), u);      // (.w: the chunk index's bits)
+        w3 = make_float4(v, __int_as_float(side), __int_as_float(count), 0.f);
+    }
+    __device__ __forceinline__ void at(float dst, v3 point) { w0 = make_float4(dst, point.x, point.y, point.z); }
+    __device__ __forceinline__ void store(float4* out) const { out[0] = w0; out[1] = w1; out[2] = w2; out[3] = w3; }
+};
 
 template <bool ANY, bool H>
 __global__ __launch_bounds__(kBlock) void k_ray_query(DeviceScene S, QueryArgs Q)
@@ -101,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void k_ray_query(DeviceScene S, QueryArgs Q
     const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= (unsigned)Q.n) return;
     const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float4 r0 = Q.rays[2 * (size_t)i], r1 = Q.rays[2 * (size_t)i + 1];
+    const float4 r0 = Q.in[2 * (size_t)i], r1 = Q.in[2 * (size_t)i + 1];
     const v3 o = rtm::mk(r0.x, r0.y, r0.z), d = rtm::mk(r1.x, r1.y, r1.z);
     const float t_max = r0.w;
     const bool traced = t_max > 0.0f;                                   // tMax <= 0 or NaN: a miss, nothing traced

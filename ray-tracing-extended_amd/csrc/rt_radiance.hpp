@@ -20,7 +20,7 @@
 //
 // The tree is four xor-exchanges per channel at lane distances 1, 2, 4, 8 (inside a row of 16 lanes: DPP moves, no LDS traffic); every
 // lane of the wave takes part, lanes without a ray carry zeros, and the sub-stream-0 lane stores one float4.  Hit or miss is carried as
-// h.id, a value, never as a bool across the traversal (rt_query.hpp any_hit records why).
+// h.id, a value, never as a bool across the traversal (rt_kernels.hpp, the per-lane walk, records why).
 #pragma once
 #include "rt_kernels.hpp"
 

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, Visibility
             total[2] = total[2] + (h.id != kNone ? 1.0f : 0.0f);
         } else {
             const float hit_t = any_hit<H>(S, A.intersect_mode, o, d, t_bound, stk);
-            const bool open = !(hit_t < INF);                           // (compared after the merge: any_hit records why)
+            const bool open = !(hit_t < INF);                           // (compared after the merge: the per-lane walk records why)
             if constexpr (MODE == RT_VIS_SH9) {
                 // the real SH basis of bands 0..2 on the drawn direction, every product its own rounding (include/rt.h)
                 const float x = d.x, y = d.y, z = d.z;

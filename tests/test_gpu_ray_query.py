@@ -69,7 +69,7 @@ def test_camera_rays_of_the_reference_scenes(rtx, shim, name, mode):
 @pytest.mark.parametrize("compact_nodes", [0, 1])
 def test_small_lds_stack_spills_to_the_overflow_area(rtx, shim, compact_nodes):
     """three stack entries per lane in LDS, the rest of the Knight's tree in the global overflow area (both node forms)"""
-    t, params, s, tr, mi = loaded_tracer(rtx, scene_of(rtx, "Knight"), 0, lds_stack=3, compact_nodes=compact_nodes)
+    t, params, s, tr, mi = loaded_tracer(rtx, scene_of(rtx, "Knight"), 0, stream_stack=4, lds_stack=3, compact_nodes=compact_nodes)
     with t:
         check_queries(rtx, shim, t, s, tr, mi, 0, camera_rays(rtx, params, 48, 32), f"lds_stack 3 compact_nodes {compact_nodes}")
         assert t.stats()["bvhMaxStack"] > 3         # (the overflow area was in use)
