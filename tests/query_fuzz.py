@@ -3,7 +3,11 @@ query families are given on the renderer fuzz's scenes (test_gpu_fuzz.random_sce
 Test infrastructure only; no tests in it.
 
 An item is an rt_ray.  The ray families read it as origin / direction / tMax, the gather and visibility families as position / NORMAL /
-first-cast bound or reach, so every item is given to every family.  Everything is a pure function of the seed."""
+first-cast bound or reach, so every item is given to every family.  Everything is a pure function of the seed.
+
+The two per-lane families that came after those four draw from generators of their own (point_knobs, fuzz_points), so that what the
+four are given never moves: rt_trace_hits takes the items as rays, rt_closest_points the points of fuzz_points, an rt_ray each with the
+search radius in tMax."""
 import numpy as np
 
 import query_check as gc
@@ -69,6 +73,24 @@ def _lattice_targets(pos, live):
     return np.array(targets, F32), np.array(axes), np.array(sides)
 
 
+def _body(seed, scene):
+    """The finite sources of a scene: its body is what lies within 1e4 units of its shift (the 3e37 triangle is finite, and not a place).
+    -> (pos (nt, 3, 3) float32, live (nt,) the triangles of the body, the finite sphere centres, lo, hi, ext: the bounds of the body's
+    vertices and centres and their extent, at least 1 per axis, diameter: |ext|)"""
+    _, sph, tris, _ = scene
+    shift = scene_shift(seed)
+    pos = np.stack([tris["posA"], tris["posB"], tris["posC"]], 1).astype(F32)                       # (nt, 3, 3)
+    with np.errstate(invalid="ignore"):
+        live = (np.isfinite(pos) & (np.abs(pos - shift) < 1e4)).all((1, 2))
+    centres = np.asarray(sph["position"], F32).reshape(-1, 3)
+    centres = centres[np.isfinite(centres).all(1)]
+    verts = pos[live].reshape(-1, 3)
+    pool = np.concatenate([verts, centres]) if len(verts) + len(centres) else shift[None].copy()
+    lo, hi = pool.min(0), pool.max(0)
+    ext = np.maximum(hi - lo, F32(1))
+    return pos, live, centres, lo, hi, ext, F32(np.linalg.norm(ext))
+
+
 def item_split(n):
     """how n items divide: (aimed base rays — each is emitted four times, with tMax inf, dst, dst + 1 ulp and dst - 1 ulp, one third of the
     items —, surface points, special directions, the degenerate handful), in the order fuzz_items lays them out"""
@@ -84,17 +106,7 @@ def fuzz_items(rtx, seed, n=N_ITEMS, scene=None, shim=None, parts=None):
     rng = np.random.default_rng(5000 + seed)
     shift = scene_shift(seed)
 
-    # ---- finite sources: the scene's body is what lies within 1e4 units of its shift (the 3e37 triangle is finite, and not a place)
-    pos = np.stack([tris["posA"], tris["posB"], tris["posC"]], 1).astype(F32)                       # (nt, 3, 3)
-    with np.errstate(invalid="ignore"):
-        live = (np.isfinite(pos) & (np.abs(pos - shift) < 1e4)).all((1, 2))
-    centres = np.asarray(sph["position"], F32).reshape(-1, 3)
-    centres = centres[np.isfinite(centres).all(1)]
-    verts = pos[live].reshape(-1, 3)
-    pool = np.concatenate([verts, centres]) if len(verts) + len(centres) else shift[None].copy()
-    lo, hi = pool.min(0), pool.max(0)
-    ext = np.maximum(hi - lo, F32(1))
-    diameter = F32(np.linalg.norm(ext))
+    pos, live, centres, lo, hi, ext, diameter = _body(seed, (p, sph, tris, infos))
     live_tris = pos[live]
 
     def inside(k):
@@ -295,9 +307,165 @@ def inputs_table(rtx, seeds=range(24)):
     return "\n".join([head, *rows, f"sum  {'':25s} {total['traced']:6d} {total['hits']:5d} {total['misses']:6d} {total['ties']:5d} {total['flips']:5d}"]) + "\n"
 
 
+# ---- the two per-lane families that came after the four: rt_trace_hits (the items as rays) and rt_closest_points (points of their own) ----
+HIT_K = (1, 2, 3, 8)
+POINT_RADII = (INF, None, None, F32(1.5), F32(3e20), F32(1e-30))     # None: the scene's diameter, a quarter of it; R * R is +inf for 3e20, 0 for 1e-30
+
+
+def point_knobs(seed):
+    """(options, form): the two families' slice options (one value in four of each leaves the context's own) and the multi-hit call's
+    form, from a generator of their own: fuzz_knobs' draw stays what it was"""
+    rng = np.random.default_rng(13000 + seed)
+    options = {}
+    for name in ("hits_slice", "closest_slice"):
+        v = int(rng.choice((1, 7, 100, -1)))
+        if v >= 0:
+            options[name] = v
+    return options, {"K": int(rng.choice(HIT_K)), "both_sides": int(rng.integers(0, 2)), "count_all": int(rng.integers(0, 2))}
+
+
+def point_split(n):
+    """how n points divide: (free points, points on the surface, radius-flip base points — each is emitted three times, with R = dst,
+    dst + 1 ulp and dst - 1 ulp —, far points, the degenerate handful), in the order fuzz_points lays them out"""
+    n_flip, n_surf, n_far = n // 12, n // 3, n // 12
+    return n - n_surf - 3 * n_flip - n_far - N_DEGENERATE, n_surf, n_flip, n_far, N_DEGENERATE
+
+
+def fuzz_points(rtx, seed, scene, items, shim=None, parts=None):
+    """RAY (len(items),): the points of seed `seed` for rt_closest_points, the search radius in tMax (direction stays zero: it is not
+    read).  `parts` (a dict) receives the index ranges of the kinds.  Points on the surface are float32 values taken from the data, so
+    that their distance is exactly 0 and every primitive that owns them ties."""
+    import closest_check as cc
+    shim = shim or load_shim()
+    p, sph, tris, infos = scene
+    n = len(items)
+    rng = np.random.default_rng(17000 + seed)
+    pos, live, centres, lo, hi, ext, diameter = _body(seed, scene)
+    n_free, n_surf, n_flip, n_far, n_deg = point_split(n)
+    body = items[:n - n_deg]
+
+    def radii(k, values):
+        r = [values[j] for j in rng.integers(0, len(values), k)]
+        return F32([diameter if v is None else v for v in r])
+
+    def closest_dst(xyz):
+        return cc.oracle_closest(rtx, sph, tris, infos, cc.points_of(rtx, xyz))["dst"]
+
+    # ---- free points: origins of the items (one of each aimed base ray's four copies)
+    n_aim = item_split(n)[0]
+    pick = rng.permutation(np.concatenate([np.arange(n_aim), np.arange(4 * n_aim, n - n_deg)]))[:n_free]
+    free_values = list(POINT_RADII)
+    free_values[1], free_values[2] = diameter, F32(0.25) * diameter
+    free = cc.points_of(rtx, body["origin"][pick], radii(n_free, free_values))
+
+    # ---- points exactly on the surface
+    verts = pos[live]                                                           # (k, 3, 3)
+    seen, stacked = {}, []
+    for tri in verts:                                                           # a triangle uploaded three times: a "stack" chunk's
+        c = seen[tri.tobytes()] = seen.get(tri.tobytes(), 0) + 1
+        if c == 3:
+            stacked.append(tri)
+    lt = _lattice_targets(pos, live)[0]
+    # (where the items land as rays: the aimed base rays are the first probe rays of fuzz_items, the surface items sit 1e-3 above the rest)
+    hit = oracle_hits(rtx, shim, sph, tris, infos, int(p["intersectMode"]), body)
+    landed = np.asarray(hit["hitPoint"], F32)[(hit["kind"] != 0) & np.isfinite(hit["hitPoint"]).all(1)]
+    zero = np.asarray(sph["position"], F32).reshape(-1, 3)[np.asarray(sph["radius"]) == 0]
+    n_centres = len(centres) + len(zero)
+    n_lat, n_stack = min(len(lt), n_surf // 4), min(3 * len(stacked), n_surf // 8)
+    n_vert = (n_surf // 4 if len(verts) else 0)
+    n_land = n_surf - n_centres - n_lat - n_stack - n_vert
+    fill = verts.reshape(-1, 3) if len(verts) else scene_shift(seed)[None]
+    some = [lt[:n_lat], np.array(stacked, F32).reshape(-1, 3)[:n_stack], fill[rng.integers(0, len(fill), n_vert)],
+            landed[rng.permutation(len(landed))[:n_land]]]
+    short = n_land - len(some[-1])                                               # (fewer probe hits than room: more vertices)
+    some.append(fill[rng.integers(0, len(fill), short)])
+    r_some = radii(n_surf - n_centres, (INF, INF, INF, diameter, F32(1.5), F32(1e-30)))
+    surf = cc.points_of(rtx, np.concatenate([*some, centres, zero]).astype(F32),
+                        np.concatenate([r_some, np.full(len(centres), INF), np.full(len(zero), F32(1.5))]).astype(F32))
+    assert len(surf) == n_surf
+
+    # ---- radius flips: the checker's dst of a point at R = inf, and the point with R = dst and one ulp either side of it
+    base = body["origin"][rng.permutation(n - n_deg)[:n_flip]]
+    dst = closest_dst(base)
+    flips = cc.points_of(rtx, np.concatenate([base, base, base]), np.concatenate([dst, np.nextafter(dst, INF), np.nextafter(dst, F32(0))]))
+
+    # ---- far points: up to 1e3 outside the bounds, unbounded and with a radius just short of the scene
+    out_dir = _unit(rng.standard_normal((n_far, 3)))
+    far_xyz = (0.5 * (lo + hi) + out_dir * (0.5 * diameter + rng.uniform(1, 1e3, (n_far, 1)))).astype(F32)
+    r_far = np.full(n_far, INF)
+    r_far[n_far // 2:] = closest_dst(far_xyz[n_far // 2:]) * F32(0.999)
+    far = cc.points_of(rtx, far_xyz, r_far)
+
+    # ---- the degenerate handful of the items, as it is: a NaN and an infinite coordinate, R of 0, -0, -1 and NaN
+    deg = cc.points_of(rtx, items["origin"][n - n_deg:], items["tMax"][n - n_deg:])
+
+    points = np.concatenate([free, surf, flips, far, deg])
+    assert len(points) == n
+    if parts is not None:
+        a, b, c, d = n_free, n_free + n_surf, n_free + n_surf + 3 * n_flip, n - n_deg
+        parts.update(free=(0, a), surface=(a, b), lattice=(a, a + n_lat), stacked=(a + n_lat, a + n_lat + n_stack), flips=(b, c),
+                     flip_base=(b, b + n_flip), far=(c, d), degenerate=(d, n))
+    return points
+
+
+def run_hits(t, items, form):
+    """rt_trace_hits in the drawn form on a Tracer or MultiTracer (items: a RAY array, or a tensor for the device entry)"""
+    return t.trace_hits(items, form["K"], bool(form["both_sides"]), bool(form["count_all"]))
+
+
+def check_hits(rtx, scene, items, form):
+    """the multi-hit checker's answer for a form, at the scene's intersect mode"""
+    import hits_check as hc
+    p, sph, tris, infos = scene
+    return hc.oracle_hits(rtx, sph, tris, infos, items, form["K"], hc.BOTH if form["both_sides"] else hc.FRONT, bool(form["count_all"]),
+                          int(p["intersectMode"]))
+
+
+DEEP = {"K": 8, "both_sides": 1, "count_all": 1}         # the form every seed also runs: the whole list, evictions included
+
+
+def point_power_counts(rtx, scene, items, points, shim=None):
+    """What the two checkers find.  Points: searched (R > 0), found, missed, tied (two or more candidates at the winner's key), at
+    distance exactly 0, flips (a base point found at R = dst + 1 ulp and not at dst - 1 ulp), and the largest tie.  Rays (two-sided,
+    countAll, the scene's intersect mode): rays with two or more hits, with more than eight, the largest count, and closest hits of the
+    ray-query checker without a second candidate at their dst."""
+    import closest_check as cc
+    shim = shim or load_shim()
+    p, sph, tris, infos = scene
+    at_best = np.zeros(len(points), np.int32)
+    got = cc.oracle_closest(rtx, sph, tris, infos, points, at_best=at_best)
+    with np.errstate(invalid="ignore"):
+        searched = points["tMax"] > 0
+    found = got["kind"] != 0
+    n_free, n_surf, n_flip = point_split(len(points))[:3]
+    b = n_free + n_surf
+    above, below = found[b + n_flip:b + 2 * n_flip], found[b + 2 * n_flip:b + 3 * n_flip]
+    count = check_hits(rtx, scene, items, DEEP)[:, 0]["hitCount"]
+    mode = int(p["intersectMode"])
+    first, cand = oracle_hits(rtx, shim, sph, tris, infos, mode, items), oracle_candidates(rtx, shim, sph, tris, infos, mode, items)
+    return {"searched": int(searched.sum()), "found": int(found.sum()), "missed": int((searched & ~found).sum()), "tied": int((at_best >= 2).sum()),
+            "zero": int((found & (got["dst"] == 0)).sum()), "flips": int((above & ~below).sum()), "widest": int(at_best.max()),
+            "two": int((count >= 2).sum()), "deep": int((count > 8).sum()), "most": int(count.max()),
+            "untied": int(((first["kind"] != 0) & (cand < 2)).sum())}
+
+
+POINT_COLUMNS = ("searched", "found", "missed", "tied", "zero", "flips", "widest", "two", "deep", "most", "untied")
+
+
+def points_table(rtx, seeds=range(24)):
+    """the text of profiles/query_fuzz_points.txt: what point_power_counts finds per seed"""
+    rows = []
+    for seed in seeds:
+        scene, items, _, _ = fuzz_case(rtx, seed)
+        c = point_power_counts(rtx, scene, items, fuzz_points(rtx, seed, scene, items))
+        rows.append(f"{seed:4d} " + " ".join(f"{c[k]:8d}" for k in POINT_COLUMNS))
+    return "\n".join(["seed " + " ".join(f"{k:>8s}" for k in POINT_COLUMNS), *rows]) + "\n"
+
+
 if __name__ == "__main__":
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import rtx_pkg
-    print(inputs_table(rtx_pkg.load()), end="")
+    # `python tests/query_fuzz.py` prints profiles/query_fuzz_inputs.txt, `python tests/query_fuzz.py points` profiles/query_fuzz_points.txt
+    print((points_table if sys.argv[1:] == ["points"] else inputs_table)(rtx_pkg.load()), end="")

@@ -5,7 +5,12 @@ units away, the far mirror sphere), with the items and the knob draw of tests/qu
 at a hit's distance and one ulp either side, surface points, special directions and a degenerate handful; builder options, lds_stack, the
 three slice sizes, the sample count, the stream seed, a wrapping firstIndex and the intersect mode drawn together.  Every family equals
 its CPU checker bit for bit, the families agree with each other where they must, the device entries equal the host entries, and an
-rt_multi of three contexts gives the single context's bits.  RTX_FUZZ_SEEDS / RTX_FUZZ_FIRST choose the seeds, as for test_gpu_fuzz.py."""
+rt_multi of three contexts gives the single context's bits.  The two per-lane families that came later, rt_trace_hits and
+rt_closest_points, have a test of their own on the same scenes and builder options: the items as rays in a drawn (K, sides, countAll)
+form and as the whole eight-record list, and points of their own (qf.fuzz_points: on shared corners and triplicated triangles, at a
+hit's distance and one ulp either side of it as the radius, far outside, radii whose square overflows or underflows), every word of
+every record against hits_check and closest_check, and against rt_trace_rays / rt_occluded where the definitions meet.
+RTX_FUZZ_SEEDS / RTX_FUZZ_FIRST choose the seeds, as for test_gpu_fuzz.py."""
 import json
 import os
 import subprocess
@@ -14,6 +19,8 @@ import sys
 import numpy as np
 import pytest
 
+import closest_check as cc
+import hits_check as hc
 import query_check as gc
 import query_fuzz as qf
 import query_check as vc
@@ -60,7 +67,7 @@ def device_entries():
     """seed -> None or what differed: tests/query_fuzz_torch_worker.py, once for all seeds, in a fresh process"""
     try:
         r = subprocess.run([sys.executable, os.path.join(HERE, "query_fuzz_torch_worker.py"), str(_FIRST), str(_SEEDS)],
-                           capture_output=True, text=True, timeout=120 + _SEEDS)      # (measured: 4.6 s for 24 seeds, 24.9 s for 400)
+                           capture_output=True, text=True, timeout=120 + _SEEDS)      # (measured: 4.6 s for 24 seeds, 24.9 s for 400; with rt_trace_hits and rt_closest_points in it 5.2 s for 24, 21.3 s for 200)
         out, err, rc = r.stdout, r.stderr, r.returncode
     except subprocess.TimeoutExpired as e:
         out, err, rc = (e.stdout or b"").decode(errors="replace"), (e.stderr or b"").decode(errors="replace"), "timeout"
@@ -113,6 +120,73 @@ def test_query_families_on_a_random_scene(rtx, shim, device_entries, seed):
                 same_bits(m.occluded(items), occ, items, "rt_multi occluded, " + ctx)
                 for family, fmode in qf.FAMILIES:
                     same_bits(qf.run_family(m, items, call, family, fmode), got[family, fmode], items, f"rt_multi {family} mode {fmode}, " + ctx)
+    finally:
+        t.close()
+
+
+SHARED = ("dst", "hitPoint", "normal", "kind", "primitive", "chunk", "mesh", "u", "v")      # of a ray-query hit and a multi-hit record
+
+
+def same_records(check, rtx, got, want, items, what):
+    """check.assert_same_records (hits_check's or closest_check's: every word of every record), its message naming the first item whose
+    records differ in any bit"""
+    g, w = (np.ascontiguousarray(a).reshape(len(items), -1).view(np.uint32) for a in (got, want))
+    differ = np.flatnonzero((g != w).any(1)) if g.shape == w.shape else []
+    check.assert_same_records(rtx, got, want, what + (f"; first {qf.describe(items, differ[0])}" if len(differ) else ""))
+
+
+@pytest.mark.parametrize("seed", range(_FIRST, _FIRST + _SEEDS))
+def test_point_and_multihit_queries_on_a_random_scene(rtx, shim, device_entries, seed):
+    """rt_trace_hits on the items and rt_closest_points on qf.fuzz_points, on the same scenes and builder options, with slices and a
+    multi-hit form of their own draw (qf.point_knobs)"""
+    scene, items, options, _ = qf.fuzz_case(rtx, seed, shim)
+    p, sph, tris, infos = scene
+    more, form = qf.point_knobs(seed)
+    options = {**options, **more}
+    points = qf.fuzz_points(rtx, seed, scene, items, shim)
+    mode = int(p["intersectMode"])
+    ctx = f"fuzz seed {seed} ({len(tris)} triangles in {len(infos)} chunks, {len(sph)} spheres), options {options}, intersectMode {mode}"
+    t = rtx.Tracer(0)                                    # a context of its own: the options include the builder's
+    try:
+        qf.load_scene(t, scene, options)
+        # ---- multi-hit queries: the drawn form and the whole list (eight records, both sides, every hit counted) against the checker
+        got = {}
+        for name, f in (("drawn", form), ("deep", qf.DEEP)):
+            got[name] = qf.run_hits(t, items, f)
+            same_records(hc, rtx, got[name], qf.check_hits(rtx, scene, items, f), items, f"trace_hits {f}, " + ctx)
+        # ---- ... against the device's own ray queries: record 0, front faces, is rt_trace_rays' hit where that hit is untied (at a
+        # tie the two entries keep different candidates by definition), and a hit is there when rt_occluded says so, on every ray
+        first = t.trace_hits(items, 1)[:, 0]
+        hits, occ = t.trace_rays(items), t.occluded(items)
+        clear = np.flatnonzero(oracle_candidates(rtx, shim, sph, tris, infos, mode, items) < 2)
+        for f in SHARED:
+            a, b = first[f][clear].reshape(len(clear), -1), hits[f][clear].reshape(len(clear), -1)
+            same = a.view(np.uint32) == b.view(np.uint32)
+            if a.dtype == np.float32:
+                same |= np.isnan(a) & np.isnan(b)
+            bad = clear[~same.all(1)]
+            assert not len(bad), f"trace_hits K = 1 against trace_rays, {f}, {ctx}: {len(bad)} rays differ, first {qf.describe(items, bad[0])}:\n got  {first[bad[0]]}\n want {hits[bad[0]]}"
+        same_bits(first["hitCount"].astype(np.uint8), occ, items, "trace_hits K = 1 hitCount against occluded, " + ctx)
+        # ---- ... and against itself: K records are the first K of eight
+        for both, count_all in ((0, 0), (1, 1)):
+            f8 = {"K": 8, "both_sides": both, "count_all": count_all}
+            deep = got["deep"] if f8 == qf.DEEP else qf.run_hits(t, items, f8)
+            for K in (1, 2, 3):
+                want = deep[:, :K].copy()
+                if not count_all:
+                    want["hitCount"] = np.minimum(want["hitCount"], K)
+                same_records(hc, rtx, qf.run_hits(t, items, {**f8, "K": K}), want, items, f"trace_hits K = {K} against the first {K} of {f8}, " + ctx)
+        # ---- closest-point queries against the checker
+        near = t.closest_points(points)
+        same_records(cc, rtx, near, cc.oracle_closest(rtx, sph, tris, infos, points), points, "closest_points, " + ctx)
+        assert device_entries[seed] is None, device_entries[seed]
+        # ---- through an rt_multi of three contexts on the device
+        if seed % 3 == 0:
+            with rtx.MultiTracer([0] * 3) as m:
+                qf.load_scene(m, scene, options)
+                for name, f in (("drawn", form), ("deep", qf.DEEP)):
+                    same_records(hc, rtx, qf.run_hits(m, items, f), got[name], items, f"rt_multi trace_hits {f}, " + ctx)
+                same_records(cc, rtx, m.closest_points(points), near, points, "rt_multi closest_points, " + ctx)
     finally:
         t.close()
 
