@@ -5,7 +5,7 @@ from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
 import numpy as np
 
-from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _radiance_params, _ray_array, _visibility_params, _visibility_shape, CLOSEST, MULTIHIT
+from ._cabi import MESHINFO, PARAMS, SPHERE, TRIANGLE, RtError, _gather_params, _gather_shape, _ptr, _radiance_params, _ray_array, _visibility_params, _visibility_shape, CLOSEST, MULTIHIT
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_host.so")
 _lib = None
@@ -26,9 +26,8 @@ def load_host_library():
         L.rth_render.argtypes = [c_void_p, c_int, c_int, POINTER(c_float)]
         L.rth_render_multi.argtypes = [c_void_p, POINTER(c_int), c_int, c_int, POINTER(c_float)]
         L.rth_render_animated.argtypes = [c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float)]
-        L.rth_trace_radiance.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
-        L.rth_gather.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
-        L.rth_visibility.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
+        for f in (L.rth_trace_radiance, L.rth_gather, L.rth_visibility):            # (scene, devices, count, items, n, params, out)
+            f.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p, c_void_p]
         L.rth_closest_points.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_int, c_void_p]
         L.rth_raycast_all.argtypes = [c_void_p, POINTER(c_int), c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p]
         L.rth_split_mesh.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]
@@ -65,6 +64,13 @@ def cpp_split_mesh(vertices, normals, indices, sub_ranges, mode=0, transform=Non
     return out
 
 
+def _devices(devices, device):
+    """the (c_int array, count) arguments of a (devices, device) pair: `devices` and their number for an rt_multi, else [device] and 0
+    (a fresh rt_ctx on it)"""
+    devs = list(devices) if devices else [device]
+    return (c_int * len(devs))(*devs), len(devices)
+
+
 class CppScene:
     """A reference scene loaded and marshalled by the C++ host."""
 
@@ -82,6 +88,13 @@ class CppScene:
 
     def __del__(self):
         self.close()
+
+    def _query(self, entry, what, r, params, out, devices, device):
+        """A query of the host, rth_*(scene, devices, count, items, n, [params,] out): r the items as _ray_array returned them; params ()
+        for an entry without a params argument, else (a record or None,); -> out, a zeroed array that the entry fills."""
+        if getattr(self._L, entry)(self._h, *_devices(devices, device), _ptr(r), int(r.shape[0]), *[_ptr(q) for q in params], _ptr(out)):
+            raise RtError(what + ": " + self._L.rth_last_error().decode())
+        return out
 
     def build_buffers(self):
         counts = (c_int * 7)()
@@ -104,8 +117,7 @@ class CppScene:
     def render_multi(self, frames: int, devices) -> np.ndarray:
         """RayTracingManager::OnRenderImage(rt_multi*, frames): the frame tiled over len(devices) contexts; returns [H, W, 4]."""
         out = np.empty((self.height, self.width, 4), np.float32)
-        arr = (c_int * len(devices))(*devices)
-        if self._L.rth_render_multi(self._h, arr, len(devices), frames, out.ctypes.data_as(POINTER(c_float))):
+        if self._L.rth_render_multi(self._h, *_devices(devices, 0), frames, out.ctypes.data_as(POINTER(c_float))):
             raise RtError("OnRenderImage(rt_multi): " + self._L.rth_last_error().decode())
         return out
 
@@ -114,11 +126,9 @@ class CppScene:
         OnRenderImage(frames_per_step), through one rt_ctx (devices empty) or an rt_multi; device_geometry = the on-device pipeline (poses only
         per step).  Returns the last image."""
         out = np.empty((self.height, self.width, 4), np.float32)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
         q4 = (c_float * 4)(*[float(v) for v in q])
         sh = (c_float * 3)(*[float(v) for v in shift])
-        if self._L.rth_render_animated(self._h, arr, len(devices), 1 if device_geometry else 0, steps, frames_per_step, q4, sh,
+        if self._L.rth_render_animated(self._h, *_devices(devices, device), 1 if device_geometry else 0, steps, frames_per_step, q4, sh,
                                        out.ctypes.data_as(POINTER(c_float))):
             raise RtError("render_animated: " + self._L.rth_last_error().decode())
         return out
@@ -128,26 +138,14 @@ class CppScene:
         (n, 8)) -> float32 (n, 4); samples None = the library's defaults."""
         r = _ray_array(rays)
         q = _radiance_params(samples, seed, first_index)
-        out = np.zeros((r.shape[0], 4), np.float32)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
-        if self._L.rth_trace_radiance(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
-                                      None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
-            raise RtError("TraceRadiance: " + self._L.rth_last_error().decode())
-        return out
+        return self._query("rth_trace_radiance", "TraceRadiance", r, (q,), np.zeros((r.shape[0], 4), np.float32), devices, device)
 
     def gather(self, points, samples=None, seed=0, first_index=0, mode=0, devices=(), device: int = 0) -> np.ndarray:
         """RayTracingManager::Gather on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: points (a RAY array or float32
         (n, 8), the normal in the direction field) -> float32 (n, 4) in mode 0, (n, 9, 4) in mode 1; samples None = the library's defaults."""
         r = _ray_array(points)
         q = _gather_params(samples, seed, first_index, mode)
-        out = np.zeros(_gather_shape(r.shape[0], q), np.float32)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
-        if self._L.rth_gather(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
-                              None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
-            raise RtError("Gather: " + self._L.rth_last_error().decode())
-        return out
+        return self._query("rth_gather", "Gather", r, (q,), np.zeros(_gather_shape(r.shape[0], q), np.float32), devices, device)
 
     def visibility(self, points, samples=None, seed=0, first_index=0, mode=0, devices=(), device: int = 0) -> np.ndarray:
         """RayTracingManager::Visibility on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: points (a RAY array or float32
@@ -155,33 +153,20 @@ class CppScene:
         None = the library's defaults."""
         r = _ray_array(points)
         q = _visibility_params(samples, seed, first_index, mode)
-        out = np.zeros(_visibility_shape(r.shape[0], q), np.float32)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
-        if self._L.rth_visibility(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]),
-                                  None if q is None else q.ctypes.data_as(c_void_p), out.ctypes.data_as(c_void_p)):
-            raise RtError("Visibility: " + self._L.rth_last_error().decode())
-        return out
+        return self._query("rth_visibility", "Visibility", r, (q,), np.zeros(_visibility_shape(r.shape[0], q), np.float32), devices, device)
 
     def closest_points(self, points, devices=(), device: int = 0) -> np.ndarray:
         """RayTracingManager::ClosestPoints on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: points (a RAY array or float32
         (n, 8), the point in origin and the search radius in tMax) -> a CLOSEST array."""
         r = _ray_array(points)
-        out = np.zeros(r.shape[0], CLOSEST)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
-        if self._L.rth_closest_points(self._h, arr, len(devices), r.ctypes.data_as(c_void_p), int(r.shape[0]), out.ctypes.data_as(c_void_p)):
-            raise RtError("ClosestPoints: " + self._L.rth_last_error().decode())
-        return out
+        return self._query("rth_closest_points", "ClosestPoints", r, (), np.zeros(r.shape[0], CLOSEST), devices, device)
 
     def raycast_all(self, origin, direction, max_distance=np.inf, max_hits=8, both_sides=False, devices=(), device: int = 0) -> np.ndarray:
         """RayTracingManager::RaycastAll on a fresh rt_ctx (devices empty) or an rt_multi over `devices`: the non-empty MULTIHIT records of
         one ray, nearest first."""
         o, d = np.ascontiguousarray(origin, np.float32).reshape(3), np.ascontiguousarray(direction, np.float32).reshape(3)
         out = np.zeros(max(int(max_hits), 1), MULTIHIT)
-        devs = list(devices) if devices else [device]
-        arr = (c_int * len(devs))(*devs)
-        n = self._L.rth_raycast_all(self._h, arr, len(devices), o.ctypes.data_as(c_void_p), d.ctypes.data_as(c_void_p), float(max_distance),
+        n = self._L.rth_raycast_all(self._h, *_devices(devices, device), o.ctypes.data_as(c_void_p), d.ctypes.data_as(c_void_p), float(max_distance),
                                     int(max_hits), int(bool(both_sides)), out.ctypes.data_as(c_void_p))
         if n < 0:
             raise RtError("RaycastAll: " + self._L.rth_last_error().decode())

@@ -7,6 +7,8 @@
   scene_totals.json      chunk / triangle totals serialised by the reference itself (RayTracingManager.cs:156-157)
   *_golden.npz           oracle outputs ("parity unpinned" at float level: they pin the oracle against drift and give the
                          GPU tests fixed expected images)
+  cabi_*.json            (`make_fixtures.py cabi`, needs only the built libraries) the Python binding's surface and its call
+                         transcript, see cabi()
 """
 import glob
 import hashlib
@@ -74,5 +76,14 @@ def main():
         print(name, cnt)
 
 
+def cabi():
+    """cabi_surface.json / cabi_transcript.json: the Python binding as tests/cabi_record.py sees it.  They pin a refactor of the
+    binding to the binding before it, so they are written from the commit BEFORE such a change and never from the code under test."""
+    import cabi_record
+    for name, data in (("cabi_surface.json", cabi_record.surface(rtx)), ("cabi_transcript.json", cabi_record.transcript(rtx))):
+        json.dump(data, open(os.path.join(HERE, name), "w"), indent=1)
+        print(name, os.path.getsize(os.path.join(HERE, name)), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    cabi() if sys.argv[1:] == ["cabi"] else main()
