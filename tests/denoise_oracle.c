@@ -33,7 +33,8 @@ static float exp2_(float x)
 float denoise_exp2(float x) { return exp2_(x); }
 
 /* C, A, G, out: H*W*4 floats, row 0 first.  variant 0 = the definition; 1 = taps outside the image clamped to the border instead of
- * skipped; 2 = a colour sigma that does not halve (kc_i = kc_0): two deliberate misreadings the tests must be able to tell apart.
+ * skipped; 2 = a colour sigma that does not halve (kc_i = kc_0); 3 = d = max(A.ch + cov1, 0.01f) as a max that returns its NaN operand
+ * (the definition's select gives 0.01f): deliberate misreadings the tests must be able to tell apart.
  * Returns 0, or -1 when memory runs out. */
 int denoise_image(const float* C, const float* A, const float* G, int W, int H, int iterations, int demodulate,
                   float sigmaColour, float sigmaNormal, float sigmaDepth, int variant, float* out)
@@ -50,7 +51,7 @@ int denoise_image(const float* C, const float* A, const float* G, int W, int H, 
             float dv = 1.0f;
             if (demodulate) {
                 const float t = A[4 * i + ch] + cov1;
-                dv = t > 0.01f ? t : 0.01f;
+                dv = variant == 3 ? (t < 0.01f ? 0.01f : t) : (t > 0.01f ? t : 0.01f);
                 e[3 * i + ch] = C[4 * i + ch] / dv;
             } else e[3 * i + ch] = C[4 * i + ch];
             d[3 * i + ch] = dv;

@@ -20,7 +20,8 @@ static v3 normalize(v3 a)
  * and the previous planes and camera are not looked at.  code (may be null): per pixel 3 ints, the decisions taken: bit 0 valid,
  * bits 1..4 tap k counts, bit 5 sw >= 0.01, bit 6 the history length was capped; then x0 and y0 (0 when not valid).
  * variant 0 = the definition; 1 = taps outside the image clamped to the border instead of skipped; 2 = no depth test; 3 = the history
- * length is not capped: three deliberate misreadings the tests must be able to tell apart. */
+ * length is not capped; 4 = t <= maxHistory for t < maxHistory in the cap (the same n at equality: only bit 6 of the code tells); 5 = the
+ * depth test relative to G'.w instead of ze; 6 = no normal test: deliberate misreadings the tests must be able to tell apart. */
 int temporal_step(const float* C, const float* A, const float* G, int W, int H,
                   const float* M, const float* O, const float* V, const float* Mp, const float* Op, const float* Vp,
                   const float* Tp, const float* Np, const float* Gp, int have_history,
@@ -90,8 +91,8 @@ int temporal_step(const float* C, const float* A, const float* G, int W, int H,
                             if (surf) {
                                 const v3 e = sub(nc, V3(gp[0], gp[1], gp[2]));
                                 if (!(gp[3] > 0.0f)) continue;
-                                if (variant != 2 && !(fabsf(gp[3] - ze) <= ztol)) continue;
-                                if (!(dot(e, e) <= nt2)) continue;
+                                if (variant != 2 && !(fabsf(gp[3] - ze) <= (variant == 5 ? depthTolerance * gp[3] : ztol))) continue;
+                                if (variant != 6 && !(dot(e, e) <= nt2)) continue;
                             } else if (!(gp[3] == 0.0f)) continue;
                             bits |= 2 << (j * 2 + i);
                             sw = sw + b;
@@ -104,10 +105,10 @@ int temporal_step(const float* C, const float* A, const float* G, int W, int H,
             float* t = T + pi * 4;
             if (sw >= 0.01f) {
                 const float tt = hn / sw + 1.0f;
-                n = tt < mh ? tt : mh;
+                n = (variant == 4 ? tt <= mh : tt < mh) ? tt : mh;
                 if (variant == 3) n = tt;
                 bits |= 32;
-                if (!(tt < mh)) bits |= 64;
+                if (variant == 4 ? !(tt <= mh) : !(tt < mh)) bits |= 64;
                 const float a = 1.0f / n;
                 const float om = 1.0f - a;
                 t[0] = (hx / sw) * om + c[0] * a;

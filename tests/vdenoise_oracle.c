@@ -38,7 +38,8 @@ static float lum(const float* e) { return (0.2126f * e[0] + 0.7152f * e[1]) + 0.
 /* Planes of H*W pixels, row 0 first: e = 3 floats per pixel, G = 4, var = 1.
  * variant 0 = the definition; deliberate misreadings the tests must be able to tell apart: 1 = taps outside the image clamped to the
  * border instead of skipped (estimate, prefilter and passes), 2 = the prefilter at spacing s instead of 1, 3 = the variance weighted by
- * w instead of w*w (var_{i+1} = sv / sw). */
+ * w instead of w*w (var_{i+1} = sv / sw), 4 = d = max(A.ch + cov1, 0.01f) as a max that returns its NaN operand (the definition's select
+ * gives 0.01f), 5 = var_0 = max(v, 0) as a max that returns its NaN operand (the definition's select gives 0). */
 
 /* var_0 from e0 */
 static void estimate(const float* e, const float* G, int W, int H, float kn, float kz, int variant, float* var)
@@ -70,7 +71,7 @@ static void estimate(const float* e, const float* G, int W, int H, float kn, flo
                 }
             const float mu = m1 / sg;
             const float v = m2 / sg - mu * mu;
-            var[p] = v > 0.0f ? v : 0.0f;
+            var[p] = variant == 5 ? (v < 0.0f ? 0.0f : v) : (v > 0.0f ? v : 0.0f);
         }
 }
 
@@ -129,7 +130,7 @@ static void pass(const float* e, const float* var, const float* G, int W, int H,
 }
 
 /* prep: e0 (3 floats per pixel) and d (3 floats per pixel) from C and A (4 floats per pixel) */
-static void prep(const float* C, const float* A, size_t n, int demodulate, float* e, float* d)
+static void prep(const float* C, const float* A, size_t n, int demodulate, int variant, float* e, float* d)
 {
     for (size_t i = 0; i < n; ++i) {
         const float cov1 = 1.0f - A[4 * i + 3];
@@ -137,7 +138,7 @@ static void prep(const float* C, const float* A, size_t n, int demodulate, float
             float dv = 1.0f;
             if (demodulate) {
                 const float t = A[4 * i + ch] + cov1;
-                dv = t > 0.01f ? t : 0.01f;
+                dv = variant == 4 ? (t < 0.01f ? 0.01f : t) : (t > 0.01f ? t : 0.01f);
                 e[3 * i + ch] = C[4 * i + ch] / dv;
             } else e[3 * i + ch] = C[4 * i + ch];
             d[3 * i + ch] = dv;
@@ -156,7 +157,7 @@ int vdenoise_image(const float* C, const float* A, const float* G, int W, int H,
     float* v = malloc(m * sizeof(float));
     float* v2 = malloc(m * sizeof(float));
     if (!e || !e2 || !d || !v || !v2) { free(e); free(e2); free(d); free(v); free(v2); return -1; }
-    prep(C, A, n, demodulate, e, d);
+    prep(C, A, n, demodulate, variant, e, d);
     const float kn = 1.0f / (sigmaNormal * sigmaNormal);
     const float kz = 1.0f / (sigmaDepth * sigmaDepth);
     estimate(e, G, W, H, kn, kz, variant, v);
@@ -182,7 +183,7 @@ int vdenoise_variance(const float* C, const float* A, const float* G, int W, int
     float* e = malloc(m * 3 * sizeof(float));
     float* d = malloc(m * 3 * sizeof(float));
     if (!e || !d) { free(e); free(d); return -1; }
-    prep(C, A, n, demodulate, e, d);
+    prep(C, A, n, demodulate, variant, e, d);
     estimate(e, G, W, H, 1.0f / (sigmaNormal * sigmaNormal), 1.0f / (sigmaDepth * sigmaDepth), variant, var0);
     free(e); free(d);
     return 0;
