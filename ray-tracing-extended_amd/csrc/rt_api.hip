@@ -580,7 +580,7 @@ int deform_update(rt_ctx* c)
     if (check_area) {
         const float area = c->area_after_refit;
         c->stats.refitAreaRatio = area / c->area_at_build;
-        if (area > c->area_at_build * (float)c->opt_rebuild_percent / 100.0f) {
+        if (c->stats.refitAreaRatio > (float)c->opt_rebuild_percent / 100.0f) {    // (the ratio, not area_at_build * percent: that product overflows for a tree of 1e36)
             int r = device_build(c, nt, std::max(c->bvh.magnitude, 2.0f * std::max(camera_magnitude(c->params), c->sphere_mag))); if (r) return r;
             RT_HIP(c, hipStreamSynchronize(c->stream));
             c->stats.bvhRebuilds++;
@@ -599,7 +599,11 @@ float local_scene_magnitude(const rt_ctx* c)
         const rt_mesh_transform& t = c->h_xf[m];
         float p = std::max(std::fabs(t.position[0]), std::max(std::fabs(t.position[1]), std::fabs(t.position[2])));
         float sc = std::max(std::fabs(t.lossyScale[0]), std::max(std::fabs(t.lossyScale[1]), std::fabs(t.lossyScale[2])));
-        G = std::max(G, p + 1.01f * sc * c->mesh_radius[m]);
+        // a quaternion q = s u (u of unit length) turns p into (1 - s^2) p + s^2 R_u p, at most |1 - s^2| + s^2 times as long: the ABI
+        // takes any quaternion.  Within half a percent of unit length the 1.01 covers it and G is what it always was.
+        const float q2 = t.rotation[0] * t.rotation[0] + t.rotation[1] * t.rotation[1] + t.rotation[2] * t.rotation[2] + t.rotation[3] * t.rotation[3];
+        const float stretch = std::fabs(1.0f - q2) + q2;
+        G = std::max(G, p + 1.01f * (stretch > 1.005f ? stretch : 1.0f) * sc * c->mesh_radius[m]);
     }
     return G;
 }
@@ -644,7 +648,7 @@ int run_geometry_kernels(rt_ctx* c, bool have_bvh, float min_G = 0.f)
     if (check_area) {
         const float area = c->area_after_refit;
         c->stats.refitAreaRatio = area / c->area_at_build;
-        if (area > c->area_at_build * (float)c->opt_rebuild_percent / 100.0f) {
+        if (c->stats.refitAreaRatio > (float)c->opt_rebuild_percent / 100.0f) {    // (the ratio, not area_at_build * percent: that product overflows for a tree of 1e36)
             int r = device_build(c, nt, std::max(local_scene_magnitude(c), min_G)); if (r) return r;
             c->stats.bvhRebuilds++;
             finish_build(c, true);

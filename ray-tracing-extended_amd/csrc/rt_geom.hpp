@@ -65,10 +65,18 @@ __global__ __launch_bounds__(256) void k_chunk_bounds(const float* __restrict__ 
     const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= nm) return;
     const uint32_t first = range[2 * m], count = range[2 * m + 1];
-    float mn[3] = { __builtin_inff(), __builtin_inff(), __builtin_inff() }, mx[3] = { -mn[0], -mn[0], -mn[0] };
+    // RayTracedMesh.cs:60-80: boundsMin = boundsMax = the first world A, then Vector3.Min / Max with A, B, C of every triangle in buffer
+    // order; Mathf.Min(a, b) is a < b ? a : b and Max is a > b ? a : b, so a NaN coordinate replaces the running value and
+    // the next coordinate replaces the NaN: the comparisons are spelled out, fminf / fmaxf would skip the NaN
+    float mn[3] = { 0.f, 0.f, 0.f }, mx[3] = { 0.f, 0.f, 0.f };
+    if (count) for (int a = 0; a < 3; ++a) mn[a] = mx[a] = world_tris[(size_t)first * 18 + a];
     for (uint32_t t = 0; t < count; ++t) {
         const float* p = world_tris + (size_t)(first + t) * 18;
-        for (int k = 0; k < 9; ++k) { mn[k % 3] = __builtin_fminf(mn[k % 3], p[k]); mx[k % 3] = __builtin_fmaxf(mx[k % 3], p[k]); }
+        for (int k = 0; k < 9; ++k) {
+            const float v = p[k];
+            mn[k % 3] = mn[k % 3] < v ? mn[k % 3] : v;
+            mx[k % 3] = mx[k % 3] > v ? mx[k % 3] : v;
+        }
     }
     float lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {

@@ -52,6 +52,21 @@ def quat_rotate(q: Sequence[float], p: np.ndarray) -> np.ndarray:
     return np.stack([rx, ry, rz], axis=-1).astype(np.float32)
 
 
+def _running_extreme(v: np.ndarray, before) -> np.float32:
+    """What `r = v[0]; for x in v: r = r if before(r, x) else x` leaves in r (before: np.less for Vector3.Min, np.greater for
+    Vector3.Max — Mathf.Min(a, b) is a < b ? a : b and Mathf.Max a > b ? a : b), without the loop.  A NaN replaces the
+    running value and the next coordinate replaces the NaN, so only what follows the last NaN counts; among equal extremes (+0 and -0)
+    the last one stays."""
+    v = np.asarray(v, np.float32)
+    nan = np.flatnonzero(np.isnan(v))
+    if len(nan):
+        if nan[-1] == len(v) - 1:
+            return f32(np.nan)
+        v = v[nan[-1] + 1:]
+    m = v.min() if before is np.less else v.max()
+    return v[np.flatnonzero(v == m)[-1]]
+
+
 def quat_mul(a: Sequence[float], b: Sequence[float]) -> np.ndarray:
     ax, ay, az, aw = (f32(c) for c in a)
     bx, by, bz, bw = (f32(c) for c in b)
@@ -230,8 +245,9 @@ class RayTracedMesh:
             pts.append(w)
         for k in ("normalA", "normalB", "normalC"):
             wt[k] = quat_rotate(rot, lt[k])                                                      # DirectionLocalToWorld :91-94
-        allp = np.concatenate(pts, axis=0)
-        bmin, bmax = allp.min(axis=0), allp.max(axis=0)
+        allp = np.stack(pts, axis=1).reshape(-1, 3)                                              # A, B, C per triangle in buffer order :74-79
+        bmin = np.array([_running_extreme(allp[:, a], np.less) for a in range(3)], np.float32)
+        bmax = np.array([_running_extreme(allp[:, a], np.greater) for a in range(3)], np.float32)
         bounds = Bounds(((bmin + bmax) / f32(2)).astype(np.float32), (bmax - bmin).astype(np.float32))   # :82
         return MeshChunk(wt, bounds, local.subMeshIndex)
 

@@ -188,6 +188,8 @@ std::vector<MeshChunk> RayTracedMesh::GetSubMeshes()
         MeshChunk& wc = world[c];
         wc.triangles.resize(lc.triangles.size());
         wc.subMeshIndex = lc.subMeshIndex;
+        // :60-61, :74-79 — the box starts at the first world A and takes A, B, C in order through Vector3.Min / Max, whose Mathf.Min(a, b)
+        // is a < b ? a : b and Max a > b ? a : b: a NaN coordinate replaces the running value, the next one replaces the NaN
         float mn[3] = { INFINITY, INFINITY, INFINITY }, mx[3] = { -INFINITY, -INFINITY, -INFINITY };
         for (size_t i = 0; i < lc.triangles.size(); ++i) {
             const float* s = lc.triangles[i].posA;
@@ -195,7 +197,11 @@ std::vector<MeshChunk> RayTracedMesh::GetSubMeshes()
             for (int k = 0; k < 3; ++k) {                                        // PointLocalToWorld :86-89
                 Vector3 r = rot * Vector3{ s[3 * k] * scale.x, s[3 * k + 1] * scale.y, s[3 * k + 2] * scale.z };
                 d[3 * k] = r.x + pos.x; d[3 * k + 1] = r.y + pos.y; d[3 * k + 2] = r.z + pos.z;
-                for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], d[3 * k + a]); mx[a] = std::max(mx[a], d[3 * k + a]); }
+                if (i == 0 && k == 0) for (int a = 0; a < 3; ++a) mn[a] = mx[a] = d[a];
+                for (int a = 0; a < 3; ++a) {
+                    const float v = d[3 * k + a];
+                    mn[a] = mn[a] < v ? mn[a] : v; mx[a] = mx[a] > v ? mx[a] : v;
+                }
             }
             for (int k = 3; k < 6; ++k) {                                        // DirectionLocalToWorld :91-94
                 Vector3 r = rot * Vector3{ s[3 * k], s[3 * k + 1], s[3 * k + 2] };

@@ -132,3 +132,135 @@ def test_random_transforms_device_geometry_equals_host_marshal(rtx, tracer, seed
         assert_bitwise(got, want, f"seed {seed} round {round_}: image through the device pipeline")
         if round_ == 0:
             upload_local(tracer, mgr)                                # back to the local-mesh path for the refit round
+
+
+# ---- chunk boxes over NaN vertices: the reference's order and comparison --------------------------------------------
+
+def test_chunk_bounds_follow_the_reference_rule_on_nan_vertices(rtx):
+    """k_chunk_bounds on the hand cases of tests/test_dynamic_fuzz_cpu.py — one chunk per case, identity pose, so a NaN vertex is NaN on
+    every axis: a NaN coordinate replaces the running bound and the next vertex replaces the NaN (fminf / fmaxf would skip it)."""
+    import dynamic_fuzz as df
+    from test_dynamic_fuzz_cpu import HAND
+    n = sum(len(seq) // 3 for _, seq, _, _ in HAND)
+    tris, chunks = np.zeros(n, rtx.TRIANGLE), np.zeros(len(HAND), rtx._cabi.LOCAL_CHUNK)
+    at = 0
+    for c, (_, seq, _, _) in enumerate(HAND):
+        pts = np.repeat(np.asarray(seq, np.float32)[:, None], 3, 1)
+        k = len(seq) // 3
+        tris["posA"][at:at + k], tris["posB"][at:at + k], tris["posC"][at:at + k] = pts[0::3], pts[1::3], pts[2::3]
+        chunks[c]["firstTriangleIndex"], chunks[c]["numTriangles"] = at, k
+        at += k
+    xf = np.zeros(1, rtx._cabi.MESH_TRANSFORM)
+    xf["rotation"], xf["lossyScale"] = (0, 0, 0, 1), (1, 1, 1)
+    params = rtx.scenes.mesh_test_scene(16, 8).build_buffers()[0]
+    with rtx.Tracer(0) as t:
+        t.set_params(params)
+        t.upload_local_meshes(tris, chunks, 1)
+        t.set_mesh_transforms(xf)
+        for round_ in range(2):                            # the build's pass, then a refit's
+            if round_:                                     # away and back, a frame in each pose, so that the pass runs again on a standing tree
+                t.render(0, 1)
+                away = xf.copy(); away["position"] = (1.0, 2.0, 4.0)
+                t.set_mesh_transforms(away)
+                t.render(0, 1)
+                assert t.read_world_geometry()[1]["boundsMin"].tobytes() != infos["boundsMin"].tobytes(), "the pose did not move the boxes"
+                builds = t.stats()["bvhBuilds"]
+                t.set_mesh_transforms(xf)
+                t.render(0, 1)
+                assert t.stats()["bvhBuilds"] == builds, "round 1 is a refit"
+            _, infos = t.read_world_geometry()
+            for c, (what, _, lo, hi) in enumerate(HAND):
+                want = df.bounds_round_trip(np.float32([lo] * 3), np.float32([hi] * 3))
+                for got, w, name in ((infos[c]["boundsMin"], want[0], "boundsMin"), (infos[c]["boundsMax"], want[1], "boundsMax")):
+                    assert got.tobytes() == w.tobytes() or (np.isnan(got).all() and np.isnan(w).all()), f"{what} (round {round_}): {name} {got}, want {w}"
+
+
+@pytest.mark.parametrize("hostile", ["quaternion of norm 3", "quaternion of norm 3 on a mesh scaled 1e18", "infinite local vertex"])
+def test_refit_padding_covers_a_long_quaternion_and_an_infinite_vertex(rtx, hostile):
+    """the two bounds of the local door's padding that reading alone left open (local_scene_magnitude took p + 1.01 |s| radius, and a
+    quaternion of norm 3 makes the mesh up to seventeen times larger; radius runs over |p| with infinity in it): two meshes stand, one
+    is posed again, and the refitted tree (rebuild_percent 0: never rebuilt) passes the audit whole, padding check included
+    (refitted=True), over the reference's world triangles.  The 1e18 case is what tests/dynamic_fuzz.py seeds 36 and 96 showed at
+    step 6: the faces near zero were 4 to 7 times short of the 2e-6 G a build gives, because G took the quaternion for a unit one;
+    local_scene_magnitude bounds the mesh by (|1 - |q|^2| + |q|^2) |s| radius since."""
+    import dynamic_fuzz as df
+    from bvh_audit import awkward_triangles
+    from test_gpu_bvh_audit import audit_tracer
+    local, _ = awkward_triangles(rtx, 65)
+    if hostile == "infinite local vertex":
+        local["posC"][7, 1] = np.inf
+        local["posB"][40, 0] = -np.inf
+    chunks = np.zeros(2, rtx._cabi.LOCAL_CHUNK)
+    chunks["firstTriangleIndex"], chunks["numTriangles"], chunks["meshIndex"] = (0, 33), (33, 32), (0, 1)
+    xf = np.zeros(2, rtx._cabi.MESH_TRANSFORM)
+    xf["rotation"], xf["lossyScale"], xf["position"] = (0, 0, 0, 1), (1, 1, 1), ((0, 0, 0), (3, 0, 1))
+    if "1e18" in hostile:
+        xf["lossyScale"][1] = 1e18
+    params = rtx.scenes.mesh_test_scene(16, 8).build_buffers()[0]
+    with rtx.Tracer(0) as t:
+        t.set_option("device_bvh", 1)
+        t.set_option("rebuild_percent", 0)
+        t.set_params(params)
+        t.upload_local_meshes(local, chunks, 2)
+        t.set_mesh_transforms(xf)
+        t.render(0, 1)
+        builds = t.stats()["bvhBuilds"]
+        again = xf.copy()
+        q = np.float64([0.3, -0.5, 0.4, 0.7])
+        again["rotation"][1] = q / np.linalg.norm(q) * (1.0 if hostile == "infinite local vertex" else 3.0)
+        again["position"][1] = (2.5, 0.5, 1.0)
+        t.set_mesh_transforms(again)
+        t.render(1, 1)
+        assert t.stats()["bvhBuilds"] == builds, "a pose on a standing tree refits"
+        world, _ = df.world_from_local(rtx, local, chunks, again)
+        audit_tracer(t, world, f"{hostile}, refitted", refitted=True)
+
+
+def test_area_rule_rebuilds_a_tree_whose_built_area_is_5e36(rtx):
+    """a standing tree whose area at the build is about 5e36 and whose mesh then doubles in size: the refitted area is four times the
+    built one and rebuild_percent (200) asks for a rebuild.  The threshold used to be area_at_build * percent / 100, whose product
+    overflows float from 1.7e36 on: inf > inf is false, the tree stayed while refitAreaRatio said 4 (tests/dynamic_fuzz.py seed 96
+    step 6 reported inf).  Both area rules compare the ratio with percent / 100 since."""
+    rng = np.random.default_rng(11)
+    local = np.zeros(64, rtx.TRIANGLE)
+    for k in ("posA", "posB", "posC"):
+        local[k] = rng.uniform(-1, 1, (64, 3))
+    chunks = np.zeros(1, rtx._cabi.LOCAL_CHUNK)
+    chunks["numTriangles"] = 64
+    xf = np.zeros(1, rtx._cabi.MESH_TRANSFORM)
+    xf["rotation"], xf["lossyScale"] = (0, 0, 0, 1), (1, 1, 1)
+    params = rtx.scenes.mesh_test_scene(16, 8).build_buffers()[0]
+    with rtx.Tracer(0) as t:
+        t.set_option("device_bvh", 1)
+        t.set_params(params)
+        t.upload_local_meshes(local, chunks, 1)
+        t.set_mesh_transforms(xf)
+        t.render(0, 1)
+        unit = float(t.stats()["bvhInternalArea"])
+        assert 1.0 < unit < 1e4
+        scale = np.float32(np.sqrt(5e36 / unit))                # areas go with the square of the scale
+        xf["lossyScale"] = scale
+        t.upload_local_meshes(local, chunks, 1)                 # a new scene: built in this pose
+        t.set_mesh_transforms(xf)
+        t.render(0, 1)
+        before = t.stats()
+        assert 2e36 < before["bvhInternalArea"] < 2e37, before["bvhInternalArea"]
+        xf["lossyScale"] = np.float32(2) * scale
+        t.set_mesh_transforms(xf)
+        t.render(1, 1)
+        after = t.stats()
+        assert 3.0 < after["refitAreaRatio"] < 5.0, after["refitAreaRatio"]
+        assert (after["bvhBuilds"] - before["bvhBuilds"], after["bvhRebuilds"] - before["bvhRebuilds"]) == (1, 1)
+
+
+@pytest.mark.parametrize("kernel", [0, 1])
+def test_nan_chunk_box_faces_cut_what_the_reference_cuts(rtx, oracle, tracer, kernel):
+    """chunk boxes with a NaN boundsMin component, a NaN boundsMax component and all faces NaN (what a chunk whose last vertex is NaN now
+    gets): both kernels equal the oracle, whose tree equals its loop on this scene (tests/test_dynamic_fuzz_cpu.py)"""
+    from test_dynamic_fuzz_cpu import nan_box_scene
+    b = nan_box_scene(rtx)
+    acc, last = run_gpu(tracer, b, 0, 2, kernel=kernel)
+    want_acc, want_last, cnt = oracle.render(*b, 0, 2, accel=True)
+    assert_bitwise(last, want_last, f"NaN chunk boxes, kernel {kernel}, last frame")
+    assert_bitwise(acc, want_acc, f"NaN chunk boxes, kernel {kernel}, accum")
+    assert tracer.stats()["rays"] == cnt["rays"]

@@ -124,6 +124,29 @@ def test_oracle_closest_hit_on_random_scaled_and_surface_rays(rtx, shim, mode):
     assert len(rays) > 400 and (twin["kind"] != 0).sum() > 50
 
 
+def test_oracle_closest_hit_through_nan_chunk_boxes(rtx, shim):
+    """RayBoundingBox :177-187 on chunk boxes with a NaN boundsMin component, a NaN boundsMax component and every face NaN (what the
+    reference's marshal gives a chunk whose last vertex is NaN): the float64 twin's min / max skip a NaN operand as HLSL's
+    do, and the oracle's loop cuts the same triangles off.  The NaN faces decide: with the finite boxes those chunks are hit."""
+    key, geometry, mode, rays = tc.nan_box_case(rtx)
+    twin = tw.closest_hit(tw.Scene(None, *geometry, mode=mode), rays)
+    tc.check_hits(oracle_hits(rtx, shim, *geometry, mode, rays), twin, rays, key)     # (no geometric check: these boxes cut triangles off)
+    spheres, tris, infos = geometry
+    nan_chunks = np.nonzero(np.isnan(infos["boundsMin"]).any(1) | np.isnan(infos["boundsMax"]).any(1))[0]
+    all_nan = np.nonzero(np.isnan(infos["boundsMin"]).all(1) & np.isnan(infos["boundsMax"]).all(1))[0]
+    assert len(nan_chunks) == 3 and len(all_nan) == 1
+    finite = rtx.scenes.mesh_test_scene(32, 24).build_buffers()[3]
+    plain = tw.closest_hit(tw.Scene(None, spheres, tris, finite, mode=mode), rays)
+    tri = tw.RT_HIT_TRIANGLE
+    seen = [int(((plain["kind"] == tri) & (plain["chunk"] == c)).sum()) for c in nan_chunks]
+    print("rays that end in the three chunks with their finite boxes:", seen, "and with the NaN faces:",
+          [int(((twin["kind"] == tri) & (twin["chunk"] == c)).sum()) for c in nan_chunks])
+    assert sum(seen) > 60 and ((plain["kind"] == tri) & (plain["chunk"] == all_nan[0])).sum() > 20, seen
+    assert not ((twin["kind"] == tri) & (twin["chunk"] == all_nan[0])).any(), "a box of NaN faces let a ray through"
+    moved = (twin["kind"] != plain["kind"]) | (twin["primitive"] != plain["primitive"])
+    assert moved.sum() > 60
+
+
 # ---- whole frames ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rng_mode", [0, 1], ids=["pcg", "philox"])
 @pytest.mark.parametrize("case", list(tc.FRAME_CASES))

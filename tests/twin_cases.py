@@ -66,6 +66,7 @@ MEASURED = {
     "environment_focus_500/philox/frame0": (4.417e-05, None, 5.569e-07),
     "aov/mesh/frame2": (1.443e-05, None, None),
     "camera_moved/mode0": (5.939e-05, None, None),
+    "camera_nan_boxes/mode0": (5.939e-05, None, None),
     "camera/Balls_Outdoors/mode0": (5.061e-05, None, None),
     "camera/Balls_Outdoors/mode1": (5.061e-05, None, None),
     "camera/Chess/mode0": (2.447e-05, None, None),
@@ -413,6 +414,14 @@ def twin_pair_on_rays(geometry, mode, rays):
 RAY_SCENES = ["Balls_Outdoors", "Chess", "Knight", "Reflective_Balls", "Suzanne", "Thumbnail", "mesh_test_scene"]
 
 
+def nan_box_case(rtx):
+    """camera rays through chunk boxes with NaN faces (tests/dynamic_fuzz.py nan_box_scene: what a chunk whose last vertex is NaN gets),
+    FLAT_CHUNKS: RayBoundingBox's min / max skip a NaN operand, and a box of NaN faces passes no ray"""
+    from dynamic_fuzz import nan_box_scene
+    params, spheres, tris, infos = nan_box_scene(rtx)
+    return "camera_nan_boxes/mode0", (spheres, tris, infos), int(params["intersectMode"]), camera_rays(rtx, params)
+
+
 def ray_cases(rtx):
     """(key, geometry, mode, rays) of every ray set; the surface rays need the twin's own hits of the random set"""
     for name in RAY_SCENES:
@@ -421,6 +430,7 @@ def ray_cases(rtx):
             yield f"camera/{name}/mode{mode}", (spheres, tris, infos), mode, camera_rays(rtx, params)
     _, _, (params, spheres, tris, infos) = moved_mesh_scene(rtx)
     yield "camera_moved/mode0", (spheres, tris, infos), 0, camera_rays(rtx, params)
+    yield nan_box_case(rtx)
     params, spheres, tris, infos = rtx.scenes.mesh_test_scene(64, 48).build_buffers()
     for mode in (0, 1):
         sets = random_ray_sets(rtx, spheres, tris, mode)
