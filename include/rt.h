@@ -253,6 +253,10 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     (default 0: those stay 0); the results are the same bits
  *   "hits_slice"      rt_trace_hits: rays per launch and per staging slice, 1..4194304 (default 262144: at most 128 MiB of staged records
  *                     at maxHits = 8); the result never depends on it
+ *   "sweep"           0 (default) = the ray queries trace rays; 1 = rt_trace_rays, rt_trace_rays_device, rt_multi_trace_rays, rt_occluded,
+ *                     rt_occluded_device and rt_multi_occluded answer for a BALL swept along each ray, its radius the float whose bits are
+ *                     rt_ray._reserved: see "sphere casts" below.  Other values are refused with -2.  rt_trace_hits, the radiance,
+ *                     gather, visibility and closest-point calls and every frame ignore it; at 0 nothing reads rt_ray._reserved
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -410,7 +414,7 @@ typedef struct rt_ray {                 /* 32 B */
     float   origin[3];
     float   tMax;                       /* only hits with dst < tMax count; +inf = unbounded; <= 0 or NaN = a miss, nothing is traced */
     float   direction[3];               /* not normalised by the library: dst is in units of |direction|, as in the shader             */
-    int32_t _reserved;
+    int32_t _reserved;                  /* option "sweep" = 1: the bits of the ball's radius, a float; never read otherwise            */
 } rt_ray;
 
 enum { RT_HIT_NONE = 0, RT_HIT_SPHERE = 1, RT_HIT_TRIANGLE = 2 };
@@ -426,7 +430,7 @@ typedef struct rt_hit {                 /* 64 B; a miss: dst = +inf, hitPoint = 
     int32_t chunk;                      /* triangle: its rt_meshinfo index (the chunk whose material shades it); else -1                 */
     int32_t mesh;                       /* triangle of an rt_upload_local_meshes scene: its mesh index; else -1                          */
     float   u, v;                       /* triangle: RayTriangle's u, v (:163-165; w = 1 - u - v); else 0                                */
-    int32_t _reserved[3];
+    int32_t _reserved[3];               /* 0; option "sweep" = 1: [0] = the contact's feature code                                       */
 } rt_hit;
 
 /* Host memory; return when the results are in hits / occluded.  The rays go through device buffers of the context in slices of at
@@ -439,6 +443,55 @@ int rt_occluded   (rt_ctx* ctx, const rt_ray* rays, int n, uint8_t* occluded);
  * its 4-byte result (a stream synchronisation) before it enqueues the query.                                                     */
 int rt_trace_rays_device(rt_ctx* ctx, const void* rays, int n, void* hits);
 int rt_occluded_device  (rt_ctx* ctx, const void* rays, int n, void* occluded);
+
+/* ---- sphere casts: how far a ball travels along a caller-supplied ray before it touches something --------------------------------
+ * Option "sweep" = 1 (rt_set_option) turns the six ray-query calls above into Unity's Physics.SphereCast / CheckSphere along a path:
+ * character controllers, camera collision, line of sight with clearance, thick projectiles, probe placement.  No new entry: the rays,
+ * the records, the slicing (the result never depends on it), the origin-bound reduction and padding rule, the stream ordering, the
+ * error rules and "nothing else moves" are the ray queries'.  The reference has no such function; the definition is this library's own
+ * and frozen to the bit: float32, every product and sum rounded on its own (no FMA), / and sqrtf IEEE, dot and cross as in
+ * "closest-point queries" below.  The answer is the same bits whatever the tree, the builder, the leaf size or the order of the visit.
+ *
+ *   input         origin o, direction d (not normalised: dst is in units of |d|) and tMax as for a ray; r = the float whose bits are
+ *                 _reserved.  Not traced — the miss record, occluded 0 — when tMax <= 0 or NaN, or r <= 0, NaN or infinite.
+ *   candidates    every uploaded sphere, and every triangle of the tree: the ones rt_read_bvh_order lists, as for closest-point
+ *                 queries.  intersectMode plays no part (no chunk box is tested) and no rt_params are needed.
+ *   scene sphere  (centre s, radius R)  RaySphere (RayTracing.shader:120-146) with the radius R + r: oc = o - s; a = dot(d, d);
+ *                 b = 2 * dot(oc, d); c = dot(oc, oc) - (R + r) * (R + r); disc = b * b - 4 * a * c; t = (-b - sqrtf(disc)) / (2 * a),
+ *                 accepted when disc >= 0 and t >= 0 — so a ball that starts overlapping a sphere does not report that sphere, as a ray
+ *                 that starts inside does not.  centre = o + d * t; normal = normalize(centre - s); hitPoint = centre - normal * r.
+ *                 Feature code 0.
+ *   triangle      A = posA, eAB = posB - posA, eAC = posC - posA, n = cross(eAB, eAC) (the floats RayTriangle forms), B = A + eAB,
+ *                 C = A + eAC.  Two-sided, seven features, in this order:
+ *                   faces     N = n * (1 / sqrtf(dot(n, n))).  Front (code 1): the two-sided RayTriangle of the multi-hit queries from the
+ *                             origin o - N * r, accepted when it reports the front face (det >= 1e-6f).  Back (code 2): from o + N * r,
+ *                             the back face (det <= -1e-6f).  t, u, v are that test's; hitPoint = the moved origin + d * t.
+ *                   edges     AB (code 3: P = A, e = eAB), AC (4: P = A, e = eAC), BC (5: P = B, e = eAC - eAB): m = o - P;
+ *                             ee = dot(e, e); md = dot(m, e); nd = dot(d, e); dd = dot(d, d); qa = ee * dd - nd * nd;
+ *                             qb = ee * dot(m, d) - nd * md; qc = ee * (dot(m, m) - r * r) - md * md; disc = qb * qb - qa * qc;
+ *                             accepted when qa > 0 && disc >= 0, t = (-qb - sqrtf(disc)) / qa >= 0, and s = md + t * nd has 0 < s < ee.
+ *                             q = s / ee; hitPoint = P + e * q; (u, v) = (q, 0), (0, q), (1 - q, q).
+ *                   vertices  A, B, C (codes 6, 7, 8): RaySphere with the vertex as centre and radius r.  hitPoint = the vertex;
+ *                             (u, v) = (0, 0), (1, 0), (0, 1).
+ *   guard         a triangle feature's candidate counts only if the ball at its time really touches the triangle: with
+ *                 c = o + d * t, the key k of the closest-point query of c against this triangle (below) must satisfy k <= g * g,
+ *                 g = r * (1 + 2^-6), both products floats.  (An edge's quadratic cancels badly when d is nearly parallel to e; a t
+ *                 that is wrong by more than the guard allows is refused rather than reported, and it is the guard that makes the
+ *                 answer independent of the tree: the BVH's boxes are moved outwards by at least g plus their padding, so no candidate
+ *                 that counts lies in a node that is skipped.)  A scene sphere has no guard.
+ *   answer        among the candidates with t < tMax (strict) the smallest (t, kind, primitive, feature code): at equal t a sphere
+ *                 before a triangle, then the lower uploaded index, then the lower code.  dst = t; hitPoint as above; for a triangle
+ *                 normal = normalize((o + d * t) - hitPoint).  normal is the CONTACT normal — from the contact point to the ball's
+ *                 centre — not rt_hit's shading normal: no vertex normal is read.  kind, primitive, chunk, mesh, u, v as in rt_hit;
+ *                 _reserved[0] = the feature code, _reserved[1..2] = 0.  occluded[i] = 1 exactly when this answer is a hit.
+ *   limits        float32 limits the balls that are found.  A quadratic's root puts the ball about 2^-25 * (|o - P| / r)^2 * r off the
+ *                 feature at the computed time, P the feature: within the guard's 2^-6 * r up to about 700 radii away — there the
+ *                 first contact is found, a float64 evaluation names the same feature, and a ball that started free is within 2 % of r
+ *                 of every surface.  From thousands of radii away contacts are reported late, through a neighbouring feature, or not at
+ *                 all, and a scene sphere's root is RaySphere's, off by whole radii at 1e4 scene extents: a caller that far away advances
+ *                 the origin along d first and adds the advance to dst.  A ball smaller than the float spacing of the coordinates finds
+ *                 little.  None of this is repaired: the definition is what tests/sweep_oracle.c restates, bit for bit.  r * r or g * g
+ *                 beyond float range: whatever the arithmetic gives (the tree then prunes nothing).                                  */
 
 /* ---- radiance queries: how much light arrives along a caller-supplied ray ---------------------------------------------
  * Between "what image does the camera see?" (the frame calls) and "what does this ray hit?" (the ray queries): Trace

@@ -35,6 +35,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_visibility.hpp"
 #include "rt_closest.hpp"
 #include "rt_multihit.hpp"
+#include "rt_sweep.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -251,6 +252,7 @@ struct rt_ctx : ErrOwner {
     // closest-point queries: points per launch; 1 = the counting kernel (node steps and primitive tests of a call, summed on the device
     // and fetched by rt_get_closest_info when counts_pending says the last call left some there)
     int opt_closest_slice = 1 << 22, opt_closest_count = 0;
+    int opt_sweep = 0;              // 1: the ray queries answer for a ball (csrc/rt_sweep.hpp)
     DevBuf<unsigned long long> d_closest_counts;
     bool closest_counts_pending = false;
     unsigned long long closest_counts[2]{};
@@ -1562,6 +1564,13 @@ int sampled_arguments(rt_ctx* c, QueryCall& q, bool need_params, const void* in,
 
 template <bool ANY> hipError_t launch_rays(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
+    if (c->opt_sweep) {                                     // sphere casts: the same rays, results and launch shape (csrc/rt_sweep.hpp)
+        rtk::SweepArgs A{};
+        fill_head(c, s, A);
+        A.hits = ANY ? nullptr : static_cast<float4*>(s.out);
+        A.occluded = ANY ? static_cast<uint8_t*>(s.out) : nullptr;
+        return launch_slice(c, pick_nodes(c, rtk::k_sweep<ANY, true>, rtk::k_sweep<ANY, false>), s, A);
+    }
     rtk::QueryArgs Q{};
     fill_head(c, s, Q);
     Q.full_sort = c->opt_full_sort;
@@ -2394,6 +2403,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "closest_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "closest_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_closest_slice = value; }
     else if (!std::strcmp(name, "hits_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "hits_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_hits_slice = value; }
     else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
+    else if (!std::strcmp(name, "sweep")) { if (value != 0 && value != 1) return fail(c, -2, "sweep must be 0 or 1"); c->opt_sweep = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
     else return fail(c, -2, "unknown option '%s'", name);

@@ -505,6 +505,15 @@ class RayTracingManager:
         self.InitFrame()
         return self.backend.closest_points(points)
 
+    def SphereCast(self, rays, radius):
+        """Beyond the reference: Physics.SphereCast against the scene the next frame traces — how far a ball of `radius` (a scalar or one
+        value per ray) travels along each ray before it touches a sphere or a triangle's face, edge or vertex, and where (sweep.py,
+        include/rt.h "sphere casts").  rays as for trace_rays -> HIT records with dst = the travel, hitPoint = the contact, normal = the
+        contact normal and _reserved[0] = the contact feature."""
+        from . import sweep
+        self.InitFrame()
+        return sweep.sphere_cast(self.backend, rays, radius)
+
     def RenderFeatures(self, frames: int = 1, firstFrame: int = None):
         """Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, accumulated into
         the two planes a denoiser takes beside the image.  Returns (albedo_coverage, normal_depth), each (rows, W, 4); frame indices

@@ -1,0 +1,210 @@
+/*
+ * sweep_oracle.c — sphere casts (include/rt.h "sphere casts": option "sweep" = 1 on rt_trace_rays / rt_occluded) restated in plain C as a
+ * brute-force loop over every sphere and every triangle a chunk addresses: the checker of tests/test_gpu_sweep.py, itself pinned by
+ * tests/test_sweep_cpu.py (analytic cases, a float64 twin).  TEST INFRASTRUCTURE: compiled by the tests with the oracle's own CFLAGS
+ * (oracle/Makefile, tests/checker_build.py: -ffp-contract=off, so every product and sum below rounds on its own, as the header demands).
+ * It includes nothing but the public header: the definition is the library's own.
+ */
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+#include "../include/rt.h"
+
+typedef struct { float x, y, z; } v3;
+static v3 V(float x, float y, float z) { v3 r = { x, y, z }; return r; }
+static v3 ld(const float* p) { return V(p[0], p[1], p[2]); }
+static v3 add(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
+static v3 sub(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
+static v3 scale(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
+static float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+static v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+static v3 normalize(v3 a) { const float len = sqrtf(dot(a, a)); return V(a.x / len, a.y / len, a.z / len); }
+
+/* RaySphere (RayTracing.shader:120-146): 1 and the near root when it is accepted */
+static int ray_sphere(v3 o, v3 d, v3 centre, float radius, float* dst)
+{
+    const v3 oc = sub(o, centre);
+    const float a = dot(d, d);
+    const float b = 2.0f * dot(oc, d);
+    const float c = dot(oc, oc) - radius * radius;
+    const float disc = b * b - 4.0f * a * c;
+    if (disc >= 0.0f) {
+        *dst = (-b - sqrtf(disc)) / (2.0f * a);
+        return *dst >= 0.0f;
+    }
+    return 0;
+}
+
+/* RayTriangle with both faces (the multi-hit queries' test): +1 front, -1 back, 0 none */
+static int ray_triangle_sided(v3 o, v3 d, v3 A, v3 eAB, v3 eAC, v3 n, float* dst, float* u, float* v)
+{
+    const v3 ao = sub(o, A);
+    const v3 dao = cross(ao, d);
+    const float det = -dot(d, n);
+    const float inv = 1.0f / det;
+    *dst = dot(ao, n) * inv;
+    *u = dot(eAC, dao) * inv;
+    *v = -dot(eAB, dao) * inv;
+    const float w = 1.0f - *u - *v;
+    if (!(*dst >= 0.0f && *u >= 0.0f && *v >= 0.0f && w >= 0.0f)) return 0;
+    return det >= 1e-6f ? 1 : det <= -1e-6f ? -1 : 0;
+}
+
+/* the closest-point queries' key of point p (tests/closest_oracle.c triangle_key, include/rt.h "closest-point queries") */
+static float triangle_key(v3 p, v3 A, v3 eAB, v3 eAC)
+{
+    const v3 ap = sub(p, A);
+    const float d1 = dot(eAB, ap), d2 = dot(eAC, ap);
+    const v3 bp = sub(ap, eAB);
+    const float d3 = dot(eAB, bp), d4 = dot(eAC, bp);
+    const v3 cp = sub(ap, eAC);
+    const float d5 = dot(eAB, cp), d6 = dot(eAC, cp);
+    const float vc = d1 * d4 - d3 * d2;
+    const float vb = d5 * d2 - d1 * d6;
+    const float va = d3 * d6 - d5 * d4;
+    const float d43 = d4 - d3, d56 = d5 - d6;
+    float u, v;
+    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; }
+    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; }
+    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { u = d1 / (d1 - d3); v = 0.0f; }
+    else if (d6 >= 0.0f && d5 <= d6) { u = 0.0f; v = 1.0f; }
+    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { u = 0.0f; v = d2 / (d2 - d6); }
+    else if (va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f) { v = d43 / (d43 + d56); u = 1.0f - v; }
+    else {
+        const float den = (va + vb) + vc;
+        u = vb / den; v = vc / den;
+        u = u < 0.0f ? 0.0f : u;
+        u = u > 1.0f ? 1.0f : u;
+        v = v < 0.0f ? 0.0f : v;
+        const float room = 1.0f - u;
+        v = v > room ? room : v;
+    }
+    const v3 q = add(add(A, scale(eAB, u)), scale(eAC, v));
+    const v3 e = sub(p, q);
+    return dot(e, e);
+}
+
+/* One feature of a triangle: 1 when it answers, with its time, contact point and (u, v).  code 1..8 as in the header. */
+static int feature(int code, v3 o, v3 d, float r, v3 A, v3 eAB, v3 eAC, float* t, v3* point, float* u, float* v)
+{
+    const v3 B = add(A, eAB), C = add(A, eAC);
+    *u = 0.0f; *v = 0.0f;
+    if (code <= 2) {
+        const v3 n = cross(eAB, eAC);
+        const v3 N = scale(n, 1.0f / sqrtf(dot(n, n)));
+        const v3 o2 = code == 1 ? sub(o, scale(N, r)) : add(o, scale(N, r));
+        if (ray_triangle_sided(o2, d, A, eAB, eAC, n, t, u, v) != (code == 1 ? 1 : -1)) return 0;
+        *point = add(o2, scale(d, *t));
+        return 1;
+    }
+    if (code <= 5) {
+        const v3 P = code == 5 ? B : A;
+        const v3 e = code == 3 ? eAB : code == 4 ? eAC : sub(eAC, eAB);
+        const v3 m = sub(o, P);
+        const float ee = dot(e, e), md = dot(m, e), nd = dot(d, e), dd = dot(d, d);
+        const float qa = ee * dd - nd * nd;
+        const float qb = ee * dot(m, d) - nd * md;
+        const float qc = ee * (dot(m, m) - r * r) - md * md;
+        const float disc = qb * qb - qa * qc;
+        if (!(qa > 0.0f && disc >= 0.0f)) return 0;
+        *t = (-qb - sqrtf(disc)) / qa;
+        const float s = md + *t * nd;
+        if (!(*t >= 0.0f && s > 0.0f && s < ee)) return 0;
+        const float q = s / ee;
+        *point = add(P, scale(e, q));
+        if (code == 3) *u = q;
+        else if (code == 4) *v = q;
+        else { *v = q; *u = 1.0f - q; }
+        return 1;
+    }
+    *point = code == 6 ? A : code == 7 ? B : C;
+    *u = code == 7 ? 1.0f : 0.0f;
+    *v = code == 8 ? 1.0f : 0.0f;
+    return ray_sphere(o, d, *point, r, t);
+}
+
+static void miss(rt_hit* o)
+{
+    memset(o, 0, sizeof *o);
+    o->dst = INFINITY;
+    o->kind = RT_HIT_NONE;
+    o->primitive = o->chunk = o->mesh = -1;
+}
+
+/* out[i] = the sphere-cast record of rays[i]; occluded (may be NULL) [i] = 1 when it is a hit.  chunk_mesh: per chunk its mesh index (a
+ * local-mesh scene), or NULL (mesh = -1).  second (may be NULL): per ray the time of the best candidate of ANOTHER primitive (+inf:
+ * none) — how close the runner-up came.  -3: a chunk's range leaves the triangle buffer. */
+int sw_cast(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt, const rt_meshinfo* mi, int nm, const int32_t* chunk_mesh,
+            const rt_ray* rays, int n, rt_hit* out, uint8_t* occluded, float* second)
+{
+    for (int m = 0; m < nm; m++)
+        if ((uint64_t)mi[m].firstTriangleIndex + mi[m].numTriangles > (uint64_t)nt) return -3;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int i = 0; i < n; i++) {
+        rt_hit* h = &out[i];
+        miss(h);
+        if (occluded) occluded[i] = 0;
+        if (second) second[i] = INFINITY;
+        const v3 o = ld(rays[i].origin), d = ld(rays[i].direction);
+        const float t_max = rays[i].tMax;
+        float r;
+        memcpy(&r, &rays[i]._reserved, sizeof r);
+        if (!(t_max > 0.0f) || !(r > 0.0f) || !(r <= 3.4028235e38f)) continue;     /* not traced */
+        const float g = r * (1.0f + 0x1p-6f), g2 = g * g;
+        /* the smallest (t, kind, primitive, feature) with t < tMax */
+        int have = 0, kind = 0, chunk = -1, feat = 0;
+        uint32_t prim = 0;
+        float best = 0.0f, bu = 0.0f, bv = 0.0f, runner = INFINITY;
+        v3 bp = V(0, 0, 0);
+        for (int s = 0; s < ns; s++) {
+            float t;
+            if (!ray_sphere(o, d, ld(spheres[s].position), spheres[s].radius + r, &t) || !(t < t_max)) continue;
+            if (!have || t < best) {
+                if (have) runner = best;
+                have = 1; kind = RT_HIT_SPHERE; prim = (uint32_t)s; best = t;
+            } else if (t < runner) runner = t;
+        }
+        for (int m = 0; m < nm; m++)
+            for (uint32_t j = 0; j < mi[m].numTriangles; j++) {
+                const uint32_t ti = mi[m].firstTriangleIndex + j;
+                const v3 A = ld(tris[ti].posA), eAB = sub(ld(tris[ti].posB), A), eAC = sub(ld(tris[ti].posC), A);
+                /* the triangle's own best: codes in ascending order, strict '<' keeps the lower code at a tie */
+                int thave = 0, tfeat = 0;
+                float tt = 0.0f, tu = 0.0f, tv = 0.0f;
+                v3 tp = V(0, 0, 0);
+                for (int code = 1; code <= 8; code++) {
+                    float t, u, v;
+                    v3 point;
+                    if (!feature(code, o, d, r, A, eAB, eAC, &t, &point, &u, &v) || !(t < t_max)) continue;
+                    if (!(triangle_key(add(o, scale(d, t)), A, eAB, eAC) <= g2)) continue;      /* the guard */
+                    if (!thave || t < tt) { thave = 1; tfeat = code; tt = t; tu = u; tv = v; tp = point; }
+                }
+                if (!thave) continue;
+                if (!have || tt < best || (tt == best && kind == RT_HIT_TRIANGLE && ti < prim)) {
+                    if (have) runner = best;
+                    have = 1; kind = RT_HIT_TRIANGLE; prim = ti; best = tt; bu = tu; bv = tv; bp = tp; chunk = m; feat = tfeat;
+                } else if (tt < runner) runner = tt;
+            }
+        if (!have) continue;
+        if (occluded) occluded[i] = 1;
+        if (second) second[i] = runner;
+        const v3 centre = add(o, scale(d, best));
+        v3 nn;
+        h->kind = kind;
+        h->primitive = (int32_t)prim;
+        h->dst = best;
+        if (kind == RT_HIT_SPHERE) {
+            nn = normalize(sub(centre, ld(spheres[prim].position)));
+            bp = sub(centre, scale(nn, r));
+        } else {
+            nn = normalize(sub(centre, bp));
+            h->chunk = chunk;
+            h->mesh = chunk_mesh ? chunk_mesh[chunk] : -1;
+            h->u = bu; h->v = bv;
+            h->_reserved[0] = feat;
+        }
+        h->hitPoint[0] = bp.x; h->hitPoint[1] = bp.y; h->hitPoint[2] = bp.z;
+        h->normal[0] = nn.x; h->normal[1] = nn.y; h->normal[2] = nn.z;
+    }
+    return 0;
+}
