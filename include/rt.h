@@ -251,6 +251,12 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     depends on it
  *   "closest_count"   rt_closest_points: 1 = the counting build of the kernel, which fills rt_closest_info.lastNodeSteps / lastPrimTests
  *                     (default 0: those stay 0); the results are the same bits
+ *   "closest_k"       K, 1..8 (RT_HITS_MAX), default 1: rt_closest_points, rt_closest_points_device and rt_multi_closest_points write K
+ *                     rt_closest records per point, the K nearest candidates in order: see "K-nearest queries" below.  Other values are
+ *                     refused with -2 and nothing changes.  Every other call ignores it
+ *   "closest_all"     0 (default) or 1: with 1 the count those three calls report is the number of ALL candidates within the radius and the
+ *                     search is bounded by the radius alone ("K-nearest queries").  Other values are refused with -2 and nothing changes.
+ *                     Every other call ignores it.  At "closest_k" = 1 and "closest_all" = 0 the three calls are exactly what they were
  *   "hits_slice"      rt_trace_hits: rays per launch and per staging slice, 1..4194304 (default 262144: at most 128 MiB of staged records
  *                     at maxHits = 8); the result never depends on it
  *   "sweep"           0 (default) = the ray queries trace rays; 1 = rt_trace_rays, rt_trace_rays_device, rt_multi_trace_rays, rt_occluded,
@@ -726,7 +732,7 @@ typedef struct rt_closest {             /* 64 B; nothing within reach: dst = +in
     int32_t mesh;
     float   u, v;                       /* triangle: point = A + (B - A) * u + (C - A) * v, rt_hit's convention; else 0                 */
     int32_t side;                       /* +1 / -1 / 0, see above                                                                       */
-    int32_t _reserved[2];
+    int32_t _reserved[2];               /* 0; "closest_k" > 1 or "closest_all" = 1: [0] = the point's count (K-nearest queries), [1] = 0   */
 } rt_closest;
 typedef struct rt_closest_info {        /* 40 B */
     int32_t  calls;                     /* calls so far                                                                                 */
@@ -736,13 +742,43 @@ typedef struct rt_closest_info {        /* 40 B */
                                                points of the last call; else 0                                                          */
 } rt_closest_info;
 /* Host memory; returns when the results are in out.  The points go through device buffers of the context in slices of "closest_slice"
- * points, sized to min(n, slice).                                                                                                */
+ * points, sized to min(n, slice).  out: n rt_closest — n * K, point-major, when option "closest_k" is K (K-nearest queries below), the
+ * slices then min("closest_slice", 4194304 / K) points.                                                                          */
 int rt_closest_points       (rt_ctx* ctx, const rt_ray* points, int n, rt_closest* out);
-/* Device memory of the context's GPU (points: n rt_ray, out: n rt_closest, both 16-byte aligned), ordered on the context's stream as
+/* Device memory of the context's GPU (points: n rt_ray, out: n rt_closest — n * K with option "closest_k" = K —, both 16-byte aligned), ordered on the context's stream as
  * rt_trace_rays_device is, with its one synchronisation for the origin bound; rt_closest_info counts the call and keeps the host
  * entry's times.  After a counting call rt_get_closest_info waits for the stream once to fetch the counts.                        */
 int rt_closest_points_device(rt_ctx* ctx, const void* points, int n, void* out);
 int rt_get_closest_info     (rt_ctx* ctx, rt_closest_info* out);
+
+/* ---- K-nearest queries: every surface within a radius of a point, nearest first, and how many there are -------------------------------
+ * Unity's Physics.OverlapSphere beside ClosestPoint: rt_closest_points returns one winner; a capsule pressed into a corner touches two or
+ * three faces, the faces that meet at a crease tie bit for bit and only a caller who receives all of them can decide the sign there, and
+ * "how many primitives lie within R" is a question of its own (probe culling, level of detail, smoothing a baked field).  No new entry
+ * and no new record: the options "closest_k" (K, 1..8 = RT_HITS_MAX, default 1) and "closest_all" (0 or 1, default 0) of rt_set_option /
+ * rt_multi_set_option change what rt_closest_points, rt_closest_points_device and rt_multi_closest_points write, and nothing else: every
+ * other call ignores them.  At K = 1 and all = 0 the three calls are exactly the closest-point queries above — the same kernel, the
+ * same bytes, _reserved 0.  Otherwise they write n * K rt_closest, point-major (record j of point i at out[i * K + j]):
+ *
+ *   candidates    exactly the closest-point queries': every uploaded sphere and every triangle rt_read_bvh_order lists.  The sphere key
+ *   keys          and the seven-region triangle key are those of "closest-point queries", operation for operation.  A candidate counts
+ *   records       when k < R * R (the product a float, the comparison strict; a NaN k never counts).  The fields of a record are those
+ *                 rt_closest defines: point, dst, normal, side, u, v and the indices of that candidate.
+ *   order         ascending (k, kind, primitive): k compares as a float; at equal k a sphere comes before a triangle, then the lower
+ *                 uploaded index.  With total = the number of candidates that count, records 0 .. min(total, K) - 1 are the nearest
+ *                 candidates in that order; the remaining records are the miss record.
+ *   count         _reserved[0] of ALL K records of a point holds the point's count, _reserved[1] = 0.  all = 0: the count is
+ *                 min(total, K); a count equal to K means "there may be more".  all = 1: the count is total, the number of ALL
+ *                 candidates with k < R * R; the search is then bounded by R alone (with an unbounded R every primitive is examined).
+ *                 K = 1 with all = 1 is legal: the closest point plus the overlap count.  Record 0 of any form equals the default
+ *                 call's record in every word but _reserved[0].
+ *   not searched  R <= 0, R NaN, a point with a NaN or infinite component: K miss records with count 0.
+ *   scene, state  the closest-point queries' (scene, state, errors): the queue is settled, the scene made current, the padding widened;
+ *   slicing       nothing else moves.  A batch cut anywhere into two calls gives the bits of one; rt_multi is invisible (set the options
+ *   errors        with rt_multi_set_option: every context must hold the same K).  The points per launch and per staging slice are
+ *                 min("closest_slice", 4194304 / K): the staged results never exceed the 256 MiB of K = 1.
+ *   counting      "closest_count" = 1 works in every form and fills rt_closest_info.lastNodeSteps / lastPrimTests.
+ *   refusals      "closest_k" outside 1..8 and "closest_all" other than 0 or 1: -2 with a message; the option keeps its value.        */
 
 /* ---- multi-hit ray queries: the first K surfaces along a ray, in order -----------------------------------------------------------------
  * Beside closest hit (rt_trace_rays) and any hit (rt_occluded): EVERYTHING a ray passes through, nearest first — Unity's

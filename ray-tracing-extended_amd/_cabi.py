@@ -382,6 +382,9 @@ class _Handle:
 
     _PREFIX = None                  # "rt_" or "rt_multi_": the handle's create, destroy, last_error, set_option and upload entries
     _DEVICE_ENTRIES = False         # whether the query families have _device entries for CUDA tensors (a context's do)
+    _closest_k = 1                  # option "closest_k" as this handle's set_option set it last: the records closest_points allocates per
+                                    # point.  The option must be set through the handle: set behind its back (the raw library, another
+                                    # host on the same rt_ctx) the C call would write K records per point into a buffer of one per point
     # per instance: _lib, _handle, and _params — the PARAMS set last, once there are any (the default sample count of gather)
 
     def _open(self, *args):
@@ -425,6 +428,8 @@ class _Handle:
         self._check(getattr(self._lib, entry)(self._handle, name.encode(), int(value)), f"{entry}({name})")
         if name == "device_geometry":
             self._device_geometry = int(value)
+        elif name == "closest_k":
+            self._closest_k = int(value)        # (records per point of closest_points: the shape of its result)
 
     def _upload(self, spheres, triangles, meshinfo):
         for arr, dt, what in ((spheres, SPHERE, "spheres"), (triangles, TRIANGLE, "triangles"), (meshinfo, MESHINFO, "meshinfo")):
@@ -492,6 +497,8 @@ class _Handle:
         if check is not None:
             check(name, params)
         shape = (n,) if shape is None else shape(n, params)
+        if dtype is CLOSEST and self._closest_k != 1:
+            shape += (self._closest_k,)         # K-nearest queries (option "closest_k"): K records per point
         entry, qp = getattr(self._lib, name), None if params is None else params.ctypes.data_as(c_void_p)
         if tensor:
             import torch
@@ -662,6 +669,8 @@ class Tracer(_Handle):
         or float32 (n, 8) — the point, the search radius in tMax (inf: unbounded), the rest unread -> a CLOSEST array.  No params are
         needed.  A float32 CUDA tensor (n, 8) on the context's device takes the device entry, ordered with torch's current stream as
         trace_rays is, and returns a float32 (n, 16) tensor (the CLOSEST records)."""
+        # (after set_option("closest_k", K) with K > 1 every point gets K records, nearest first — include/rt.h "K-nearest queries",
+        # nearest.py: a CLOSEST array (n, K), a tensor (n, K, 16); _query adds the axis)
         return self._query("rt_closest_points", points)
 
     closest_points_device = closest_points  # (a tensor takes rt_closest_points_device; the name says so at the call site)

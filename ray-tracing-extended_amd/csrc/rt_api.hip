@@ -36,6 +36,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_closest.hpp"
 #include "rt_multihit.hpp"
 #include "rt_sweep.hpp"
+#include "rt_nearest.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -253,6 +254,7 @@ struct rt_ctx : ErrOwner {
     // and fetched by rt_get_closest_info when counts_pending says the last call left some there)
     int opt_closest_slice = 1 << 22, opt_closest_count = 0;
     int opt_sweep = 0;              // 1: the ray queries answer for a ball (csrc/rt_sweep.hpp)
+    int opt_closest_k = 1, opt_closest_all = 0;     // K-nearest queries: records per point, count every candidate (csrc/rt_nearest.hpp); 1 and 0: k_closest
     DevBuf<unsigned long long> d_closest_counts;
     bool closest_counts_pending = false;
     unsigned long long closest_counts[2]{};
@@ -1661,6 +1663,17 @@ int begin_closest(rt_ctx* c)
 }
 hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
+    if (c->opt_closest_k != 1 || c->opt_closest_all) {      // K-nearest queries: the same points and launch shape, K records each (csrc/rt_nearest.hpp)
+        rtk::NearestArgs A{};
+        fill_head(c, s, A);
+        A.out = static_cast<float4*>(s.out);
+        A.k = c->opt_closest_k; A.count_all = c->opt_closest_all;
+        if (c->opt_closest_count) {
+            A.counters = c->d_closest_counts.p;
+            return launch_slice(c, pick_nodes(c, rtk::k_nearest<true, true>, rtk::k_nearest<false, true>), s, A);
+        }
+        return launch_slice(c, pick_nodes(c, rtk::k_nearest<true, false>, rtk::k_nearest<false, false>), s, A);
+    }
     rtk::ClosestArgs A{};
     fill_head(c, s, A);
     A.out = static_cast<float4*>(s.out);
@@ -1670,10 +1683,12 @@ hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
     }
     return launch_slice(c, pick_nodes(c, rtk::k_closest<true, false>, rtk::k_closest<false, false>), s, A);
 }
-// n rt_closest (4 float4 each); no params of either kind
+// n * K rt_closest (4 float4 each), K = option "closest_k"; no params of either kind.  The points per launch are min("closest_slice",
+// 4194304 / K): the staged results never exceed the 256 MiB of K = 1
 int closest_call(rt_ctx* c, const char* what, const void* points, int n, const void*, const void* out, QueryCall& q)
 {
-    q = QueryCall{ kClosest, what, "points", "out", c->opt_closest_slice, sizeof(rt_closest), true, nullptr, launch_closest };
+    const int K = c->opt_closest_k;
+    q = QueryCall{ kClosest, what, "points", "out", std::min(c->opt_closest_slice, kQuerySlice / K), sizeof(rt_closest) * (size_t)K, true, nullptr, launch_closest };
     q.begin = begin_closest;
     return query_pointers(c, q, points, n, out);
 }
@@ -2403,6 +2418,8 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "closest_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "closest_slice must be in [1,%d] (points per launch)", kQuerySlice); c->opt_closest_slice = value; }
     else if (!std::strcmp(name, "hits_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "hits_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_hits_slice = value; }
     else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
+    else if (!std::strcmp(name, "closest_k")) { if (value < 1 || value > RT_HITS_MAX) return fail(c, -2, "closest_k must be in [1,%d] (records per point)", RT_HITS_MAX); c->opt_closest_k = value; }
+    else if (!std::strcmp(name, "closest_all")) { if (value != 0 && value != 1) return fail(c, -2, "closest_all must be 0 or 1"); c->opt_closest_all = value; }
     else if (!std::strcmp(name, "sweep")) { if (value != 0 && value != 1) return fail(c, -2, "sweep must be 0 or 1"); c->opt_sweep = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }

@@ -505,6 +505,15 @@ class RayTracingManager:
         self.InitFrame()
         return self.backend.closest_points(points)
 
+    def OverlapSphere(self, points, radius=None, maxResults=8, countAll=True):
+        """Beyond the reference: Physics.OverlapSphere against the scene the next frame traces — the surfaces within `radius` of each
+        point, nearest first (nearest.py, include/rt.h "K-nearest queries").  points as for ClosestPoints; radius None keeps the radii in
+        tMax -> CLOSEST records (n, maxResults), the unused ones miss records, _reserved[0] of every record the number of ALL surfaces
+        within the radius (countAll False: at most maxResults, and the search prunes by the last one listed)."""
+        from . import nearest
+        self.InitFrame()
+        return nearest.nearest_k(self.backend, points, maxResults, radius, countAll)
+
     def SphereCast(self, rays, radius):
         """Beyond the reference: Physics.SphereCast against the scene the next frame traces — how far a ball of `radius` (a scalar or one
         value per ray) travels along each ray before it touches a sphere or a triangle's face, edge or vertex, and where (sweep.py,

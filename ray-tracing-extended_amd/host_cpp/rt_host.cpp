@@ -566,6 +566,61 @@ std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_multi* m, const std:
 }
 
 namespace {
+// the K records of one point -> the non-empty ones; total: _reserved[0] (every record of a point carries it)
+std::vector<rt_closest> overlaps_found(std::vector<rt_closest> all, int* total)
+{
+    if (total) *total = all.empty() ? 0 : all[0]._reserved[0];
+    size_t n = 0;
+    while (n < all.size() && all[n].kind != RT_HIT_NONE) ++n;
+    all.resize(n);
+    return all;
+}
+rt_ray overlap_point(const float center[3], float radius, int maxResults)
+{
+    if (maxResults < 1 || maxResults > RT_HITS_MAX) throw std::runtime_error("OverlapSphere: maxResults outside 1..RT_HITS_MAX");
+    rt_ray r{};
+    for (int k = 0; k < 3; ++k) r.origin[k] = center[k];
+    r.tMax = radius;
+    return r;
+}
+// both options back to their defaults when the scope ends, whether the call in it returned or threw (nearest.py's `finally`): a
+// context left at K > 1 would write K records per point into a later ClosestPoints' buffer of one per point
+template <class Reset> struct AtScopeEnd {
+    Reset reset;
+    ~AtScopeEnd() { reset(); }
+};
+template <class Reset> AtScopeEnd<Reset> at_scope_end(Reset r) { return AtScopeEnd<Reset>{ r }; }
+} // namespace
+
+std::vector<rt_closest> RayTracingManager::OverlapSphere(rt_ctx* ctx, const float center[3], float radius, int maxResults, int* total)
+{
+    const rt_ray r = overlap_point(center, radius, maxResults);
+    InitFrame(ctx);
+    std::vector<rt_closest> all((size_t)maxResults);
+    {
+        const auto defaults = at_scope_end([ctx]() { rt_set_option(ctx, "closest_k", 1); rt_set_option(ctx, "closest_all", 0); });
+        check(ctx, rt_set_option(ctx, "closest_k", maxResults), "rt_set_option(closest_k)");
+        check(ctx, rt_set_option(ctx, "closest_all", 1), "rt_set_option(closest_all)");
+        check(ctx, rt_closest_points(ctx, &r, 1, all.data()), "rt_closest_points");
+    }
+    return overlaps_found(std::move(all), total);
+}
+
+std::vector<rt_closest> RayTracingManager::OverlapSphere(rt_multi* m, const float center[3], float radius, int maxResults, int* total)
+{
+    const rt_ray r = overlap_point(center, radius, maxResults);
+    InitFrame(m);
+    std::vector<rt_closest> all((size_t)maxResults);
+    {
+        const auto defaults = at_scope_end([m]() { rt_multi_set_option(m, "closest_k", 1); rt_multi_set_option(m, "closest_all", 0); });
+        mcheck(m, rt_multi_set_option(m, "closest_k", maxResults), "rt_multi_set_option(closest_k)");
+        mcheck(m, rt_multi_set_option(m, "closest_all", 1), "rt_multi_set_option(closest_all)");
+        mcheck(m, rt_multi_closest_points(m, &r, 1, all.data()), "rt_multi_closest_points");
+    }
+    return overlaps_found(std::move(all), total);
+}
+
+namespace {
 rt_ray one_ray(const float origin[3], const float direction[3], float maxDistance)
 {
     rt_ray r{};

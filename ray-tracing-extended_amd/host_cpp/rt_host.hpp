@@ -169,6 +169,11 @@ public:
     // rt_closest_points / rt_multi_closest_points: which sphere or triangle, where on it, how far and on which side.
     std::vector<rt_closest> ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points);
     std::vector<rt_closest> ClosestPoints(rt_multi* multi, const std::vector<rt_ray>& points);
+    // Physics.OverlapSphere for the traced scene (rt_closest_points with the options "closest_k" = maxResults (1..RT_HITS_MAX) and
+    // "closest_all" = 1, put back to 1 and 0 afterwards): the surfaces within `radius` of `center`, nearest first.  Returns the non-empty
+    // records; _reserved[0] in them is the number of ALL surfaces within the radius (total, if given, receives it also when none is).
+    std::vector<rt_closest> OverlapSphere(rt_ctx* ctx, const float center[3], float radius, int maxResults = RT_HITS_MAX, int* total = nullptr);
+    std::vector<rt_closest> OverlapSphere(rt_multi* multi, const float center[3], float radius, int maxResults = RT_HITS_MAX, int* total = nullptr);
     // Physics.RaycastAll for the traced scene (rt_trace_hits / rt_multi_trace_hits): everything origin + t * direction passes through for
     // t < maxDistance, nearest first, at most maxHits (1..RT_HITS_MAX) surfaces; bothSides: back faces and sphere exits count too
     // (side = -1).  Returns the non-empty records; hitCount == maxHits in them means there may be more.

@@ -196,6 +196,29 @@ int rth_raycast_all(void* hp, const int* devices, int n_contexts, const float* o
     return rc;
 }
 
+// RayTracingManager::OverlapSphere of the loaded scene for one point, on a fresh rt_ctx or an rt_multi as rth_gather; out holds
+// max_results rt_closest; total (may be null) receives the number of all surfaces within the radius; returns the number of records
+// written (0 .. max_results), -1 on an error.
+int rth_overlap_sphere(void* hp, const int* devices, int n_contexts, const float* center, float radius, int max_results, rt_closest* out, int* total)
+{
+    auto* h = static_cast<Handle*>(hp);
+    if (!h || !center || !out || max_results < 1 || max_results > RT_HITS_MAX) { g_err = "rth_overlap_sphere: bad arguments"; return -1; }
+    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
+    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
+    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
+    int rc = 0;
+    try {
+        rthost::RayTracingManager mgr = h->mgr;
+        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
+        const std::vector<rt_closest> res = m ? mgr.OverlapSphere(m, center, radius, max_results, total) : mgr.OverlapSphere(ctx, center, radius, max_results, total);
+        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(rt_closest));
+        rc = (int)res.size();
+    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
+    if (m) rt_multi_destroy(m);
+    if (ctx) rt_destroy(ctx);
+    return rc;
+}
+
 // Animated scene through the compiled manager: `steps` times { every mesh is turned by the quaternion q4 (x, y, z, w: rotation = q * rotation)
 // and mesh i moves by shift3 * (i + 1); Start; OnRenderImage(frames_per_step) }, through one rt_ctx (n_contexts = 0) or an rt_multi of
 // n_contexts contexts, with or without the on-device geometry pipeline.  rgba = the last step's resultTexture.  What the reference does
