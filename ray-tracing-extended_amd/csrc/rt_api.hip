@@ -1661,27 +1661,22 @@ int begin_closest(rt_ctx* c)
     c->closest_counts_pending = true;
     return 0;
 }
+// k_closest or k_nearest<node form, counting>
+template <bool COUNT> const void* pick_closest(const rt_ctx* c, bool nearest)
+{
+    return nearest ? pick_nodes(c, rtk::k_nearest<true, COUNT>, rtk::k_nearest<false, COUNT>)
+                   : pick_nodes(c, rtk::k_closest<true, COUNT>, rtk::k_closest<false, COUNT>);
+}
 hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
-    if (c->opt_closest_k != 1 || c->opt_closest_all) {      // K-nearest queries: the same points and launch shape, K records each (csrc/rt_nearest.hpp)
-        rtk::NearestArgs A{};
-        fill_head(c, s, A);
-        A.out = static_cast<float4*>(s.out);
-        A.k = c->opt_closest_k; A.count_all = c->opt_closest_all;
-        if (c->opt_closest_count) {
-            A.counters = c->d_closest_counts.p;
-            return launch_slice(c, pick_nodes(c, rtk::k_nearest<true, true>, rtk::k_nearest<false, true>), s, A);
-        }
-        return launch_slice(c, pick_nodes(c, rtk::k_nearest<true, false>, rtk::k_nearest<false, false>), s, A);
-    }
-    rtk::ClosestArgs A{};
+    // K-nearest queries: the same points and launch shape, K records each (csrc/rt_nearest.hpp); k_closest takes the Args' ClosestArgs part
+    const bool nearest = c->opt_closest_k != 1 || c->opt_closest_all;
+    rtk::NearestArgs A{};
     fill_head(c, s, A);
     A.out = static_cast<float4*>(s.out);
-    if (c->opt_closest_count) {
-        A.counters = c->d_closest_counts.p;
-        return launch_slice(c, pick_nodes(c, rtk::k_closest<true, true>, rtk::k_closest<false, true>), s, A);
-    }
-    return launch_slice(c, pick_nodes(c, rtk::k_closest<true, false>, rtk::k_closest<false, false>), s, A);
+    A.counters = c->opt_closest_count ? c->d_closest_counts.p : nullptr;
+    A.k = c->opt_closest_k; A.count_all = c->opt_closest_all;
+    return launch_slice(c, c->opt_closest_count ? pick_closest<true>(c, nearest) : pick_closest<false>(c, nearest), s, A);
 }
 // n * K rt_closest (4 float4 each), K = option "closest_k"; no params of either kind.  The points per launch are min("closest_slice",
 // 4194304 / K): the staged results never exceed the 256 MiB of K = 1

@@ -13,6 +13,8 @@
 // best key so far (R * R at the start): DESIGN.md "Closest-point queries" derives that this never skips a triangle whose key could
 // count, equal keys included (a tie can still win on its index).  Entries already on the stack are not culled again when they are
 // popped: a stale internal node costs one node step whose children are all skipped, a stale leaf its triangle tests.
+// Shared: a node step's child boxes and sort (child_boxes, sort_children: rt_kernels.hpp, sweep_node_step's too); with k_nearest
+// (rt_nearest.hpp) point_query, sphere_key, closest_triangle_record / closest_sphere_record, add_wave_counts, all below.
 #pragma once
 #include "rt_query.hpp"
 
@@ -81,45 +83,23 @@ __device__ __forceinline__ void closest_on_triangle(v3 p, v3 A, v3 ab, v3 ac, fl
 }
 
 // The four children of node `cur`: their squared lower bounds sorted ascending with their references; a child that is empty or whose
-// bound exceeds thr carries kNone (and +inf).
+// bound exceeds thr carries kNone (and +inf).  The boxes are child_boxes' (rt_kernels.hpp).
 template <bool H>
 __device__ __forceinline__ void closest_node_step(const float4* __restrict__ nodes, uint32_t cur, v3 p, float thr,
                                                   float& l0, float& l1, float& l2, float& l3,
                                                   uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
 {
-    const char* nb = reinterpret_cast<const char*>(nodes);
-    const uint32_t base = cur << 7;                                         // (the host refuses BVHs of 2^25 nodes or more)
     const float INF = __builtin_inff();
-#define RT_LB(LOX, HIX, LOY, HIY, LOZ, HIZ, LK)                                                                          \
+    const ChildBoxes b = child_boxes<H>(nodes, cur);
+    c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
+#define RT_LB(K, LK)                                                                                                     \
     {                                                                                                                    \
-        const float dx_ = __builtin_fmaxf(__builtin_fmaxf((LOX) - p.x, p.x - (HIX)), 0.0f);                              \
-        const float dy_ = __builtin_fmaxf(__builtin_fmaxf((LOY) - p.y, p.y - (HIY)), 0.0f);                              \
-        const float dz_ = __builtin_fmaxf(__builtin_fmaxf((LOZ) - p.z, p.z - (HIZ)), 0.0f);                              \
+        const float dx_ = __builtin_fmaxf(__builtin_fmaxf(b.lox.K - p.x, p.x - b.hix.K), 0.0f);                          \
+        const float dy_ = __builtin_fmaxf(__builtin_fmaxf(b.loy.K - p.y, p.y - b.hiy.K), 0.0f);                          \
+        const float dz_ = __builtin_fmaxf(__builtin_fmaxf(b.loz.K - p.z, p.z - b.hiz.K), 0.0f);                          \
         LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
     }
-    if constexpr (H) {
-        // Node4h (bvh.hpp): plane set 0 = (minx, miny), set 3 = (maxx, maxy), the first z quad = (minz, maxz), children, origin: five
-        // loads.  plane = origin + offset is one rounding of a sum whose exact value lies outside the f32 box (the offsets were rounded
-        // outwards from it), and rounding is monotone: the plane used here is outside the f32 box's as well
-        const uint4 lo = *reinterpret_cast<const uint4*>(nb + base), hi = *reinterpret_cast<const uint4*>(nb + (base + 48u));
-        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + 64u));
-        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
-        const float4 og = *reinterpret_cast<const float4*>(nb + (base + 112u));
-        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
-#define RT_LBH(XW, YW, ZLW, ZHW, E, LK)                                                                                   \
-        RT_LB(og.x + (float)as_half2(lo.XW).E, og.x + (float)as_half2(hi.XW).E, og.y + (float)as_half2(lo.YW).E,         \
-              og.y + (float)as_half2(hi.YW).E, og.z + (float)as_half2(zz.ZLW).E, og.z + (float)as_half2(zz.ZHW).E, LK)
-        RT_LBH(x, z, x, z, x, l0) RT_LBH(x, z, x, z, y, l1) RT_LBH(y, w, y, w, x, l2) RT_LBH(y, w, y, w, y, l3)
-#undef RT_LBH
-    } else {
-        const float4 mnx = *reinterpret_cast<const float4*>(nb + base), mny = *reinterpret_cast<const float4*>(nb + (base + 16u));
-        const float4 mnz = *reinterpret_cast<const float4*>(nb + (base + 32u)), mxx = *reinterpret_cast<const float4*>(nb + (base + 48u));
-        const float4 mxy = *reinterpret_cast<const float4*>(nb + (base + 64u)), mxz = *reinterpret_cast<const float4*>(nb + (base + 80u));
-        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
-        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
-        RT_LB(mnx.x, mxx.x, mny.x, mxy.x, mnz.x, mxz.x, l0) RT_LB(mnx.y, mxx.y, mny.y, mxy.y, mnz.y, mxz.y, l1)
-        RT_LB(mnx.z, mxx.z, mny.z, mxy.z, mnz.z, mxz.z, l2) RT_LB(mnx.w, mxx.w, mny.w, mxy.w, mnz.w, mxz.w, l3)
-    }
+    RT_LB(x, l0) RT_LB(y, l1) RT_LB(z, l2) RT_LB(w, l3)
 #undef RT_LB
     // an empty slot holds a (+inf, -inf) box: its bound is +inf, which is not above a threshold of +inf — it is dropped by its reference
     if (c0 == kNone || l0 > thr) { c0 = kNone; l0 = INF; }
@@ -128,10 +108,74 @@ __device__ __forceinline__ void closest_node_step(const float4* __restrict__ nod
     if (c3 == kNone || l3 > thr) { c3 = kNone; l3 = INF; }
     // sorted by (bound, dropped last): a kept child can have a bound of +inf too (thr = +inf, a point so far away that the squares
     // overflow), so the reference breaks the tie
-#define RT_CSWAP(LA, CA, LB, CB) { const bool s_ = LB < LA || (LB == LA && CA == kNone); const float lt_ = s_ ? LB : LA, lu_ = s_ ? LA : LB; \
-                                   const uint32_t ct_ = s_ ? CB : CA, cu_ = s_ ? CA : CB; LA = lt_; LB = lu_; CA = ct_; CB = cu_; }
-    RT_CSWAP(l0, c0, l1, c1) RT_CSWAP(l2, c2, l3, c3) RT_CSWAP(l0, c0, l2, c2) RT_CSWAP(l1, c1, l3, c3) RT_CSWAP(l1, c1, l2, c2)
-#undef RT_CSWAP
+    sort_children<true>(l0, l1, l2, l3, c0, c1, c2, c3);
+}
+
+// ---- what k_closest and k_nearest (rt_nearest.hpp) share ----
+// (p, R) of point i.  R <= 0 or NaN: not searched.  A point with a component that is not finite has no candidate either — every key it
+// forms is +inf or NaN, and neither is below R * R — so it is answered without a search (its bounds would be +inf or NaN at every node)
+struct PointQuery { v3 p; float R; bool searched; };
+__device__ __forceinline__ PointQuery point_query(const float4* __restrict__ in, unsigned int i, bool present)
+{
+    const float FMAX = 3.4028235e38f;
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (present) r0 = in[2 * (size_t)i];
+    PointQuery q{ rtm::mk(r0.x, r0.y, r0.z), r0.w, false };
+    q.searched = present && q.R > 0.0f && __builtin_fabsf(q.p.x) <= FMAX && __builtin_fabsf(q.p.y) <= FMAX && __builtin_fabsf(q.p.z) <= FMAX;
+    return q;
+}
+
+// The key of scene sphere sp = (centre, radius): the squared distance from p to its surface
+__device__ __forceinline__ float sphere_key(v3 p, float4 sp)
+{
+    const v3 m = p - rtm::mk(sp.x, sp.y, sp.z);
+    const float len = rtm::sqrt_(rtm::dot(m, m));
+    const float ds = __builtin_fabsf(len - sp.w);
+    return ds * ds;
+}
+
+// The record of a winner, one function per kind, each called from the kernel's own `if (id & kTriBit)`: one function that branches
+// on the id cost k_multihit up to 0.8 % (profiles/walk_refactor_timing.txt).
+// BVH-order triangle ti at (u, v) with key `key`: the point again from (u, v), the same operations as in the search, the same bits
+__device__ __forceinline__ HitRecord closest_triangle_record(const DeviceScene& S, const QueryHead& Q, v3 p, uint32_t ti, float u, float v,
+                                                             float key, int count)
+{
+    float4 g0, g1, g2;
+    load_tri(S.tri_geo, ti, g0, g1, g2);
+    const v3 point = (rtm::mk(g0.x, g0.y, g0.z) + rtm::mk(g0.w, g1.x, g1.y) * u) + rtm::mk(g1.z, g1.w, g2.x) * v;
+    const float s = rtm::dot(p - point, rtm::mk(g2.y, g2.z, g2.w));        // (n = cross(eAB, eAC), formed at the upload)
+    const float dst = rtm::sqrt_(key);
+    Hit h; h.id = kTriBit | ti; h.t = 0.0f; h.u = u; h.v = v;
+    v3 normal; const float4* mat;
+    surface_of(S, h, point, normal, mat);
+    HitRecord rec;
+    rec.triangle(S, Q, ti, normal, u, v, s > 0.0f ? 1 : s < 0.0f ? -1 : 0, count);
+    rec.at(dst, point);
+    return rec;
+}
+// scene sphere si
+__device__ __forceinline__ HitRecord closest_sphere_record(const DeviceScene& S, v3 p, uint32_t si, int count)
+{
+    const float4 sp = S.sph_geom[si];
+    const v3 c = rtm::mk(sp.x, sp.y, sp.z), m = p - c;
+    const float len = rtm::sqrt_(rtm::dot(m, m));
+    const float dst = __builtin_fabsf(len - sp.w);
+    const v3 point = c + m * (sp.w / len);
+    Hit h; h.id = si; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f;
+    v3 normal; const float4* mat;
+    surface_of(S, h, point, normal, mat);
+    HitRecord rec;
+    rec.sphere(si, normal, len >= sp.w ? 1 : -1, count);
+    rec.at(dst, point);
+    return rec;
+}
+
+// The counting build's tail: the wave's sums of node steps and primitive tests, one pair of atomics per wave (every lane takes part)
+__device__ __forceinline__ void add_wave_counts(unsigned long long* counters, uint32_t n_nodes, uint32_t n_prims)
+{
+    unsigned long long a = n_nodes, b = n_prims;
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[0], a); atomicAdd(&counters[1], b); }
 }
 
 template <bool H, bool COUNT>
@@ -142,26 +186,16 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
     const bool present = i < (unsigned)Q.n;
     if (!COUNT && !present) return;                                     // (the counting build keeps every lane for the wave's sums)
     const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float INF = __builtin_inff(), FMAX = 3.4028235e38f;
-    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (present) r0 = Q.in[2 * (size_t)i];
-    const v3 p = rtm::mk(r0.x, r0.y, r0.z);
-    const float R = r0.w;
-    // R <= 0 or NaN: not searched.  A point with a component that is not finite has no candidate either — every key it forms is +inf
-    // or NaN, and neither is below R * R — so it is answered without a search (its bounds would be +inf or NaN at every node)
-    const bool searched = present && R > 0.0f && __builtin_fabsf(p.x) <= FMAX && __builtin_fabsf(p.y) <= FMAX && __builtin_fabsf(p.z) <= FMAX;
-    float kb = R * R;                                                   // the best key so far; before the first candidate, the bound
+    const PointQuery q = point_query(Q.in, i, present);
+    const v3 p = q.p;
+    float kb = q.R * q.R;                                               // the best key so far; before the first candidate, the bound
     uint32_t best = kNone;                                              // kNone | sphere index | kTriBit + triangle in BVH order
     float bu = 0.0f, bv = 0.0f;
     uint32_t n_nodes = 0, n_prims = 0;
 
-    if (searched) {
+    if (q.searched) {
         for (int s = 0; s < S.ns; ++s) {
-            const float4 sp = S.sph_geom[s];
-            const v3 m = p - rtm::mk(sp.x, sp.y, sp.z);
-            const float len = rtm::sqrt_(rtm::dot(m, m));
-            const float ds = __builtin_fabsf(len - sp.w);
-            const float k = ds * ds;
+            const float k = sphere_key(p, S.sph_geom[s]);
             if (COUNT) ++n_prims;
             if (k < kb) { kb = k; best = (uint32_t)s; }                // strict: the lower index keeps a tie
         }
@@ -190,39 +224,11 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
     if (present) {
         HitRecord rec;
         if (best == kNone) rec.miss(0);
-        else {
-            Hit h; h.id = best; h.t = 0.0f; h.u = bu; h.v = bv;
-            v3 point, normal; const float4* mat;
-            float dst;
-            if (best & kTriBit) {
-                // the winner's point again from its (u, v): the same operations as in the search, the same bits
-                const uint32_t ti = best & ~kTriBit;
-                float4 g0, g1, g2;
-                load_tri(S.tri_geo, ti, g0, g1, g2);
-                point = (rtm::mk(g0.x, g0.y, g0.z) + rtm::mk(g0.w, g1.x, g1.y) * bu) + rtm::mk(g1.z, g1.w, g2.x) * bv;
-                const float s = rtm::dot(p - point, rtm::mk(g2.y, g2.z, g2.w));    // (n = cross(eAB, eAC), formed at the upload)
-                dst = rtm::sqrt_(kb);
-                surface_of(S, h, point, normal, mat);
-                rec.triangle(S, Q, ti, normal, bu, bv, s > 0.0f ? 1 : s < 0.0f ? -1 : 0, 0);
-            } else {
-                const float4 sp = S.sph_geom[best];
-                const v3 c = rtm::mk(sp.x, sp.y, sp.z), m = p - c;
-                const float len = rtm::sqrt_(rtm::dot(m, m));
-                dst = __builtin_fabsf(len - sp.w);
-                point = c + m * (sp.w / len);
-                surface_of(S, h, point, normal, mat);
-                rec.sphere(best, normal, len >= sp.w ? 1 : -1, 0);
-            }
-            rec.at(dst, point);
-        }
+        else if (best & kTriBit) rec = closest_triangle_record(S, Q, p, best & ~kTriBit, bu, bv, kb, 0);
+        else rec = closest_sphere_record(S, p, best, 0);
         rec.store(Q.out + 4 * (size_t)i);
     }
-
-    if (COUNT) {
-        unsigned long long a = n_nodes, b = n_prims;
-        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-        if ((threadIdx.x & 63) == 0) { atomicAdd(&Q.counters[0], a); atomicAdd(&Q.counters[1], b); }
-    }
+    if (COUNT) add_wave_counts(Q.counters, n_nodes, n_prims);
 }
 
 } // namespace rtk

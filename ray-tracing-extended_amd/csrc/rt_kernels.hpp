@@ -337,6 +337,56 @@ __device__ __forceinline__ void node_step(const float4* __restrict__ nodes, uint
 #undef RT_CSWAP
 }
 
+// The four child boxes of node `cur` as absolute planes, component k for child k, and the children's references: what the point
+// queries' and the sphere casts' node steps start from (rt_closest.hpp, rt_sweep.hpp; node_step picks near and far planes by address).
+//   Node4   the six plane quads and the children: seven loads.
+//   Node4h  (bvh.hpp) plane set 0 = (minx, miny), set 3 = (maxx, maxy), the first z quad = (minz, maxz), children, origin: five loads.
+//           plane = origin + offset is one rounding of a sum whose exact value lies outside the f32 box (the offsets were rounded
+//           outwards from it), and rounding is monotone: the plane formed here is outside the f32 box's as well.
+struct ChildBoxes { float4 lox, hix, loy, hiy, loz, hiz; uint4 ch; };
+
+template <bool H>
+__device__ __forceinline__ ChildBoxes child_boxes(const float4* __restrict__ nodes, uint32_t cur)
+{
+    const char* nb = reinterpret_cast<const char*>(nodes);
+    const uint32_t base = cur << 7;                                         // (the host refuses BVHs of 2^25 nodes or more)
+    ChildBoxes b;
+    if constexpr (H) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(nb + base), hi = *reinterpret_cast<const uint4*>(nb + (base + 48u));
+        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + 64u));
+        b.ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
+        const float4 og = *reinterpret_cast<const float4*>(nb + (base + 112u));
+        // child K's offsets are half E of the x word XW and the y word YW of lo / hi, and of the z words ZLW (min) and ZHW (max) of zz
+#define RT_CHILD(K, XW, YW, ZLW, ZHW, E)                                                                                  \
+        b.lox.K = og.x + (float)as_half2(lo.XW).E; b.hix.K = og.x + (float)as_half2(hi.XW).E; b.loy.K = og.y + (float)as_half2(lo.YW).E; \
+        b.hiy.K = og.y + (float)as_half2(hi.YW).E; b.loz.K = og.z + (float)as_half2(zz.ZLW).E; b.hiz.K = og.z + (float)as_half2(zz.ZHW).E;
+        RT_CHILD(x, x, z, x, z, x) RT_CHILD(y, x, z, x, z, y) RT_CHILD(z, y, w, y, w, x) RT_CHILD(w, y, w, y, w, y)
+#undef RT_CHILD
+    } else {
+        b.lox = *reinterpret_cast<const float4*>(nb + base);          b.loy = *reinterpret_cast<const float4*>(nb + (base + 16u));
+        b.loz = *reinterpret_cast<const float4*>(nb + (base + 32u));  b.hix = *reinterpret_cast<const float4*>(nb + (base + 48u));
+        b.hiy = *reinterpret_cast<const float4*>(nb + (base + 64u));  b.hiz = *reinterpret_cast<const float4*>(nb + (base + 80u));
+        b.ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
+    }
+    return b;
+}
+
+// Four (key, child reference) pairs sorted ascending by key, in five exchanges (node_step's own three-plus-two form is conditional
+// on full_sort).  DROPPED_LAST is the point queries' tie rule: at equal keys a dropped reference (kNone) goes behind a kept one.
+template <bool DROPPED_LAST>
+__device__ __forceinline__ void sort_exchange(float& ta, uint32_t& ca, float& tb, uint32_t& cb)
+{
+    const bool s = tb < ta || (DROPPED_LAST && tb == ta && ca == kNone);
+    const float tt = s ? tb : ta, tu = s ? ta : tb;       ta = tt; tb = tu;
+    const uint32_t ct = s ? cb : ca, cu = s ? ca : cb;    ca = ct; cb = cu;
+}
+template <bool DROPPED_LAST>
+__device__ __forceinline__ void sort_children(float& t0, float& t1, float& t2, float& t3, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
+{
+    sort_exchange<DROPPED_LAST>(t0, c0, t1, c1); sort_exchange<DROPPED_LAST>(t2, c2, t3, c3); sort_exchange<DROPPED_LAST>(t0, c0, t2, c2);
+    sort_exchange<DROPPED_LAST>(t1, c1, t3, c3); sort_exchange<DROPPED_LAST>(t1, c1, t2, c2);
+}
+
 // The three float4s of BVH-order triangle `ti` (A, eAB, eAC, n) through a 32-bit byte offset from the wave-uniform array
 // (the host refuses scenes of 2^32 / 48 triangles or more).
 __device__ __forceinline__ void load_tri(const float4* __restrict__ tri_geo, uint32_t ti, float4& g0, float4& g1, float4& g2)

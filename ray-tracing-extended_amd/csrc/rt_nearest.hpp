@@ -6,8 +6,9 @@
 // candidate counts when k < R * R; records 0 .. min(total, K) - 1 are the first of them in ascending (k, kind, uploaded index), the rest
 // the miss record; _reserved[0] of all K records is min(total, K), or with closest_all the number of ALL candidates below R * R.
 //
-// k_closest's launch and walk (closest_node_step, closest_on_triangle, kCullSlack, kCullFloor: rt_closest.hpp) with k_multihit's list
-// (HitList, rt_multihit.hpp: eight (key, id) pairs in registers, indexed at compile time only).  A sphere's id is s << 1, a triangle's
+// k_closest's launch, walk and pieces (point_query, sphere_key, closest_node_step, closest_on_triangle, kCullSlack, kCullFloor, the two
+// record writers, add_wave_counts: rt_closest.hpp) with k_multihit's list (HitList, rt_multihit.hpp: eight (key, id) pairs in
+// registers, indexed at compile time only).  The kernels stay two for their registers: 49 VGPRs there, 64 here.  A sphere's id is s << 1, a triangle's
 // kTriBit | ti << 1 with ti in BVH order: as unsigned numbers a sphere comes before a triangle, and between two triangles at one key
 // HitList::insert compares the UPLOADED indices through order[].
 //
@@ -21,10 +22,8 @@
 
 namespace rtk {
 
-struct NearestArgs : QueryHead {
-    float4* out;                // [n*K*4]  rt_closest, point-major
-    unsigned long long* counters;   // counting build: [0] node steps, [1] primitive tests of the call so far
-    int k;                      // K, 1..8
+struct NearestArgs : ClosestArgs {      // (k_closest's fields first, in their order: out, counters)
+    int k;                      // K, 1..8; out is [n*K*4] rt_closest, point-major
     int count_all;              // 1: the count is every candidate below R * R, and no pruning by the K-th key
 };
 
@@ -36,16 +35,12 @@ __global__ __launch_bounds__(kBlock) void k_nearest(DeviceScene S, NearestArgs Q
     const bool present = i < (unsigned)Q.n;
     if (!COUNT && !present) return;                                     // (the counting build keeps every lane for the wave's sums)
     const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float INF = __builtin_inff(), FMAX = 3.4028235e38f;
-    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (present) r0 = Q.in[2 * (size_t)i];
-    const v3 p = rtm::mk(r0.x, r0.y, r0.z);
-    const float R = r0.w;
+    const float INF = __builtin_inff();
+    const PointQuery q = point_query(Q.in, i, present);
+    const v3 p = q.p;
     const int K = Q.k;
     const bool count_all = Q.count_all != 0;
-    // k_closest's rule: R <= 0 or NaN, or a point with a component that is not finite, is answered without a search
-    const bool searched = present && R > 0.0f && __builtin_fabsf(p.x) <= FMAX && __builtin_fabsf(p.y) <= FMAX && __builtin_fabsf(p.z) <= FMAX;
-    const float r2 = R * R;
+    const float r2 = q.R * q.R;
     HitList L;
     float kth = INF;                                    // key of slot K - 1: +inf until K candidates are in
     int total = 0;                                      // candidates below R * R (complete only when count_all)
@@ -54,13 +49,9 @@ __global__ __launch_bounds__(kBlock) void k_nearest(DeviceScene S, NearestArgs Q
     // (a macro: a lambda that captures the list by reference kept it in scratch, rt_multihit.hpp)
 #define RT_OFFER(KEY, ID) { if ((KEY) < r2) { ++total; if ((KEY) <= kth) { L.insert((KEY), (ID), Q.order); kth = L.kth(K); } } }
 
-    if (searched) {
+    if (q.searched) {
         for (int s = 0; s < S.ns; ++s) {
-            const float4 sp = S.sph_geom[s];
-            const v3 m = p - rtm::mk(sp.x, sp.y, sp.z);
-            const float len = rtm::sqrt_(rtm::dot(m, m));
-            const float ds = __builtin_fabsf(len - sp.w);
-            const float k = ds * ds;
+            const float k = sphere_key(p, S.sph_geom[s]);
             if (COUNT) ++n_prims;
             RT_OFFER(k, (uint32_t)s << 1)
         }
@@ -82,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest(DeviceScene S, NearestArgs Q
     }
 #undef RT_OFFER
 
-    // ---- the records: the winners' tests again (their u, v: the same operations, the same bits), then k_closest's record with the count
+    // ---- the records: a winning triangle's test again for its (u, v) (the same operations, the same bits), then k_closest's record
     if (present) {
         const int count = count_all ? total : L.filled(K);
         float4* out = Q.out + 4 * ((size_t)i * (size_t)K);
@@ -91,45 +82,18 @@ __global__ __launch_bounds__(kBlock) void k_nearest(DeviceScene S, NearestArgs Q
             L.pop_front(key, id);
             HitRecord rec;
             if (id == kNone) rec.miss(count);
-            else {
-                Hit h; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f;
-                v3 point, normal; const float4* mat;
-                float dst;
-                if (id & kTriBit) {
-                    const uint32_t ti = (id & ~kTriBit) >> 1;
-                    float4 g0, g1, g2;
-                    load_tri(S.tri_geo, ti, g0, g1, g2);
-                    const v3 A = rtm::mk(g0.x, g0.y, g0.z), ab = rtm::mk(g0.w, g1.x, g1.y), ac = rtm::mk(g1.z, g1.w, g2.x);
-                    float k_again;
-                    closest_on_triangle(p, A, ab, ac, k_again, h.u, h.v);
-                    point = (A + ab * h.u) + ac * h.v;
-                    const float s = rtm::dot(p - point, rtm::mk(g2.y, g2.z, g2.w));    // (n = cross(eAB, eAC), formed at the upload)
-                    dst = rtm::sqrt_(key);
-                    h.id = kTriBit | ti;
-                    surface_of(S, h, point, normal, mat);
-                    rec.triangle(S, Q, ti, normal, h.u, h.v, s > 0.0f ? 1 : s < 0.0f ? -1 : 0, count);
-                } else {
-                    const uint32_t si = id >> 1;
-                    const float4 sp = S.sph_geom[si];
-                    const v3 c = rtm::mk(sp.x, sp.y, sp.z), m = p - c;
-                    const float len = rtm::sqrt_(rtm::dot(m, m));
-                    dst = __builtin_fabsf(len - sp.w);
-                    point = c + m * (sp.w / len);
-                    h.id = si;
-                    surface_of(S, h, point, normal, mat);
-                    rec.sphere(si, normal, len >= sp.w ? 1 : -1, count);
-                }
-                rec.at(dst, point);
-            }
+            else if (id & kTriBit) {
+                const uint32_t ti = (id & ~kTriBit) >> 1;
+                float4 g0, g1, g2;
+                load_tri(S.tri_geo, ti, g0, g1, g2);
+                float k_again, u, v;
+                closest_on_triangle(p, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), k_again, u, v);
+                rec = closest_triangle_record(S, Q, p, ti, u, v, key, count);
+            } else rec = closest_sphere_record(S, p, id >> 1, count);
             rec.store(out + 4 * (size_t)j);
         }
     }
-
-    if (COUNT) {
-        unsigned long long a = n_nodes, b = n_prims;
-        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off, 64); b += __shfl_down(b, off, 64); }
-        if ((threadIdx.x & 63) == 0) { atomicAdd(&Q.counters[0], a); atomicAdd(&Q.counters[1], b); }
-    }
+    if (COUNT) add_wave_counts(Q.counters, n_nodes, n_prims);
 }
 
 } // namespace rtk

@@ -11,7 +11,8 @@
 // wins, whatever the tree, the builder, the leaf size or the visiting order.
 //
 // k_ray_query's launch: one ray per lane, 256-thread blocks, one launch per slice, lane_stack's LDS stack with the global overflow, the
-// per-lane walk (rt_kernels.hpp).  The node step is this file's own: the slab test of boxes moved outwards by r * (1 + 2^-5) (at least
+// per-lane walk (rt_kernels.hpp).  The node step's formula is this file's own, on the boxes child_boxes reads and with sort_children
+// (rt_kernels.hpp, as closest_node_step): the slab test of boxes moved outwards by r * (1 + 2^-5) (at least
 // 2^-60; +inf when g * g overflows), written as (plane - o) * (1 / d) so that a zero direction component gives -inf / +inf by the side of
 // the plane the origin lies on, not a NaN.  DESIGN.md "Sphere casts" derives that no accepted candidate lies in a child that is skipped.
 // A child is kept when its entry distance is <= min(tMax, best t): equality passes, a tie can still win on its index.
@@ -57,40 +58,20 @@ __device__ __forceinline__ void sweep_node_step(const float4* __restrict__ nodes
                                                 float infl, float bound, float& t0, float& t1, float& t2, float& t3,
                                                 uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
 {
-    const char* nb = reinterpret_cast<const char*>(nodes);
-    const uint32_t base = cur << 7;                                         // (the host refuses BVHs of 2^25 nodes or more)
     const float INF = __builtin_inff();
+    const ChildBoxes b = child_boxes<H>(nodes, cur);
+    c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
     // a NaN (0 * inf: the origin on a plane the ray runs along; inf - inf: an infinite inflation) is dropped by fmax / fmin: it passes
-#define RT_SW(LOX, HIX, LOY, HIY, LOZ, HIZ, TK)                                                                          \
+#define RT_SW(K, TK)                                                                                                     \
     {                                                                                                                    \
-        const float ax_ = (((LOX) - infl) - o.x) * inv.x, bx_ = (((HIX) + infl) - o.x) * inv.x;                          \
-        const float ay_ = (((LOY) - infl) - o.y) * inv.y, by_ = (((HIY) + infl) - o.y) * inv.y;                          \
-        const float az_ = (((LOZ) - infl) - o.z) * inv.z, bz_ = (((HIZ) + infl) - o.z) * inv.z;                          \
+        const float ax_ = ((b.lox.K - infl) - o.x) * inv.x, bx_ = ((b.hix.K + infl) - o.x) * inv.x;                      \
+        const float ay_ = ((b.loy.K - infl) - o.y) * inv.y, by_ = ((b.hiy.K + infl) - o.y) * inv.y;                      \
+        const float az_ = ((b.loz.K - infl) - o.z) * inv.z, bz_ = ((b.hiz.K + infl) - o.z) * inv.z;                      \
         const float tn_ = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(sx ? bx_ : ax_, sy ? by_ : ay_), sz ? bz_ : az_), 0.0f);    \
         const float tf_ = __builtin_fminf(__builtin_fminf(__builtin_fminf(sx ? ax_ : bx_, sy ? ay_ : by_), sz ? az_ : bz_), bound);   \
         TK = (tn_ <= tf_) ? tn_ : INF;                                                                                   \
     }
-    if constexpr (H) {
-        // Node4h as closest_node_step reads it: plane = origin + offset, one monotone rounding of a sum that lies outside the f32 box
-        const uint4 lo = *reinterpret_cast<const uint4*>(nb + base), hi = *reinterpret_cast<const uint4*>(nb + (base + 48u));
-        const uint4 zz = *reinterpret_cast<const uint4*>(nb + (base + 64u));
-        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
-        const float4 og = *reinterpret_cast<const float4*>(nb + (base + 112u));
-        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
-#define RT_SWH(XW, YW, ZLW, ZHW, E, TK)                                                                                   \
-        RT_SW(og.x + (float)as_half2(lo.XW).E, og.x + (float)as_half2(hi.XW).E, og.y + (float)as_half2(lo.YW).E,         \
-              og.y + (float)as_half2(hi.YW).E, og.z + (float)as_half2(zz.ZLW).E, og.z + (float)as_half2(zz.ZHW).E, TK)
-        RT_SWH(x, z, x, z, x, t0) RT_SWH(x, z, x, z, y, t1) RT_SWH(y, w, y, w, x, t2) RT_SWH(y, w, y, w, y, t3)
-#undef RT_SWH
-    } else {
-        const float4 mnx = *reinterpret_cast<const float4*>(nb + base), mny = *reinterpret_cast<const float4*>(nb + (base + 16u));
-        const float4 mnz = *reinterpret_cast<const float4*>(nb + (base + 32u)), mxx = *reinterpret_cast<const float4*>(nb + (base + 48u));
-        const float4 mxy = *reinterpret_cast<const float4*>(nb + (base + 64u)), mxz = *reinterpret_cast<const float4*>(nb + (base + 80u));
-        const uint4 ch = *reinterpret_cast<const uint4*>(nb + (base + 96u));
-        c0 = ch.x; c1 = ch.y; c2 = ch.z; c3 = ch.w;
-        RT_SW(mnx.x, mxx.x, mny.x, mxy.x, mnz.x, mxz.x, t0) RT_SW(mnx.y, mxx.y, mny.y, mxy.y, mnz.y, mxz.y, t1)
-        RT_SW(mnx.z, mxx.z, mny.z, mxy.z, mnz.z, mxz.z, t2) RT_SW(mnx.w, mxx.w, mny.w, mxy.w, mnz.w, mxz.w, t3)
-    }
+    RT_SW(x, t0) RT_SW(y, t1) RT_SW(z, t2) RT_SW(w, t3)
 #undef RT_SW
     // an empty slot holds a (+inf, -inf) box, which an infinite inflation turns into NaNs that pass: it is dropped by its reference
     if (c0 == kNone) t0 = INF;
@@ -98,10 +79,7 @@ __device__ __forceinline__ void sweep_node_step(const float4* __restrict__ nodes
     if (c2 == kNone) t2 = INF;
     if (c3 == kNone) t3 = INF;
     // stack entries carry no distance, so the order in which the other three are popped is worth the two extra exchanges
-#define RT_CSWAP(TA, CA, TB, CB) { const bool s_ = TB < TA; const float tt_ = s_ ? TB : TA, tu_ = s_ ? TA : TB;         \
-                                   const uint32_t ct_ = s_ ? CB : CA, cu_ = s_ ? CA : CB; TA = tt_; TB = tu_; CA = ct_; CB = cu_; }
-    RT_CSWAP(t0, c0, t1, c1) RT_CSWAP(t2, c2, t3, c3) RT_CSWAP(t0, c0, t2, c2) RT_CSWAP(t1, c1, t3, c3) RT_CSWAP(t1, c1, t2, c2)
-#undef RT_CSWAP
+    sort_children<false>(t0, t1, t2, t3, c0, c1, c2, c3);
 }
 
 template <bool ANY, bool H>
