@@ -1454,6 +1454,14 @@ template <class Args> void fill_head(const rt_ctx* c, const QuerySlice& s, Args&
     A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS; k_closest does not read it)
 }
 
+// What the sampled kernels start from (rtk::SampledHead's fields, and the two every Args of theirs goes on with)
+template <class Args> void fill_sampled(const rt_ctx* c, const QueryCall& q, const QuerySlice& s, Args& A)
+{
+    A.in = s.in; A.out = static_cast<float4*>(s.out);
+    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
+    A.full_sort = c->opt_full_sort;
+}
+
 // What every launch function ends with: the fields all the Args share, then the launch on the context's stream
 template <class Args> hipError_t launch_slice(rt_ctx* c, const void* fn, const QuerySlice& s, Args& A)
 {
@@ -1595,10 +1603,8 @@ int occluded_call(rt_ctx* c, const char* what, const void* rays, int n, const vo
 hipError_t launch_radiance(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
     rtk::RadianceArgs A{};
+    fill_sampled(c, q, s, A);
     A.p = c->params;
-    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
-    A.full_sort = c->opt_full_sort;
-    A.rays = s.in; A.rgba = static_cast<float4*>(s.out);
     return launch_slice(c, pick_nodes(c, rtk::k_radiance<true>, rtk::k_radiance<false>), s, A);
 }
 // n float4; params == NULL: the context's numRaysPerPixel samples
@@ -1611,10 +1617,8 @@ int radiance_call(rt_ctx* c, const char* what, const void* rays, int n, const vo
 hipError_t launch_gather(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
     rtk::GatherArgs A{};
+    fill_sampled(c, q, s, A);
     A.p = c->params;
-    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
-    A.full_sort = c->opt_full_sort;
-    A.points = s.in; A.out = static_cast<float4*>(s.out);
     return launch_slice(c, q.p.mode == RT_GATHER_SH9 ? pick_nodes(c, rtk::k_gather<RT_GATHER_SH9, true>, rtk::k_gather<RT_GATHER_SH9, false>)
                                                      : pick_nodes(c, rtk::k_gather<RT_GATHER_COSINE, true>, rtk::k_gather<RT_GATHER_COSINE, false>), s, A);
 }
@@ -1630,10 +1634,8 @@ int gather_call(rt_ctx* c, const char* what, const void* points, int n, const vo
 hipError_t launch_visibility(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
 {
     rtk::VisibilityArgs A{};
-    A.samples = q.p.samples; A.seed = q.p.seed; A.first_index = s.first_index; A.sample_lanes_log2 = q.sample_lanes_log2;
+    fill_sampled(c, q, s, A);
     A.intersect_mode = c->params.intersectMode;         // (zero-initialised params: RT_INTERSECT_FLAT_CHUNKS)
-    A.full_sort = c->opt_full_sort;
-    A.points = s.in; A.out = static_cast<float4*>(s.out);
     switch (q.p.mode) {
     case RT_VIS_SH9:      return launch_slice(c, pick_nodes(c, rtk::k_visibility<RT_VIS_SH9, true>, rtk::k_visibility<RT_VIS_SH9, false>), s, A);
     case RT_VIS_DISTANCE: return launch_slice(c, pick_nodes(c, rtk::k_visibility<RT_VIS_DISTANCE, true>, rtk::k_visibility<RT_VIS_DISTANCE, false>), s, A);

@@ -10,38 +10,29 @@
 //   sum           the Philox mode's tree over the N samples; COSINE: one float4 (root.rgb / N, 1); SH9: nine float4, the tree over
 //                 L_s.c * Y_k(d), (root / N) * 4 pi, w = 1 for k = 0 and 0 otherwise.  tMax <= 0 or NaN: zeros, no draw, no cast
 //
-// One launch per slice of points, no persistent loop.  A point's S = 16 / 4 / 1 sub-streams sit on S ADJACENT lanes (lane = point * S +
-// sub-stream), lane k walks samples k, k + S, ...  The loop is k_aov's: flat, ONE closest_hit site per trip, then the shading of that
-// hit.  Every sample has its own first cast (there is nothing for k_radiance's first-cast reuse to keep): the direction of a lane's next
-// sample is drawn in the step that ends its path, and once before the loop, so lanes meet again at the traversal whatever their path
-// lengths.  The point is read again from memory there instead of living in seven registers across the loop.
+// The launch, the lane layout (an item is a point) and the estimator's tree are the sample-lane frame's (rt_sampled.hpp).  The loop is
+// k_aov's: flat, ONE closest_hit site per trip, then the shading of that hit.  Every sample has its own first cast (there is nothing
+// for k_radiance's first-cast reuse to keep): the direction of a lane's next sample is drawn in the step that ends its path, and once
+// before the loop.  The point is read again from memory there instead of living in seven registers across the loop.
 //
 // The shading step is k_radiance's, expression for expression, COPIED.  Sharing it was tried: one __forceinline__ function for the hit
 // (:309-343) that both kernels call, k_radiance handing its entry bookkeeping (e_h / e_o / e_bounce) in as a callback that runs once the
 // material's flag is read.  k_radiance's code object changed with it: 3049 -> 3061 and 3055 -> 3067 instructions, and the f32-node
-// instantiation went from 109 to 111 VGPRs (tools/kernel_resources.py), so the kernels keep a copy each.  A change to one is a change
-// to both; tests/test_gpu_gather.py holds N = 1 of this kernel bitwise to k_radiance.
-//
-// The tree is four xor-exchanges per channel at lane distances 1, 2, 4, 8; every lane of the wave takes part, lanes without a point
-// carry zeros, and the sub-stream-0 lane stores one or nine float4.  Hit or miss is carried as h.id, a value, never as a bool across
-// the traversal (rt_kernels.hpp, the per-lane walk, records why).
+// instantiation went from 109 to 111 VGPRs (tools/kernel_resources.py), so the kernels keep a copy each.  A second form, the step
+// as two functions with k_radiance's bookkeeping between them in its own body, cost no instruction and no register in any instantiation
+// but reordered 109 / 79 positions of k_radiance and 9 / 17 of k_gather, untimed: not kept (profiles/sampled_frame_notes.txt).
+// A change to one is a change to both; tests/test_gpu_gather.py holds N = 1 of this kernel bitwise to k_radiance.
 #pragma once
-#include "rt_kernels.hpp"
+#include "rt_sampled.hpp"
 
 namespace rtk {
 
-struct GatherArgs {
-    rt_params p;                // the settings that apply: maxBounceCount, intersectMode, the environment
-    const float4* points;       // [n*2]  rt_ray: (origin, tMax) (normal, -)
-    float4* out;                // [n] (COSINE) or [n*9] (SH9)
-    int n;
-    int samples;                // N
-    uint32_t seed;              // second key word
-    uint32_t first_index;       // first key word of point 0 of this launch
+struct GatherArgs : ShadingHead, SampledHead {      // in: the points, (normal, -) second; out: [n] (COSINE) or [n*9] (SH9)
     int sample_lanes_log2;      // log2 S
     int stack_cap, full_sort;   // as QueryArgs
     uint32_t* gstack; unsigned int gstack_stride;
 };
+static_assert(sizeof(SampledHead) == 32 && sizeof(GatherArgs) == sizeof(rt_params) + 64, "a kernel argument moved");
 
 constexpr uint32_t kGatherBlock = 0xFFFFFFFEu;     // first Philox block of a sample's direction draw
 
@@ -61,37 +52,32 @@ __global__ __launch_bounds__(kBlock) void k_gather(DeviceScene S, GatherArgs A)
 {
     extern __shared__ uint32_t lds_stack[];
     constexpr int NC = MODE == RT_GATHER_SH9 ? 9 : 1;                   // float4 per point
-    const int sl = A.sample_lanes_log2, nsub = 1 << sl;
-    const unsigned int g = blockIdx.x * kBlock + threadIdx.x;          // (the host keeps points-per-launch * S below 2^31)
-    if ((g & ~63u) >> sl >= (unsigned)A.n) return;                      // (wave-uniform: no lane of this wave has a point)
+    const SampleLane L = sample_lane(A);
+    if (L.idle_wave) return;
     const TravStack stk = lane_stack(lds_stack, A.stack_cap, A.gstack, A.gstack_stride);
     const rt_params& p = A.p;
-    const unsigned int point = g >> sl;
-    const int sub = (int)(g & (unsigned)(nsub - 1));
-    const bool present = point < (unsigned)A.n;
 
     v3 o = rtm::mk(0.f, 0.f, 0.f), d = o;
     float t_bound = 0.0f;
-    if (present) {
-        const float4 r0 = A.points[2 * (size_t)point];
+    if (L.present) {
+        const float4 r0 = A.in[2 * (size_t)L.item];
         o = rtm::mk(r0.x, r0.y, r0.z);
         t_bound = r0.w;
     }
     const bool traced = t_bound > 0.0f;                                 // tMax <= 0 or NaN: zeros, nothing drawn or traced
-    const uint32_t key = A.first_index + point;
+    const uint32_t key = A.first_index + L.item;                        // first Philox key word: the item's index in the call's stream
 
-    // this lane's sub-stream: samples sub, sub + S, ... in increasing order, every channel summed from 0
     v3 total[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) total[k] = rtm::mk(0.f, 0.f, 0.f);
     v3 rayColour = rtm::mk(1.f, 1.f, 1.f), light = rtm::mk(0.f, 0.f, 0.f);
     v3 d_first = d;                                                     // the sample's drawn direction (SH9: the basis is evaluated on it)
-    int sample = sub, bounce = 0;
+    int sample = L.sub, bounce = 0;
     Counters cnt = {};
     const bool full_sort = A.full_sort != 0;
-    bool alive = present && traced && sample < A.samples && p.maxBounceCount >= 0;     // (Trace casts MaxBounceCount + 1 rays at most)
+    bool alive = L.present && traced && sample < A.samples && p.maxBounceCount >= 0;   // (Trace casts MaxBounceCount + 1 rays at most)
     if (alive) {
-        const float4 r1 = A.points[2 * (size_t)point + 1];
+        const float4 r1 = A.in[2 * (size_t)L.item + 1];
         d = gather_direction<MODE>(key, A.seed, (uint32_t)sample, rtm::mk(r1.x, r1.y, r1.z));
         if (MODE == RT_GATHER_SH9) d_first = d;
     }
@@ -140,26 +126,16 @@ __global__ __launch_bounds__(kBlock) void k_gather(DeviceScene S, GatherArgs A)
         }
         if (path_done) {
             if (MODE == RT_GATHER_SH9) {
-                // the real SH basis of bands 0..2 on the drawn direction, every product its own rounding (include/rt.h)
-                const float x = d_first.x, y = d_first.y, z = d_first.z;
                 float Y[9];
-                Y[0] = 0.28209479f;
-                Y[1] = 0.48860251f * y;
-                Y[2] = 0.48860251f * z;
-                Y[3] = 0.48860251f * x;
-                Y[4] = 1.09254843f * (x * y);
-                Y[5] = 1.09254843f * (y * z);
-                Y[6] = 0.31539157f * (3.0f * (z * z) - 1.0f);
-                Y[7] = 1.09254843f * (x * z);
-                Y[8] = 0.54627421f * (x * x - y * y);
+                sh9_basis(d_first, Y);
 #pragma unroll
                 for (int k = 0; k < NC; ++k) total[k] = total[k] + light * Y[k];
             } else total[0] = total[0] + light;
-            sample += nsub;
+            sample += L.nsub;
             if (sample >= A.samples) alive = false;
             else {
                 // the next sample starts at the point again, along a direction of its own, its first cast bounded
-                const float4 r0 = A.points[2 * (size_t)point], r1 = A.points[2 * (size_t)point + 1];
+                const float4 r0 = A.in[2 * (size_t)L.item], r1 = A.in[2 * (size_t)L.item + 1];
                 o = rtm::mk(r0.x, r0.y, r0.z);
                 t_bound = r0.w;
                 d = gather_direction<MODE>(key, A.seed, (uint32_t)sample, rtm::mk(r1.x, r1.y, r1.z));
@@ -170,18 +146,10 @@ __global__ __launch_bounds__(kBlock) void k_gather(DeviceScene S, GatherArgs A)
         }
     }
 
-    // the estimator's tree: (k, k + 1) for even k, then (k, k + 2) for k = 0 mod 4, ...
-    for (int off = 1; off < nsub; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-            total[k].x = total[k].x + __shfl_xor(total[k].x, off, 64);
-            total[k].y = total[k].y + __shfl_xor(total[k].y, off, 64);
-            total[k].z = total[k].z + __shfl_xor(total[k].z, off, 64);
-        }
-    }
-    if (present && sub == 0) {
+    tree_sum<3 * NC>(&total[0].x, L.nsub);                              // (a v3 is its three floats)
+    if (L.stores()) {
         const float nf = (float)A.samples;
-        float4* out = A.out + (size_t)NC * point;
+        float4* out = A.out + (size_t)NC * L.item;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             if (!traced) { out[k] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }

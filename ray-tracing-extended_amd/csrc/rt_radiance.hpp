@@ -7,72 +7,56 @@
 //   first cast    counts only hits with dst < tMax (rt_trace_rays' rule); every later cast is unbounded
 //   sum           the estimator's tree of the Philox mode over the N samples, root / N; alpha 1.  tMax <= 0 or NaN: four zeros, no cast
 //
-// One launch per slice of rays, no persistent loop.  A ray's S = 16 / 4 / 1 sub-streams sit on S ADJACENT lanes (lane = ray * S +
-// sub-stream; a wave holds 64 / S rays), lane k walks samples k, k + S, ...  A flat state machine shaped like render_pixel / k_aov: one
-// closest_hit per trip, then the shading of that hit; sample and bounce advance in the same loop, so lanes meet again at the traversal
-// whatever their path lengths.
+// The launch, the lane layout (an item is a ray) and the estimator's tree are the sample-lane frame's (rt_sampled.hpp).  A flat state
+// machine shaped like render_pixel / k_aov: one closest_hit per trip, then the shading of that hit; sample and bounce advance in the
+// same loop.
 //
 // First-cast reuse.  What Trace does before its first draw depends on the ray alone: the bounded cast at loop index 0 and, when that
 // hits an InvisibleLight (flag 2) with a bounce left, the pass-through cast from hitPoint + dir * 0.001.  A lane makes these casts once,
 // keeps the answer — the "entry": origin, loop index and Hit of the last ray-only cast — and every further sample of the lane re-enters
 // the shading step from it without a traversal (closest_hit is a function of its arguments, so the repeated cast would return these
 // bits).  At N = 64, S = 16 that removes three of each lane's four first casts.
-//
-// The tree is four xor-exchanges per channel at lane distances 1, 2, 4, 8 (inside a row of 16 lanes: DPP moves, no LDS traffic); every
-// lane of the wave takes part, lanes without a ray carry zeros, and the sub-stream-0 lane stores one float4.  Hit or miss is carried as
-// h.id, a value, never as a bool across the traversal (rt_kernels.hpp, the per-lane walk, records why).
 #pragma once
-#include "rt_kernels.hpp"
+#include "rt_sampled.hpp"
 
 namespace rtk {
 
-struct RadianceArgs {
-    rt_params p;                // the settings that apply: maxBounceCount, intersectMode, the environment
-    const float4* rays;         // [n*2]  rt_ray: (origin, tMax) (direction, -)
-    float4* rgba;               // [n]
-    int n;
-    int samples;                // N
-    uint32_t seed;              // second key word
-    uint32_t first_index;       // first key word of ray 0 of this launch
+struct RadianceArgs : ShadingHead, SampledHead {    // in: the rays; out: [n] rgba
     int sample_lanes_log2;      // log2 S
     int stack_cap, full_sort;   // as QueryArgs
     uint32_t* gstack; unsigned int gstack_stride;
 };
+static_assert(sizeof(SampledHead) == 32 && sizeof(RadianceArgs) == sizeof(rt_params) + 64, "a kernel argument moved");
 
 template <bool H>
 __global__ __launch_bounds__(kBlock) void k_radiance(DeviceScene S, RadianceArgs A)
 {
     extern __shared__ uint32_t lds_stack[];
-    const int sl = A.sample_lanes_log2, nsub = 1 << sl;
-    const unsigned int g = blockIdx.x * kBlock + threadIdx.x;          // (the host keeps rays-per-launch * S below 2^31)
-    if ((g & ~63u) >> sl >= (unsigned)A.n) return;                      // (wave-uniform: no lane of this wave has a ray)
+    const SampleLane L = sample_lane(A);
+    if (L.idle_wave) return;
     const TravStack stk = lane_stack(lds_stack, A.stack_cap, A.gstack, A.gstack_stride);
     const rt_params& p = A.p;
-    const unsigned int ray = g >> sl;
-    const int sub = (int)(g & (unsigned)(nsub - 1));
-    const bool present = ray < (unsigned)A.n;
 
     v3 o = rtm::mk(0.f, 0.f, 0.f), d0 = o;
     float t_bound = 0.0f;
-    if (present) {
-        const float4 r0 = A.rays[2 * (size_t)ray], r1 = A.rays[2 * (size_t)ray + 1];
+    if (L.present) {
+        const float4 r0 = A.in[2 * (size_t)L.item], r1 = A.in[2 * (size_t)L.item + 1];
         o = rtm::mk(r0.x, r0.y, r0.z); d0 = rtm::mk(r1.x, r1.y, r1.z);
         t_bound = r0.w;
     }
     const bool traced = t_bound > 0.0f;                                 // tMax <= 0 or NaN: four zeros, nothing traced
-    const uint32_t key = A.first_index + ray;
+    const uint32_t key = A.first_index + L.item;                        // first Philox key word: the item's index in the call's stream
 
-    // this lane's sub-stream: samples sub, sub + S, ... in increasing order, summed from 0
     v3 total = rtm::mk(0.f, 0.f, 0.f);
     v3 d = d0, rayColour = rtm::mk(1.f, 1.f, 1.f), light = rtm::mk(0.f, 0.f, 0.f);
-    int sample = sub, bounce = 0;
+    int sample = L.sub, bounce = 0;
     // the entry (file header): set at the first shading step that is not a pass-through with a cast to follow
     Hit e_h; e_h.t = 0.f; e_h.id = kNone; e_h.u = 0.f; e_h.v = 0.f;
     v3 e_o = o;
     int e_bounce = -1;                                                  // -1: not set yet
     Counters cnt = {};
     const bool full_sort = A.full_sort != 0;
-    bool alive = present && traced && sample < A.samples && p.maxBounceCount >= 0;     // (Trace casts MaxBounceCount + 1 rays at most)
+    bool alive = L.present && traced && sample < A.samples && p.maxBounceCount >= 0;   // (Trace casts MaxBounceCount + 1 rays at most)
 
     while (alive) {
         Hit h = closest_hit<false, H>(S, p.intersectMode, full_sort, o, d, stk, cnt, t_bound);
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void k_radiance(DeviceScene S, RadianceArgs
             }
             if (path_done) {
                 total = total + light;
-                sample += nsub;
+                sample += L.nsub;
                 if (sample >= A.samples) alive = false;
                 else {
                     // the next sample re-enters at the entry: no cast
@@ -136,15 +120,11 @@ __global__ __launch_bounds__(kBlock) void k_radiance(DeviceScene S, RadianceArgs
         } while (again);
     }
 
-    // the estimator's tree: (k, k + 1) for even k, then (k, k + 2) for k = 0 mod 4, ...
-    for (int off = 1; off < nsub; off <<= 1) {
-        total.x = total.x + __shfl_xor(total.x, off, 64);
-        total.y = total.y + __shfl_xor(total.y, off, 64);
-        total.z = total.z + __shfl_xor(total.z, off, 64);
-    }
-    if (present && sub == 0) {
+    float sum[3] = { total.x, total.y, total.z };
+    tree_sum<3>(sum, L.nsub);
+    if (L.stores()) {
         const float nf = (float)A.samples;
-        A.rgba[ray] = traced ? make_float4(total.x / nf, total.y / nf, total.z / nf, 1.0f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        A.out[L.item] = traced ? make_float4(sum[0] / nf, sum[1] / nf, sum[2] / nf, 1.0f) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 

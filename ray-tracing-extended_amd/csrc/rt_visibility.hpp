@@ -14,30 +14,21 @@
 //   sum           the Philox mode's tree over the N samples per channel, root / N; mode 1: coefficients * 4 pi after the division.
 //                 tMax <= 0 or NaN: zeros, no draw, no cast
 //
-// k_gather's launch, lane layout and tree: a point's S = 16 / 4 / 1 sub-streams sit on S ADJACENT lanes (lane = point * S + sub-stream),
-// lane k walks samples k, k + S, ..., four xor-exchanges per channel at lane distances 1, 2, 4, 8, every lane of the wave takes part,
-// lanes without a point carry zeros, the sub-stream-0 lane stores.  The loop is flatter than k_gather's: a sample is ONE cast, so a
-// trip is one traversal site (any_hit or closest_hit) and the sums.  The two lessons the other kernels record hold here: hit or miss
-// crosses the traversal as a value (any_hit's hit_t, closest_hit's h.id), never as a bool; and the next sample's direction is drawn at
-// the END of a trip, once before the loop, so every lane arrives at the traversal with its ray ready.  The point is read again from memory
-// there: the normal does not live across the traversal.
+// The launch, the lane layout (an item is a point) and the estimator's tree are the sample-lane frame's (rt_sampled.hpp); the next
+// sample's ray is made as k_gather makes it, written out here.  The loop is flatter than k_gather's: a sample is ONE cast, so a trip is one traversal site
+// (any_hit or closest_hit) and the sums.
 #pragma once
 #include "rt_gather.hpp"
 
 namespace rtk {
 
-struct VisibilityArgs {
-    const float4* points;       // [n*2]  rt_ray: (origin, tMax) (normal, -)
-    float4* out;                // [n] (COSINE, DISTANCE) or [n*3] (SH9)
-    int n;
-    int samples;                // N
-    uint32_t seed;              // second key word
-    uint32_t first_index;       // first key word of point 0 of this launch
+struct VisibilityArgs : SampledHead {               // in: the points, (normal, -) second; out: [n] (COSINE, DISTANCE) or [n*3] (SH9)
     int sample_lanes_log2;      // log2 S
     int intersect_mode;         // as QueryArgs
     int stack_cap, full_sort;   // as QueryArgs
     uint32_t* gstack; unsigned int gstack_stride;
 };
+static_assert(sizeof(SampledHead) == 32 && sizeof(VisibilityArgs) == 64, "a kernel argument moved");
 
 template <int MODE, bool H>
 __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, VisibilityArgs A)
@@ -45,35 +36,30 @@ __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, Visibility
     extern __shared__ uint32_t lds_stack[];
     constexpr int NC = MODE == RT_VIS_SH9 ? 10 : MODE == RT_VIS_DISTANCE ? 3 : 4;       // channels per point
     constexpr int DIR = MODE == RT_VIS_SH9 ? RT_GATHER_SH9 : RT_GATHER_COSINE;         // the draw rt_gather makes for these directions
-    const int sl = A.sample_lanes_log2, nsub = 1 << sl;
-    const unsigned int g = blockIdx.x * kBlock + threadIdx.x;          // (the host keeps points-per-launch * S below 2^31)
-    if ((g & ~63u) >> sl >= (unsigned)A.n) return;                      // (wave-uniform: no lane of this wave has a point)
+    const SampleLane L = sample_lane(A);
+    if (L.idle_wave) return;
     const TravStack stk = lane_stack(lds_stack, A.stack_cap, A.gstack, A.gstack_stride);
-    const unsigned int point = g >> sl;
-    const int sub = (int)(g & (unsigned)(nsub - 1));
-    const bool present = point < (unsigned)A.n;
     const float INF = __builtin_inff();
 
     v3 o = rtm::mk(0.f, 0.f, 0.f), d = o;
     float t_bound = 0.0f;
-    if (present) {
-        const float4 r0 = A.points[2 * (size_t)point];
+    if (L.present) {
+        const float4 r0 = A.in[2 * (size_t)L.item];
         o = rtm::mk(r0.x, r0.y, r0.z);
         t_bound = r0.w;
     }
     const bool traced = t_bound > 0.0f;                                 // tMax <= 0 or NaN: zeros, nothing drawn or traced
-    const uint32_t key = A.first_index + point;
+    const uint32_t key = A.first_index + L.item;                        // first Philox key word: the item's index in the call's stream
 
-    // this lane's sub-stream: samples sub, sub + S, ... in increasing order, every channel summed from 0
     float total[NC];
 #pragma unroll
     for (int k = 0; k < NC; ++k) total[k] = 0.0f;
-    int sample = sub;
+    int sample = L.sub;
     Counters cnt = {};
     const bool full_sort = A.full_sort != 0;
-    bool alive = present && traced && sample < A.samples;
+    bool alive = L.present && traced && sample < A.samples;
     if (alive) {
-        const float4 r1 = A.points[2 * (size_t)point + 1];
+        const float4 r1 = A.in[2 * (size_t)L.item + 1];
         d = gather_direction<DIR>(key, A.seed, (uint32_t)sample, rtm::mk(r1.x, r1.y, r1.z));
     }
 
@@ -88,18 +74,8 @@ __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, Visibility
             const float hit_t = any_hit<H>(S, A.intersect_mode, o, d, t_bound, stk);
             const bool open = !(hit_t < INF);                           // (compared after the merge: the per-lane walk records why)
             if constexpr (MODE == RT_VIS_SH9) {
-                // the real SH basis of bands 0..2 on the drawn direction, every product its own rounding (include/rt.h)
-                const float x = d.x, y = d.y, z = d.z;
                 float Y[9];
-                Y[0] = 0.28209479f;
-                Y[1] = 0.48860251f * y;
-                Y[2] = 0.48860251f * z;
-                Y[3] = 0.48860251f * x;
-                Y[4] = 1.09254843f * (x * y);
-                Y[5] = 1.09254843f * (y * z);
-                Y[6] = 0.31539157f * (3.0f * (z * z) - 1.0f);
-                Y[7] = 1.09254843f * (x * z);
-                Y[8] = 0.54627421f * (x * x - y * y);
+                sh9_basis(d, Y);
 #pragma unroll
                 for (int k = 0; k < 9; ++k) total[k] = total[k] + (open ? Y[k] : 0.0f);
                 total[9] = total[9] + (open ? 1.0f : 0.0f);
@@ -110,26 +86,22 @@ __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, Visibility
                 total[3] = total[3] + (open ? 1.0f : 0.0f);
             }
         }
-        sample += nsub;
+        sample += L.nsub;
         if (sample >= A.samples) alive = false;
         else {
             // the next sample starts at the point again, along a direction of its own
-            const float4 r0 = A.points[2 * (size_t)point], r1 = A.points[2 * (size_t)point + 1];
+            const float4 r0 = A.in[2 * (size_t)L.item], r1 = A.in[2 * (size_t)L.item + 1];
             o = rtm::mk(r0.x, r0.y, r0.z);
             t_bound = r0.w;
             d = gather_direction<DIR>(key, A.seed, (uint32_t)sample, rtm::mk(r1.x, r1.y, r1.z));
         }
     }
 
-    // the estimator's tree: (k, k + 1) for even k, then (k, k + 2) for k = 0 mod 4, ...
-    for (int off = 1; off < nsub; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < NC; ++k) total[k] = total[k] + __shfl_xor(total[k], off, 64);
-    }
-    if (present && sub == 0) {
+    tree_sum<NC>(total, L.nsub);
+    if (L.stores()) {
         const float nf = (float)A.samples;
         if constexpr (MODE == RT_VIS_SH9) {
-            float4* out = A.out + 3 * (size_t)point;
+            float4* out = A.out + 3 * (size_t)L.item;
             float c[12];
 #pragma unroll
             for (int k = 0; k < 9; ++k) c[k] = (total[k] / nf) * 12.566371f;
@@ -138,9 +110,9 @@ __global__ __launch_bounds__(kBlock) void k_visibility(DeviceScene S, Visibility
             for (int k = 0; k < 3; ++k)
                 out[k] = traced ? make_float4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
         } else if constexpr (MODE == RT_VIS_DISTANCE) {
-            A.out[point] = traced ? make_float4(total[0] / nf, total[1] / nf, total[2] / nf, 1.0f) : make_float4(0.f, 0.f, 0.f, 0.f);
+            A.out[L.item] = traced ? make_float4(total[0] / nf, total[1] / nf, total[2] / nf, 1.0f) : make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
-            A.out[point] = traced ? make_float4(total[0] / nf, total[1] / nf, total[2] / nf, total[3] / nf) : make_float4(0.f, 0.f, 0.f, 0.f);
+            A.out[L.item] = traced ? make_float4(total[0] / nf, total[1] / nf, total[2] / nf, total[3] / nf) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 }
