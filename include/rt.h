@@ -257,6 +257,10 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *   "closest_all"     0 (default) or 1: with 1 the count those three calls report is the number of ALL candidates within the radius and the
  *                     search is bounded by the radius alone ("K-nearest queries").  Other values are refused with -2 and nothing changes.
  *                     Every other call ignores it.  At "closest_k" = 1 and "closest_all" = 0 the three calls are exactly what they were
+ *   "closest_box"     0 (default) or 1: with 1 rt_closest_points, rt_closest_points_device and rt_multi_closest_points read each input as an
+ *                     axis-aligned box (origin = centre, direction = half-extents) and answer for the candidates that touch it: see
+ *                     "box overlap queries" below.  Other values are refused with -2 and nothing changes.  Every other call ignores it;
+ *                     at 0 the three calls are exactly what they were
  *   "hits_slice"      rt_trace_hits: rays per launch and per staging slice, 1..4194304 (default 262144: at most 128 MiB of staged records
  *                     at maxHits = 8); the result never depends on it
  *   "sweep"           0 (default) = the ray queries trace rays; 1 = rt_trace_rays, rt_trace_rays_device, rt_multi_trace_rays, rt_occluded,
@@ -779,6 +783,57 @@ int rt_get_closest_info     (rt_ctx* ctx, rt_closest_info* out);
  *                 min("closest_slice", 4194304 / K): the staged results never exceed the 256 MiB of K = 1.
  *   counting      "closest_count" = 1 works in every form and fills rt_closest_info.lastNodeSteps / lastPrimTests.
  *   refusals      "closest_k" outside 1..8 and "closest_all" other than 0 or 1: -2 with a message; the option keeps its value.        */
+
+/* ---- box overlap queries: every surface that touches a box, nearest to its centre first, and how many there are -----------------------
+ * Unity's Physics.OverlapBox / CheckBox beside OverlapSphere: which surfaces pass through a trigger volume, a marquee cell, a placement
+ * footprint, one voxel of a grid (conservative voxelisation is this query with one box per cell).  A box is not a ball: the sphere around
+ * a thin box over-reports.  No new entry and no new record: option "closest_box" (0 or 1, default 0) of rt_set_option /
+ * rt_multi_set_option changes how rt_closest_points, rt_closest_points_device and rt_multi_closest_points read their input, and nothing
+ * else: every other call ignores it, and at 0 the three calls are exactly what they are without it — the same kernels, the same bytes.
+ * At 1 each input rt_ray is an axis-aligned box, and the call answers the K-nearest query of the box's centre RESTRICTED to the candidates
+ * that touch the box.  Everything is float32, every product and sum rounded on its own (no FMA); dot, cross, / and sqrtf as above.
+ *
+ *   input         origin = the centre c, direction = the half-extents h, tMax only a gate; _reserved is not read.  Searched when
+ *                 tMax > 0 (not NaN), every component of c and h is finite, and h.x, h.y, h.z >= 0; otherwise K miss records with count
+ *                 0, and nothing is read.  lo = c - h, hi = c + h, component-wise, as floats.  h = 0 is legal: a point box.
+ *   candidates    every uploaded sphere and every triangle rt_read_bvh_order lists, as for closest points.  intersectMode plays no part
+ *                 and no rt_params are needed.
+ *   sphere        (centre s, radius R, solid) per axis a: e_a = fmaxf(fmaxf(lo.a - s.a, s.a - hi.a), 0.0f);
+ *                 d2 = (e_x * e_x + e_y * e_y) + e_z * e_z; it touches when d2 <= R * R.
+ *   triangle      A, eAB, eAC the floats the closest-point query reads, B = A + eAB, C = A + eAC.  It touches when ALL of these hold
+ *                 (each is written so that a NaN makes it false):
+ *                   1 finite   fabsf of each of the nine coordinates of A, B, C is < 1e30f;
+ *                   2 bounds   per axis a: fminf(fminf(A.a, B.a), C.a) <= hi.a && fmaxf(fmaxf(A.a, B.a), C.a) >= lo.a;
+ *                   3 plane    v0 = A - c, v1 = B - c, v2 = C - c; n = cross(eAB, eAC); d = dot(n, v0);
+ *                              rr = (h.x * fabsf(n.x) + h.y * fabsf(n.y)) + h.z * fabsf(n.z); fabsf(d) <= rr;
+ *                   4 edges    for each edge f of f0 = eAB, f1 = eAC - eAB, f2 = eAC and each box axis, with j = 0, 1, 2:
+ *                                x: p_j = v_j.z * f.y - v_j.y * f.z, r = h.y * fabsf(f.z) + h.z * fabsf(f.y)
+ *                                y: p_j = v_j.x * f.z - v_j.z * f.x, r = h.x * fabsf(f.z) + h.z * fabsf(f.x)
+ *                                z: p_j = v_j.y * f.x - v_j.x * f.y, r = h.x * fabsf(f.y) + h.y * fabsf(f.x)
+ *                              (all three p_j are computed, none is assumed equal to another)
+ *                              fminf(fminf(p0, p1), p2) <= r && fmaxf(fmaxf(p0, p1), p2) >= -r.
+ *                 Touching counts: the sets are closed.
+ *   key, records  a touching candidate gets the key k and the rt_closest record of the closest-point query OF THE POINT c against it
+ *   order, count  (the sphere key and the seven-region triangle key of "closest-point queries", operation for operation).  It counts
+ *                 when it touches and k is not NaN; there is no radius.  k can be +inf (a large box far from a surface it still
+ *                 reaches: |c - q|^2 overflows): such a candidate counts and is listed like any other, after every finite key.  Order, the K records per box ("closest_k") and _reserved[0] are
+ *                 exactly the K-nearest queries': ascending (k, kind, primitive), miss records after min(total, K), the count in all K
+ *                 records min(total, K), or total with "closest_all" = 1.  Unlike the defaults, K = 1 with all = 0 writes the count too:
+ *                 0 or 1, CheckBox.  K = 1 with all = 1 is a voxel's count plus the nearest surface to the cell's centre.
+ *   the tree      plays no part: the same bits whatever the tree, the builder, the leaf size, the node form or the order of the visit.
+ *                 The walk skips a child only when its (f32 or f16) box is disjoint from [lo, hi] by exact comparison on some axis, or —
+ *                 without "closest_all" — when its squared lower bound from c exceeds max(kth * (1 + 2^-19), 2^-100), the K-nearest
+ *                 rule.  The first is safe because of condition 2: a leaf slot's box reaches at least 0.99 * 3e-5 * m beyond its
+ *                 triangles' uploaded coordinates (m the largest |coordinate|, the padding the BVH audit enforces), A + (B - A) differs
+ *                 from the uploaded B by at most about 2^-22 * m, so the bounds of (A, B, C) as formed above lie inside every box on the
+ *                 way down; condition 1 removes the coordinates that padding rule exempts.
+ *   limits        float32 decides near-misses: a triangle within about 1e-6 (relative to the coordinates) of touching may go either
+ *                 way.  The definition is what the checker restates (tests/overlap_oracle.c).
+ *   scene, state  the closest-point queries', unchanged: the origin-bound reduction runs on the centres (inputs with tMax > 0);
+ *   slicing       "closest_slice" (min("closest_slice", 4194304 / K) boxes per launch) and rt_multi are invisible, a batch cut anywhere
+ *   errors        into two calls gives the bits of one; "closest_count" = 1 fills rt_closest_info.lastNodeSteps / lastPrimTests (every
+ *                 sphere and every triangle tested against the box is one primitive test).
+ *   refusals      "closest_box" other than 0 or 1: -2 with a message; the option keeps its value.                                     */
 
 /* ---- multi-hit ray queries: the first K surfaces along a ray, in order -----------------------------------------------------------------
  * Beside closest hit (rt_trace_rays) and any hit (rt_occluded): EVERYTHING a ray passes through, nearest first — Unity's

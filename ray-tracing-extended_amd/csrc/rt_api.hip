@@ -37,6 +37,7 @@ const void* cam_stream_kernel(bool philox, bool compact, bool triangles);
 #include "rt_multihit.hpp"
 #include "rt_sweep.hpp"
 #include "rt_nearest.hpp"
+#include "rt_overlap.hpp"
 #include "rt_aov.hpp"
 #include "rt_denoise.hpp"
 #include "rt_temporal.hpp"
@@ -255,6 +256,7 @@ struct rt_ctx : ErrOwner {
     int opt_closest_slice = 1 << 22, opt_closest_count = 0;
     int opt_sweep = 0;              // 1: the ray queries answer for a ball (csrc/rt_sweep.hpp)
     int opt_closest_k = 1, opt_closest_all = 0;     // K-nearest queries: records per point, count every candidate (csrc/rt_nearest.hpp); 1 and 0: k_closest
+    int opt_closest_box = 0;                        // box overlap queries: 1 = each input is a box (centre, half-extents), k_overlap (csrc/rt_overlap.hpp)
     DevBuf<unsigned long long> d_closest_counts;
     bool closest_counts_pending = false;
     unsigned long long closest_counts[2]{};
@@ -1663,22 +1665,24 @@ int begin_closest(rt_ctx* c)
     c->closest_counts_pending = true;
     return 0;
 }
-// k_closest or k_nearest<node form, counting>
-template <bool COUNT> const void* pick_closest(const rt_ctx* c, bool nearest)
+// k_closest, k_nearest or k_overlap<node form, counting>
+template <bool COUNT> const void* pick_closest(const rt_ctx* c, bool nearest, bool box)
 {
-    return nearest ? pick_nodes(c, rtk::k_nearest<true, COUNT>, rtk::k_nearest<false, COUNT>)
+    return box     ? pick_nodes(c, rtk::k_overlap<true, COUNT>, rtk::k_overlap<false, COUNT>)
+         : nearest ? pick_nodes(c, rtk::k_nearest<true, COUNT>, rtk::k_nearest<false, COUNT>)
                    : pick_nodes(c, rtk::k_closest<true, COUNT>, rtk::k_closest<false, COUNT>);
 }
 hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
     // K-nearest queries: the same points and launch shape, K records each (csrc/rt_nearest.hpp); k_closest takes the Args' ClosestArgs part
-    const bool nearest = c->opt_closest_k != 1 || c->opt_closest_all;
+    // box overlap queries ("closest_box" = 1): each input is a box, whatever K and all are (csrc/rt_overlap.hpp)
+    const bool nearest = c->opt_closest_k != 1 || c->opt_closest_all, box = c->opt_closest_box != 0;
     rtk::NearestArgs A{};
     fill_head(c, s, A);
     A.out = static_cast<float4*>(s.out);
     A.counters = c->opt_closest_count ? c->d_closest_counts.p : nullptr;
     A.k = c->opt_closest_k; A.count_all = c->opt_closest_all;
-    return launch_slice(c, c->opt_closest_count ? pick_closest<true>(c, nearest) : pick_closest<false>(c, nearest), s, A);
+    return launch_slice(c, c->opt_closest_count ? pick_closest<true>(c, nearest, box) : pick_closest<false>(c, nearest, box), s, A);
 }
 // n * K rt_closest (4 float4 each), K = option "closest_k"; no params of either kind.  The points per launch are min("closest_slice",
 // 4194304 / K): the staged results never exceed the 256 MiB of K = 1
@@ -2417,6 +2421,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
     else if (!std::strcmp(name, "closest_k")) { if (value < 1 || value > RT_HITS_MAX) return fail(c, -2, "closest_k must be in [1,%d] (records per point)", RT_HITS_MAX); c->opt_closest_k = value; }
     else if (!std::strcmp(name, "closest_all")) { if (value != 0 && value != 1) return fail(c, -2, "closest_all must be 0 or 1"); c->opt_closest_all = value; }
+    else if (!std::strcmp(name, "closest_box")) { if (value != 0 && value != 1) return fail(c, -2, "closest_box must be 0 or 1"); c->opt_closest_box = value; }
     else if (!std::strcmp(name, "sweep")) { if (value != 0 && value != 1) return fail(c, -2, "sweep must be 0 or 1"); c->opt_sweep = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }

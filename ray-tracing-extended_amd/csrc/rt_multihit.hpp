@@ -48,13 +48,17 @@ struct HitList {
         return b;
     }
     __device__ __forceinline__ float kth(int K) const { return pick(K, d0, d1, d2, d3, d4, d5, d6, d7); }
-    // the candidate goes down the list: it takes the first slot whose key is larger and carries that slot's entry on
+    // the candidate goes down the list: it takes the first slot whose key is larger and carries that slot's entry on.
+    // INF_KEYS: the caller may offer a key of +inf (k_overlap: no radius bounds its keys), which ties with an EMPTY slot (+inf, kNone);
+    // kNone has kTriBit set, so the tie read must be kept away from it — order[kNone >> 1] lies far outside the array.  The other
+    // kernels offer finite keys only (dst < tMax, k < R * R) and keep the test they had.
+    template <bool INF_KEYS = false>
     __device__ __forceinline__ void insert(float cd, uint32_t ci, const uint32_t* __restrict__ order)
     {
 #define RT_X(J)                                                                                                          \
         {                                                                                                                \
             uint32_t ka_ = ci, kb_ = i##J;                                                                               \
-            if (cd == d##J && ci != kNone && (ci & i##J & kTriBit)) {           /* two triangles at one dst: rare */      \
+            if (cd == d##J && ci != kNone && (!INF_KEYS || i##J != kNone) && (ci & i##J & kTriBit)) {   /* two triangles at one dst: rare */ \
                 ka_ = order[(ci & ~kTriBit) >> 1]; kb_ = order[(i##J & ~kTriBit) >> 1];                                  \
             }                                                                                                            \
             const bool lt_ = cd < d##J || (cd == d##J && ka_ < kb_);                                                     \
