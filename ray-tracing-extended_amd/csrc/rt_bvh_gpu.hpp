@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "bvh.hpp"
+#include "rt_types.hpp"             // Buf, Workspace
 
 namespace rtgb {
 
@@ -659,40 +660,7 @@ __global__ __launch_bounds__(256) void k_internal_area(const rtbvh::Node4* __res
     if ((threadIdx.x & 63) == 0) atomicAdd(out, s);
 }
 
-// ---- host driver ------------------------------------------------------------------------------------------------------------------
-template <class T> struct Buf {
-    T* p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = std::max<size_t>(n, 1);
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-struct Workspace {
-    Buf<float> top_boxes; Buf<int32_t> top_pairs;       // the host-built top of the tree (boxes out, nodes back)
-    std::vector<float> h_boxes, h_top_boxes; std::vector<int32_t> h_pairs;
-    Buf<uint64_t> keys0, keys1;
-    Buf<uint32_t> ids0, ids1, c0, c1, tmp, block_count, block_offset, ctr;
-    Buf<unsigned char> sort_tmp;
-    Buf<float4> bmin, bmax;
-    Buf<int2> child;
-    Buf<uint2> f0, f1;
-    Buf<uint32_t> t0, t1;                               // collapse: first triangle position of each frontier entry
-    Buf<int> need;
-    Buf<float> area;
-    void release()
-    {
-        keys0.release(); keys1.release(); ids0.release(); ids1.release(); c0.release(); c1.release(); tmp.release(); block_count.release();
-        block_offset.release(); ctr.release(); sort_tmp.release(); bmin.release(); bmax.release(); child.release(); f0.release(); f1.release();
-        need.release(); area.release(); top_boxes.release(); top_pairs.release(); t0.release(); t1.release();
-    }
-};
-
+// ---- host driver (its scratch, Buf and Workspace: rt_types.hpp) -----------------------------------------------------------------------
 struct Result {
     uint32_t n_nodes = 0;
     int max_stack = 0, rounds = 0, levels = 0;

@@ -14,12 +14,11 @@
 // All are streaming kernels: 240 B of HBM traffic per triangle end to end.
 #pragma once
 #include "rt_kernels.hpp"
+#include "rt_types.hpp"             // MeshXf
 
 namespace rtg {
 
 using rtm::v3;
-
-struct MeshXf { float px, py, pz, qx, qy, qz, qw, sx, sy, sz; };            // rt_mesh_transform
 
 // UnityEngine Quaternion * Vector3 (same operation order as host.py quat_rotate)
 __device__ __forceinline__ v3 quat_rotate(const MeshXf& t, v3 p)

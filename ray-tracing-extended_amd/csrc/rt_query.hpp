@@ -3,7 +3,7 @@
 //
 // One ray per lane, 256-thread blocks, one launch per batch (no persistent loop: every ray is one query).  The traversal stack is the
 // renderer's: the first stack_cap entries per lane in LDS (stack[entry][lane]), deeper ones in the global overflow area, sized by the
-// rule k_trace uses (rt_api.hip tile_stack_cap).
+// rule k_trace uses (rt_api.hip tile_stack_cap, plan_lane_stack).
 //   ANY = false   closest hit: closest_hit with best.t starting at the ray's tMax, mapped to the rt_hit record with the expressions
 //                 render_pixel uses for hitPoint, normal and the chunk; the BVH-order triangle goes back to the uploaded one through the
 //                 build's order map and, for local meshes, to its mesh.

@@ -17,7 +17,7 @@
 
 namespace rtk {
 
-// What the three kernels' Args have under one name each (rt_api.hip fill_sampled, launch_slice).  The head ends at 32 bytes: with
+// What the three kernels' Args have under one name each (rt_queries.hip fill_sampled, launch_slice).  The head ends at 32 bytes: with
 // sample_lanes_log2 in it, it would be padded to 40 and every later argument would move (rt_query.hpp, QueryArgs, records what a moved
 // argument cost), so each Args goes on with sample_lanes_log2 and the stack fields itself, at the offsets its kernel was measured with.
 struct SampledHead {

@@ -20,6 +20,7 @@
 // tie-break), so the image is bit-identical to k_trace and to the oracle.
 #pragma once
 #include "rt_kernels.hpp"
+#include "rt_types.hpp"             // CamRecord
 
 namespace rtk {
 
@@ -57,14 +58,7 @@ static_assert(alignof(StreamArgs) <= 8, "kernarg layout = struct layout");
 static_assert(offsetof(StreamKernArgs, F) == ((sizeof(DeviceScene) + 7) & ~size_t(7))
               && offsetof(StreamKernArgs, A) == ((offsetof(StreamKernArgs, F) + sizeof(FrameArgs) + 7) & ~size_t(7)), "kernarg layout = struct layout");
 
-// k_cam_stream (rt_render_params): the camera of every frame of a launch, indexed by the frame's offset in the launch.  The camera fields
-// of rt_params (viewParams, camLocalToWorld, worldSpaceCameraPos) in the order the camera block reads them; the last row of the matrix is
-// never read.  F.p still carries every other uniform, which all frames of the launch share.
-struct CamRecord {
-    float4 view;                // viewParams, -
-    float4 m0, m1, m2;          // rows 0..2 of camLocalToWorld
-    float4 pos;                 // worldSpaceCameraPos, -
-};
+// k_cam_stream (rt_render_params): the camera of every frame of a launch is a CamRecord (rt_types.hpp)
 struct StreamCamKernArgs { DeviceScene S; FrameArgs F; StreamArgs A; const CamRecord* cams; };     // k_cam_stream's argument segment
 static_assert(offsetof(StreamCamKernArgs, A) == offsetof(StreamKernArgs, A)
               && offsetof(StreamCamKernArgs, cams) == ((offsetof(StreamCamKernArgs, A) + sizeof(StreamArgs) + 7) & ~size_t(7)), "kernarg layout = struct layout");

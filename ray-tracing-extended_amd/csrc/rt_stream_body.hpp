@@ -59,7 +59,7 @@
     uint32_t pxy = kNoPixel;            // current pixel: x | local row << 16 (the host keeps k_stream to targets of at most 65535 x 65535); kNoPixel: none
     uint32_t rng = 0u;                  // RT_RNG_PCG: the reference's stream, a serial chain through the pixel's samples and bounces.  RT_RNG_PHILOX keeps
                                         // no generator state at all: a draw is a function of (pixel, frame, sample, bounce) — rtm::PhiloxScope
-    int sample = 0;                     // sample | bounce << 16 in one register (k_stream takes at most 65000 samples and 32000 bounces, rt_api.hip plan_launch:
+    int sample = 0;                     // sample | bounce << 16 in one register (k_stream takes at most 65000 samples and 32000 bounces, rt_render.hip plan_launch:
                                         // the signed shift stays positive)
     v3 total = rtm::mk(0.f, 0.f, 0.f), light = total, rayColour = total, o = total, d = total;
     RaySlabT<H> slab = make_slab<H>(rtm::mk(0.f, 0.f, 0.f), rtm::mk(1.f, 1.f, 1.f));

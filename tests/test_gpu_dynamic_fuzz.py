@@ -101,7 +101,7 @@ def check_counters(s, before, mid, after, device_bvh, what):
 
 
 def lists_eligible(params, kernel, st):
-    """rt_api.hip ensure_primary_lists: k_stream (kernel 1, or the counter-based mode under either), a fixed camera origin, a tree"""
+    """rt_render.hip ensure_primary_lists: k_stream (kernel 1, or the counter-based mode under either), a fixed camera origin, a tree"""
     return (kernel == 1 or int(params["rngMode"]) == 1) and float(params["defocusStrength"]) == 0.0 and st["numBvhNodes"] > 0 and st["bvhMaxStack"] <= 160
 
 

@@ -75,7 +75,7 @@ def test_axis_aligned_rays_zero_direction_components(rtx, oracle, tracer):
 
 def test_fixed_camera_origin_shortcut_and_the_cases_it_must_not_take(rtx, oracle, tracer):
     """defocusStrength = +-0 lets camera_ray take the camera position as the ray origin without the jitter arithmetic
-    (pos + (+-0) = pos; rt_api.hip camera_origin_is_fixed).  A camera coordinate of -0 is the one value that arithmetic
+    (pos + (+-0) = pos; rt_render.hip camera_origin_is_fixed).  A camera coordinate of -0 is the one value that arithmetic
     changes (-0 + +0 = +0), so such a camera has to stay on the general path; a tiny non-zero defocus as well."""
     m = rtx.scenes.mesh_test_scene(48, 30)
     m.numRaysPerPixel, m.maxBounceCount = 3, 3

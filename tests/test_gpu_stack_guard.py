@@ -7,7 +7,7 @@ forms many times), with and without the camera rays' candidate lists (their set-
 image bit for bit with a render whose whole stack is in LDS and with the oracle.  Sample and bounce counters share a register: the
 largest counts the host hands to k_stream are rendered against the oracle.  A CPU test reads the registers, scratch and occupancy of
 every non-counting instantiation from the code object (tools/kernel_resources.py).  rt_stats.lastKernel says which kernel ran; nothing
-in rt_stats says whether a launch had a global stack part, so the no-spill case rests on the host's rule (rt_api.hip plan_launch: a
+in rt_stats says whether a launch had a global stack part, so the no-spill case rests on the host's rule (rt_render.hip plan_launch: a
 global part exactly when bvhMaxStack + 3 exceeds the LDS part) and the statistic it reads."""
 import os
 import sys
@@ -88,7 +88,7 @@ def test_the_scene_is_deep_and_the_plain_path_alone_renders_it(deep):
     st = deep["stats"]
     assert 1800 <= st["numTriangles"] <= 2300, st["numTriangles"]
     print(f"deep scene: {st['numTriangles']} triangles, bvhMaxStack {st['bvhMaxStack']}")
-    assert st["bvhMaxStack"] + 3 <= FULL_LDS                 # rt_api.hip plan_launch: a global stack only when the worst case + 3 exceeds the LDS part
+    assert st["bvhMaxStack"] + 3 <= FULL_LDS                 # rt_render.hip plan_launch: a global stack only when the worst case + 3 exceeds the LDS part
     assert st["bvhMaxStack"] + 3 >= 21 + 6                   # ... and far beyond the product's 21 entries
     assert_bitwise(crop(deep["last"]), deep["want_last"], "whole stack in LDS vs oracle, last frame")
     assert_bitwise(crop(deep["acc"]), deep["want"], "whole stack in LDS vs oracle, accum")

@@ -3,11 +3,13 @@
 
     python tools/isa_diff.py <parent tree> <branch tree> [--keep DIR]      (e.g. a `git worktree add --detach` of the parent, and `.`)
 
-Each tree's rt_api.hip and rt_stream_kernels.hip are assembled as tools/static_valu.py assemble() does it, with the flags of THAT
-tree's __graft_entry__.  Per kernel (its label to its .Lfunc_end): comments dropped, the function's ordinal taken out of the block
-labels (.LBB<ordinal>_<n>: the ordinal is the function's position in the file), then the lines compared one by one.  VGPRs, SGPRs,
-scratch, occupancy and spills come from the summary lines the compiler prints after each kernel.  One line per kernel: identical, or
-the instruction delta with those figures.  Text is compared; no instruction is interpreted."""
+Each tree's .hip units — those its own __graft_entry__.hip_sources() lists — are assembled as tools/static_valu.py assemble() does
+it, with the flags of THAT tree's __graft_entry__, and the kernels are matched by mangled name across all units of a tree: a kernel may
+move between units from one tree to the other, and one that a tree holds twice is reported.  Per kernel (its label to its
+.Lfunc_end): comments dropped, the function's ordinal taken out of the block labels (.LBB<ordinal>_<n>: the ordinal is the function's
+position in the file), then the lines compared one by one.  VGPRs, SGPRs, scratch, occupancy and spills come from the summary lines
+the compiler prints after each kernel.  One line per kernel: identical, or the instruction delta with those figures.  Text is
+compared; no instruction is interpreted."""
 import argparse
 import os
 import re
@@ -16,18 +18,30 @@ import shutil
 import subprocess
 import tempfile
 
-UNITS = ("rt_api.hip", "rt_stream_kernels.hip")
 FIGURES = (("VGPRs", "NumVgprs"), ("SGPRs", "TotalNumSgprs"), ("scratch", "ScratchSize"), ("occupancy", "Occupancy"),
            ("SGPR spills", "SGPRSpillCount"), ("VGPR spills", "VGPRSpillCount"))       # (the spill counts only where the compiler prints them)
 
 
-def assemble(tree, unit, out):
+def tree_kernels(tree, side, work):
+    """mangled name -> kernels() entry over all .hip units of `tree`, and the names it holds more than once"""
     g = runpy.run_path(os.path.join(tree, "__graft_entry__.py"), run_name="isa_diff")
     flags = [f for f in g["HIPCC_FLAGS"] if f not in ("-shared", "-fPIC")]
-    extra = g["STREAM_TU_FLAGS"] if unit == "rt_stream_kernels.hip" else []
-    subprocess.check_call([shutil.which("hipcc") or "/opt/rocm/bin/hipcc", *flags, *extra, "--offload-device-only", "-S",
-                           os.path.join(tree, "ray-tracing-extended_amd", "csrc", unit), "-o", out], stderr=subprocess.DEVNULL)
-    return open(out).read()
+    units = [s for s in g["hip_sources"]()[0] if s.endswith(".hip")]
+    outs, procs = [], []
+    for src in units:                       # side by side, as build() compiles them
+        extra = g["STREAM_TU_FLAGS"] if src.endswith("rt_stream_kernels.hip") else []
+        outs.append(os.path.join(work, side + "_" + os.path.basename(src)[:-4] + ".s"))
+        procs.append(subprocess.Popen([shutil.which("hipcc") or "/opt/rocm/bin/hipcc", *flags, *extra, "--offload-device-only", "-S",
+                                       src, "-o", outs[-1]], stderr=subprocess.DEVNULL))
+    if any(p.wait() != 0 for p in procs):
+        raise SystemExit(f"hipcc failed on a unit of {tree}")
+    found, twice = {}, []
+    for src, out in zip(units, outs):
+        ks = kernels(open(out).read())
+        print(f"== {side} {os.path.basename(src)}: {len(ks)} kernels")
+        twice += [n for n in ks if n in found]
+        found.update(ks)
+    return found, twice
 
 
 def kernels(text):
@@ -70,29 +84,29 @@ def main():
     work = a.keep or tempfile.mkdtemp()
     os.makedirs(work, exist_ok=True)
     differing = 0
-    for unit in UNITS:
-        stem = unit.split(".")[0]
-        kp = kernels(assemble(a.parent, unit, os.path.join(work, "parent_" + stem + ".s")))
-        kb = kernels(assemble(a.branch, unit, os.path.join(work, "branch_" + stem + ".s")))
-        print(f"== {stem}.s: {len(kp)} kernels at the parent, {len(kb)} at the branch")
-        pretty = demangle(sorted(set(kp) | set(kb)))
-        library = [n for n in pretty if pretty[n].startswith("rocprim::")]
-        if library:             # the device BVH build's sort / scan templates, which the project does not write: one line
-            same = sum(1 for n in library if n in kp and n in kb and kp[n][1] == kb[n][1])
-            print(f"rocprim::* ({len(library)} instantiations of the library's templates): {same} identical, {len(library) - same} not")
-            differing += len(library) - same
-        for n in sorted(set(pretty) - set(library), key=lambda n: pretty[n]):
-            if n not in kp or n not in kb:
-                print(f"{pretty[n]}: only at the {'parent' if n in kp else 'branch'}"); differing += 1
-                continue
-            (ip, bp, fp), (ib, bb, fb) = kp[n], kb[n]
-            if bp == bb and fp == fb:
-                print(f"{pretty[n]}: identical ({len(ip)} instructions, {fp.get('VGPRs')} VGPRs)")
-                continue
-            differing += 1
-            moved = sum(1 for x, y in zip(ip, ib) if x != y) + abs(len(ip) - len(ib))
-            figs = ", ".join(f"{w} {fp.get(w)} -> {fb.get(w)}" for w, _ in FIGURES if w in fp or w in fb)
-            print(f"{pretty[n]}: DIFFERS instructions {len(ip)} -> {len(ib)} ({len(ib) - len(ip):+d}; {moved} positions differ), {figs}")
+    (kp, twice_p), (kb, twice_b) = tree_kernels(a.parent, "parent", work), tree_kernels(a.branch, "branch", work)
+    print(f"== {len(kp)} kernels at the parent, {len(kb)} at the branch")
+    pretty = demangle(sorted(set(kp) | set(kb)))
+    for side, twice in (("parent", twice_p), ("branch", twice_b)):
+        for n in twice:
+            print(f"{pretty[n]}: more than once at the {side}"); differing += 1
+    library = [n for n in pretty if pretty[n].startswith("rocprim::")]
+    if library:             # the device BVH build's sort / scan templates, which the project does not write: one line
+        same = sum(1 for n in library if n in kp and n in kb and kp[n][1] == kb[n][1])
+        print(f"rocprim::* ({len(library)} instantiations of the library's templates): {same} identical, {len(library) - same} not")
+        differing += len(library) - same
+    for n in sorted(set(pretty) - set(library), key=lambda n: pretty[n]):
+        if n not in kp or n not in kb:
+            print(f"{pretty[n]}: only at the {'parent' if n in kp else 'branch'}"); differing += 1
+            continue
+        (ip, bp, fp), (ib, bb, fb) = kp[n], kb[n]
+        if bp == bb and fp == fb:
+            print(f"{pretty[n]}: identical ({len(ip)} instructions, {fp.get('VGPRs')} VGPRs)")
+            continue
+        differing += 1
+        moved = sum(1 for x, y in zip(ip, ib) if x != y) + abs(len(ip) - len(ib))
+        figs = ", ".join(f"{w} {fp.get(w)} -> {fb.get(w)}" for w, _ in FIGURES if w in fp or w in fb)
+        print(f"{pretty[n]}: DIFFERS instructions {len(ip)} -> {len(ib)} ({len(ib) - len(ip):+d}; {moved} positions differ), {figs}")
     print(f"{differing} kernels differ")
     if not a.keep:
         shutil.rmtree(work)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of the kernels of one translation unit (hipcc -Rpass-analysis=kernel-resource-usage),
-with the flags of the product build.  usage: tools/kernel_resources.py [rt_stream_kernels.hip|rt_api.hip] [-D...]"""
+with the flags of the product build.  usage: tools/kernel_resources.py [unit] [-D...]
+unit: one of the .hip files __graft_entry__.hip_sources() lists (default rt_stream_kernels.hip), or `all` for every one of them"""
 import os
 import re
 import subprocess
@@ -36,6 +37,9 @@ def table(src, extra=()):
 if __name__ == "__main__":
     src = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else "rt_stream_kernels.hip"
     extra = [a for a in sys.argv[1:] if a.startswith("-")]
-    for r in table(src, extra):
+    units = [os.path.basename(s) for s in g.hip_sources()[0] if s.endswith(".hip")]
+    if src != "all" and src not in units:
+        raise SystemExit(f"{src}: not a unit of the library ({', '.join(units)})")
+    for r in [r for u in (units if src == "all" else [src]) for r in table(u, extra)]:
         print(f"{r['name'][:70]:70s} VGPR {r.get('VGPRs', -1):3d} SGPR {r.get('TotalSGPRs', -1):3d} scratch {r.get('ScratchSize', -1):4d} B "
               f"vspill {r.get('VGPRs Spill', -1):3d} sspill {r.get('SGPRs Spill', -1):3d} occ {r.get('Occupancy', -1)}")
