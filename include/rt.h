@@ -260,7 +260,11 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *   "closest_box"     0 (default) or 1: with 1 rt_closest_points, rt_closest_points_device and rt_multi_closest_points read each input as an
  *                     axis-aligned box (origin = centre, direction = half-extents) and answer for the candidates that touch it: see
  *                     "box overlap queries" below.  Other values are refused with -2 and nothing changes.  Every other call ignores it;
- *                     at 0 the three calls are exactly what they were
+ *                     at 0 the three calls are exactly what they were.  Refused with -2 at 1 while "closest_capsule" is 1
+ *   "closest_capsule" 0 (default) or 1: with 1 the same three calls read each input as a segment (origin = P0, direction = P1 - P0,
+ *                     tMax = the reach) and answer the K-nearest question for it: see "capsule overlap queries" below.  Other values, and 1
+ *                     while "closest_box" is 1, are refused with -2 and nothing changes.  Every other call ignores it; at 0 the three
+ *                     calls are exactly what they were
  *   "hits_slice"      rt_trace_hits: rays per launch and per staging slice, 1..4194304 (default 262144: at most 128 MiB of staged records
  *                     at maxHits = 8); the result never depends on it
  *   "sweep"           0 (default) = the ray queries trace rays; 1 = rt_trace_rays, rt_trace_rays_device, rt_multi_trace_rays, rt_occluded,
@@ -834,6 +838,76 @@ int rt_get_closest_info     (rt_ctx* ctx, rt_closest_info* out);
  *   errors        into two calls gives the bits of one; "closest_count" = 1 fills rt_closest_info.lastNodeSteps / lastPrimTests (every
  *                 sphere and every triangle tested against the box is one primitive test).
  *   refusals      "closest_box" other than 0 or 1: -2 with a message; the option keeps its value.                                     */
+
+/* ---- capsule overlap queries: every surface within reach of a segment, nearest first, and how many there are -------------------------
+ * Unity's Physics.OverlapCapsule / CheckCapsule, and the question underneath them: which surface is nearest to a SEGMENT, where on the
+ * surface, where on the segment, and how far.  Character controllers, ropes and cables, a limb's bone, depenetration of a capsule,
+ * clearance along a straight move.  The ball around a capsule over-reports by the capsule's length; a string of balls along its axis
+ * under-reports between them.  No new entry and no new record: option "closest_capsule" (0 or 1, default 0) of rt_set_option /
+ * rt_multi_set_option changes how rt_closest_points, rt_closest_points_device and rt_multi_closest_points read their input and what they
+ * write, and nothing else: every other call ignores it, and at 0 the three calls are exactly what they are without it — the same kernels,
+ * the same bytes.  At 1 each input rt_ray is a segment, and the call answers the K-nearest question for it.  Everything is float32, every
+ * product and sum rounded on its own (no FMA); dot, cross, / and sqrtf as in "closest-point queries".
+ * clamp01(x) below is x < 0 ? 0 : x > 1 ? 1 : x, two selects: a NaN stays a NaN.
+ *
+ *   input         origin = endpoint P0, direction = the axis d, P1 = P0 + d as floats, tMax = the reach R (the capsule's radius; +inf for
+ *                 unbounded); rt_ray._reserved is not read.  Searched when R > 0 (not NaN) and every component of P0, d and P1 is finite;
+ *                 otherwise K miss records with count 0, and nothing is read.  d = 0 is legal: a point.  dd = dot(d, d).
+ *   candidates    every uploaded sphere and every triangle rt_read_bvh_order lists, as for closest points.  intersectMode plays no part
+ *                 and no rt_params are needed.
+ *   triangle      A, eAB, eAC the floats the closest-point query reads.  The key is the minimum of up to six sub-candidates, each a
+ *                 (k, s, u, v), formed in this order; a later one replaces the running best only when its k is strictly smaller, and a
+ *                 NaN k never replaces anything.  When dd == 0 only the first is formed.
+ *                   1 endpoint P0   the closest-point query's seven-region test from P0, operation for operation: (k, u, v); s = 0.
+ *                   2 endpoint P1   the same from P1; s = 1.
+ *                   3 edge AB       E0 = A, e = eAB;  4 edge AC  E0 = A, e = eAC;  5 edge BC  E0 = A + eAB, e = eAC - eAB.  The clamped
+ *                                   closest pair of the segment and the edge E0 + e * t (Ericson, Real-Time Collision Detection 5.1.9):
+ *                                     r = P0 - E0;  ee = dot(e, e);  f = dot(e, r);  c = dot(d, r);  b = dot(d, e);
+ *                                     den = dd * ee - b * b;
+ *                                     s0 = den > 0 ? clamp01((b * f - c * ee) / den) : 0;
+ *                                     t0 = (b * s0 + f) / ee;
+ *                                     ee == 0 || t0 < 0:  t = 0, s = clamp01(-c / dd)          (a degenerate edge is its point E0)
+ *                                     else t0 > 1:        t = 1, s = clamp01((b - c) / dd)
+ *                                     else:               t = t0, s = s0                       (a NaN t0 ends here, in a NaN key)
+ *                                   (u, v) as the seven-region test reports its edge regions: AB (t, 0), AC (0, t), BC (1 - t, t).
+ *                   6 piercing      the two-sided RayTriangle of "multi-hit ray queries" from P0 along d, accepted when |det| >= 1e-6f,
+ *                                   t, u, v, w >= 0 and t <= 1: s = t and (u, v) that test's.
+ *                 Sub-candidates 3 to 6 form their key from their own (s, u, v): x = P0 + d * s; q = (A + eAB * u) + eAC * v; e = x - q;
+ *                 k = dot(e, e).  A piercing segment's k is therefore 0 whenever x and q coincide as floats — on exactly representable
+ *                 inputs — and otherwise the tiny square of their rounding, never a constant 0 that no computed pair of points backs:
+ *                 the search below prunes by distances between computed points, and a key without them could be pruned by no sound rule.
+ *   the record    point = q = (A + eAB * u) + eAC * v; dst = sqrtf(k); normal = rt_hit's shading normal at (u, v); u, v; side = the sign
+ *                 of dot(x - q, cross(eAB, eAC)) with x = P0 + d * s, 0 for a zero or NaN result, and 0 when the piercing sub-candidate
+ *                 is the one that stands.
+ *   sphere        (centre c, radius r, SOLID as in box overlap): t = clamp01(dot(c - P0, d) / dd), t = 0 when dd == 0; x = P0 + d * t;
+ *                 m = x - c; len = sqrtf(dot(m, m)); ds = len - r, then ds < 0 ? 0 : ds (fmaxf(len - r, 0) for every number; a NaN stays
+ *                 a NaN and never counts); k = ds * ds; s = t.  Record: dst = ds; point = c + m * (r / len); normal as for closest points;
+ *                 side = len >= r ? +1 : -1.  For len >= r these are the closest-point query's operations from x.
+ *   acceptance    a candidate counts when k < R * R, the product a float and the comparison strict; NaN never counts.
+ *   order, count  exactly the K-nearest queries': ascending (k, kind, primitive), miss records after min(total, K), _reserved[0] of all
+ *                 K records min(total, K), or total with "closest_all" = 1.  As for boxes, K = 1 with all = 0 writes the count too (0 or
+ *                 1: CheckCapsule).  _reserved[1] = the bits of the float s in [0, 1], the parameter of the segment's closest point; 0 in
+ *                 a miss record.  (rt_ray: origin, direction and tMax are read as above.  rt_closest._reserved: [0] the count, [1] s.)
+ *   a point       with d = 0 every record equals the K-nearest query's of the point P0 with the same R, K and all in every word but
+ *                 _reserved, whenever P0 lies on or outside every uploaded sphere (inside one the solid sphere's key is 0).
+ *   the tree      plays no part: the same bits whatever the tree, the builder, the leaf size, the node form or the order of the visit.
+ *                 The walk skips a child only when the squared distance between its (f32 or f16) box and the segment's own bounds
+ *                 [min(P0, P1), max(P0, P1)] — per axis max(lo - segmax, segmin - hi, 0), squared and summed as for closest points —
+ *                 exceeds max(kb * (1 + 2^-19), 2^-100), kb = R * R while fewer than K candidates are listed or with "closest_all",
+ *                 else the K-th key.  Rounding is monotone, so every x = P0 + d * s with s in [0, 1] lies inside those bounds exactly,
+ *                 and every q lies in the triangle's padded box as for closest points: the closest-point proof carries over.
+ *   limits        float32 decides: the piercing test refuses segments with |det| < 1e-6f (nearly parallel to the face, or a tiny face
+ *                 or axis), and those are answered through the edge and endpoint sub-candidates with a small positive k; a segment
+ *                 nearly parallel to an edge cancels in den, and s0 may then be any point of the overlap (the pair is still a pair of
+ *                 points of the segment and the edge, so k is never below the true distance by more than rounding, and can exceed it
+ *                 by the cancellation).  The definition is what the checker restates (tests/capsule_oracle.c).
+ *   scene, state  the closest-point queries', with one change: the origin-bound reduction takes the largest finite |coordinate| of P0
+ *   slicing       AND of P0 + d over the inputs with tMax > 0, on the host and on the device path.  "closest_slice"
+ *   errors        (min("closest_slice", 4194304 / K) segments per launch) and rt_multi are invisible, a batch cut anywhere into two calls
+ *                 gives the bits of one; "closest_count" = 1 fills rt_closest_info.lastNodeSteps / lastPrimTests (one sphere or one
+ *                 triangle examined is one primitive test, whatever its sub-candidates).
+ *   refusals      "closest_capsule" other than 0 or 1: -2 with a message; 1 while "closest_box" is 1, and "closest_box" = 1 while
+ *                 "closest_capsule" is 1: -2 with a message (an input is a box or a segment).  The option keeps its value.            */
 
 /* ---- multi-hit ray queries: the first K surfaces along a ray, in order -----------------------------------------------------------------
  * Beside closest hit (rt_trace_rays) and any hit (rt_occluded): EVERYTHING a ray passes through, nearest first — Unity's

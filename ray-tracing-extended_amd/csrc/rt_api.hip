@@ -18,7 +18,8 @@
 #include "rt_ctx.hpp"
 #include "rt_geom.hpp"
 #include "rt_bvh_gpu.hpp"
-#include "rt_overlap.hpp"           // (with rt_nearest.hpp, rt_closest.hpp and rt_query.hpp: trace_kernel .. cover_origins_device below)
+#include "rt_overlap.hpp"
+#include "rt_capsule.hpp"           // (with rt_nearest.hpp, rt_closest.hpp and rt_query.hpp: trace_kernel .. cover_origins_device below)
 
 using namespace rth;
 
@@ -456,12 +457,13 @@ int rth::cover_origins(rt_ctx* c, float G)
 
 // cover_origins for rays in device memory: the origin bound of the batch is measured on the device — one small kernel and a 4-byte
 // read-back (the call's one synchronisation)
-int rth::cover_origins_device(rt_ctx* c, const float4* rays, int n)
+int rth::cover_origins_device(rt_ctx* c, const float4* rays, int n, bool both_ends)
 {
     RT_HIP(c, c->d_q_bound.ensure(1));
     RT_HIP(c, hipMemsetAsync(c->d_q_bound.p, 0, sizeof(unsigned int), c->stream));
     const int grid = std::max(1, std::min((n + 255) / 256, 4 * std::max(1, c->n_cu)));
-    hipLaunchKernelGGL(rtk::k_query_origin_bound<0>, dim3(grid), dim3(256), 0, c->stream, rays, n, c->d_q_bound.p);
+    if (both_ends) hipLaunchKernelGGL(rtk::k_query_origin_bound<1>, dim3(grid), dim3(256), 0, c->stream, rays, n, c->d_q_bound.p);     // (a segment's two endpoints)
+    else hipLaunchKernelGGL(rtk::k_query_origin_bound<0>, dim3(grid), dim3(256), 0, c->stream, rays, n, c->d_q_bound.p);
     RT_HIP(c, hipGetLastError());
     unsigned int bits = 0;
     RT_HIP(c, hipMemcpyAsync(&bits, c->d_q_bound.p, sizeof bits, hipMemcpyDeviceToHost, c->stream));
@@ -479,15 +481,16 @@ const void* rth::trace_kernel(bool counting, bool flat, bool compact, bool spher
     return counting ? (const void*)rtk::k_trace<true, false, false> : (const void*)rtk::k_trace<false, false, false>;
 }
 
-// k_closest, k_nearest or k_overlap<node form, counting> (rt_queries.hip launch_closest)
-template <bool H, bool COUNT> static const void* closest_kernel_of(bool nearest, bool box)
+// k_closest, k_nearest, k_overlap or k_capsule<node form, counting> (rt_queries.hip launch_closest)
+template <bool H, bool COUNT> static const void* closest_kernel_of(bool nearest, bool box, bool capsule)
 {
+    if (capsule) return (const void*)rtk::k_capsule<H, COUNT>;
     return box ? (const void*)rtk::k_overlap<H, COUNT> : nearest ? (const void*)rtk::k_nearest<H, COUNT> : (const void*)rtk::k_closest<H, COUNT>;
 }
-const void* rth::closest_kernel(bool compact, bool counting, bool nearest, bool box)
+const void* rth::closest_kernel(bool compact, bool counting, bool nearest, bool box, bool capsule)
 {
-    if (compact) return counting ? closest_kernel_of<true, true>(nearest, box) : closest_kernel_of<true, false>(nearest, box);
-    return counting ? closest_kernel_of<false, true>(nearest, box) : closest_kernel_of<false, false>(nearest, box);
+    if (compact) return counting ? closest_kernel_of<true, true>(nearest, box, capsule) : closest_kernel_of<true, false>(nearest, box, capsule);
+    return counting ? closest_kernel_of<false, true>(nearest, box, capsule) : closest_kernel_of<false, false>(nearest, box, capsule);
 }
 
 // Give `dst` the scene `src` has built (world-space uploads): every device buffer is copied device to device — over xGMI when the
@@ -924,7 +927,16 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
     else if (!std::strcmp(name, "closest_count")) { if (value != 0 && value != 1) return fail(c, -2, "closest_count must be 0 or 1"); c->opt_closest_count = value; }
     else if (!std::strcmp(name, "closest_k")) { if (value < 1 || value > RT_HITS_MAX) return fail(c, -2, "closest_k must be in [1,%d] (records per point)", RT_HITS_MAX); c->opt_closest_k = value; }
     else if (!std::strcmp(name, "closest_all")) { if (value != 0 && value != 1) return fail(c, -2, "closest_all must be 0 or 1"); c->opt_closest_all = value; }
-    else if (!std::strcmp(name, "closest_box")) { if (value != 0 && value != 1) return fail(c, -2, "closest_box must be 0 or 1"); c->opt_closest_box = value; }
+    else if (!std::strcmp(name, "closest_box")) {
+        if (value != 0 && value != 1) return fail(c, -2, "closest_box must be 0 or 1");
+        if (value == 1 && c->opt_closest_capsule) return fail(c, -2, "closest_box cannot be 1 while closest_capsule is 1 (an input is a box or a segment)");
+        c->opt_closest_box = value;
+    }
+    else if (!std::strcmp(name, "closest_capsule")) {
+        if (value != 0 && value != 1) return fail(c, -2, "closest_capsule must be 0 or 1");
+        if (value == 1 && c->opt_closest_box) return fail(c, -2, "closest_capsule cannot be 1 while closest_box is 1 (an input is a box or a segment)");
+        c->opt_closest_capsule = value;
+    }
     else if (!std::strcmp(name, "sweep")) { if (value != 0 && value != 1) return fail(c, -2, "sweep must be 0 or 1"); c->opt_sweep = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }

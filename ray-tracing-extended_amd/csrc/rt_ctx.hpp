@@ -244,6 +244,7 @@ struct rt_ctx : rth::ErrOwner {
     int opt_sweep = 0;              // 1: the ray queries answer for a ball (csrc/rt_sweep.hpp)
     int opt_closest_k = 1, opt_closest_all = 0;     // K-nearest queries: records per point, count every candidate (csrc/rt_nearest.hpp); 1 and 0: k_closest
     int opt_closest_box = 0;                        // box overlap queries: 1 = each input is a box (centre, half-extents), k_overlap (csrc/rt_overlap.hpp)
+    int opt_closest_capsule = 0;                    // capsule overlap queries: 1 = each input is a segment (P0, d, reach), k_capsule (csrc/rt_capsule.hpp)
     DevBuf<unsigned long long> d_closest_counts;
     bool closest_counts_pending = false;
     unsigned long long closest_counts[2]{};
@@ -335,8 +336,8 @@ int read_srgb8(ErrOwner* o, rt_ctx* on, const float4* plane, size_t pixels, DevB
 // over a wave with __shfl_down.  HIP declares it static inline, so the compiler specialises it per unit from all its callers; only
 // beside the device builder's library templates (other widths) does it stay general and these kernels keep the code they always had.
 const void* trace_kernel(bool counting, bool flat, bool compact, bool spheres_only);       // k_trace
-const void* closest_kernel(bool compact, bool counting, bool nearest, bool box);           // k_closest, k_nearest or k_overlap
-int cover_origins_device(rt_ctx* c, const float4* rays, int n);                            // k_query_origin_bound
+const void* closest_kernel(bool compact, bool counting, bool nearest, bool box, bool capsule);     // k_closest, k_nearest, k_overlap or k_capsule
+int cover_origins_device(rt_ctx* c, const float4* rays, int n, bool both_ends);            // k_query_origin_bound
 
 // ---- rt_render.hip: frames, the queue, the feature planes ------------------------------------------------------------------------------
 enum class Variant { Fast, Counting, Flat };
@@ -378,6 +379,7 @@ struct QueryCall {
     rt_gather_params p;             // the sampled families' params, defaults filled in (mode 0 for radiance queries)
     int (*begin)(rt_ctx*);          // what the family does once per call, after the scene is current and before the first launch; may be null
     rt_hits_params h;               // multi-hit queries: their params, defaults filled in
+    bool both_ends = false;         // capsule overlap queries: origin + direction is a point of the query too (the origin bound covers it)
     bool sampled() const { return family < kClosest; }      // takes params and draws samples
     bool timed() const { return family != kRays; }          // has an info record with calls and kernel times
 };

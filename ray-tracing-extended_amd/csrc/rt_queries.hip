@@ -1,5 +1,5 @@
 // rt_queries.hip — the one path of the six query families: ray queries and sphere casts, radiance queries, gather queries, visibility
-// gathers, closest-point / K-nearest / box overlap queries and multi-hit ray queries; their entries and info getters.
+// gathers, closest-point / K-nearest / box and capsule overlap queries and multi-hit ray queries; their entries and info getters.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -12,7 +12,7 @@
 #include "rt_visibility.hpp"
 #include "rt_multihit.hpp"
 #include "rt_sweep.hpp"
-#include "rt_nearest.hpp"           // NearestArgs and rt_closest.hpp's walk; k_closest, k_nearest and k_overlap themselves: rt_api.hip closest_kernel
+#include "rt_nearest.hpp"           // NearestArgs and rt_closest.hpp's walk; k_closest, k_nearest, k_overlap and k_capsule themselves: rt_api.hip closest_kernel
 
 using namespace rth;
 
@@ -23,12 +23,15 @@ namespace {
 
 // ---- ray queries (rt_trace_rays / rt_occluded, csrc/rt_query.hpp) ---------------------------------------------------------------
 // Largest finite |origin coordinate| over the rays a query traces (tMax > 0)
-float query_origin_bound(const rt_ray* rays, int n)
+// both_ends (capsule overlap queries): an input is a segment, and its other endpoint origin + direction counts as well
+float query_origin_bound(const rt_ray* rays, int n, bool both_ends)
 {
     float m = 0.f;
     for (int i = 0; i < n; ++i) {
         if (!(rays[i].tMax > 0.0f)) continue;
         for (int a = 0; a < 3; ++a) { const float v = std::fabs(rays[i].origin[a]); if (v > m && v <= 3.4028235e38f) m = v; }
+        if (!both_ends) continue;
+        for (int a = 0; a < 3; ++a) { const float v = std::fabs(rays[i].origin[a] + rays[i].direction[a]); if (v > m && v <= 3.4028235e38f) m = v; }
     }
     return m;
 }
@@ -135,7 +138,7 @@ int launch_slices(rt_ctx* c, const QueryCall& q, const float4* in, void* out, in
 int query_host(rt_ctx* c, const QueryCall& q, const rt_ray* in, int n, void* out)
 {
     if (n == 0) return 0;
-    { int r = query_prepare(c, query_origin_bound(in, n)); if (r) return r; }
+    { int r = query_prepare(c, query_origin_bound(in, n, q.both_ends)); if (r) return r; }
     if (q.begin) { int r = q.begin(c); if (r) return r; }
     const size_t staged = (size_t)std::min(n, q.slice);
     RT_HIP(c, c->d_q_rays.ensure(2 * staged));
@@ -171,7 +174,7 @@ int query_device(rt_ctx* c, const QueryCall& q, const void* in, int n, void* out
     if ((reinterpret_cast<uintptr_t>(in) & 15u) || (q.out_aligned && (reinterpret_cast<uintptr_t>(out) & 15u)))
         return fail(c, -2, "%s: %s%s%s must be 16-byte aligned", q.what, q.in_word, q.out_aligned ? " and " : "", q.out_aligned ? q.out_word : "");
     { int r = prepare_scene(c); if (r) return r; }
-    { int r = cover_origins_device(c, static_cast<const float4*>(in), n); if (r) return r; }
+    { int r = cover_origins_device(c, static_cast<const float4*>(in), n, q.both_ends); if (r) return r; }
     if (q.begin) { int r = q.begin(c); if (r) return r; }
     { int r = launch_slices(c, q, static_cast<const float4*>(in), out, n, q.p.firstIndex); if (r) return r; }
     if (q.timed()) c->query_info[q.family].calls++;
@@ -267,13 +270,14 @@ hipError_t launch_closest(rt_ctx* c, const QueryCall&, const QuerySlice& s)
 {
     // K-nearest queries: the same points and launch shape, K records each (csrc/rt_nearest.hpp); k_closest takes the Args' ClosestArgs part
     // box overlap queries ("closest_box" = 1): each input is a box, whatever K and all are (csrc/rt_overlap.hpp)
+    // capsule overlap queries ("closest_capsule" = 1): each input is a segment, whatever K and all are (csrc/rt_capsule.hpp)
     const bool nearest = c->opt_closest_k != 1 || c->opt_closest_all, box = c->opt_closest_box != 0;
     rtk::NearestArgs A{};
     fill_head(c, s, A);
     A.out = static_cast<float4*>(s.out);
     A.counters = c->opt_closest_count ? c->d_closest_counts.p : nullptr;
     A.k = c->opt_closest_k; A.count_all = c->opt_closest_all;
-    return launch_slice(c, closest_kernel(c->opt_compact_nodes != 0, c->opt_closest_count != 0, nearest, box), s, A);     // (instantiated in rt_api.hip)
+    return launch_slice(c, closest_kernel(c->opt_compact_nodes != 0, c->opt_closest_count != 0, nearest, box, c->opt_closest_capsule != 0), s, A);     // (instantiated in rt_api.hip)
 }
 
 hipError_t launch_hits(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
@@ -334,6 +338,7 @@ int rth::closest_call(rt_ctx* c, const char* what, const void* points, int n, co
     const int K = c->opt_closest_k;
     q = QueryCall{ kClosest, what, "points", "out", std::min(c->opt_closest_slice, kQuerySlice / K), sizeof(rt_closest) * (size_t)K, true, nullptr, launch_closest };
     q.begin = begin_closest;
+    q.both_ends = c->opt_closest_capsule != 0;          // a segment's other endpoint needs the box padding too
     return query_pointers(c, q, points, n, out);
 }
 

@@ -163,7 +163,8 @@ __global__ __launch_bounds__(kBlock) void k_ray_query(DeviceScene S, QueryArgs Q
 
 // Largest finite |origin coordinate| over the rays a query traces (tMax > 0): the box padding must cover it (bvh.cpp pad_box).  Non-negative
 // floats order as their bit patterns, so the maximum is one integer atomic per wave.
-template <int = 0>
+// ENDS = 1 (capsule overlap queries, rt_capsule.hpp): an input is a segment, and its other endpoint origin + direction counts as well.
+template <int ENDS = 0>
 __global__ __launch_bounds__(256) void k_query_origin_bound(const float4* __restrict__ rays, int n, unsigned int* __restrict__ bound)
 {
     unsigned int m = 0;
@@ -173,6 +174,12 @@ __global__ __launch_bounds__(256) void k_query_origin_bound(const float4* __rest
         const float c[3] = { __builtin_fabsf(r0.x), __builtin_fabsf(r0.y), __builtin_fabsf(r0.z) };
         for (int a = 0; a < 3; ++a)
             if (c[a] <= 3.4028235e38f) m = max(m, __float_as_uint(c[a]));       // (finite only: NaN and inf fail the test)
+        if constexpr (ENDS != 0) {
+            const float4 r1 = rays[2 * i + 1];
+            const float e[3] = { __builtin_fabsf(r0.x + r1.x), __builtin_fabsf(r0.y + r1.y), __builtin_fabsf(r0.z + r1.z) };
+            for (int a = 0; a < 3; ++a)
+                if (e[a] <= 3.4028235e38f) m = max(m, __float_as_uint(e[a]));
+        }
     }
     for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned int)__shfl_down((int)m, off, 64));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(bound, m);
