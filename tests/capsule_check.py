@@ -1,12 +1,14 @@
 """The checker of the capsule overlap queries: tests/capsule_oracle.c bound with ctypes, and what the capsule tests share — the batch of
-segments every scene gets (module-level `batch_of`), the word-for-word comparison, the float64 twin by golden section.  Test
+segments every scene gets (module-level `batch_of`), the float64 twin by golden section.  The binding's one call, the word-for-word
+comparison, the counts and the scene's bounds are listed_check.py's, shared with nearest_check.py and overlap_check.py.  Test
 infrastructure only."""
 import ctypes
 
 import numpy as np
 
 from checker_build import compile_checker
-from nearest_check import COUNT_WORD, assert_same_records, different, words      # noqa: F401  (the K-nearest records' comparison fits as it is)
+from listed_check import (COUNT_WORD, _live, _p, assert_same_records, bind_listed, counts, different, oracle_listed,   # noqa: F401
+                          scene_bounds, words)
 
 _lib = None
 
@@ -24,18 +26,13 @@ def lib(directory=None):
     if _lib is None:
         so = compile_checker("capsule_oracle.c", directory)
         vp, ci = ctypes.c_void_p, ctypes.c_int
-        so.cp_capsule.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp]
-        so.cp_capsule.restype = ci
+        bind_listed(so.cp_capsule)
         so.cp_keys.argtypes = [vp, ci, vp, ci, vp, ci, ci, vp, vp]
         so.cp_keys.restype = ci
         so.cp_origin_bound.argtypes = [vp, ci, ci]
         so.cp_origin_bound.restype = ctypes.c_float
         _lib = so
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def segments_of(rtx, p0, p1=None, radius=np.inf, d=None):
@@ -50,19 +47,7 @@ def segments_of(rtx, p0, p1=None, radius=np.inf, d=None):
 
 def oracle_capsule(rtx, spheres, tris, infos, segs, k, count_all=0, chunk_mesh=None, variant=DEFINITION, totals=None, kth_ties=None):
     """CLOSEST (n, k): the brute-force answer for every segment.  totals / kth_ties as nearest_check.oracle_nearest's"""
-    s = np.ascontiguousarray(spheres, rtx.SPHERE)
-    t = np.ascontiguousarray(tris, rtx.TRIANGLE)
-    m = np.ascontiguousarray(infos, rtx.MESHINFO)
-    r = np.ascontiguousarray(segs, rtx.RAY).reshape(-1)
-    cm = None if chunk_mesh is None else np.ascontiguousarray(chunk_mesh, np.int32)
-    assert cm is None or len(cm) == len(m)
-    for a in (totals, kth_ties):
-        assert a is None or (a.dtype == np.int32 and a.shape == (len(r),) and a.flags.c_contiguous)
-    out = np.zeros((len(r), int(k)), rtx.CLOSEST)
-    rc = lib().cp_capsule(_p(s), len(s), _p(t), len(t), _p(m), len(m), _p(cm), _p(r), len(r), int(k), int(count_all), int(variant),
-                          _p(out), _p(totals), _p(kth_ties))
-    assert rc == 0, f"cp_capsule failed: {rc}"
-    return out
+    return oracle_listed(lib().cp_capsule, rtx, spheres, tris, infos, segs, k, count_all, chunk_mesh, variant, totals, kth_ties)
 
 
 def oracle_keys(rtx, spheres, tris, segs, variant=DEFINITION):
@@ -89,30 +74,12 @@ def searched(segs):
         return (segs["tMax"] > 0) & np.isfinite(segs["origin"]).all(1) & np.isfinite(segs["direction"]).all(1) & np.isfinite(p1).all(1)
 
 
-def counts(records):
-    return records["_reserved"][..., 0]
-
-
 def params(records):
     """the float s of every record, from _reserved[1]"""
     return np.array(records["_reserved"][..., 1], np.int32).view(np.float32)
 
 
 # ---- the batch ------------------------------------------------------------------------------------------------------------------------------
-def _live(m):
-    return np.concatenate([np.arange(i["firstTriangleIndex"], i["firstTriangleIndex"] + i["numTriangles"]) for i in m]) if len(m) else np.zeros(0, int)
-
-
-def scene_bounds(s, t, m):
-    live = _live(m)
-    parts = [np.asarray(t[k][live], np.float64).reshape(-1, 3) for k in ("posA", "posB", "posC")] if len(live) else []
-    if len(s):
-        c, r = np.asarray(s["position"], np.float64), np.asarray(s["radius"], np.float64)[:, None]
-        parts += [c - r, c + r]
-    allp = np.concatenate(parts)
-    return allp.min(0), allp.max(0)
-
-
 def batch_of(rtx, s, t, m, base, seed=23, per_kind=16):
     """the scene's own closest-point batch `base` (test_gpu_closest.batch_of) read as segments, and per kind up to `per_kind` segments built on
     triangles picked at random:

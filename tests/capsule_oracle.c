@@ -5,7 +5,9 @@
  * The checker of tests/test_gpu_capsule.py, itself pinned by tests/test_capsule_cpu.py (hand cases, nearest_oracle.c at d = 0, a float64
  * twin by golden section, and the mutants below).  TEST INFRASTRUCTURE: compiled by the tests with the oracle's own CFLAGS
  * (tests/checker_build.py: -ffp-contract=off, so every product and sum rounds on its own, as the header demands).  It includes nothing
- * but the public header.
+ * but the public header, through point_oracle.h: the vectors, the point's triangle key (sub-candidates 1 and 2), the miss record, a
+ * triangle's record, the order of the list and the list's driver (the argument check, the sort, the count rule, the K writes) live there,
+ * shared with the other point checkers.  Here: the segment's keys, its record, `searched`, the origin bound, and the loop.
  *
  * variant: 0 the definition;
  *          1 `<=` for `<` in the replacement rule of the sub-candidates;
@@ -14,21 +16,7 @@
  *          4 the origin bound from P0 only (cp_origin_bound);
  *          12 .. 16: sub-candidate 2 .. 6 (endpoint P1, edge AB, edge AC, edge BC, piercing) is dropped.
  */
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-#include "../include/rt.h"
-
-typedef struct { float x, y, z; } v3;
-static v3 V(float x, float y, float z) { v3 r = { x, y, z }; return r; }
-static v3 ld(const float* p) { return V(p[0], p[1], p[2]); }
-static v3 add(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
-static v3 sub(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
-static v3 scale(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
-static float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-static v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-static v3 normalize(v3 a) { const float len = sqrtf(dot(a, a)); return V(a.x / len, a.y / len, a.z / len); }
+#include "point_oracle.h"
 
 static float clamp01(float x)
 {
@@ -37,41 +25,6 @@ static float clamp01(float x)
 }
 
 typedef struct { v3 p0, d, p1; float R, dd; } seg;
-
-/* ---- the closest-point queries' triangle key from a point, operation for operation (closest_oracle.c, nearest_oracle.c) ---- */
-static float point_triangle(v3 p, v3 A, v3 eAB, v3 eAC, float* pu, float* pv)
-{
-    const v3 ap = sub(p, A);
-    const float d1 = dot(eAB, ap), d2 = dot(eAC, ap);
-    const v3 bp = sub(ap, eAB);
-    const float d3 = dot(eAB, bp), d4 = dot(eAC, bp);
-    const v3 cp = sub(ap, eAC);
-    const float d5 = dot(eAB, cp), d6 = dot(eAC, cp);
-    const float vc = d1 * d4 - d3 * d2;
-    const float vb = d5 * d2 - d1 * d6;
-    const float va = d3 * d6 - d5 * d4;
-    const float d43 = d4 - d3, d56 = d5 - d6;
-    float u, v;
-    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; }
-    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; }
-    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { u = d1 / (d1 - d3); v = 0.0f; }
-    else if (d6 >= 0.0f && d5 <= d6) { u = 0.0f; v = 1.0f; }
-    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { u = 0.0f; v = d2 / (d2 - d6); }
-    else if (va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f) { v = d43 / (d43 + d56); u = 1.0f - v; }
-    else {
-        const float den = (va + vb) + vc;
-        u = vb / den; v = vc / den;
-        u = u < 0.0f ? 0.0f : u;
-        u = u > 1.0f ? 1.0f : u;
-        v = v < 0.0f ? 0.0f : v;
-        const float room = 1.0f - u;
-        v = v > room ? room : v;
-    }
-    const v3 q = add(add(A, scale(eAB, u)), scale(eAC, v));
-    const v3 e = sub(p, q);
-    *pu = u; *pv = v;
-    return dot(e, e);
-}
 
 /* ---- the clamped closest pair of the segment and the edge E0 + e t (Ericson 5.1.9), the header's operation order ---- */
 static void segment_edge(const seg* g, v3 E0, v3 e, int variant, float* ps, float* pt)
@@ -121,12 +74,12 @@ static tkey segment_triangle(const seg* g, const rt_triangle* t, int variant)
 {
     const v3 A = ld(t->posA), eAB = sub(ld(t->posB), A), eAC = sub(ld(t->posC), A);
     tkey best;
-    best.k = point_triangle(g->p0, A, eAB, eAC, &best.u, &best.v);
+    best.k = triangle_key(g->p0, A, eAB, eAC, &best.u, &best.v);
     best.s = 0.0f; best.pierced = 0;
     if (g->dd == 0.0f) return best;
     if (variant != 12) {
         float u, v;
-        const float k = point_triangle(g->p1, A, eAB, eAC, &u, &v);
+        const float k = triangle_key(g->p1, A, eAB, eAC, &u, &v);
         if (replaces(k, best.k, variant)) { best.k = k; best.s = 1.0f; best.u = u; best.v = v; }
     }
     float s, e;
@@ -157,39 +110,19 @@ static float segment_sphere(const seg* g, const rt_sphere* sp, int variant, skey
     return ds * ds;
 }
 
-static void miss(rt_closest* o, int count)
+/* the capsule's own record: s in _reserved[1]; a SOLID sphere; the triangle's fields seen from x = P0 + d s (point_oracle.h's, operation
+ * for operation), and side 0 where the segment pierces it */
+static void record(rt_closest* o, const void* input, const cand* c, const list_scene* sc, int count)
 {
-    memset(o, 0, sizeof *o);
-    o->dst = INFINITY;
-    o->kind = RT_HIT_NONE;
-    o->primitive = o->chunk = o->mesh = -1;
-    o->_reserved[0] = count;
-}
-
-typedef struct { float k, s, u, v; int pierced, kind; uint32_t prim; int chunk; } cand;
-
-static int before(const cand* a, const cand* b)
-{
-    if (a->k != b->k) return a->k < b->k;
-    if (a->kind != b->kind) return a->kind < b->kind;
-    return a->prim < b->prim;
-}
-static int by_key(const void* a, const void* b)
-{
-    return before((const cand*)a, (const cand*)b) ? -1 : before((const cand*)b, (const cand*)a) ? 1 : 0;
-}
-
-static void record(rt_closest* o, const seg* g, const cand* c, const rt_sphere* spheres, const rt_triangle* tris, const int32_t* chunk_mesh,
-                   int count, int variant)
-{
+    const seg* g = (const seg*)input;
     miss(o, count);
     o->kind = c->kind;
     o->primitive = (int32_t)c->prim;
     memcpy(&o->_reserved[1], &c->s, sizeof(float));
     if (c->kind == RT_HIT_SPHERE) {
-        const rt_sphere* s = &spheres[c->prim];
+        const rt_sphere* s = &sc->spheres[c->prim];
         skey k;
-        segment_sphere(g, s, variant, &k);
+        segment_sphere(g, s, sc->variant, &k);
         const v3 ce = ld(s->position);
         const v3 q = add(ce, scale(k.m, s->radius / k.len));
         const v3 nn = normalize(sub(q, ce));
@@ -198,24 +131,10 @@ static void record(rt_closest* o, const seg* g, const cand* c, const rt_sphere* 
         o->normal[0] = nn.x; o->normal[1] = nn.y; o->normal[2] = nn.z;
         o->side = k.len >= s->radius ? 1 : -1;
     } else {
-        const rt_triangle* t = &tris[c->prim];
-        const v3 A = ld(t->posA), eAB = sub(ld(t->posB), A), eAC = sub(ld(t->posC), A);
-        const v3 x = add(g->p0, scale(g->d, c->s));
-        const v3 q = add(add(A, scale(eAB, c->u)), scale(eAC, c->v));
-        const v3 e = sub(x, q);
-        const float sd = dot(e, cross(eAB, eAC));
-        const float w = 1.0f - c->u - c->v;
-        const v3 nn = normalize(add(add(scale(ld(t->normalA), w), scale(ld(t->normalB), c->u)), scale(ld(t->normalC), c->v)));
-        o->dst = sqrtf(c->k);
-        o->point[0] = q.x; o->point[1] = q.y; o->point[2] = q.z;
-        o->normal[0] = nn.x; o->normal[1] = nn.y; o->normal[2] = nn.z;
-        o->chunk = c->chunk;
-        o->mesh = chunk_mesh ? chunk_mesh[c->chunk] : -1;
-        o->u = c->u; o->v = c->v;
-        o->side = c->pierced ? 0 : sd > 0.0f ? 1 : sd < 0.0f ? -1 : 0;
+        record_triangle(o, add(g->p0, scale(g->d, c->s)), c, sc->tris, sc->chunk_mesh);
+        if (c->pierced) o->side = 0;
     }
 }
-
 static int searched(const rt_ray* b, seg* g)
 {
     g->p0 = ld(b->origin); g->d = ld(b->direction); g->p1 = add(g->p0, g->d);
@@ -267,19 +186,15 @@ int cp_keys(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt, c
 int cp_capsule(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt, const rt_meshinfo* mi, int nm, const int32_t* chunk_mesh,
                const rt_ray* segs, int n, int K, int all, int variant, rt_closest* out, int32_t* totals, int32_t* kth_ties)
 {
-    if (K < 1 || K > RT_HITS_MAX || (all != 0 && all != 1)) return -4;
-    size_t addressed = 0;
-    for (int m = 0; m < nm; m++) {
-        if ((uint64_t)mi[m].firstTriangleIndex + mi[m].numTriangles > (uint64_t)nt) return -3;
-        addressed += mi[m].numTriangles;
-    }
+    size_t addressed;
+    const int bad = list_check(mi, nm, nt, K, all, &addressed);
+    if (bad) return bad;
+    const list_scene scene = { spheres, tris, chunk_mesh, variant };
     int failed = 0;
 #pragma omp parallel for schedule(dynamic, 16)
     for (int i = 0; i < n; i++) {
         rt_closest* o = &out[(size_t)i * K];
-        for (int j = 0; j < K; j++) miss(&o[j], 0);
-        if (totals) totals[i] = 0;
-        if (kth_ties) kth_ties[i] = 0;
+        list_clear(o, K, totals, kth_ties, i);
         seg g;
         if (!searched(&segs[i], &g)) continue;
         const float r2 = g.R * g.R;
@@ -290,7 +205,7 @@ int cp_capsule(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt
             skey sk;
             const float k = segment_sphere(&g, &spheres[s], variant, &sk);
             if (!(k < r2)) continue;
-            cand e = { k, sk.s, 0.0f, 0.0f, 0, RT_HIT_SPHERE, (uint32_t)s, -1 };
+            const cand e = { .k = k, .s = sk.s, .kind = RT_HIT_SPHERE, .prim = (uint32_t)s, .chunk = -1 };
             cd[total++] = e;
         }
         for (int m = 0; m < nm; m++)
@@ -298,18 +213,10 @@ int cp_capsule(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt
                 const uint32_t t = mi[m].firstTriangleIndex + j;
                 const tkey tk = segment_triangle(&g, &tris[t], variant);
                 if (!(tk.k < r2)) continue;
-                cand e = { tk.k, tk.s, tk.u, tk.v, tk.pierced, RT_HIT_TRIANGLE, t, m };
+                const cand e = { .k = tk.k, .s = tk.s, .u = tk.u, .v = tk.v, .pierced = tk.pierced, .kind = RT_HIT_TRIANGLE, .prim = t, .chunk = m };
                 cd[total++] = e;
             }
-        qsort(cd, (size_t)total, sizeof(cand), by_key);
-        const int listed = total < K ? total : K;
-        if (kth_ties && total > K && cd[K - 1].k == cd[K].k) kth_ties[i] = 1;
-        if (totals) totals[i] = total;
-        const int count = all ? total : listed;
-        for (int j = 0; j < K; j++) {
-            if (j < listed) record(&o[j], &g, &cd[j], spheres, tris, chunk_mesh, count, variant);
-            else miss(&o[j], count);
-        }
+        list_finish(o, cd, total, K, all, COUNT_RULE, record, &g, &scene, totals, kth_ties, i);
         free(cd);
     }
     return failed ? -5 : 0;

@@ -1,11 +1,12 @@
 """The checker of the K-nearest point queries: tests/nearest_oracle.c bound with ctypes, and what the K-nearest tests share — the batches
-whose points tie at the K-th key, the word-for-word comparison, the float64 twin's sorted distances.  Test infrastructure only."""
-import ctypes
-
+whose points tie at the K-th key, the float64 twin's sorted distances.  The binding's one call, the word-for-word comparison and the
+count word are listed_check.py's, shared with overlap_check.py and capsule_check.py.  Test infrastructure only."""
 import numpy as np
 
 import closest_check as cc
 from checker_build import compile_checker
+from listed_check import (COUNT_WORD, _live, assert_first_is_the_default, assert_same_records, bind_listed, different,   # noqa: F401
+                          oracle_listed, words)
 
 _lib = None
 
@@ -19,62 +20,15 @@ FORMS = ((2, 0), (8, 0), (3, 1), (1, 1))            # (K, all) of the GPU tests
 def lib(directory=None):
     global _lib
     if _lib is None:
-        so = compile_checker("nearest_oracle.c", directory)
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        so.np_nearest.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp]
-        so.np_nearest.restype = ci
-        _lib = so
+        _lib = compile_checker("nearest_oracle.c", directory)
+        bind_listed(_lib.np_nearest)
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def oracle_nearest(rtx, spheres, tris, infos, points, k, count_all=0, chunk_mesh=None, variant=DEFINITION, totals=None, kth_ties=None):
     """CLOSEST (n, k): the brute-force answer for every point.  totals / kth_ties: int32 (n,) arrays that receive, per point, the number of
     all candidates below R * R and whether the k-th and (k+1)-th keys of the full sort are bit-equal"""
-    s = np.ascontiguousarray(spheres, rtx.SPHERE)
-    t = np.ascontiguousarray(tris, rtx.TRIANGLE)
-    m = np.ascontiguousarray(infos, rtx.MESHINFO)
-    r = np.ascontiguousarray(points, rtx.RAY).reshape(-1)
-    cm = None if chunk_mesh is None else np.ascontiguousarray(chunk_mesh, np.int32)
-    assert cm is None or len(cm) == len(m)
-    for a in (totals, kth_ties):
-        assert a is None or (a.dtype == np.int32 and a.shape == (len(r),) and a.flags.c_contiguous)
-    out = np.zeros((len(r), int(k)), rtx.CLOSEST)
-    rc = lib().np_nearest(_p(s), len(s), _p(t), len(t), _p(m), len(m), _p(cm), _p(r), len(r), int(k), int(count_all), int(variant),
-                          _p(out), _p(totals), _p(kth_ties))
-    assert rc == 0, f"np_nearest failed: {rc}"
-    return out
-
-
-def words(rtx, records):
-    """the records as uint32 (..., 16)"""
-    a = np.ascontiguousarray(records, rtx.CLOSEST)
-    return a.view(np.uint32).reshape(a.shape + (16,))
-
-
-COUNT_WORD = 14                                      # _reserved[0] among a record's 16 words
-
-
-def assert_same_records(rtx, got, want, what):
-    """every word of every record (closest_check's comparison) and the shape (n, K)"""
-    got, want = np.ascontiguousarray(got, rtx.CLOSEST), np.ascontiguousarray(want, rtx.CLOSEST)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    cc.assert_same_records(rtx, got, want, what)
-
-
-def assert_first_is_the_default(rtx, got, default, what):
-    """record 0 of any form equals the default call's record in every word but _reserved[0]"""
-    g, d = words(rtx, np.ascontiguousarray(got, rtx.CLOSEST)[:, 0]).copy(), words(rtx, default).copy()
-    assert (d[:, COUNT_WORD:] == 0).all(), what
-    g[:, COUNT_WORD] = 0
-    cc.assert_same_records(rtx, g.view(rtx.CLOSEST).reshape(-1), d.view(rtx.CLOSEST).reshape(-1), what + ": record 0 against the default call")
-
-
-def different(rtx, a, b):
-    return not np.array_equal(words(rtx, a), words(rtx, b))
+    return oracle_listed(lib().np_nearest, rtx, spheres, tris, infos, points, k, count_all, chunk_mesh, variant, totals, kth_ties)
 
 
 def tie_plane(rtx, n=16, spacing=2.0):
@@ -106,7 +60,7 @@ def around_vertex(n, i, j):
 def vertex_tie_points(rtx, s, t, m, count=128, seed=11):
     """`count` points straight above (or on) vertices of the scene's triangles, at dyadic heights, with a radius that takes in more than
     eight candidates where the scene has them: the points whose K-th and (K+1)-th keys tie wherever several triangles share the vertex"""
-    live = np.concatenate([np.arange(i["firstTriangleIndex"], i["firstTriangleIndex"] + i["numTriangles"]) for i in m]) if len(m) else np.zeros(0, int)
+    live = _live(m)
     if not len(live):
         return cc.points_of(rtx, np.zeros((0, 3)))
     rng = np.random.default_rng(seed)

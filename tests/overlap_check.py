@@ -1,12 +1,14 @@
 """The checker of the box overlap queries: tests/overlap_oracle.c bound with ctypes, and what the overlap tests share — the batch of
-boxes every scene gets (module-level `batch_of`), the word-for-word comparison.  Test infrastructure only."""
+boxes every scene gets (module-level `batch_of`).  The binding's one call, the word-for-word comparison, the counts and the scene's
+bounds are listed_check.py's, shared with nearest_check.py and capsule_check.py.  Test infrastructure only."""
 import ctypes
 
 import numpy as np
 
 import closest_check as cc
 from checker_build import compile_checker
-from nearest_check import COUNT_WORD, assert_same_records, different, words      # noqa: F401  (the K-nearest records' comparison fits as it is)
+from listed_check import (COUNT_WORD, _live, _p, assert_same_records, bind_listed, counts, different, oracle_listed,   # noqa: F401
+                          scene_bounds, words)
 
 _lib = None
 
@@ -22,16 +24,11 @@ def lib(directory=None):
     if _lib is None:
         so = compile_checker("overlap_oracle.c", directory)
         vp, ci = ctypes.c_void_p, ctypes.c_int
-        so.ov_overlap.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp]
-        so.ov_overlap.restype = ci
+        bind_listed(so.ov_overlap)
         so.ov_touches.argtypes = [vp, ci, vp, ci, vp, ci, ci, vp]
         so.ov_touches.restype = ci
         _lib = so
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def boxes_of(rtx, centres, half_extents, gate=1.0):
@@ -47,19 +44,7 @@ def boxes_of(rtx, centres, half_extents, gate=1.0):
 def oracle_overlap(rtx, spheres, tris, infos, boxes, k, count_all=0, chunk_mesh=None, variant=DEFINITION, totals=None, kth_ties=None):
     """CLOSEST (n, k): the brute-force answer for every box.  totals / kth_ties: int32 (n,) arrays that receive, per box, the number of
     all candidates that count and whether the k-th and (k+1)-th keys of the full sort are bit-equal"""
-    s = np.ascontiguousarray(spheres, rtx.SPHERE)
-    t = np.ascontiguousarray(tris, rtx.TRIANGLE)
-    m = np.ascontiguousarray(infos, rtx.MESHINFO)
-    r = np.ascontiguousarray(boxes, rtx.RAY).reshape(-1)
-    cm = None if chunk_mesh is None else np.ascontiguousarray(chunk_mesh, np.int32)
-    assert cm is None or len(cm) == len(m)
-    for a in (totals, kth_ties):
-        assert a is None or (a.dtype == np.int32 and a.shape == (len(r),) and a.flags.c_contiguous)
-    out = np.zeros((len(r), int(k)), rtx.CLOSEST)
-    rc = lib().ov_overlap(_p(s), len(s), _p(t), len(t), _p(m), len(m), _p(cm), _p(r), len(r), int(k), int(count_all), int(variant),
-                          _p(out), _p(totals), _p(kth_ties))
-    assert rc == 0, f"ov_overlap failed: {rc}"
-    return out
+    return oracle_listed(lib().ov_overlap, rtx, spheres, tris, infos, boxes, k, count_all, chunk_mesh, variant, totals, kth_ties)
 
 
 def oracle_touches(rtx, spheres, tris, boxes, variant=DEFINITION):
@@ -72,26 +57,7 @@ def oracle_touches(rtx, spheres, tris, boxes, variant=DEFINITION):
     return out
 
 
-def counts(records):
-    return records["_reserved"][..., 0]
-
-
 # ---- the batch ------------------------------------------------------------------------------------------------------------------------------
-def _live(m):
-    return np.concatenate([np.arange(i["firstTriangleIndex"], i["firstTriangleIndex"] + i["numTriangles"]) for i in m]) if len(m) else np.zeros(0, int)
-
-
-def scene_bounds(s, t, m):
-    """(lo, hi) float64 over every addressed triangle corner and every sphere's box"""
-    live = _live(m)
-    parts = [np.asarray(t[k][live], np.float64).reshape(-1, 3) for k in ("posA", "posB", "posC")] if len(live) else []
-    if len(s):
-        c, r = np.asarray(s["position"], np.float64), np.asarray(s["radius"], np.float64)[:, None]
-        parts += [c - r, c + r]
-    allp = np.concatenate(parts)
-    return allp.min(0), allp.max(0)
-
-
 def batch_of(rtx, s, t, m, base, seed=17, per_kind=24):
     """the scene's own closest-point batch `base` (test_gpu_closest.batch_of) read as boxes of a half-extent comparable to the scene's
     triangles, and appended to it, per kind up to `per_kind` boxes built on triangles picked at random:

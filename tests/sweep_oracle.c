@@ -3,22 +3,10 @@
  * brute-force loop over every sphere and every triangle a chunk addresses: the checker of tests/test_gpu_sweep.py, itself pinned by
  * tests/test_sweep_cpu.py (analytic cases, a float64 twin).  TEST INFRASTRUCTURE: compiled by the tests with the oracle's own CFLAGS
  * (oracle/Makefile, tests/checker_build.py: -ffp-contract=off, so every product and sum below rounds on its own, as the header demands).
- * It includes nothing but the public header: the definition is the library's own.
+ * It includes nothing but the public header, through point_oracle.h, from which it takes the vectors and the closest-point queries'
+ * triangle key: the definition is the library's own.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-#include "../include/rt.h"
-
-typedef struct { float x, y, z; } v3;
-static v3 V(float x, float y, float z) { v3 r = { x, y, z }; return r; }
-static v3 ld(const float* p) { return V(p[0], p[1], p[2]); }
-static v3 add(v3 a, v3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
-static v3 sub(v3 a, v3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
-static v3 scale(v3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
-static float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-static v3 cross(v3 a, v3 b) { return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-static v3 normalize(v3 a) { const float len = sqrtf(dot(a, a)); return V(a.x / len, a.y / len, a.z / len); }
+#include "point_oracle.h"
 
 /* RaySphere (RayTracing.shader:120-146): 1 and the near root when it is accepted */
 static int ray_sphere(v3 o, v3 d, v3 centre, float radius, float* dst)
@@ -48,40 +36,6 @@ static int ray_triangle_sided(v3 o, v3 d, v3 A, v3 eAB, v3 eAC, v3 n, float* dst
     const float w = 1.0f - *u - *v;
     if (!(*dst >= 0.0f && *u >= 0.0f && *v >= 0.0f && w >= 0.0f)) return 0;
     return det >= 1e-6f ? 1 : det <= -1e-6f ? -1 : 0;
-}
-
-/* the closest-point queries' key of point p (tests/closest_oracle.c triangle_key, include/rt.h "closest-point queries") */
-static float triangle_key(v3 p, v3 A, v3 eAB, v3 eAC)
-{
-    const v3 ap = sub(p, A);
-    const float d1 = dot(eAB, ap), d2 = dot(eAC, ap);
-    const v3 bp = sub(ap, eAB);
-    const float d3 = dot(eAB, bp), d4 = dot(eAC, bp);
-    const v3 cp = sub(ap, eAC);
-    const float d5 = dot(eAB, cp), d6 = dot(eAC, cp);
-    const float vc = d1 * d4 - d3 * d2;
-    const float vb = d5 * d2 - d1 * d6;
-    const float va = d3 * d6 - d5 * d4;
-    const float d43 = d4 - d3, d56 = d5 - d6;
-    float u, v;
-    if (d1 <= 0.0f && d2 <= 0.0f) { u = 0.0f; v = 0.0f; }
-    else if (d3 >= 0.0f && d4 <= d3) { u = 1.0f; v = 0.0f; }
-    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { u = d1 / (d1 - d3); v = 0.0f; }
-    else if (d6 >= 0.0f && d5 <= d6) { u = 0.0f; v = 1.0f; }
-    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { u = 0.0f; v = d2 / (d2 - d6); }
-    else if (va <= 0.0f && d43 >= 0.0f && d56 >= 0.0f) { v = d43 / (d43 + d56); u = 1.0f - v; }
-    else {
-        const float den = (va + vb) + vc;
-        u = vb / den; v = vc / den;
-        u = u < 0.0f ? 0.0f : u;
-        u = u > 1.0f ? 1.0f : u;
-        v = v < 0.0f ? 0.0f : v;
-        const float room = 1.0f - u;
-        v = v > room ? room : v;
-    }
-    const v3 q = add(add(A, scale(eAB, u)), scale(eAC, v));
-    const v3 e = sub(p, q);
-    return dot(e, e);
 }
 
 /* One feature of a triangle: 1 when it answers, with its time, contact point and (u, v).  code 1..8 as in the header. */
@@ -123,7 +77,7 @@ static int feature(int code, v3 o, v3 d, float r, v3 A, v3 eAB, v3 eAC, float* t
     return ray_sphere(o, d, *point, r, t);
 }
 
-static void miss(rt_hit* o)
+static void no_hit(rt_hit* o)
 {
     memset(o, 0, sizeof *o);
     o->dst = INFINITY;
@@ -142,7 +96,7 @@ int sw_cast(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt, c
 #pragma omp parallel for schedule(dynamic, 16)
     for (int i = 0; i < n; i++) {
         rt_hit* h = &out[i];
-        miss(h);
+        no_hit(h);
         if (occluded) occluded[i] = 0;
         if (second) second[i] = INFINITY;
         const v3 o = ld(rays[i].origin), d = ld(rays[i].direction);
@@ -173,10 +127,11 @@ int sw_cast(const rt_sphere* spheres, int ns, const rt_triangle* tris, int nt, c
                 float tt = 0.0f, tu = 0.0f, tv = 0.0f;
                 v3 tp = V(0, 0, 0);
                 for (int code = 1; code <= 8; code++) {
-                    float t, u, v;
+                    float t, u, v, ku, kv;
                     v3 point;
                     if (!feature(code, o, d, r, A, eAB, eAC, &t, &point, &u, &v) || !(t < t_max)) continue;
-                    if (!(triangle_key(add(o, scale(d, t)), A, eAB, eAC) <= g2)) continue;      /* the guard */
+                    /* the guard: the closest-point queries' key of the centre at t (point_oracle.h, include/rt.h "closest-point queries") */
+                    if (!(triangle_key(add(o, scale(d, t)), A, eAB, eAC, &ku, &kv) <= g2)) continue;
                     if (!thave || t < tt) { thave = 1; tfeat = code; tt = t; tu = u; tv = v; tp = point; }
                 }
                 if (!thave) continue;

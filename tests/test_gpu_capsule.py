@@ -17,8 +17,9 @@ import capsule_check as kc
 import closest_check as cc
 import nearest_check as nc
 import overlap_check as oc
+from listed_gpu import ask, check_a_call_moves_no_other_state, check_forms, check_split_calls_and_counting, make_cases
 from ray_query_helpers import scene_of
-from test_gpu_closest import STATS_MAY_MOVE, batch_of, buffers_of, plane, tracer_of
+from test_gpu_closest import batch_of, buffers_of, plane, tracer_of
 from test_gpu_ray_query import local_tracer
 
 pytestmark = pytest.mark.gpu
@@ -58,36 +59,7 @@ def scene(rtx, name):
 @pytest.fixture(scope="module")
 def cases(rtx):
     """name -> (spheres, triangles, meshinfo, segments, {(K, all): the checker's answer}), each computed once"""
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            s, t, m = scene(rtx, name)
-            g = kc.batch_of(rtx, s, t, m, batch_of(rtx, s, t, m))
-            want = {f: kc.oracle_capsule(rtx, s, t, m, g, *f) for f in kc.FORMS}
-            for a in (g, *want.values()):
-                a.setflags(write=False)
-            cache[name] = (s, t, m, g, want)
-        return cache[name]
-    return get
-
-
-def ask(tr, g, k, count_all):
-    """closest_points with the three options set for the one call; (n, K) whatever K"""
-    tr.set_option("closest_capsule", 1)
-    tr.set_option("closest_k", k)
-    tr.set_option("closest_all", count_all)
-    try:
-        return tr.closest_points(g).reshape(len(g), k)
-    finally:
-        tr.set_option("closest_capsule", 0)
-        tr.set_option("closest_k", 1)
-        tr.set_option("closest_all", 0)
-
-
-def check_forms(rtx, tr, g, want, what, forms=kc.FORMS):
-    for f in forms:
-        kc.assert_same_records(rtx, ask(tr, g, *f), want[f], f"{what}, (K, all) = {f}")
+    return make_cases(rtx, "capsule", scene)
 
 
 @pytest.mark.parametrize("device_bvh", [0, 1])
@@ -96,7 +68,7 @@ def check_forms(rtx, tr, g, want, what, forms=kc.FORMS):
 def test_scenes_node_forms_and_builders(rtx, cases, name, compact_nodes, device_bvh):
     s, t, m, g, want = cases(name)
     with tracer_of(rtx, s, t, m, compact_nodes=compact_nodes, device_bvh=device_bvh, max_leaf=1 if name == "plane" else 2) as tr:
-        check_forms(rtx, tr, g, want, f"{name} compact_nodes {compact_nodes} device_bvh {device_bvh}")
+        check_forms(rtx, tr, "capsule", g, want, f"{name} compact_nodes {compact_nodes} device_bvh {device_bvh}")
         if name == "plane":
             assert tr.stats()["numBvhNodes"] > 5                # (several levels)
     found = kc.counts(want[3, 1])[:, 0]
@@ -114,7 +86,7 @@ def test_batch_sizes_at_the_wave_and_block_edges(rtx, cases, n):
     with tracer_of(rtx, s, t, m) as tr:
         for counting in (0, 1):
             tr.set_option("closest_count", counting)
-            check_forms(rtx, tr, g[first:first + n], {f: w[first:first + n] for f, w in want.items()}, f"{n} segments, closest_count {counting}",
+            check_forms(rtx, tr, "capsule", g[first:first + n], {f: w[first:first + n] for f, w in want.items()}, f"{n} segments, closest_count {counting}",
                         [(1, 0), (8, 0), (3, 1)])
 
 
@@ -123,14 +95,14 @@ def test_leaf_sizes(rtx, cases, max_leaf):
     for name in ("cube", "plane", "mixed"):
         s, t, m, g, want = cases(name)
         with tracer_of(rtx, s, t, m, max_leaf=max_leaf) as tr:
-            check_forms(rtx, tr, g, want, f"{name} max_leaf {max_leaf}", [(8, 0), (1, 1)])
+            check_forms(rtx, tr, "capsule", g, want, f"{name} max_leaf {max_leaf}", [(8, 0), (1, 1)])
 
 
 @pytest.mark.parametrize("compact_nodes", [0, 1])
 def test_small_lds_stack_spills_to_the_overflow_area(rtx, cases, compact_nodes):
     s, t, m, g, want = cases("mixed")
     with tracer_of(rtx, s, t, m, stream_stack=4, lds_stack=3, compact_nodes=compact_nodes, max_leaf=1) as tr:
-        check_forms(rtx, tr, g, want, f"lds_stack 3, compact_nodes {compact_nodes}", [(8, 0), (3, 1)])
+        check_forms(rtx, tr, "capsule", g, want, f"lds_stack 3, compact_nodes {compact_nodes}", [(8, 0), (3, 1)])
         assert tr.stats()["bvhMaxStack"] > 3                    # (the overflow area was in use)
 
 
@@ -140,7 +112,7 @@ def test_local_meshes_after_a_refit(rtx, device_bvh):
     with tr:
         g = kc.batch_of(rtx, s, world, infos, batch_of(rtx, s, world, infos, seed=5))
         for f in ((8, 0), (3, 1)):
-            got = ask(tr, g, *f)
+            got = ask(tr, "capsule", g, *f)
             kc.assert_same_records(rtx, got, kc.oracle_capsule(rtx, s, world, infos, g, *f, chunk_mesh=chunk_mesh), f"local meshes, device_bvh {device_bvh}, {f}")
         tri = got[got["kind"] == 2]
         assert len(tri) > 100 and (tri["mesh"] >= 0).all() and len(np.unique(tri["mesh"])) > 1
@@ -162,7 +134,7 @@ def test_scene_and_segments_far_from_the_origin(rtx, cases, name):
     assert (kc.counts(want[3, 1])[:, 0] > 0).sum() > 100
     for compact_nodes in (0, 1):
         with tracer_of(rtx, s2, t2, m2, compact_nodes=compact_nodes) as tr:
-            check_forms(rtx, tr, g2, want, f"{name} translated, compact_nodes {compact_nodes}", list(want))
+            check_forms(rtx, tr, "capsule", g2, want, f"{name} translated, compact_nodes {compact_nodes}", list(want))
 
 
 def test_the_origin_bound_sees_both_endpoints(rtx, cases):
@@ -182,41 +154,32 @@ def test_the_origin_bound_sees_both_endpoints(rtx, cases):
         tr.closest_points(far)                                  # as points: P0 alone
         assert tr.stats()["bvhRepads"] == before
         for f in ((8, 0), (3, 1)):
-            kc.assert_same_records(rtx, ask(tr, far, *f), kc.oracle_capsule(rtx, s, t, m, far, *f), f"P1 far away, {f}")
+            kc.assert_same_records(rtx, ask(tr, "capsule", far, *f), kc.oracle_capsule(rtx, s, t, m, far, *f), f"P1 far away, {f}")
         assert tr.stats()["bvhRepads"] == before + 1
-        ask(tr, far[:7], 2, 0)
+        ask(tr, "capsule", far[:7], 2, 0)
         assert tr.stats()["bvhRepads"] == before + 1
         # P0 and d finite, P0 + d = +inf: not searched
         over = kc.segments_of(rtx, [(3e38, 0, 0), (1, 1, 1)], d=[(3e38, 0, 0), (0, 0, 1)], radius=np.inf)
-        kc.assert_same_records(rtx, ask(tr, over, 2, 1), kc.oracle_capsule(rtx, s, t, m, over, 2, 1), "P1 overflows")
+        kc.assert_same_records(rtx, ask(tr, "capsule", over, 2, 1), kc.oracle_capsule(rtx, s, t, m, over, 2, 1), "P1 overflows")
 
 
 def test_slices_split_calls_and_counting(rtx, cases):
     s, t, m, g, want = cases("mixed")
     with tracer_of(rtx, s, t, m) as tr:
         tr.set_option("closest_slice", 1)
-        check_forms(rtx, tr, g[500:560], {f: w[500:560] for f, w in want.items()}, "closest_slice 1", [(2, 0), (3, 1)])
+        check_forms(rtx, tr, "capsule", g[500:560], {f: w[500:560] for f, w in want.items()}, "closest_slice 1", [(2, 0), (3, 1)])
         tr.set_option("closest_slice", 100)
-        check_forms(rtx, tr, g, want, "closest_slice 100", [(8, 0)])
-        tr.set_option("closest_slice", 1 << 22)
-        for cut in (1, 333):
-            for f in ((8, 0), (3, 1)):
-                kc.assert_same_records(rtx, np.concatenate([ask(tr, g[:cut], *f), ask(tr, g[cut:], *f)]), want[f], f"cut at {cut}, {f}")
-        assert tr.closest_info()["lastPrimTests"] == 0 and tr.closest_info()["lastNodeSteps"] == 0
+        check_forms(rtx, tr, "capsule", g, want, "closest_slice 100", [(8, 0)])
         # counts: one sphere or triangle examined is one test; never more than brute force, and exactly brute force with R = +inf and all = 1
-        tr.set_option("closest_count", 1)
         live = int(sum(i["numTriangles"] for i in m)) + len(s)
         searched = int(kc.searched(g).sum())
-        for f in kc.FORMS:
-            kc.assert_same_records(rtx, ask(tr, g, *f), want[f], f"the counting kernel, {f}")
-            info = tr.closest_info()
-            assert 0 < info["lastPrimTests"] <= searched * live and info["lastNodeSteps"] > 0, info
-        u = _unbounded(g)
-        kc.assert_same_records(rtx, ask(tr, u, 1, 1), kc.oracle_capsule(rtx, s, t, m, u, 1, 1), "unbounded, all")
-        assert tr.closest_info()["lastPrimTests"] == searched * live, (tr.closest_info(), searched, live)
-        tr.set_option("closest_count", 0)
-        check_forms(rtx, tr, g, want, "after the counting kernel", [(2, 0)])
-        assert tr.closest_info()["lastPrimTests"] == 0
+
+        def unbounded_is_brute_force():
+            u = _unbounded(g)
+            kc.assert_same_records(rtx, ask(tr, "capsule", u, 1, 1), kc.oracle_capsule(rtx, s, t, m, u, 1, 1), "unbounded, all")
+            assert tr.closest_info()["lastPrimTests"] == searched * live, (tr.closest_info(), searched, live)
+        check_split_calls_and_counting(rtx, "capsule", tr, g, want, lambda info: 0 < info["lastPrimTests"] <= searched * live and info["lastNodeSteps"] > 0,
+                                       unbounded_is_brute_force)
 
 
 def _unbounded(g):
@@ -229,14 +192,14 @@ def test_multi_tracer_gives_the_single_context_bits(rtx, cases):
     s, t, m, g, want = cases("mixed")
     with rtx.MultiTracer([0] * 3) as mt:
         mt.upload(spheres=s, triangles=t, meshinfo=m)
-        check_forms(rtx, mt, g, want, "three contexts")
-        kc.assert_same_records(rtx, ask(mt, g[:1], 8, 0), want[8, 0][:1], "fewer segments than contexts")
+        check_forms(rtx, mt, "capsule", g, want, "three contexts")
+        kc.assert_same_records(rtx, ask(mt, "capsule", g[:1], 8, 0), want[8, 0][:1], "fewer segments than contexts")
         cc.assert_same_records(rtx, mt.closest_points(g), cc.oracle_closest(rtx, s, t, m, g), "three contexts, the defaults")
 
 
 def test_device_entry_on_tensors_matches_the_checker():
-    """(in a fresh process that imports torch first: tests/capsule_torch_worker.py)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "capsule_torch_worker.py")], capture_output=True, text=True, timeout=300)
+    """(in a fresh process that imports torch first: tests/listed_torch_worker.py capsule)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "listed_torch_worker.py"), "capsule"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "capsule device entry ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
@@ -252,7 +215,7 @@ def test_a_point_segment_is_the_k_nearest_query(rtx, cases):
         q = q[outside]
         with tracer_of(rtx, s, t, m) as tr:
             for f in ((8, 0), (3, 1)):
-                got = kc.words(rtx, ask(tr, q, *f)).copy()
+                got = kc.words(rtx, ask(tr, "capsule", q, *f)).copy()
                 assert (got[..., kc.S_WORD] == 0).all()
                 tr.set_option("closest_k", f[0])
                 tr.set_option("closest_all", f[1])
@@ -314,7 +277,7 @@ def test_the_option_at_0_after_1_gives_todays_bytes(rtx, cases):
             return out
         before = others()
         cc.assert_same_records(rtx, np.frombuffer(before[0], rtx.CLOSEST), cc.oracle_closest(rtx, s, t, m, q), "before the option")
-        check_forms(rtx, tr, g, want, "in between")
+        check_forms(rtx, tr, "capsule", g, want, "in between")
         assert others() == before
         # every other call ignores the option
         hits, rays = tr.trace_hits(q[:64], 4), tr.trace_rays(q[:64])
@@ -323,37 +286,8 @@ def test_the_option_at_0_after_1_gives_todays_bytes(rtx, cases):
 
 
 def test_a_call_moves_no_other_state(rtx, cases):
-    mgr = scene_of(rtx, "mesh_test_scene")
-    params, s, t, m = mgr.build_buffers()
     _, _, _, g, want = cases("mixed")
-    with rtx.Tracer(0) as tb:
-        tb.set_params(params)
-        tb.upload(spheres=s, triangles=t, meshinfo=m)
-        tb.render(0, 2)
-        tb.render_aov(0, 2)
-        tb.denoise(iterations=2)
-        tb.temporal()
-        tb.visibility(g[:64], 4)
-        tb.trace_hits(g[:64], 4)
-
-        def state():
-            return {"accum": tb.read_accum(), "last": tb.read_last_frame(), "albedo": tb.read_aov(0), "normal_depth": tb.read_aov(1),
-                    "denoised": tb.read_denoised(), "temporal": tb.read_temporal(), "history": tb.read_temporal_history(),
-                    "aov_info": tb.aov_info(), "denoise_info": tb.denoise_info(), "temporal_info": tb.temporal_info(),
-                    "radiance_info": tb.radiance_info(), "gather_info": tb.gather_info(), "visibility_info": tb.visibility_info(),
-                    "hits_info": tb.hits_info(), "stats": tb.stats()}
-        before = state()
-        assert tb.closest_info()["calls"] == 0
-        check_forms(rtx, tb, g, want, "beside an image")
-        assert tb.closest_info()["calls"] == len(kc.FORMS)
-        after = state()
-        for k in ("accum", "last", "albedo", "normal_depth", "denoised", "temporal", "history"):
-            assert before[k].tobytes() == after[k].tobytes(), k
-        for k in ("aov_info", "denoise_info", "temporal_info", "radiance_info", "gather_info", "visibility_info", "hits_info"):
-            assert before[k] == after[k], k
-        for k, v in before["stats"].items():
-            if k not in STATS_MAY_MOVE:
-                assert np.array_equal(v, after["stats"][k]), k
+    check_a_call_moves_no_other_state(rtx, "capsule", g, want)
 
 
 def test_the_helpers_of_capsule_py(rtx, cases):
@@ -394,7 +328,7 @@ def test_the_segments_bounds_prune(rtx):
     for name, d in (("vertical", (0, 0, 2 * cell)), ("diagonal", (2 * cell, 2 * cell, 2 * cell))):
         g = kc.segments_of(rtx, p0, d=np.repeat(np.float32([d]), n, 0), radius=1.5 * cell)
         with tracer_of(rtx, s, t, m, closest_count=1) as tr:
-            kc.assert_same_records(rtx, ask(tr, g, 8, 0), kc.oracle_capsule(rtx, s, t, m, g, 8, 0), f"plane of 8192, {name}")
+            kc.assert_same_records(rtx, ask(tr, "capsule", g, 8, 0), kc.oracle_capsule(rtx, s, t, m, g, 8, 0), f"plane of 8192, {name}")
             info, nodes = tr.closest_info(), tr.stats()["numBvhNodes"]
             print(f"{name}: node steps {info['lastNodeSteps'] / n:.2f} prim tests {info['lastPrimTests'] / n:.2f} per capsule of {nodes} nodes, {len(t)} triangles")
             # a capsule of reach 1.5 cells whose bounds span 2 cells meets at most 6 x 6 cells = 72 triangles: under 1/32 of the tree

@@ -14,8 +14,9 @@ import pytest
 
 import closest_check as cc
 import nearest_check as nc
+from listed_gpu import ask, check_a_call_moves_no_other_state, check_forms, check_split_calls_and_counting, make_cases
 from ray_query_helpers import scene_of
-from test_gpu_closest import NAMES, STATS_MAY_MOVE, batch_of, buffers_of, plane, tracer_of
+from test_gpu_closest import NAMES, batch_of, buffers_of, plane, tracer_of
 from test_gpu_ray_query import local_tracer
 
 pytestmark = pytest.mark.gpu
@@ -26,34 +27,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 @pytest.fixture(scope="module")
 def cases(rtx):
     """name -> (spheres, triangles, meshinfo, points, {(K, all): the checker's answer}), each computed once"""
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            s, t, m = buffers_of(rtx, name)
-            p = nc.batch_of(rtx, s, t, m, batch_of(rtx, s, t, m))
-            want = {f: nc.oracle_nearest(rtx, s, t, m, p, *f) for f in nc.FORMS}
-            for a in (p, *want.values()):
-                a.setflags(write=False)
-            cache[name] = (s, t, m, p, want)
-        return cache[name]
-    return get
-
-
-def ask(tr, p, k, count_all):
-    """closest_points with the options set for the one call; (n, K) whatever K"""
-    tr.set_option("closest_k", k)
-    tr.set_option("closest_all", count_all)
-    try:
-        return tr.closest_points(p).reshape(len(p), k)
-    finally:
-        tr.set_option("closest_k", 1)
-        tr.set_option("closest_all", 0)
-
-
-def check_forms(rtx, tr, p, want, what, forms=nc.FORMS):
-    for f in forms:
-        nc.assert_same_records(rtx, ask(tr, p, *f), want[f], f"{what}, (K, all) = {f}")
+    return make_cases(rtx, "nearest", buffers_of)
 
 
 @pytest.mark.parametrize("device_bvh", [0, 1])
@@ -62,7 +36,7 @@ def check_forms(rtx, tr, p, want, what, forms=nc.FORMS):
 def test_scenes_node_forms_and_builders(rtx, cases, name, compact_nodes, device_bvh):
     s, t, m, p, want = cases(name)
     with tracer_of(rtx, s, t, m, compact_nodes=compact_nodes, device_bvh=device_bvh, max_leaf=1 if name == "plane" else 2) as tr:
-        check_forms(rtx, tr, p, want, f"{name} compact_nodes {compact_nodes} device_bvh {device_bvh}")
+        check_forms(rtx, tr, "nearest", p, want, f"{name} compact_nodes {compact_nodes} device_bvh {device_bvh}")
         if name == "plane":
             assert tr.stats()["numBvhNodes"] > 5                # (several levels)
 
@@ -72,7 +46,7 @@ def test_leaf_sizes(rtx, cases, max_leaf):
     for name in ("plane", "Knight"):
         s, t, m, p, want = cases(name)
         with tracer_of(rtx, s, t, m, max_leaf=max_leaf) as tr:
-            check_forms(rtx, tr, p, want, f"{name} max_leaf {max_leaf}", [(8, 0)])
+            check_forms(rtx, tr, "nearest", p, want, f"{name} max_leaf {max_leaf}", [(8, 0)])
 
 
 @pytest.mark.parametrize("name", ["two", "mixed", "Knight"])
@@ -90,14 +64,14 @@ def test_scene_and_points_far_from_the_origin(rtx, cases, name):
     want = {f: nc.oracle_nearest(rtx, s2, t2, m2, p2, *f) for f in ((8, 0), (3, 1))}
     for compact_nodes in (0, 1):
         with tracer_of(rtx, s2, t2, m2, compact_nodes=compact_nodes) as tr:
-            check_forms(rtx, tr, p2, want, f"{name} translated, compact_nodes {compact_nodes}", list(want))
+            check_forms(rtx, tr, "nearest", p2, want, f"{name} translated, compact_nodes {compact_nodes}", list(want))
 
 
 @pytest.mark.parametrize("compact_nodes", [0, 1])
 def test_small_lds_stack_spills_to_the_overflow_area(rtx, cases, compact_nodes):
     s, t, m, p, want = cases("Knight")
     with tracer_of(rtx, s, t, m, stream_stack=4, lds_stack=3, compact_nodes=compact_nodes, max_leaf=1) as tr:
-        check_forms(rtx, tr, p, want, f"lds_stack 3, compact_nodes {compact_nodes}", [(8, 0), (3, 1)])
+        check_forms(rtx, tr, "nearest", p, want, f"lds_stack 3, compact_nodes {compact_nodes}", [(8, 0), (3, 1)])
         assert tr.stats()["bvhMaxStack"] > 3                    # (the overflow area was in use)
 
 
@@ -107,7 +81,7 @@ def test_local_meshes_after_a_refit(rtx, device_bvh):
     with tr:
         p = nc.batch_of(rtx, s, world, infos, batch_of(rtx, s, world, infos, seed=5))
         for f in ((8, 0), (3, 1)):
-            got = ask(tr, p, *f)
+            got = ask(tr, "nearest", p, *f)
             nc.assert_same_records(rtx, got, nc.oracle_nearest(rtx, s, world, infos, p, *f, chunk_mesh=chunk_mesh), f"local meshes, device_bvh {device_bvh}, {f}")
         tri = got[got["kind"] == 2]
         assert len(tri) > 100 and (tri["mesh"] >= 0).all() and len(np.unique(tri["mesh"])) > 1
@@ -117,23 +91,12 @@ def test_slices_split_calls_and_counting_are_invisible(rtx, cases):
     s, t, m, p, want = cases("mixed")
     with tracer_of(rtx, s, t, m) as tr:
         tr.set_option("closest_slice", 100)
-        check_forms(rtx, tr, p, want, "closest_slice 100")
+        check_forms(rtx, tr, "nearest", p, want, "closest_slice 100")
         tr.set_option("closest_slice", 333)
-        check_forms(rtx, tr, p, want, "closest_slice 333", [(8, 0)])
-        tr.set_option("closest_slice", 1 << 22)
-        for cut in (1, 333):
-            for f in ((8, 0), (3, 1)):
-                nc.assert_same_records(rtx, np.concatenate([ask(tr, p[:cut], *f), ask(tr, p[cut:], *f)]), want[f], f"cut at {cut}, {f}")
-        assert tr.closest_info()["lastPrimTests"] == 0 and tr.closest_info()["lastNodeSteps"] == 0
-        tr.set_option("closest_count", 1)
+        check_forms(rtx, tr, "nearest", p, want, "closest_slice 333", [(8, 0)])
         searched = int((p["tMax"] > 0).sum())
-        for f in nc.FORMS:
-            nc.assert_same_records(rtx, ask(tr, p, *f), want[f], f"the counting kernel, {f}")
-            info = tr.closest_info()
-            assert info["lastPrimTests"] >= searched * len(s) and info["lastNodeSteps"] >= searched, info
-        tr.set_option("closest_count", 0)
-        check_forms(rtx, tr, p, want, "after the counting kernel", [(2, 0)])
-        assert tr.closest_info()["lastPrimTests"] == 0
+        check_split_calls_and_counting(rtx, "nearest", tr, p, want,
+                                       lambda info: info["lastPrimTests"] >= searched * len(s) and info["lastNodeSteps"] >= searched)
 
 
 def test_a_batch_longer_than_the_effective_slice_at_k_8(rtx):
@@ -145,25 +108,25 @@ def test_a_batch_longer_than_the_effective_slice_at_k_8(rtx):
     rng = np.random.default_rng(8)
     p = cc.points_of(rtx, rng.uniform(-1, 9, (n, 3)).astype(np.float32), 3.0)
     with tracer_of(rtx, s, t, m) as tr:
-        got = ask(tr, p, 8, 0)
+        got = ask(tr, "nearest", p, 8, 0)
         assert got.shape == (n, 8)
         edge = np.r_[0:64, n - 67:n]
         nc.assert_same_records(rtx, got[edge], nc.oracle_nearest(rtx, s, t, m, p[edge], 8, 0), "around the cut at 524288")
-        nc.assert_same_records(rtx, got[edge], ask(tr, p[edge], 8, 0), "the same points alone")
+        nc.assert_same_records(rtx, got[edge], ask(tr, "nearest", p[edge], 8, 0), "the same points alone")
 
 
 def test_multi_tracer_gives_the_single_context_bits(rtx, cases):
     s, t, m, p, want = cases("mixed")
     with rtx.MultiTracer([0] * 3) as mt:
         mt.upload(spheres=s, triangles=t, meshinfo=m)
-        check_forms(rtx, mt, p, want, "three contexts")
-        nc.assert_same_records(rtx, ask(mt, p[:1], 8, 0), want[8, 0][:1], "fewer points than contexts")
+        check_forms(rtx, mt, "nearest", p, want, "three contexts")
+        nc.assert_same_records(rtx, ask(mt, "nearest", p[:1], 8, 0), want[8, 0][:1], "fewer points than contexts")
         cc.assert_same_records(rtx, mt.closest_points(p), cc.oracle_closest(rtx, s, t, m, p), "three contexts, the defaults")
 
 
 def test_device_entry_on_tensors_matches_the_checker():
-    """(in a fresh process that imports torch first: tests/nearest_torch_worker.py)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "nearest_torch_worker.py")], capture_output=True, text=True, timeout=300)
+    """(in a fresh process that imports torch first: tests/listed_torch_worker.py nearest)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "listed_torch_worker.py"), "nearest"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "nearest device entry ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
@@ -194,52 +157,24 @@ def test_the_defaults_are_todays_bytes(rtx, cases):
         got = tr.closest_points(p)
         assert got.shape == (len(p),) and (got["_reserved"] == 0).all()
         cc.assert_same_records(rtx, got, default, "before any option")
-        check_forms(rtx, tr, p, want, "in between")
+        check_forms(rtx, tr, "nearest", p, want, "in between")
         tr.set_option("closest_k", 1)
         tr.set_option("closest_all", 0)
         again = tr.closest_points(p)
         assert again.shape == (len(p),) and again.tobytes() == got.tobytes()
         for f in nc.FORMS:
-            nc.assert_first_is_the_default(rtx, ask(tr, p, *f), got, f"{f}")
+            nc.assert_first_is_the_default(rtx, ask(tr, "nearest", p, *f), got, f"{f}")
 
 
 def test_a_call_moves_no_other_state(rtx, cases):
-    mgr = scene_of(rtx, "mesh_test_scene")
-    params, s, t, m = mgr.build_buffers()
     _, _, _, p, want = cases("mixed")
-    with rtx.Tracer(0) as tb:
-        tb.set_params(params)
-        tb.upload(spheres=s, triangles=t, meshinfo=m)
-        tb.render(0, 2)
-        tb.render_aov(0, 2)
-        tb.denoise(iterations=2)
-        tb.temporal()
-        tb.visibility(p[:64], 4)
-        tb.trace_hits(p[:64], 4)
 
-        def state():
-            return {"accum": tb.read_accum(), "last": tb.read_last_frame(), "albedo": tb.read_aov(0), "normal_depth": tb.read_aov(1),
-                    "denoised": tb.read_denoised(), "temporal": tb.read_temporal(), "history": tb.read_temporal_history(),
-                    "aov_info": tb.aov_info(), "denoise_info": tb.denoise_info(), "temporal_info": tb.temporal_info(),
-                    "radiance_info": tb.radiance_info(), "gather_info": tb.gather_info(), "visibility_info": tb.visibility_info(),
-                    "hits_info": tb.hits_info(), "stats": tb.stats()}
-        before = state()
-        assert tb.closest_info()["calls"] == 0
-        check_forms(rtx, tb, p, want, "beside an image")            # (the far points widen the padding)
-        assert tb.closest_info()["calls"] == len(nc.FORMS)
-        after = state()
-        for k in ("accum", "last", "albedo", "normal_depth", "denoised", "temporal", "history"):
-            assert before[k].tobytes() == after[k].tobytes(), k
-        for k in ("aov_info", "denoise_info", "temporal_info", "radiance_info", "gather_info", "visibility_info", "hits_info"):
-            assert before[k] == after[k], k
-        for k, v in before["stats"].items():
-            if k not in STATS_MAY_MOVE:
-                assert np.array_equal(v, after["stats"][k]), k
-        # every other call ignores the options: the same hits, rays and frame with them set
+    def every_other_call_ignores_the_options(tb):               # the same hits, rays and frame with them set
         hits, rays = tb.trace_hits(p[:64], 4), tb.trace_rays(p[:64])
         tb.set_option("closest_k", 8)
         tb.set_option("closest_all", 1)
         assert tb.trace_hits(p[:64], 4).tobytes() == hits.tobytes() and tb.trace_rays(p[:64]).tobytes() == rays.tobytes()
+    check_a_call_moves_no_other_state(rtx, "nearest", p, want, every_other_call_ignores_the_options)   # (the far points widen the padding)
 
 
 def test_the_kth_key_prunes_and_the_radius_alone_does_not(rtx):
@@ -251,10 +186,10 @@ def test_the_kth_key_prunes_and_the_radius_alone_does_not(rtx):
     p = cc.points_of(rtx, np.concatenate([rng.uniform(0, 8, (n, 2)), np.full((n, 1), 8.0 / 64)], 1))
     for compact_nodes in (0, 1):
         with tracer_of(rtx, s, t, m, compact_nodes=compact_nodes, closest_count=1) as tr:
-            nc.assert_same_records(rtx, ask(tr, p, 1, 1), nc.oracle_nearest(rtx, s, t, m, p, 1, 1), "plane of 8192, (1, 1)")
+            nc.assert_same_records(rtx, ask(tr, "nearest", p, 1, 1), nc.oracle_nearest(rtx, s, t, m, p, 1, 1), "plane of 8192, (1, 1)")
             everything = tr.closest_info()
             assert everything["lastPrimTests"] == n * (len(s) + len(t)), everything
-            nc.assert_same_records(rtx, ask(tr, p, 8, 0), nc.oracle_nearest(rtx, s, t, m, p, 8, 0), "plane of 8192, (8, 0)")
+            nc.assert_same_records(rtx, ask(tr, "nearest", p, 8, 0), nc.oracle_nearest(rtx, s, t, m, p, 8, 0), "plane of 8192, (8, 0)")
             pruned = tr.closest_info()
             print(f"compact_nodes {compact_nodes}: prim tests / point {pruned['lastPrimTests'] / n:.2f} at (8, 0) against {everything['lastPrimTests'] / n:.0f} at (1, 1); "
                   f"node steps / point {pruned['lastNodeSteps'] / n:.2f} against {everything['lastNodeSteps'] / n:.2f}")
