@@ -13,7 +13,7 @@ by the device entry with a tensor (n, k, 16) / uint8 (n,) / ((n, 16), (n,)).  d 
 for the one call and put back to their defaults (0, 1 and 0) in nested `finally` blocks — to the defaults, not to what they were."""
 import numpy as np
 
-from . import _cabi
+from . import _cabi, _listed
 
 K_MAX = _cabi.HITS_MAX
 
@@ -52,48 +52,24 @@ def _segments(p0, p1, radius):
     return out
 
 
-def _capsule(tracer, p0, p1, radius, k, count_all):
-    if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
-        raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= K_MAX:
-        raise ValueError(f"k: an int in 1..{K_MAX}, not {k!r}")
-    segments = _segments(p0, p1, radius)
-    # each option is put back on its own: one restoring call that raises does not keep the others from being made
-    try:
-        try:
-            try:
-                tracer.set_option("closest_capsule", 1)
-                tracer.set_option("closest_k", int(k))
-                tracer.set_option("closest_all", 1 if count_all else 0)
-                out = tracer.closest_points(segments)
-            finally:
-                tracer.set_option("closest_capsule", 0)
-        finally:
-            tracer.set_option("closest_k", 1)
-    finally:
-        tracer.set_option("closest_all", 0)
-    # (k = 1: closest_points answers (n,) / (n, 16); the helpers' shape does not depend on k)
-    return out.reshape(out.shape[0], 1, 16) if _cabi._is_tensor(out) and k == 1 else out.reshape(-1, 1) if k == 1 else out
-
-
 def overlap_capsule(tracer, p0, p1, radius, k=4, count_all=False):
     """Physics.OverlapCapsule: rt_closest_points with "closest_capsule" = 1 and "closest_k" = k (and "closest_all" = count_all) -> CLOSEST
     records (n, k); _reserved[1] of a record holds the bits of s"""
-    return _capsule(tracer, p0, p1, radius, k, count_all)
+    return _listed.query(tracer, k, count_all, "closest_capsule", _segments, p0, p1, radius)
 
 
 def check_capsule(tracer, p0, p1, radius):
     """Physics.CheckCapsule: 1 where a sphere or a triangle lies within `radius` of the segment -> uint8 (n,)"""
-    out = _capsule(tracer, p0, p1, radius, 1, False)
-    if _cabi._is_tensor(out):
+    c = _listed.counts(_listed.query(tracer, 1, False, "closest_capsule", _segments, p0, p1, radius))
+    if _cabi._is_tensor(c):
         import torch
-        return (out[:, 0, 14].contiguous().view(torch.int32) != 0).to(torch.uint8)
-    return (out["_reserved"][:, 0, 0] != 0).astype(np.uint8)
+        return (c != 0).to(torch.uint8)
+    return (c != 0).astype(np.uint8)
 
 
 def closest_to_segment(tracer, p0, p1, radius=np.inf):
     """the nearest surface to each segment -> (records (n,), s float32 (n,)), s read from _reserved[1]: x = p0 + (p1 - p0) * s"""
-    out = _capsule(tracer, p0, p1, radius, 1, False)
+    out = _listed.query(tracer, 1, False, "closest_capsule", _segments, p0, p1, radius)
     if _cabi._is_tensor(out):
         rec = out[:, 0, :]
         return rec, rec[:, 15].contiguous()

@@ -18,8 +18,9 @@
 #include "rt_ctx.hpp"
 #include "rt_geom.hpp"
 #include "rt_bvh_gpu.hpp"
+#include "rt_nearest.hpp"
 #include "rt_overlap.hpp"
-#include "rt_capsule.hpp"           // (with rt_nearest.hpp, rt_closest.hpp and rt_query.hpp: trace_kernel .. cover_origins_device below)
+#include "rt_capsule.hpp"           // (with rt_listed.hpp, rt_closest.hpp and rt_query.hpp: trace_kernel .. cover_origins_device below)
 
 using namespace rth;
 

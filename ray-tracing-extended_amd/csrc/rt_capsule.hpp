@@ -9,9 +9,9 @@
 // from the segment's point nearest to its centre.  It counts when k < R * R.  Records, order and count are the K-nearest queries'
 // (rt_nearest.hpp); _reserved[1] of a record carries the bits of s.
 //
-// k_nearest's launch, walk, list and record writers with three pieces of its own: segment_query, segment_triangle / segment_sphere, and
-// a node step whose lower bound is the squared distance between a child's box and the segment's own axis-aligned bounds.  The list holds
-// (key, id) only: the epilogue runs a listed winner's test again for its (s, u, v), as k_overlap does.
+// The listed-query frame (rt_listed.hpp) and k_closest's record writers with three pieces of its own: segment_query, segment_triangle /
+// segment_sphere, and closest_node_step taken from the segment's own axis-aligned bounds: a child's lower bound is the squared distance
+// between its box and them.  A listed winner's test is run again for its (s, u, v).
 //
 // Pruning.  kb as in k_nearest; a child is skipped only when lb2 > max(kb * kCullSlack, kCullFloor).  Every sub-candidate's key is
 // |x - q|^2 of a COMPUTED x = fl(P0 + fl(d * s)), s in [0, 1], and a computed q on the triangle.  Rounding is monotone, so x lies in
@@ -23,7 +23,7 @@
 // scratch, no spills in any of the four instantiations; five waves per SIMD, k_overlap's occupancy (k_nearest: 64 / 69, eight / seven).
 // The six sub-candidates are evaluated one after the other into a running (k, s, u, v), not side by side.
 #pragma once
-#include "rt_nearest.hpp"
+#include "rt_listed.hpp"
 
 namespace rtk {
 
@@ -141,115 +141,65 @@ __device__ __forceinline__ void segment_triangle(const SegmentQuery& q, v3 A, v3
     }
 }
 
-// closest_node_step with the bounds taken from the segment's box [lo, hi]: per axis max(child lo - hi, lo - child hi, 0)
-template <bool H>
-__device__ __forceinline__ void capsule_node_step(const float4* __restrict__ nodes, uint32_t cur, v3 lo, v3 hi, float thr,
-                                                  float& l0, float& l1, float& l2, float& l3,
-                                                  uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
-{
-    const float INF = __builtin_inff();
-    const ChildBoxes b = child_boxes<H>(nodes, cur);
-    c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
-#define RT_LB(K, LK)                                                                                                     \
-    {                                                                                                                    \
-        const float dx_ = __builtin_fmaxf(__builtin_fmaxf(b.lox.K - hi.x, lo.x - b.hix.K), 0.0f);                        \
-        const float dy_ = __builtin_fmaxf(__builtin_fmaxf(b.loy.K - hi.y, lo.y - b.hiy.K), 0.0f);                        \
-        const float dz_ = __builtin_fmaxf(__builtin_fmaxf(b.loz.K - hi.z, lo.z - b.hiz.K), 0.0f);                        \
-        LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
+// (R * R can be +inf but a counted key is below it, so the keys offered are finite)
+struct SegmentShape : WithinReach<SegmentQuery> {
+    static __device__ __forceinline__ SegmentShape load(const float4* __restrict__ in, unsigned int i, bool present)
+    {
+        return SegmentShape{ { segment_query(in, i, present) } };
     }
-    RT_LB(x, l0) RT_LB(y, l1) RT_LB(z, l2) RT_LB(w, l3)
-#undef RT_LB
-    if (c0 == kNone || l0 > thr) { c0 = kNone; l0 = INF; }
-    if (c1 == kNone || l1 > thr) { c1 = kNone; l1 = INF; }
-    if (c2 == kNone || l2 > thr) { c2 = kNone; l2 = INF; }
-    if (c3 == kNone || l3 > thr) { c3 = kNone; l3 = INF; }
-    sort_children<true>(l0, l1, l2, l3, c0, c1, c2, c3);
-}
+    template <bool H>
+    __device__ __forceinline__ void node_step(const float4* __restrict__ nodes, uint32_t cur, float thr, float& l0, float& l1, float& l2, float& l3,
+                                              uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3) const
+    {
+        closest_node_step<H>(nodes, cur, lo, hi, thr, l0, l1, l2, l3, c0, c1, c2, c3);
+    }
+    __device__ __forceinline__ bool sphere(float4 sp, float& k) const
+    {
+        float s, len, ds; v3 m;
+        k = segment_sphere(*this, sp, s, m, len, ds);
+        return true;
+    }
+    __device__ __forceinline__ bool triangle(v3 A, v3 AB, v3 AC, v3 n, float& k) const
+    {
+        float s, u, v; bool pierced;
+        segment_triangle(*this, A, AB, AC, n, k, s, u, v, pierced);
+        return true;
+    }
+    // k_closest's triangle record from x = P0 + d * s; the sphere record is the solid sphere's.  _reserved[1] (w3.w) carries the bits of s.
+    __device__ __forceinline__ HitRecord triangle_record(const DeviceScene& S, const QueryHead& Q, uint32_t ti, v3 A, v3 AB, v3 AC, v3 n,
+                                                         float key, int count) const
+    {
+        float k_again, s, u, v; bool pierced;
+        segment_triangle(*this, A, AB, AC, n, k_again, s, u, v, pierced);
+        HitRecord rec = closest_triangle_record(S, Q, p0 + d * s, ti, u, v, key, count);
+        if (pierced) rec.w3.y = __int_as_float(0);                      // (a piercing segment lies on neither side)
+        rec.w3.w = s;
+        return rec;
+    }
+    __device__ __forceinline__ HitRecord sphere_record(const DeviceScene& S, uint32_t si, int count) const
+    {
+        const float4 sp = S.sph_geom[si];
+        float s, len, ds; v3 m;
+        segment_sphere(*this, sp, s, m, len, ds);
+        const v3 c = rtm::mk(sp.x, sp.y, sp.z);
+        const v3 point = c + m * (sp.w / len);
+        Hit h; h.id = si; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f;
+        v3 normal; const float4* mat;
+        surface_of(S, h, point, normal, mat);
+        HitRecord rec;
+        rec.sphere(si, normal, len >= sp.w ? 1 : -1, count);
+        rec.at(ds, point);
+        rec.w3.w = s;
+        return rec;
+    }
+};
 
 template <bool H, bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_capsule(DeviceScene S, NearestArgs Q)
 {
     extern __shared__ uint32_t lds_stack[];
-    const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
-    const bool present = i < (unsigned)Q.n;
-    if (!COUNT && !present) return;                                     // (the counting build keeps every lane for the wave's sums)
-    const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float INF = __builtin_inff();
-    const SegmentQuery q = segment_query(Q.in, i, present);
-    const int K = Q.k;
-    const bool count_all = Q.count_all != 0;
-    const float r2 = q.R * q.R;
-    HitList L;
-    float kth = INF;                                    // key of slot K - 1: +inf until K candidates are in
-    int total = 0;                                      // candidates below R * R (complete only when count_all)
-    uint32_t n_nodes = 0, n_prims = 0;
-
-    // (a macro, as in k_nearest; R * R can be +inf but a counted key is below it, so the keys offered are finite)
-#define RT_OFFER(KEY, ID) { if ((KEY) < r2) { ++total; if ((KEY) <= kth) { L.insert((KEY), (ID), Q.order); kth = L.kth(K); } } }
-
-    if (q.searched) {
-        for (int s = 0; s < S.ns; ++s) {
-            float t_, len_, ds_; v3 m_;
-            const float k = segment_sphere(q, S.sph_geom[s], t_, m_, len_, ds_);
-            if (COUNT) ++n_prims;
-            RT_OFFER(k, (uint32_t)s << 1)
-        }
-        if (S.nn > 0) {
-            const float4* nodes = H ? S.nodes_h : S.nodes;
-            RT_WALK_NODE(stk, 0u)                                       // from the root
-                if (COUNT) ++n_nodes;
-                float l0, l1, l2, l3;
-                uint32_t c0, c1, c2, c3;
-                const float kb = count_all ? r2 : __builtin_fminf(r2, kth);     // (every key in the list is below r2)
-                capsule_node_step<H>(nodes, node, q.lo, q.hi, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
-            RT_WALK_TRIANGLE(S.tri_geo, c0 != kNone, c1 != kNone, c2 != kNone, c3 != kNone)
-                float k, s, u, v; bool pierced;
-                segment_triangle(q, tri_A, tri_AB, tri_AC, tri_n, k, s, u, v, pierced);
-                if (COUNT) ++n_prims;
-                RT_OFFER(k, kTriBit | (ti << 1))
-            RT_WALK_END(false)
-        }
-    }
-#undef RT_OFFER
-
-    // ---- the records, as k_nearest writes them: a listed winner's test again for its (s, u, v), then k_closest's triangle record from
-    // x = P0 + d * s; the sphere record is the solid sphere's.  _reserved[1] (w3.w) carries the bits of s.
-    if (present) {
-        const int count = count_all ? total : L.filled(K);
-        float4* out = Q.out + 4 * ((size_t)i * (size_t)K);
-        for (int j = 0; j < K; ++j) {
-            float key; uint32_t id;
-            L.pop_front(key, id);
-            HitRecord rec;
-            if (id == kNone) rec.miss(count);
-            else if (id & kTriBit) {
-                const uint32_t ti = (id & ~kTriBit) >> 1;
-                float4 g0, g1, g2;
-                load_tri(S.tri_geo, ti, g0, g1, g2);
-                float k_again, s, u, v; bool pierced;
-                segment_triangle(q, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), rtm::mk(g2.y, g2.z, g2.w),
-                                 k_again, s, u, v, pierced);
-                rec = closest_triangle_record(S, Q, q.p0 + q.d * s, ti, u, v, key, count);
-                if (pierced) rec.w3.y = __int_as_float(0);              // (a piercing segment lies on neither side)
-                rec.w3.w = s;
-            } else {
-                const uint32_t si = id >> 1;
-                const float4 sp = S.sph_geom[si];
-                float s, len, ds; v3 m;
-                segment_sphere(q, sp, s, m, len, ds);
-                const v3 c = rtm::mk(sp.x, sp.y, sp.z);
-                const v3 point = c + m * (sp.w / len);
-                Hit h; h.id = si; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f;
-                v3 normal; const float4* mat;
-                surface_of(S, h, point, normal, mat);
-                rec.sphere(si, normal, len >= sp.w ? 1 : -1, count);
-                rec.at(ds, point);
-                rec.w3.w = s;
-            }
-            rec.store(out + 4 * (size_t)j);
-        }
-    }
-    if (COUNT) add_wave_counts(Q.counters, n_nodes, n_prims);
+    listed_query<SegmentShape, H, COUNT>(S, Q, lds_stack);
 }
 
 } // namespace rtk
+

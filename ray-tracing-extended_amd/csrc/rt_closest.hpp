@@ -13,8 +13,9 @@
 // best key so far (R * R at the start): DESIGN.md "Closest-point queries" derives that this never skips a triangle whose key could
 // count, equal keys included (a tie can still win on its index).  Entries already on the stack are not culled again when they are
 // popped: a stale internal node costs one node step whose children are all skipped, a stale leaf its triangle tests.
-// Shared: a node step's child boxes and sort (child_boxes, sort_children: rt_kernels.hpp, sweep_node_step's too); with k_nearest
-// (rt_nearest.hpp) point_query, sphere_key, closest_triangle_record / closest_sphere_record, add_wave_counts, all below.
+// Shared: a node step's child boxes and sort (child_boxes, sort_children: rt_kernels.hpp, sweep_node_step's too); with the listed
+// queries (rt_listed.hpp) child_gap2, closest_node_step, point_query, sphere_key, closest_triangle_record / closest_sphere_record,
+// add_wave_counts, all below.
 #pragma once
 #include "rt_query.hpp"
 
@@ -82,25 +83,33 @@ __device__ __forceinline__ void closest_on_triangle(v3 p, v3 A, v3 ab, v3 ac, fl
     k = rtm::dot(e, e);
 }
 
-// The four children of node `cur`: their squared lower bounds sorted ascending with their references; a child that is empty or whose
-// bound exceeds thr carries kNone (and +inf).  The boxes are child_boxes' (rt_kernels.hpp).
+// The squared lower bounds of the distance between the box [lo, hi] and each of the four child boxes: per axis
+// max(child lo - hi, lo - child hi, 0), the squares summed as (x + y) + z.  A point is the box lo = hi = p.
+__device__ __forceinline__ void child_gap2(const ChildBoxes& b, v3 lo, v3 hi, float& l0, float& l1, float& l2, float& l3)
+{
+#define RT_LB(K, LK)                                                                                                     \
+    {                                                                                                                    \
+        const float dx_ = __builtin_fmaxf(__builtin_fmaxf(b.lox.K - hi.x, lo.x - b.hix.K), 0.0f);                        \
+        const float dy_ = __builtin_fmaxf(__builtin_fmaxf(b.loy.K - hi.y, lo.y - b.hiy.K), 0.0f);                        \
+        const float dz_ = __builtin_fmaxf(__builtin_fmaxf(b.loz.K - hi.z, lo.z - b.hiz.K), 0.0f);                        \
+        LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
+    }
+    RT_LB(x, l0) RT_LB(y, l1) RT_LB(z, l2) RT_LB(w, l3)
+#undef RT_LB
+}
+
+// The four children of node `cur`: their squared lower bounds from the box [lo, hi] (a point: lo = hi = p; a segment: its bounds,
+// rt_capsule.hpp) sorted ascending with their references; a child that is empty or whose bound exceeds thr carries kNone (and +inf).
+// The boxes are child_boxes' (rt_kernels.hpp).
 template <bool H>
-__device__ __forceinline__ void closest_node_step(const float4* __restrict__ nodes, uint32_t cur, v3 p, float thr,
+__device__ __forceinline__ void closest_node_step(const float4* __restrict__ nodes, uint32_t cur, v3 lo, v3 hi, float thr,
                                                   float& l0, float& l1, float& l2, float& l3,
                                                   uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
 {
     const float INF = __builtin_inff();
     const ChildBoxes b = child_boxes<H>(nodes, cur);
     c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
-#define RT_LB(K, LK)                                                                                                     \
-    {                                                                                                                    \
-        const float dx_ = __builtin_fmaxf(__builtin_fmaxf(b.lox.K - p.x, p.x - b.hix.K), 0.0f);                          \
-        const float dy_ = __builtin_fmaxf(__builtin_fmaxf(b.loy.K - p.y, p.y - b.hiy.K), 0.0f);                          \
-        const float dz_ = __builtin_fmaxf(__builtin_fmaxf(b.loz.K - p.z, p.z - b.hiz.K), 0.0f);                          \
-        LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
-    }
-    RT_LB(x, l0) RT_LB(y, l1) RT_LB(z, l2) RT_LB(w, l3)
-#undef RT_LB
+    child_gap2(b, lo, hi, l0, l1, l2, l3);
     // an empty slot holds a (+inf, -inf) box: its bound is +inf, which is not above a threshold of +inf — it is dropped by its reference
     if (c0 == kNone || l0 > thr) { c0 = kNone; l0 = INF; }
     if (c1 == kNone || l1 > thr) { c1 = kNone; l1 = INF; }
@@ -111,7 +120,7 @@ __device__ __forceinline__ void closest_node_step(const float4* __restrict__ nod
     sort_children<true>(l0, l1, l2, l3, c0, c1, c2, c3);
 }
 
-// ---- what k_closest and k_nearest (rt_nearest.hpp) share ----
+// ---- what k_closest and the listed queries (rt_listed.hpp) share ----
 // (p, R) of point i.  R <= 0 or NaN: not searched.  A point with a component that is not finite has no candidate either — every key it
 // forms is +inf or NaN, and neither is below R * R — so it is answered without a search (its bounds would be +inf or NaN at every node)
 struct PointQuery { v3 p; float R; bool searched; };
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(kBlock) void k_closest(DeviceScene S, ClosestArgs Q
                 if (COUNT) ++n_nodes;
                 float l0, l1, l2, l3;
                 uint32_t c0, c1, c2, c3;
-                closest_node_step<H>(nodes, node, p, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
+                closest_node_step<H>(nodes, node, p, p, __builtin_fmaxf(kb * kCullSlack, kCullFloor), l0, l1, l2, l3, c0, c1, c2, c3);
             RT_WALK_TRIANGLE(S.tri_geo, c0 != kNone, c1 != kNone, c2 != kNone, c3 != kNone)
                 float k, u, v;
                 closest_on_triangle(p, tri_A, tri_AB, tri_AC, k, u, v);

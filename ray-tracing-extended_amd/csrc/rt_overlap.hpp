@@ -7,14 +7,15 @@
 // separating-axis test (Akenine-Möller) after a finiteness and a bounds condition — and its closest-point key from the centre c is not
 // NaN.  There is no radius.  Records, order and count are the K-nearest queries' (rt_nearest.hpp), the keys taken from c.
 //
-// k_nearest's launch, walk, list and record writers, with two pieces of its own: box_touches_triangle, and a node step that takes
-// closest_node_step's sorted lower bounds from c and also drops every child whose box is disjoint from [lo, hi] by exact comparison.
+// The listed-query frame (rt_listed.hpp) and k_nearest's keys and record writers, with two pieces of its own: box_touches_triangle, and
+// a node step that takes closest_node_step's sorted lower bounds from c and also drops every child whose box is disjoint from [lo, hi]
+// by exact comparison.
 //
 // Pruning.  A child is skipped when its box misses [lo, hi] on some axis: a touching triangle passes the bounds condition on A, A + eAB,
 // A + eAC, and those bounds lie inside every box on the way down to it (DESIGN.md "Box overlap queries").  Without closest_all a child is
 // also skipped when lb2 > max(kth * kCullSlack, kCullFloor), kth the key in slot K - 1: the K-nearest rule, on the subset that touches.
 #pragma once
-#include "rt_nearest.hpp"
+#include "rt_listed.hpp"
 
 namespace rtk {
 
@@ -82,105 +83,72 @@ __device__ __forceinline__ bool box_touches_triangle(const BoxQuery& q, v3 A, v3
     return ok != 0;
 }
 
-// closest_node_step with one more reason to drop a child: its box misses [lo, hi] on some axis (exact comparisons; an empty slot's
-// (+inf, -inf) box misses everything).  The kept children come back sorted by their squared lower bound from c, nearest first.
-template <bool H>
-__device__ __forceinline__ void overlap_node_step(const float4* __restrict__ nodes, uint32_t cur, const BoxQuery& q, float thr,
-                                                  float& l0, float& l1, float& l2, float& l3,
-                                                  uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
-{
-    const float INF = __builtin_inff();
-    const ChildBoxes b = child_boxes<H>(nodes, cur);
-    c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
-    const v3 p = q.c;
-#define RT_LB(K, LK, CK)                                                                                                 \
-    {                                                                                                                    \
-        const float dx_ = __builtin_fmaxf(__builtin_fmaxf(b.lox.K - p.x, p.x - b.hix.K), 0.0f);                          \
-        const float dy_ = __builtin_fmaxf(__builtin_fmaxf(b.loy.K - p.y, p.y - b.hiy.K), 0.0f);                          \
-        const float dz_ = __builtin_fmaxf(__builtin_fmaxf(b.loz.K - p.z, p.z - b.hiz.K), 0.0f);                          \
-        LK = (dx_ * dx_ + dy_ * dy_) + dz_ * dz_;                                                                        \
-        const bool apart_ = b.lox.K > q.hi.x || b.hix.K < q.lo.x || b.loy.K > q.hi.y || b.hiy.K < q.lo.y || b.loz.K > q.hi.z || b.hiz.K < q.lo.z; \
-        if (CK == kNone || apart_ || LK > thr) { CK = kNone; LK = INF; }                                                 \
+// A touching candidate's key, from the centre, counts unless it is NaN.  It can be +inf — a box far from the surface it still reaches —
+// and then ties with the list's empty slots: insert<true> keeps the tie read off them, and the candidate goes in front of them, kNone
+// being the largest id.
+struct BoxShape : BoxQuery {
+    static constexpr bool kInfKeys = true;
+    static __device__ __forceinline__ BoxShape load(const float4* __restrict__ in, unsigned int i, bool present)
+    {
+        return BoxShape{ box_query(in, i, present) };
     }
-    RT_LB(x, l0, c0) RT_LB(y, l1, c1) RT_LB(z, l2, c2) RT_LB(w, l3, c3)
-#undef RT_LB
-    sort_children<true>(l0, l1, l2, l3, c0, c1, c2, c3);
-}
+    __device__ __forceinline__ bool admits(float k) const { return k == k; }
+    __device__ __forceinline__ float threshold(bool count_all, float kth) const
+    {
+        return count_all ? __builtin_inff() : __builtin_fmaxf(kth * kCullSlack, kCullFloor);
+    }
+    // closest_node_step with one more reason to drop a child: its box misses [lo, hi] on some axis (exact comparisons; an empty slot's
+    // (+inf, -inf) box misses everything).  The kept children come back sorted by their squared lower bound from c, nearest first.
+    template <bool H>
+    __device__ __forceinline__ void node_step(const float4* __restrict__ nodes, uint32_t cur, float thr, float& l0, float& l1, float& l2, float& l3,
+                                              uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3) const
+    {
+        const float INF = __builtin_inff();
+        const ChildBoxes b = child_boxes<H>(nodes, cur);
+        c0 = b.ch.x; c1 = b.ch.y; c2 = b.ch.z; c3 = b.ch.w;
+        child_gap2(b, c, c, l0, l1, l2, l3);
+#define RT_DROP(K, LK, CK)                                                                                               \
+        {                                                                                                                \
+            const bool apart_ = b.lox.K > hi.x || b.hix.K < lo.x || b.loy.K > hi.y || b.hiy.K < lo.y || b.loz.K > hi.z || b.hiz.K < lo.z; \
+            if (CK == kNone || apart_ || LK > thr) { CK = kNone; LK = INF; }                                             \
+        }
+        RT_DROP(x, l0, c0) RT_DROP(y, l1, c1) RT_DROP(z, l2, c2) RT_DROP(w, l3, c3)
+#undef RT_DROP
+        sort_children<true>(l0, l1, l2, l3, c0, c1, c2, c3);
+    }
+    __device__ __forceinline__ bool sphere(float4 sp, float& k) const
+    {
+        if (!box_touches_sphere(*this, sp)) return false;
+        k = sphere_key(c, sp);
+        return true;
+    }
+    __device__ __forceinline__ bool triangle(v3 A, v3 AB, v3 AC, v3 n, float& k) const
+    {
+        if (!box_touches_triangle(*this, A, AB, AC, n)) return false;
+        float u, v;
+        closest_on_triangle(c, A, AB, AC, k, u, v);
+        return true;
+    }
+    // k_nearest's records, from the centre
+    __device__ __forceinline__ HitRecord triangle_record(const DeviceScene& S, const QueryHead& Q, uint32_t ti, v3 A, v3 AB, v3 AC, v3,
+                                                         float key, int count) const
+    {
+        float k_again, u, v;
+        closest_on_triangle(c, A, AB, AC, k_again, u, v);
+        return closest_triangle_record(S, Q, c, ti, u, v, key, count);
+    }
+    __device__ __forceinline__ HitRecord sphere_record(const DeviceScene& S, uint32_t si, int count) const
+    {
+        return closest_sphere_record(S, c, si, count);
+    }
+};
 
 template <bool H, bool COUNT>
 __global__ __launch_bounds__(kBlock) void k_overlap(DeviceScene S, NearestArgs Q)
 {
     extern __shared__ uint32_t lds_stack[];
-    const unsigned int i = blockIdx.x * kBlock + threadIdx.x;
-    const bool present = i < (unsigned)Q.n;
-    if (!COUNT && !present) return;                                     // (the counting build keeps every lane for the wave's sums)
-    const TravStack stk = lane_stack(lds_stack, Q.stack_cap, Q.gstack, Q.gstack_stride);
-    const float INF = __builtin_inff();
-    const BoxQuery q = box_query(Q.in, i, present);
-    const v3 p = q.c;
-    const int K = Q.k;
-    const bool count_all = Q.count_all != 0;
-    HitList L;
-    float kth = INF;                                    // key of slot K - 1: +inf until K candidates are in
-    int total = 0;                                      // candidates that touch (complete only when count_all)
-    uint32_t n_nodes = 0, n_prims = 0;
-
-    // (a macro, as in k_nearest; the key of a touching candidate counts unless it is NaN.  It can be +inf — a box far from the surface
-    // it still reaches — and then ties with the empty slots: insert<true> keeps the tie read off them, and the candidate goes in front
-    // of them, kNone being the largest id)
-#define RT_OFFER(KEY, ID) { if ((KEY) == (KEY)) { ++total; if ((KEY) <= kth) { L.insert<true>((KEY), (ID), Q.order); kth = L.kth(K); } } }
-
-    if (q.searched) {
-        for (int s = 0; s < S.ns; ++s) {
-            const float4 sp = S.sph_geom[s];
-            if (COUNT) ++n_prims;
-            if (box_touches_sphere(q, sp)) {
-                const float k = sphere_key(p, sp);
-                RT_OFFER(k, (uint32_t)s << 1)
-            }
-        }
-        if (S.nn > 0) {
-            const float4* nodes = H ? S.nodes_h : S.nodes;
-            RT_WALK_NODE(stk, 0u)                                       // from the root
-                if (COUNT) ++n_nodes;
-                float l0, l1, l2, l3;
-                uint32_t c0, c1, c2, c3;
-                const float thr = count_all ? INF : __builtin_fmaxf(kth * kCullSlack, kCullFloor);
-                overlap_node_step<H>(nodes, node, q, thr, l0, l1, l2, l3, c0, c1, c2, c3);
-            RT_WALK_TRIANGLE(S.tri_geo, c0 != kNone, c1 != kNone, c2 != kNone, c3 != kNone)
-                if (COUNT) ++n_prims;
-                if (box_touches_triangle(q, tri_A, tri_AB, tri_AC, tri_n)) {
-                    float k, u, v;
-                    closest_on_triangle(p, tri_A, tri_AB, tri_AC, k, u, v);
-                    RT_OFFER(k, kTriBit | (ti << 1))
-                }
-            RT_WALK_END(false)
-        }
-    }
-#undef RT_OFFER
-
-    // ---- the records, as k_nearest writes them: a listed triangle's test again for its (u, v), then k_closest's record.  (A copy of its
-    // epilogue: one shared function changed k_nearest's generated code, which this change leaves as it was.)
-    if (present) {
-        const int count = count_all ? total : L.filled(K);
-        float4* out = Q.out + 4 * ((size_t)i * (size_t)K);
-        for (int j = 0; j < K; ++j) {
-            float key; uint32_t id;
-            L.pop_front(key, id);
-            HitRecord rec;
-            if (id == kNone) rec.miss(count);
-            else if (id & kTriBit) {
-                const uint32_t ti = (id & ~kTriBit) >> 1;
-                float4 g0, g1, g2;
-                load_tri(S.tri_geo, ti, g0, g1, g2);
-                float k_again, u, v;
-                closest_on_triangle(p, rtm::mk(g0.x, g0.y, g0.z), rtm::mk(g0.w, g1.x, g1.y), rtm::mk(g1.z, g1.w, g2.x), k_again, u, v);
-                rec = closest_triangle_record(S, Q, p, ti, u, v, key, count);
-            } else rec = closest_sphere_record(S, p, id >> 1, count);
-            rec.store(out + 4 * (size_t)j);
-        }
-    }
-    if (COUNT) add_wave_counts(Q.counters, n_nodes, n_prims);
+    listed_query<BoxShape, H, COUNT>(S, Q, lds_stack);
 }
 
 } // namespace rtk
+

@@ -12,7 +12,7 @@
 #include "rt_visibility.hpp"
 #include "rt_multihit.hpp"
 #include "rt_sweep.hpp"
-#include "rt_nearest.hpp"           // NearestArgs and rt_closest.hpp's walk; k_closest, k_nearest, k_overlap and k_capsule themselves: rt_api.hip closest_kernel
+#include "rt_listed.hpp"            // NearestArgs and rt_closest.hpp's walk; k_closest, k_nearest, k_overlap and k_capsule themselves: rt_api.hip closest_kernel
 
 using namespace rth;
 

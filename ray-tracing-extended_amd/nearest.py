@@ -14,7 +14,7 @@ set for the one call and put back to their defaults (1 and 0) in a `finally` —
 set them on the tracer themselves finds them cleared after either helper."""
 import numpy as np
 
-from . import _cabi
+from . import _cabi, _listed
 
 K_MAX = _cabi.HITS_MAX
 
@@ -45,33 +45,12 @@ def _with_radius(points, radius):
     return out
 
 
-def _nearest(tracer, points, k, radius, count_all):
-    if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
-        raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= K_MAX:
-        raise ValueError(f"k: an int in 1..{K_MAX}, not {k!r}")
-    points = _with_radius(points, radius)
-    try:
-        tracer.set_option("closest_k", int(k))
-        tracer.set_option("closest_all", 1 if count_all else 0)
-        out = tracer.closest_points(points)
-    finally:
-        tracer.set_option("closest_k", 1)
-        tracer.set_option("closest_all", 0)
-    # (k = 1: closest_points answers (n,) / (n, 16); the helpers' shape does not depend on k)
-    return out.reshape(out.shape[0], 1, 16) if _cabi._is_tensor(out) and k == 1 else out.reshape(-1, 1) if k == 1 else out
-
-
 def nearest_k(tracer, points, k=4, radius=None, count_all=False):
     """rt_closest_points with option "closest_k" = k (and "closest_all" = count_all): the k nearest surfaces of every point -> CLOSEST
     records (n, k)"""
-    return _nearest(tracer, points, k, radius, count_all)
+    return _listed.query(tracer, k, count_all, None, _with_radius, points, radius)
 
 
 def overlap_count(tracer, points, radius):
     """Physics.OverlapSphere's count: the number of spheres and triangles with key < radius * radius, per point -> int32 (n,)"""
-    out = _nearest(tracer, points, 1, radius, True)
-    if _cabi._is_tensor(out):
-        import torch
-        return out[:, 0, 14].contiguous().view(torch.int32)
-    return out["_reserved"][:, 0, 0].astype(np.int32)
+    return _listed.counts(_listed.query(tracer, 1, True, None, _with_radius, points, radius))

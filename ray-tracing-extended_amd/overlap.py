@@ -16,7 +16,7 @@ arrays, or — a Tracer — CUDA tensors, answered by the device entry with a te
 the one call and put back to their defaults (0, 1 and 0) in a `finally` — to the defaults, not to what they were."""
 import numpy as np
 
-from . import _cabi
+from . import _cabi, _listed
 
 K_MAX = _cabi.HITS_MAX
 CHUNK = 1 << 22                 # cells per call of voxel_counts: the largest "closest_slice" (k = 1)
@@ -51,46 +51,15 @@ def _boxes(centres, half_extents):
     return out
 
 
-def _overlap(tracer, centres, half_extents, k, count_all):
-    if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
-        raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= K_MAX:
-        raise ValueError(f"k: an int in 1..{K_MAX}, not {k!r}")
-    boxes = _boxes(centres, half_extents)
-    # each option is put back on its own: one restoring call that raises does not keep the others from being made
-    try:
-        try:
-            try:
-                tracer.set_option("closest_box", 1)
-                tracer.set_option("closest_k", int(k))
-                tracer.set_option("closest_all", 1 if count_all else 0)
-                out = tracer.closest_points(boxes)
-            finally:
-                tracer.set_option("closest_box", 0)
-        finally:
-            tracer.set_option("closest_k", 1)
-    finally:
-        tracer.set_option("closest_all", 0)
-    # (k = 1: closest_points answers (n,) / (n, 16); the helpers' shape does not depend on k)
-    return out.reshape(out.shape[0], 1, 16) if _cabi._is_tensor(out) and k == 1 else out.reshape(-1, 1) if k == 1 else out
-
-
-def _counts(out):
-    if _cabi._is_tensor(out):
-        import torch
-        return out[:, 0, 14].contiguous().view(torch.int32)
-    return out["_reserved"][:, 0, 0].astype(np.int32)
-
-
 def overlap_box(tracer, centres, half_extents, k=4, count_all=False):
     """Physics.OverlapBox: rt_closest_points with "closest_box" = 1 and "closest_k" = k (and "closest_all" = count_all) -> CLOSEST
     records (n, k)"""
-    return _overlap(tracer, centres, half_extents, k, count_all)
+    return _listed.query(tracer, k, count_all, "closest_box", _boxes, centres, half_extents)
 
 
 def check_box(tracer, centres, half_extents):
     """Physics.CheckBox: 1 where a sphere or a triangle touches the box -> uint8 (n,)"""
-    c = _counts(_overlap(tracer, centres, half_extents, 1, False))
+    c = _listed.counts(_listed.query(tracer, 1, False, "closest_box", _boxes, centres, half_extents))
     if _cabi._is_tensor(c):
         import torch
         return (c != 0).to(torch.uint8)
@@ -115,5 +84,5 @@ def voxel_counts(tracer, lo, hi, shape):
         idx = np.arange(first, min(first + CHUNK, n))
         ijk = np.stack(np.unravel_index(idx, dims), 1).astype(np.float32)
         centres = lo + (ijk + np.float32(0.5)) * cell
-        out[idx] = _counts(_overlap(tracer, centres.astype(np.float32), half, 1, True))
+        out[idx] = _listed.counts(_listed.query(tracer, 1, True, "closest_box", _boxes, centres.astype(np.float32), half))
     return out.reshape(dims)

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import cabi_record
 import closest_check as cc
 import nearest_check as nc
 from test_camera_batch_cpu import built_library
@@ -86,6 +87,18 @@ def test_nearest_py_refuses_bad_input_before_any_c_call(rtx):
         rtx.nearest.nearest_k(tr, pts, 4, 1.0)
     q = rtx.nearest._with_radius(pts, [1.0, 2.0, 0.5, 4.0])
     assert (pts["tMax"] == 0).all() and np.array_equal(q["tMax"], np.float32([1, 2, 0.5, 4]))
+
+
+def test_closest_all_is_put_back_when_restoring_closest_k_fails(rtx):
+    lib = cabi_record.Recorder(rtx._cabi.PARAMS.itemsize)
+    lib.returns["rt_set_option"] = lambda ctx, name, value: -2 if (name, value) == (b"closest_k", 1) else 0
+    t = object.__new__(rtx._cabi.Tracer)
+    t._lib, t._ctx = lib, cabi_record.CTX
+    with pytest.raises(rtx.RtError):
+        rtx.nearest.nearest_k(t, np.zeros(4, rtx.RAY), 3, 1.0, count_all=True)
+    options = [(e["args"][1], e["args"][2]) for e in lib.log if e["call"] == "rt_set_option"]
+    assert options == [("bytes:closest_k", 3), ("bytes:closest_all", 1), ("bytes:closest_k", 1), ("bytes:closest_all", 0)]
+    assert [e["call"] for e in lib.log].index("rt_closest_points") == 2
 
 
 def test_the_handle_remembers_closest_k(rtx):
