@@ -271,6 +271,9 @@ int rt_read_world_geometry(rt_ctx* ctx, rt_triangle* tris_out, int n_tris, rt_me
  *                     rt_occluded_device and rt_multi_occluded answer for a BALL swept along each ray, its radius the float whose bits are
  *                     rt_ray._reserved: see "sphere casts" below.  Other values are refused with -2.  rt_trace_hits, the radiance,
  *                     gather, visibility and closest-point calls and every frame ignore it; at 0 nothing reads rt_ray._reserved
+ *   "hits_sweep"      0 (default) or 1: with 1 rt_trace_hits, rt_trace_hits_device and rt_multi_trace_hits list what a BALL swept along each
+ *                     ray touches, its radius the bits of rt_ray._reserved: see "sphere-cast-all" below.  Other values are refused with -2
+ *                     and nothing changes.  Independent of "sweep"; every other call ignores it; at 0 the three calls are what they were
  *   "shade_threshold" k_stream: lanes (1..64) with a complete query that end a traversal burst (default 48)
  *   "node_min"        k_stream: inside a burst the node loop goes on while at least this many lanes hold an internal node (or no
  *                     lane holds a leaf); below it the leaves are served first (default 10; 1 = classic while-while)
@@ -986,6 +989,48 @@ int rt_trace_hits       (rt_ctx* ctx, const rt_ray* rays, int n, const rt_hits_p
  * entry's times.                                                                                                                 */
 int rt_trace_hits_device(rt_ctx* ctx, const void* rays, int n, const rt_hits_params* params, void* out);
 int rt_get_hits_info    (rt_ctx* ctx, rt_hits_info* out);
+
+/* ---- sphere-cast-all: the first K surfaces a swept ball touches, in order ---------------------------------------------------------------
+ * The listing form of "sphere casts" above, as the multi-hit ray queries are the listing form of the ray queries: Unity's
+ * Physics.SphereCastAll.  Every wall a character's step touches, everything a thick projectile pierces, every blocker of a camera boom,
+ * "what else is in the way after the first thing".  K calls of a sphere cast with advancing origins do not answer it: contacts at one t
+ * are lost, and it costs K traversals.  No new entry, record or struct: option "hits_sweep" (0 or 1, default 0) of rt_set_option /
+ * rt_multi_set_option.  With "hits_sweep" = 1, rt_trace_hits, rt_trace_hits_device and rt_multi_trace_hits read each rt_ray as a sphere
+ * cast reads it — the radius r is the float whose bits are rt_ray._reserved — and write n * K rt_multihit records, ray-major.  With the
+ * option at 0 the three calls are exactly what they are without it: the same kernels and the same bytes, whatever _reserved holds.
+ * Everything is float32, every product and sum rounded on its own (no FMA); / and sqrtf are IEEE.
+ *
+ *   not traced    tMax <= 0 or NaN, or r <= 0, NaN or infinite: K empty records with hitCount 0, and nothing is read.
+ *   candidates    one per primitive at most, and exactly what "sphere casts" defines for that primitive alone.
+ *                 A scene sphere: RaySphere with radius R + r, hitPoint and normal as there; feature code 0; no guard.
+ *                 A triangle: among its eight feature codes (1, 2 the faces from the front and from behind, 3..5 the edges AB, AC, BC,
+ *                 6..8 the vertices A, B, C, each exactly as "sphere casts" writes it, qa = ee * dd - nd * nd and all) take those with
+ *                 t < tMax that pass the guard — closest_on_triangle(o + d * t)'s key <= g * g, g = r * (1 + 2^-6).  The triangle's
+ *                 candidate is the one with the smallest (t, code); a triangle none of whose features passes is no candidate.
+ *                 intersectMode plays no part, and rt_hits_params.mode is validated as ever and then not read: the test is two-sided
+ *                 by construction.
+ *   order         ascending (t, kind, primitive): t compares as a float (-0.0f == 0.0f); at equal t a sphere comes before a triangle,
+ *                 then the lower uploaded index.
+ *   records       records 0 .. min(total, K) - 1 of a ray are its first candidates in that order, the rest are rt_multihit's empty
+ *                 record.  Words 0..12 (dst .. v) of a filled record are the words the sphere cast's rt_hit has for that candidate:
+ *                 dst = t, hitPoint the contact point, normal the CONTACT normal (from the contact to the ball's centre, normalised),
+ *                 kind, primitive, chunk, mesh, u, v as there.
+ *   side          a scene sphere: +1.  A triangle: the sign of dot(centre - hitPoint, cross(eAB, eAC)) with centre = o + d * t: +1,
+ *                 -1, or 0 (also 0 for a NaN) — which side of the face the ball's centre is on at the contact.
+ *   hitCount      as in rt_trace_hits: min(total, K), or with countAll = 1 the number of ALL candidates with t < tMax (the traversal
+ *                 is then bounded by tMax alone).  The same value in all K records of a ray.
+ *   _reserved     the contact's feature code, 0..8.
+ *   consequences  Record 0 equals the "sweep" = 1 rt_trace_rays record of the same ray in words 0..12 and in the feature code, and
+ *                 hitCount > 0 exactly when the "sweep" = 1 rt_occluded says 1.  The records of a call at K are the first K records of
+ *                 a call at any larger K (hitCount apart).  The answer does not depend on the tree, the builder, the leaf size, the
+ *                 node form or the visiting order.  The library's slices ("hits_slice") and rt_multi are invisible; a batch cut anywhere
+ *                 into two calls gives the bits of one.  Scene and state: as for rt_trace_hits (rt_hits_info counts the call and its
+ *                 lastMode reports the params' mode).
+ *   limits        all of the sphere casts' limits carry over unchanged: the float32 range of the quadratics, balls that start
+ *                 overlapping (a primitive whose contact lies behind the origin reports nothing), origins many radii away.
+ *   refusals      "hits_sweep" other than 0 or 1: -2 with a message, and the option keeps its value.  It is independent of "sweep":
+ *                 either may be 0 or 1, "sweep" = 1 still changes nothing about rt_trace_hits, and "hits_sweep" = 1 changes nothing
+ *                 about any other call.  rt_hits_params is checked as ever (a reserved word that is not 0: -2).                     */
 
 /* ---- feature buffers: albedo, normal, depth and coverage of the first visible surface ---------------------------------
  * What a denoiser, a compositor or an edge-aware filter takes beside the noisy image.  The reference has no such output (its only

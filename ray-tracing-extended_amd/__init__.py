@@ -11,7 +11,7 @@ module `rtx_amd`.  Only what the hot path needs lives here:
     nearest.py K-nearest point queries over the closest-point entries (options "closest_k", "closest_all")
     overlap.py box overlap queries over the closest-point entries (option "closest_box")
     scenes.py  synthetic workloads of BASELINE.json configs
-    sweep.py   sphere casts over the ray-query entries (option "sweep")
+    sweep.py   sphere casts over the ray-query entries (option "sweep"), sphere-cast-all over rt_trace_hits (option "hits_sweep")
     unity_scene.py  loader for the reference's .unity scenes + compact scene interchange format
     distributed.py  row-strip decomposition + frame-end gather
 """

@@ -939,6 +939,7 @@ int rt_set_option(rt_ctx* c, const char* name, int value)
         c->opt_closest_capsule = value;
     }
     else if (!std::strcmp(name, "sweep")) { if (value != 0 && value != 1) return fail(c, -2, "sweep must be 0 or 1"); c->opt_sweep = value; }
+    else if (!std::strcmp(name, "hits_sweep")) { if (value != 0 && value != 1) return fail(c, -2, "hits_sweep must be 0 or 1"); c->opt_hits_sweep = value; }
     else if (!std::strcmp(name, "radiance_slice")) { if (value < 1 || value > kQuerySlice) return fail(c, -2, "radiance_slice must be in [1,%d] (rays per launch)", kQuerySlice); c->opt_radiance_slice = value; }
     else if (!std::strcmp(name, "blocks_per_cu")) { if (value < 0) return fail(c, -2, "blocks_per_cu must be >= 0"); c->opt_blocks_per_cu = value; }
     else return fail(c, -2, "unknown option '%s'", name);

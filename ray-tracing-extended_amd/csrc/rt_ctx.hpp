@@ -242,6 +242,7 @@ struct rt_ctx : rth::ErrOwner {
     // and fetched by rt_get_closest_info when counts_pending says the last call left some there)
     int opt_closest_slice = 1 << 22, opt_closest_count = 0;
     int opt_sweep = 0;              // 1: the ray queries answer for a ball (csrc/rt_sweep.hpp)
+    int opt_hits_sweep = 0;         // 1: the multi-hit ray queries list what a ball touches (csrc/rt_sweep_all.hpp)
     int opt_closest_k = 1, opt_closest_all = 0;     // K-nearest queries: records per point, count every candidate (csrc/rt_nearest.hpp); 1 and 0: k_closest
     int opt_closest_box = 0;                        // box overlap queries: 1 = each input is a box (centre, half-extents), k_overlap (csrc/rt_overlap.hpp)
     int opt_closest_capsule = 0;                    // capsule overlap queries: 1 = each input is a segment (P0, d, reach), k_capsule (csrc/rt_capsule.hpp)

@@ -12,6 +12,7 @@
 #include "rt_visibility.hpp"
 #include "rt_multihit.hpp"
 #include "rt_sweep.hpp"
+#include "rt_sweep_all.hpp"
 #include "rt_listed.hpp"            // NearestArgs and rt_closest.hpp's walk; k_closest, k_nearest, k_overlap and k_capsule themselves: rt_api.hip closest_kernel
 
 using namespace rth;
@@ -287,6 +288,8 @@ hipError_t launch_hits(rt_ctx* c, const QueryCall& q, const QuerySlice& s)
     A.max_hits = q.h.maxHits; A.count_all = q.h.countAll;
     A.out = static_cast<float4*>(s.out);
     c->hits_last = q.h;
+    // sphere-cast-all ("hits_sweep" = 1): the same rays, records and launch shape; the params' mode is validated and not read (csrc/rt_sweep_all.hpp)
+    if (c->opt_hits_sweep) return launch_slice(c, pick_nodes(c, rtk::k_sweep_all<true>, rtk::k_sweep_all<false>), s, A);
     if (q.h.mode == RT_HITS_BOTH) return launch_slice(c, pick_nodes(c, rtk::k_multihit<true, true>, rtk::k_multihit<false, true>), s, A);
     return launch_slice(c, pick_nodes(c, rtk::k_multihit<true, false>, rtk::k_multihit<false, false>), s, A);
 }

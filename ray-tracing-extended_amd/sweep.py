@@ -5,8 +5,11 @@ it touches — Unity's Physics.SphereCast / CheckSphere-along-a-path, through th
                                             _reserved[0] = the contact feature: 0 sphere, 1 / 2 front / back face, 3..5 edge AB / AC / BC,
                                             6..8 vertex A / B / C)
     sphere_check(tracer, rays, radius)   -> uint8, 1 where sphere_cast would hit
+    sphere_cast_all(tracer, rays, radius, max_hits=4, count_all=False)
+                                         -> MULTIHIT records (n, max_hits): every primitive the ball touches, in order (Unity's
+                                            Physics.SphereCastAll), through rt_trace_hits with option "hits_sweep" = 1
 
-Both take a Tracer or a MultiTracer and rays as trace_rays takes them (a RAY array, float32 (n, 8), or — a Tracer — a float32 (n, 8) CUDA
+All take a Tracer or a MultiTracer and rays as trace_rays takes them (a RAY array, float32 (n, 8), or — a Tracer — a float32 (n, 8) CUDA
 tensor, answered by the device entry with a tensor).  radius: one value for all rays or one per ray.  The radii travel as the bits of
 rt_ray._reserved in a COPY of the rays; the option is set for the one call and put back to 0 in a `finally` — to 0, not to what it was:
 a caller who has set "sweep" = 1 on the tracer themselves finds it cleared after either helper."""
@@ -55,3 +58,22 @@ def sphere_cast(tracer, rays, radius):
 def sphere_check(tracer, rays, radius):
     """rt_occluded with option "sweep" = 1: 1 where a ball of `radius` swept along the ray touches something before tMax -> uint8"""
     return _swept(tracer, "occluded", rays, radius)
+
+
+def sphere_cast_all(tracer, rays, radius, max_hits=4, count_all=False):
+    """rt_trace_hits with option "hits_sweep" = 1 (include/rt.h "sphere-cast-all"): the first max_hits (1..8) primitives a ball of
+    `radius` touches along each ray, in order of (travel, kind, uploaded index) -> MULTIHIT records (n, max_hits).  A record's fields are
+    sphere_cast's for that contact; side = which side of the face the ball's centre is on (+1 for a sphere), _reserved = the contact
+    feature; count_all: hitCount counts every primitive touched before tMax.  A Tracer or a MultiTracer; rays and radius as for
+    sphere_cast (a Tracer answers a CUDA tensor through the device entry, with a float32 (n, max_hits, 16) tensor).  The option is set
+    for the one call and put back to 0 in a `finally`, as "sweep" is."""
+    if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
+        raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= max_hits <= _cabi.HITS_MAX:
+        raise ValueError(f"max_hits: an integer in 1..{_cabi.HITS_MAX}, not {max_hits!r}")
+    rays = _with_radius(rays, radius)
+    tracer.set_option("hits_sweep", 1)
+    try:
+        return tracer.trace_hits(rays, int(max_hits), False, bool(count_all))
+    finally:
+        tracer.set_option("hits_sweep", 0)
