@@ -11,8 +11,10 @@
 // register-resident HitList with its offer macro (rt_multihit.hpp).  An id is sphere << 1, or kTriBit | BVH index << 1: the low bit,
 // k_multihit's side bit, is always 0, so HitList::insert and its tie read through Q.order need no change.  The per-triangle steps —
 // sweep_times, sweep_first_touch, sweep_contact — restate k_sweep's inline text as value-taking functions, because this kernel runs them
-// twice (search and epilogue).  k_sweep does not call them: with any of the three in place of its own text its generated code changed
-// (tools/isa_diff.py: 7 to 14 instructions, other registers), so it is left as it was, instruction for instruction.
+// twice (search and epilogue).  k_sweep does not call them, for a measured reason: with sweep_candidate and sweep_contact in place of its
+// own text (7 to 14 instructions more, 85 -> 82 VGPRs) every sphere_cast and sphere_check row ran 0.7 % to 1.6 % slower than the parent's
+// slowest run, in two sessions, and its own text inside the same library did not (profiles/ray_list_frame_timing.txt).  The same file
+// holds what one frame for this kernel and k_multihit cost k_multihit's front-face rows (+0.4 % to +1.0 %): both keep their text.
 //
 // Pruning (DESIGN.md "Sphere-cast-all").  bound = tMax while slot K-1 is empty or when countAll is set, else min(tMax, t of slot K-1);
 // sweep_node_step keeps a child whose entry distance is <= bound, and a triangle's features with t > the K-th t are dropped before the

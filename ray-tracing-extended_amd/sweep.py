@@ -39,25 +39,26 @@ def _with_radius(rays, radius):
     return out
 
 
-def _swept(tracer, method, rays, radius):
+def _swept(tracer, option, method, rays, radius, *args):
+    """tracer.method(rays with the radii, *args) with `option` = 1 for that one call, put back to 0 in a `finally`"""
     if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
         raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
     rays = _with_radius(rays, radius)
-    tracer.set_option("sweep", 1)
+    tracer.set_option(option, 1)
     try:
-        return getattr(tracer, method)(rays)
+        return getattr(tracer, method)(rays, *args)
     finally:
-        tracer.set_option("sweep", 0)
+        tracer.set_option(option, 0)
 
 
 def sphere_cast(tracer, rays, radius):
     """rt_trace_rays with option "sweep" = 1: the first contact of a ball of `radius` swept along each ray -> HIT records"""
-    return _swept(tracer, "trace_rays", rays, radius)
+    return _swept(tracer, "sweep", "trace_rays", rays, radius)
 
 
 def sphere_check(tracer, rays, radius):
     """rt_occluded with option "sweep" = 1: 1 where a ball of `radius` swept along the ray touches something before tMax -> uint8"""
-    return _swept(tracer, "occluded", rays, radius)
+    return _swept(tracer, "sweep", "occluded", rays, radius)
 
 
 def sphere_cast_all(tracer, rays, radius, max_hits=4, count_all=False):
@@ -67,13 +68,6 @@ def sphere_cast_all(tracer, rays, radius, max_hits=4, count_all=False):
     feature; count_all: hitCount counts every primitive touched before tMax.  A Tracer or a MultiTracer; rays and radius as for
     sphere_cast (a Tracer answers a CUDA tensor through the device entry, with a float32 (n, max_hits, 16) tensor).  The option is set
     for the one call and put back to 0 in a `finally`, as "sweep" is."""
-    if not isinstance(tracer, (_cabi.Tracer, _cabi.MultiTracer)):
-        raise TypeError(f"tracer: a Tracer or a MultiTracer, not {type(tracer).__name__}")
     if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)) or not 1 <= max_hits <= _cabi.HITS_MAX:
         raise ValueError(f"max_hits: an integer in 1..{_cabi.HITS_MAX}, not {max_hits!r}")
-    rays = _with_radius(rays, radius)
-    tracer.set_option("hits_sweep", 1)
-    try:
-        return tracer.trace_hits(rays, int(max_hits), False, bool(count_all))
-    finally:
-        tracer.set_option("hits_sweep", 0)
+    return _swept(tracer, "hits_sweep", "trace_hits", rays, radius, int(max_hits), False, bool(count_all))

@@ -1,7 +1,6 @@
 """The checker of sphere-cast-all: tests/sweep_all_oracle.c bound with ctypes.  The batch the GPU tests and the CPU tests share is the
 sphere casts' own, sweep_check.batch_of's 710 rays, with nothing added: tests/test_sweep_all_cpu.py asserts that on `mixed` and `Knight`
-it fills, overflows and ties the list often enough.  Test infrastructure only.  (The library also exports sw_cast, the sphere casts'
-checker it includes.)"""
+it fills, overflows and ties the list often enough.  Test infrastructure only."""
 import ctypes
 
 import numpy as np
@@ -23,14 +22,8 @@ def lib(directory=None):
         vp, ci = ctypes.c_void_p, ctypes.c_int
         so.swa_cast.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, vp]
         so.swa_cast.restype = ci
-        so.sw_cast.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp]
-        so.sw_cast.restype = ci
         _lib = so
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def oracle_cast_all(rtx, spheres, tris, infos, rays, K=4, count_all=False, chunk_mesh=None):
@@ -42,7 +35,8 @@ def oracle_cast_all(rtx, spheres, tris, infos, rays, K=4, count_all=False, chunk
     cm = None if chunk_mesh is None else np.ascontiguousarray(chunk_mesh, np.int32)
     assert cm is None or len(cm) == len(m)
     out = np.zeros((len(r), K), rtx.MULTIHIT)
-    rc = lib().swa_cast(_p(s), len(s), _p(t), len(t), _p(m), len(m), _p(cm), _p(r), len(r), int(K), int(bool(count_all)), _p(out))
+    p = sc._p
+    rc = lib().swa_cast(p(s), len(s), p(t), len(t), p(m), len(m), p(cm), p(r), len(r), int(K), int(bool(count_all)), p(out))
     assert rc == 0, f"swa_cast failed: {rc}"
     return out
 

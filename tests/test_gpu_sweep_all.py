@@ -189,8 +189,8 @@ def test_multi_tracer_gives_the_single_context_bits(rtx, cases):
 
 
 def test_device_entry_on_tensors_matches_the_host_entry():
-    """(in a fresh process that imports torch first: tests/sweep_all_torch_worker.py)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "sweep_all_torch_worker.py")], capture_output=True, text=True, timeout=300)
+    """(in a fresh process that imports torch first: tests/sweep_torch_worker.py cast_all)"""
+    r = subprocess.run([sys.executable, os.path.join(HERE, "sweep_torch_worker.py"), "cast_all"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "sweep-all device entry ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
