@@ -306,15 +306,6 @@ SceneBuffers RayTracingManager::BuildBuffers()
     return b;
 }
 
-static void check(rt_ctx* ctx, int rc, const char* what)
-{
-    if (rc != 0) throw std::runtime_error(std::string(what) + " failed: " + rt_last_error(ctx));
-}
-static void mcheck(rt_multi* m, int rc, const char* what)
-{
-    if (rc != 0) throw std::runtime_error(std::string(what) + " failed: " + rt_multi_last_error(m));
-}
-
 void RayTracingManager::CreateLocalMeshes(std::vector<rt_triangle>& tris, std::vector<rt_local_chunk>& chunks)
 {
     tris.clear(); chunks.clear();
@@ -349,31 +340,26 @@ template <class T> bool same_bytes(const std::vector<T>& a, const std::vector<T>
 {
     return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
-// the two handle kinds behind one InitFrame
-struct CtxApi {
-    void params(rt_ctx* c, const rt_params* p) const { check(c, rt_set_params(c, p), "rt_set_params"); }
-    void spheres(rt_ctx* c, const rt_sphere* s, int n) const { check(c, rt_upload_spheres(c, s, n), "rt_upload_spheres"); }
-    void triangles(rt_ctx* c, const rt_triangle* t, int n) const { check(c, rt_upload_triangles(c, t, n), "rt_upload_triangles"); }
-    void meshinfo(rt_ctx* c, const rt_meshinfo* m, int n) const { check(c, rt_upload_meshinfo(c, m, n), "rt_upload_meshinfo"); }
-    void local(rt_ctx* c, const rt_triangle* t, int nt, const rt_local_chunk* ch, int nc, int nm) const { check(c, rt_upload_local_meshes(c, t, nt, ch, nc, nm), "rt_upload_local_meshes"); }
-    void poses(rt_ctx* c, const rt_mesh_transform* x, int n) const { check(c, rt_set_mesh_transforms(c, x, n), "rt_set_mesh_transforms"); }
-};
-struct MultiApi {
-    void params(rt_multi* m, const rt_params* p) const { mcheck(m, rt_multi_set_params(m, p), "rt_multi_set_params"); }
-    void spheres(rt_multi* m, const rt_sphere* s, int n) const { mcheck(m, rt_multi_upload_spheres(m, s, n), "rt_multi_upload_spheres"); }
-    void triangles(rt_multi* m, const rt_triangle* t, int n) const { mcheck(m, rt_multi_upload_triangles(m, t, n), "rt_multi_upload_triangles"); }
-    void meshinfo(rt_multi* m, const rt_meshinfo* mi, int n) const { mcheck(m, rt_multi_upload_meshinfo(m, mi, n), "rt_multi_upload_meshinfo"); }
-    void local(rt_multi* m, const rt_triangle* t, int nt, const rt_local_chunk* ch, int nc, int nm) const { mcheck(m, rt_multi_upload_local_meshes(m, t, nt, ch, nc, nm), "rt_multi_upload_local_meshes"); }
-    void poses(rt_multi* m, const rt_mesh_transform* x, int n) const { mcheck(m, rt_multi_set_mesh_transforms(m, x, n), "rt_multi_set_mesh_transforms"); }
-};
+// A C-ABI entry returned non-zero: "<rt_ or rt_multi_><stem> failed: <that handle's last error>".  `stem` is the entry's name without
+// the prefix ("render", or "set_option(closest_k)" where one entry serves two purposes).
+[[noreturn]] void fail(Target t, const char* stem)
+{
+    throw std::runtime_error(std::string(t.isMulti ? "rt_multi_" : "rt_") + stem + " failed: " + (t.isMulti ? rt_multi_last_error(t.multi) : rt_last_error(t.ctx)));
+}
+// One C-ABI call on either handle kind: the context entry or its rt_multi twin, whichever the target is.
+template <class... P, class... A>
+void call(Target t, const char* stem, int (*entry)(rt_ctx*, P...), int (*multi_entry)(rt_multi*, P...), A... args)
+{
+    if ((t.isMulti ? multi_entry(t.multi, args...) : entry(t.ctx, args...)) != 0) fail(t, stem);
+}
 } // namespace
 
 // InitFrame (RayTracingManager.cs:95-109).  The reference rebuilds and re-uploads its three buffers every frame (its own TODO at
 // RayTracedMesh.cs:37); an upload makes the library rebuild its acceleration structure, so only what changed is sent again — and with
 // deviceGeometry nothing but the poses is sent per frame.
-template <class H, class Api> void RayTracingManager::InitFrameT(H* h, const Api& api)
+void RayTracingManager::InitFrame(Target t)
 {
-    const bool first = uploaded_to_ != h;
+    const bool first = uploaded_to_ != t.id();
     SceneBuffers b;
     std::memset(&b.params, 0, sizeof b.params);
     b.params.width = width; b.params.height = height;
@@ -381,43 +367,41 @@ template <class H, class Api> void RayTracingManager::InitFrameT(H* h, const Api
     UpdateCameraParams(b.params);
     b.spheres = CreateSpheres();
     SetShaderParams(b.params);
-    api.params(h, &b.params);
-    if (first || !same_bytes(b.spheres, sent_.spheres)) api.spheres(h, b.spheres.data(), (int)b.spheres.size());
+    call(t, "set_params", rt_set_params, rt_multi_set_params, &b.params);
+    if (first || !same_bytes(b.spheres, sent_.spheres)) call(t, "upload_spheres", rt_upload_spheres, rt_multi_upload_spheres, b.spheres.data(), (int)b.spheres.size());
     if (deviceGeometry) {
         std::vector<rt_triangle> lt; std::vector<rt_local_chunk> lc;
         CreateLocalMeshes(lt, lc);
         if (first || !sent_is_local_ || !same_bytes(lt, sent_local_) || !same_bytes(lc, sent_chunks_)) {
-            api.local(h, lt.data(), (int)lt.size(), lc.data(), (int)lc.size(), (int)meshes.size());
+            call(t, "upload_local_meshes", rt_upload_local_meshes, rt_multi_upload_local_meshes, lt.data(), (int)lt.size(), lc.data(), (int)lc.size(), (int)meshes.size());
             sent_local_.swap(lt); sent_chunks_.swap(lc); sent_is_local_ = true;
         }
         const std::vector<rt_mesh_transform> xf = CreateTransforms();
-        api.poses(h, xf.data(), (int)xf.size());
+        call(t, "set_mesh_transforms", rt_set_mesh_transforms, rt_multi_set_mesh_transforms, xf.data(), (int)xf.size());
     } else {
         CreateMeshes(b.triangles, b.meshInfo);
-        if (first || sent_is_local_ || !same_bytes(b.triangles, sent_.triangles)) api.triangles(h, b.triangles.data(), (int)b.triangles.size());
-        if (first || sent_is_local_ || !same_bytes(b.meshInfo, sent_.meshInfo)) api.meshinfo(h, b.meshInfo.data(), (int)b.meshInfo.size());
+        if (first || sent_is_local_ || !same_bytes(b.triangles, sent_.triangles)) call(t, "upload_triangles", rt_upload_triangles, rt_multi_upload_triangles, b.triangles.data(), (int)b.triangles.size());
+        if (first || sent_is_local_ || !same_bytes(b.meshInfo, sent_.meshInfo)) call(t, "upload_meshinfo", rt_upload_meshinfo, rt_multi_upload_meshinfo, b.meshInfo.data(), (int)b.meshInfo.size());
         sent_.triangles.swap(b.triangles); sent_.meshInfo.swap(b.meshInfo); sent_is_local_ = false;
     }
     sent_.spheres.swap(b.spheres);
-    uploaded_to_ = h;
+    uploaded_to_ = t.id();
 }
 
-void RayTracingManager::InitFrame(rt_ctx* ctx) { InitFrameT(ctx, CtxApi{}); }
-
-void RayTracingManager::Start(rt_ctx* ctx)
+void RayTracingManager::Start(Target t)
 {
     numRenderedFrames = 0;
-    check(ctx, rt_reset_accum(ctx), "rt_reset_accum");
+    call(t, "reset_accum", rt_reset_accum, rt_multi_reset_accum);
 }
 
-void RayTracingManager::OnRenderImage(rt_ctx* ctx, int frames, std::vector<float>* resultTexture)
+void RayTracingManager::OnRenderImage(Target t, int frames, std::vector<float>* resultTexture)
 {
-    InitFrame(ctx);
-    check(ctx, rt_render(ctx, numRenderedFrames, frames), "rt_render");
+    InitFrame(t);
+    call(t, "render", rt_render, rt_multi_render, numRenderedFrames, frames);
     numRenderedFrames += frames;
     if (resultTexture) {
         resultTexture->resize((size_t)width * height * 4);
-        check(ctx, rt_read_accum(ctx, resultTexture->data(), resultTexture->size()), "rt_read_accum");
+        call(t, "read_accum", rt_read_accum, rt_multi_read_accum, resultTexture->data(), resultTexture->size());
     }
 }
 
@@ -425,143 +409,80 @@ void RayTracingManager::RenderFeatures(rt_ctx* ctx, int frames, std::vector<floa
 {
     InitFrame(ctx);
     rt_aov_info info{};
-    check(ctx, rt_get_aov_info(ctx, &info), "rt_get_aov_info");
-    check(ctx, rt_render_aov(ctx, info.framesAccumulated, frames), "rt_render_aov");
+    if (rt_get_aov_info(ctx, &info) != 0) fail(ctx, "get_aov_info");
+    if (rt_render_aov(ctx, info.framesAccumulated, frames) != 0) fail(ctx, "render_aov");
     std::vector<float>* planes[RT_AOV_COUNT] = { albedoCoverage, normalDepth };
     for (int which = 0; which < RT_AOV_COUNT; ++which)
         if (planes[which]) {
             planes[which]->resize((size_t)width * height * 4);
-            check(ctx, rt_read_aov(ctx, which, planes[which]->data(), planes[which]->size()), "rt_read_aov");
+            if (rt_read_aov(ctx, which, planes[which]->data(), planes[which]->size()) != 0) fail(ctx, "read_aov");
         }
 }
 
-void RayTracingManager::Denoise(rt_ctx* ctx, const rt_denoise_params* params, std::vector<float>* denoised)
+void RayTracingManager::Denoise(Target t, const rt_denoise_params* params, std::vector<float>* denoised)
 {
-    check(ctx, rt_denoise(ctx, params), "rt_denoise");
+    call(t, "denoise", rt_denoise, rt_multi_denoise, params);
     if (denoised) {
         denoised->resize((size_t)width * height * 4);
-        check(ctx, rt_read_denoised(ctx, denoised->data(), denoised->size()), "rt_read_denoised");
+        call(t, "read_denoised", rt_read_denoised, rt_multi_read_denoised, denoised->data(), denoised->size());
     }
 }
 
-void RayTracingManager::Denoise(rt_multi* m, const rt_denoise_params* params, std::vector<float>* denoised)
+void RayTracingManager::DenoiseVariance(Target t, const rt_vdenoise_params* params, std::vector<float>* denoised, std::vector<float>* variance)
 {
-    mcheck(m, rt_multi_denoise(m, params), "rt_multi_denoise");
+    call(t, "denoise_variance", rt_denoise_variance, rt_multi_denoise_variance, params);
     if (denoised) {
         denoised->resize((size_t)width * height * 4);
-        mcheck(m, rt_multi_read_denoised(m, denoised->data(), denoised->size()), "rt_multi_read_denoised");
-    }
-}
-
-void RayTracingManager::DenoiseVariance(rt_ctx* ctx, const rt_vdenoise_params* params, std::vector<float>* denoised, std::vector<float>* variance)
-{
-    check(ctx, rt_denoise_variance(ctx, params), "rt_denoise_variance");
-    if (denoised) {
-        denoised->resize((size_t)width * height * 4);
-        check(ctx, rt_read_denoised(ctx, denoised->data(), denoised->size()), "rt_read_denoised");
+        call(t, "read_denoised", rt_read_denoised, rt_multi_read_denoised, denoised->data(), denoised->size());
     }
     if (variance) {
         variance->resize((size_t)width * height);
-        check(ctx, rt_read_variance(ctx, variance->data(), variance->size()), "rt_read_variance");
+        call(t, "read_variance", rt_read_variance, rt_multi_read_variance, variance->data(), variance->size());
     }
 }
 
-void RayTracingManager::DenoiseVariance(rt_multi* m, const rt_vdenoise_params* params, std::vector<float>* denoised, std::vector<float>* variance)
+void RayTracingManager::Temporal(Target t, const rt_temporal_params* params, std::vector<float>* temporal)
 {
-    mcheck(m, rt_multi_denoise_variance(m, params), "rt_multi_denoise_variance");
-    if (denoised) {
-        denoised->resize((size_t)width * height * 4);
-        mcheck(m, rt_multi_read_denoised(m, denoised->data(), denoised->size()), "rt_multi_read_denoised");
-    }
-    if (variance) {
-        variance->resize((size_t)width * height);
-        mcheck(m, rt_multi_read_variance(m, variance->data(), variance->size()), "rt_multi_read_variance");
-    }
-}
-
-void RayTracingManager::Temporal(rt_ctx* ctx, const rt_temporal_params* params, std::vector<float>* temporal)
-{
-    check(ctx, rt_temporal(ctx, params), "rt_temporal");
+    call(t, "temporal", rt_temporal, rt_multi_temporal, params);
     if (temporal) {
         temporal->resize((size_t)width * height * 4);
-        check(ctx, rt_read_temporal(ctx, temporal->data(), temporal->size()), "rt_read_temporal");
+        call(t, "read_temporal", rt_read_temporal, rt_multi_read_temporal, temporal->data(), temporal->size());
     }
 }
 
-void RayTracingManager::Temporal(rt_multi* m, const rt_temporal_params* params, std::vector<float>* temporal)
+std::vector<float> RayTracingManager::TraceRadiance(Target t, const std::vector<rt_ray>& rays, const rt_radiance_params* params)
 {
-    mcheck(m, rt_multi_temporal(m, params), "rt_multi_temporal");
-    if (temporal) {
-        temporal->resize((size_t)width * height * 4);
-        mcheck(m, rt_multi_read_temporal(m, temporal->data(), temporal->size()), "rt_multi_read_temporal");
-    }
-}
-
-std::vector<float> RayTracingManager::TraceRadiance(rt_ctx* ctx, const std::vector<rt_ray>& rays, const rt_radiance_params* params)
-{
-    InitFrame(ctx);
+    InitFrame(t);
     std::vector<float> rgba(rays.size() * 4);
-    check(ctx, rt_trace_radiance(ctx, rays.data(), (int)rays.size(), params, rgba.data()), "rt_trace_radiance");
-    return rgba;
-}
-
-std::vector<float> RayTracingManager::TraceRadiance(rt_multi* m, const std::vector<rt_ray>& rays, const rt_radiance_params* params)
-{
-    InitFrame(m);
-    std::vector<float> rgba(rays.size() * 4);
-    mcheck(m, rt_multi_trace_radiance(m, rays.data(), (int)rays.size(), params, rgba.data()), "rt_multi_trace_radiance");
+    call(t, "trace_radiance", rt_trace_radiance, rt_multi_trace_radiance, rays.data(), (int)rays.size(), params, rgba.data());
     return rgba;
 }
 
 static size_t gather_floats(const rt_gather_params* params) { return params && params->mode == RT_GATHER_SH9 ? 36 : 4; }
 
-std::vector<float> RayTracingManager::Gather(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_gather_params* params)
+std::vector<float> RayTracingManager::Gather(Target t, const std::vector<rt_ray>& points, const rt_gather_params* params)
 {
-    InitFrame(ctx);
+    InitFrame(t);
     std::vector<float> out(points.size() * gather_floats(params));
-    check(ctx, rt_gather(ctx, points.data(), (int)points.size(), params, out.data()), "rt_gather");
-    return out;
-}
-
-std::vector<float> RayTracingManager::Gather(rt_multi* m, const std::vector<rt_ray>& points, const rt_gather_params* params)
-{
-    InitFrame(m);
-    std::vector<float> out(points.size() * gather_floats(params));
-    mcheck(m, rt_multi_gather(m, points.data(), (int)points.size(), params, out.data()), "rt_multi_gather");
+    call(t, "gather", rt_gather, rt_multi_gather, points.data(), (int)points.size(), params, out.data());
     return out;
 }
 
 static size_t visibility_floats(const rt_visibility_params* params) { return params && params->mode == RT_VIS_SH9 ? 12 : 4; }
 
-std::vector<float> RayTracingManager::Visibility(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_visibility_params* params)
+std::vector<float> RayTracingManager::Visibility(Target t, const std::vector<rt_ray>& points, const rt_visibility_params* params)
 {
-    InitFrame(ctx);
+    InitFrame(t);
     std::vector<float> out(points.size() * visibility_floats(params));
-    check(ctx, rt_visibility(ctx, points.data(), (int)points.size(), params, out.data()), "rt_visibility");
+    call(t, "visibility", rt_visibility, rt_multi_visibility, points.data(), (int)points.size(), params, out.data());
     return out;
 }
 
-std::vector<float> RayTracingManager::Visibility(rt_multi* m, const std::vector<rt_ray>& points, const rt_visibility_params* params)
+std::vector<rt_closest> RayTracingManager::ClosestPoints(Target t, const std::vector<rt_ray>& points)
 {
-    InitFrame(m);
-    std::vector<float> out(points.size() * visibility_floats(params));
-    mcheck(m, rt_multi_visibility(m, points.data(), (int)points.size(), params, out.data()), "rt_multi_visibility");
-    return out;
-}
-
-std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points)
-{
-    InitFrame(ctx);
+    InitFrame(t);
     std::vector<rt_closest> out(points.size());
-    check(ctx, rt_closest_points(ctx, points.data(), (int)points.size(), out.data()), "rt_closest_points");
-    return out;
-}
-
-std::vector<rt_closest> RayTracingManager::ClosestPoints(rt_multi* m, const std::vector<rt_ray>& points)
-{
-    InitFrame(m);
-    std::vector<rt_closest> out(points.size());
-    mcheck(m, rt_multi_closest_points(m, points.data(), (int)points.size(), out.data()), "rt_multi_closest_points");
+    call(t, "closest_points", rt_closest_points, rt_multi_closest_points, points.data(), (int)points.size(), out.data());
     return out;
 }
 
@@ -592,30 +513,19 @@ template <class Reset> struct AtScopeEnd {
 template <class Reset> AtScopeEnd<Reset> at_scope_end(Reset r) { return AtScopeEnd<Reset>{ r }; }
 } // namespace
 
-std::vector<rt_closest> RayTracingManager::OverlapSphere(rt_ctx* ctx, const float center[3], float radius, int maxResults, int* total)
+std::vector<rt_closest> RayTracingManager::OverlapSphere(Target t, const float center[3], float radius, int maxResults, int* total)
 {
     const rt_ray r = overlap_point(center, radius, maxResults);
-    InitFrame(ctx);
+    InitFrame(t);
     std::vector<rt_closest> all((size_t)maxResults);
     {
-        const auto defaults = at_scope_end([ctx]() { rt_set_option(ctx, "closest_k", 1); rt_set_option(ctx, "closest_all", 0); });
-        check(ctx, rt_set_option(ctx, "closest_k", maxResults), "rt_set_option(closest_k)");
-        check(ctx, rt_set_option(ctx, "closest_all", 1), "rt_set_option(closest_all)");
-        check(ctx, rt_closest_points(ctx, &r, 1, all.data()), "rt_closest_points");
-    }
-    return overlaps_found(std::move(all), total);
-}
-
-std::vector<rt_closest> RayTracingManager::OverlapSphere(rt_multi* m, const float center[3], float radius, int maxResults, int* total)
-{
-    const rt_ray r = overlap_point(center, radius, maxResults);
-    InitFrame(m);
-    std::vector<rt_closest> all((size_t)maxResults);
-    {
-        const auto defaults = at_scope_end([m]() { rt_multi_set_option(m, "closest_k", 1); rt_multi_set_option(m, "closest_all", 0); });
-        mcheck(m, rt_multi_set_option(m, "closest_k", maxResults), "rt_multi_set_option(closest_k)");
-        mcheck(m, rt_multi_set_option(m, "closest_all", 1), "rt_multi_set_option(closest_all)");
-        mcheck(m, rt_multi_closest_points(m, &r, 1, all.data()), "rt_multi_closest_points");
+        const auto defaults = at_scope_end([t]() {
+            if (t.isMulti) { rt_multi_set_option(t.multi, "closest_k", 1); rt_multi_set_option(t.multi, "closest_all", 0); }
+            else { rt_set_option(t.ctx, "closest_k", 1); rt_set_option(t.ctx, "closest_all", 0); }
+        });
+        call(t, "set_option(closest_k)", rt_set_option, rt_multi_set_option, "closest_k", maxResults);
+        call(t, "set_option(closest_all)", rt_set_option, rt_multi_set_option, "closest_all", 1);
+        call(t, "closest_points", rt_closest_points, rt_multi_closest_points, &r, 1, all.data());
     }
     return overlaps_found(std::move(all), total);
 }
@@ -643,43 +553,14 @@ std::vector<rt_multihit> hits_found(std::vector<rt_multihit> all)
 }
 } // namespace
 
-std::vector<rt_multihit> RayTracingManager::RaycastAll(rt_ctx* ctx, const float origin[3], const float direction[3], float maxDistance, int maxHits, bool bothSides)
+std::vector<rt_multihit> RayTracingManager::RaycastAll(Target t, const float origin[3], const float direction[3], float maxDistance, int maxHits, bool bothSides)
 {
-    InitFrame(ctx);
+    InitFrame(t);
     const rt_ray r = one_ray(origin, direction, maxDistance);
     const rt_hits_params p = hits_params(maxHits, bothSides);
     std::vector<rt_multihit> all((size_t)std::max(maxHits, 1));
-    check(ctx, rt_trace_hits(ctx, &r, 1, &p, all.data()), "rt_trace_hits");
+    call(t, "trace_hits", rt_trace_hits, rt_multi_trace_hits, &r, 1, &p, all.data());
     return hits_found(std::move(all));
-}
-
-std::vector<rt_multihit> RayTracingManager::RaycastAll(rt_multi* m, const float origin[3], const float direction[3], float maxDistance, int maxHits, bool bothSides)
-{
-    InitFrame(m);
-    const rt_ray r = one_ray(origin, direction, maxDistance);
-    const rt_hits_params p = hits_params(maxHits, bothSides);
-    std::vector<rt_multihit> all((size_t)std::max(maxHits, 1));
-    mcheck(m, rt_multi_trace_hits(m, &r, 1, &p, all.data()), "rt_multi_trace_hits");
-    return hits_found(std::move(all));
-}
-
-void RayTracingManager::InitFrame(rt_multi* m) { InitFrameT(m, MultiApi{}); }
-
-void RayTracingManager::Start(rt_multi* m)
-{
-    numRenderedFrames = 0;
-    mcheck(m, rt_multi_reset_accum(m), "rt_multi_reset_accum");
-}
-
-void RayTracingManager::OnRenderImage(rt_multi* m, int frames, std::vector<float>* resultTexture)
-{
-    InitFrame(m);
-    mcheck(m, rt_multi_render(m, numRenderedFrames, frames), "rt_multi_render");
-    numRenderedFrames += frames;
-    if (resultTexture) {
-        resultTexture->resize((size_t)width * height * 4);
-        mcheck(m, rt_multi_read_accum(m, resultTexture->data(), resultTexture->size()), "rt_multi_read_accum");
-    }
 }
 
 } // namespace rthost

@@ -98,6 +98,15 @@ struct SceneBuffers {               // what InitFrame hands to the device (the r
     std::vector<rt_meshinfo> meshInfo;
 };
 
+// The device handle a RayTracingManager method works on: an rt_ctx or an rt_multi, whichever the caller passes.
+struct Target {
+    rt_ctx* ctx = nullptr; rt_multi* multi = nullptr;       // the other one is null
+    bool isMulti;                                           // (kept apart from the pointers: a null handle still reaches its own kind's entry)
+    Target(rt_ctx* c) : ctx(c), isMulti(false) {}
+    Target(rt_multi* m) : multi(m), isMulti(true) {}
+    const void* id() const { return isMulti ? static_cast<const void*>(multi) : ctx; }      // what uploaded_to_ is compared with
+};
+
 class RayTracingManager {
 public:
     static constexpr int TriangleLimit = 1500;                                   // RayTracingManager.cs:9
@@ -127,63 +136,51 @@ public:
     // the geometry pipeline's inputs: every mesh's local chunks back to back (chunk.meshIndex = index into `meshes`) and one pose per mesh
     void CreateLocalMeshes(std::vector<rt_triangle>& tris, std::vector<rt_local_chunk>& chunks);
     std::vector<rt_mesh_transform> CreateTransforms() const;
-    // With a device context: InitFrame + the two blits + frame counter (OnRenderImage :49-93).  Throws on C-ABI errors.
-    void InitFrame(rt_ctx* ctx);
-    void OnRenderImage(rt_ctx* ctx, int frames, std::vector<float>* resultTexture = nullptr);
-    void Start(rt_ctx* ctx);                                                     // :43-46
+    // With a device handle — an rt_ctx*, or an rt_multi* (the frame tiles across the GPUs of the node: interleaved row bands inside the
+    // library, one gather at the end of the call; resultTexture is the assembled full image): InitFrame + the two blits + frame counter
+    // (OnRenderImage :49-93).  Every method that takes a Target has one body for both kinds.  Throws on C-ABI errors.
+    void InitFrame(Target t);
+    void OnRenderImage(Target t, int frames, std::vector<float>* resultTexture = nullptr);
+    void Start(Target t);                                                        // :43-46
     // Beyond the reference: `frames` feature frames (rt_render_aov) of the scene and camera OnRenderImage would trace, with frame indices
     // that continue from the planes' own count; the planes (width * height * 4 floats each) are read back when asked for.  The image and
     // numRenderedFrames are left alone.
     void RenderFeatures(rt_ctx* ctx, int frames, std::vector<float>* albedoCoverage = nullptr, std::vector<float>* normalDepth = nullptr);
     // Beyond the reference: resultTexture filtered into the denoised plane (rt_denoise; params null = the library's defaults), guided by
     // the planes RenderFeatures accumulated; the plane (width * height * 4 floats) is read back when asked for.
-    void Denoise(rt_ctx* ctx, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
-    void Denoise(rt_multi* multi, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
+    void Denoise(Target t, const rt_denoise_params* params = nullptr, std::vector<float>* denoised = nullptr);
     // Beyond the reference: the variance-guided filter (rt_denoise_variance; params null = the library's defaults, source 0) into the same
     // denoised plane; `denoised` (width*height*4) and `variance` (var_0, width*height) are filled if asked for.
-    void DenoiseVariance(rt_ctx* ctx, const rt_vdenoise_params* params = nullptr, std::vector<float>* denoised = nullptr, std::vector<float>* variance = nullptr);
-    void DenoiseVariance(rt_multi* multi, const rt_vdenoise_params* params = nullptr, std::vector<float>* denoised = nullptr, std::vector<float>* variance = nullptr);
+    void DenoiseVariance(Target t, const rt_vdenoise_params* params = nullptr, std::vector<float>* denoised = nullptr, std::vector<float>* variance = nullptr);
     // Beyond the reference: the step in front of Denoise for a moving camera (rt_temporal; params null = the library's defaults): the
     // previous temporal colour reprojected into the current camera's view, the accumulated image blended in.  Call it after a frame
     // rendered from a fresh accumulation and RenderFeatures at the new pose; the colour (width * height * 4 floats) is read back when
     // asked for.  rt_denoise_temporal / rt_multi_denoise_temporal then filter it.
-    void Temporal(rt_ctx* ctx, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
-    void Temporal(rt_multi* multi, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
+    void Temporal(Target t, const rt_temporal_params* params = nullptr, std::vector<float>* temporal = nullptr);
     // Beyond the reference: how much light arrives along each of the caller's rays in the scene OnRenderImage would trace — Trace through
     // rt_trace_radiance / rt_multi_trace_radiance (params null = numRaysPerPixel samples, seed 0, firstIndex 0).  Returns rays.size() * 4
     // floats, (r, g, b, 1) per ray.
-    std::vector<float> TraceRadiance(rt_ctx* ctx, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
-    std::vector<float> TraceRadiance(rt_multi* multi, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
+    std::vector<float> TraceRadiance(Target t, const std::vector<rt_ray>& rays, const rt_radiance_params* params = nullptr);
     // Beyond the reference: the light that arrives at each of the caller's points (rt_ray: origin, tMax, the NORMAL in direction) over
     // directions the device draws — rt_gather / rt_multi_gather (params null = numRaysPerPixel samples, seed 0, firstIndex 0, mode
     // RT_GATHER_COSINE).  Returns points.size() * 4 floats (mode 0: mean radiance, 1) or points.size() * 36 (mode 1: nine SH coefficients).
-    std::vector<float> Gather(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
-    std::vector<float> Gather(rt_multi* multi, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
+    std::vector<float> Gather(Target t, const std::vector<rt_ray>& points, const rt_gather_params* params = nullptr);
     // Beyond the reference: how open each of the caller's points is (rt_ray: origin, the reach in tMax, the NORMAL in direction) over the
     // directions Gather draws — rt_visibility / rt_multi_visibility (params null = 64 samples, seed 0, firstIndex 0, mode RT_VIS_COSINE).
     // Returns points.size() * 4 floats (mode 0: bent normal, visibility; mode 2: mean distance, mean squared distance, hit fraction, 1)
     // or points.size() * 12 (mode 1: nine SH coefficients, visibility, 0, 0).
-    std::vector<float> Visibility(rt_ctx* ctx, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
-    std::vector<float> Visibility(rt_multi* multi, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
+    std::vector<float> Visibility(Target t, const std::vector<rt_ray>& points, const rt_visibility_params* params = nullptr);
     // Beyond the reference: the nearest surface to each of the caller's points (rt_ray: the point in origin, the search radius in tMax) —
     // rt_closest_points / rt_multi_closest_points: which sphere or triangle, where on it, how far and on which side.
-    std::vector<rt_closest> ClosestPoints(rt_ctx* ctx, const std::vector<rt_ray>& points);
-    std::vector<rt_closest> ClosestPoints(rt_multi* multi, const std::vector<rt_ray>& points);
+    std::vector<rt_closest> ClosestPoints(Target t, const std::vector<rt_ray>& points);
     // Physics.OverlapSphere for the traced scene (rt_closest_points with the options "closest_k" = maxResults (1..RT_HITS_MAX) and
     // "closest_all" = 1, put back to 1 and 0 afterwards): the surfaces within `radius` of `center`, nearest first.  Returns the non-empty
     // records; _reserved[0] in them is the number of ALL surfaces within the radius (total, if given, receives it also when none is).
-    std::vector<rt_closest> OverlapSphere(rt_ctx* ctx, const float center[3], float radius, int maxResults = RT_HITS_MAX, int* total = nullptr);
-    std::vector<rt_closest> OverlapSphere(rt_multi* multi, const float center[3], float radius, int maxResults = RT_HITS_MAX, int* total = nullptr);
+    std::vector<rt_closest> OverlapSphere(Target t, const float center[3], float radius, int maxResults = RT_HITS_MAX, int* total = nullptr);
     // Physics.RaycastAll for the traced scene (rt_trace_hits / rt_multi_trace_hits): everything origin + t * direction passes through for
     // t < maxDistance, nearest first, at most maxHits (1..RT_HITS_MAX) surfaces; bothSides: back faces and sphere exits count too
     // (side = -1).  Returns the non-empty records; hitCount == maxHits in them means there may be more.
-    std::vector<rt_multihit> RaycastAll(rt_ctx* ctx, const float origin[3], const float direction[3], float maxDistance, int maxHits = RT_HITS_MAX, bool bothSides = false);
-    std::vector<rt_multihit> RaycastAll(rt_multi* multi, const float origin[3], const float direction[3], float maxDistance, int maxHits = RT_HITS_MAX, bool bothSides = false);
-    // The same through an rt_multi: the frame tiles across the GPUs of the node (interleaved row bands inside the library, one
-    // gather at the end of the call); resultTexture is the assembled full image.
-    void InitFrame(rt_multi* multi);
-    void OnRenderImage(rt_multi* multi, int frames, std::vector<float>* resultTexture = nullptr);
-    void Start(rt_multi* multi);
+    std::vector<rt_multihit> RaycastAll(Target t, const float origin[3], const float direction[3], float maxDistance, int maxHits = RT_HITS_MAX, bool bothSides = false);
     // :190-194 — the reference releases its buffers here; the library owns them, so this only forgets which context holds them
     // (call it before destroying the context: the next InitFrame uploads again)
     void OnDisable() { uploaded_to_ = nullptr; }
@@ -191,7 +188,6 @@ private:
     const void* uploaded_to_ = nullptr;         // the context (or rt_multi) that holds this manager's buffers
     SceneBuffers sent_;                         // ... and what they hold (world-space path): only what changed is sent again
     std::vector<rt_triangle> sent_local_; std::vector<rt_local_chunk> sent_chunks_; bool sent_is_local_ = false;
-    template <class H, class Api> void InitFrameT(H* h, const Api& api);
 };
 
 // Loads a reference scene (Unity YAML).  Throws std::runtime_error with a message on malformed input.

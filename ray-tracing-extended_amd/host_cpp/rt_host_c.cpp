@@ -1,5 +1,6 @@
 // rt_host_c.cpp — a plain-C window onto the C++ host, used by the tests (ctypes) to compare its buffers with host.py's.
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "rt_host.hpp"
@@ -7,6 +8,34 @@
 namespace {
 thread_local std::string g_err;
 struct Handle { rthost::RayTracingManager mgr; rthost::SceneBuffers buf; bool built = false; };
+
+// The frame of the entries that work on a target of their own: body(mgr, target) on a fresh target — an rt_multi of n_contexts contexts
+// (devices[i] each) when `multi`, else an rt_ctx on HIP device devices[0] (0 without a list) — and a fresh copy of the handle's manager.
+// The target is destroyed whatever body does.  Returns what body returns; -1 with the text kept when the target cannot be made or body
+// throws.
+template <class Body> int on_fresh_target(void* hp, bool multi, const int* devices, int n_contexts, Body body)
+{
+    auto* h = static_cast<Handle*>(hp);
+    rt_multi* m = multi ? rt_multi_create(devices, n_contexts) : nullptr;
+    rt_ctx* ctx = multi ? nullptr : rt_create(devices ? devices[0] : 0);
+    if (!m && !ctx) { g_err = multi ? rt_multi_last_error(nullptr) : rt_last_error(nullptr); return -1; }
+    int rc;
+    try {
+        rthost::RayTracingManager mgr = h->mgr;
+        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this target yet)
+        rc = body(mgr, multi ? rthost::Target(m) : rthost::Target(ctx));
+    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
+    if (m) rt_multi_destroy(m);
+    if (ctx) rt_destroy(ctx);
+    return rc;
+}
+
+// result -> the caller's buffer; returns the number of elements
+template <class T> int copy_out(const std::vector<T>& result, T* out)
+{
+    if (!result.empty()) std::memcpy(out, result.data(), result.size() * sizeof(T));
+    return (int)result.size();
+}
 }
 
 extern "C" {
@@ -16,9 +45,9 @@ const char* rth_last_error(void) { return g_err.c_str(); }
 void* rth_load_unity(const char* path, int width, int height)
 {
     try {
-        auto* h = new Handle();
+        auto h = std::make_unique<Handle>();            // (freed when the loader throws)
         h->mgr = rthost::LoadUnityScene(path, width, height);
-        return h;
+        return h.release();
     } catch (const std::exception& e) { g_err = e.what(); return nullptr; }
 }
 
@@ -66,110 +95,60 @@ int rth_render(void* hp, int device, int frames, float* rgba)
     return rc;
 }
 
-// The same scene through an rt_multi of n_contexts contexts (devices[i] each): RayTracingManager::OnRenderImage(rt_multi*, ...).
+// The same scene through an rt_multi of n_contexts contexts (devices[i] each): RayTracingManager::OnRenderImage on an rt_multi.  No
+// fall-back to a single context: without devices it fails as rt_multi_create fails.
 int rth_render_multi(void* hp, const int* devices, int n_contexts, int frames, float* rgba)
 {
-    auto* h = static_cast<Handle*>(hp);
-    rt_multi* m = rt_multi_create(devices, n_contexts);
-    if (!m) { g_err = rt_multi_last_error(nullptr); return -1; }
-    int rc = 0;
-    try {
+    return on_fresh_target(hp, true, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
         std::vector<float> out;
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this rt_multi yet)
-        mgr.Start(m);
-        mgr.OnRenderImage(m, frames, &out);
+        mgr.Start(t);
+        mgr.OnRenderImage(t, frames, &out);
         std::memcpy(rgba, out.data(), out.size() * sizeof(float));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    rt_multi_destroy(m);
-    return rc;
+        return 0;
+    });
 }
 
 // RayTracingManager::TraceRadiance of the loaded scene for n rays on a fresh rt_ctx (n_contexts = 0: HIP device devices[0]) or an rt_multi
 // of n_contexts contexts; params may be null (the library's defaults); rgba = n * 4 floats.
 int rth_trace_radiance(void* hp, const int* devices, int n_contexts, const rt_ray* rays, int n, const rt_radiance_params* params, float* rgba)
 {
-    auto* h = static_cast<Handle*>(hp);
     if (n < 0 || (n > 0 && (!rays || !rgba))) { g_err = "rth_trace_radiance: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_ray> r(rays, rays + n);
-        const std::vector<float> out = m ? mgr.TraceRadiance(m, r, params) : mgr.TraceRadiance(ctx, r, params);
-        if (!out.empty()) std::memcpy(rgba, out.data(), out.size() * sizeof(float));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        copy_out(mgr.TraceRadiance(t, std::vector<rt_ray>(rays, rays + n), params), rgba);
+        return 0;
+    });
 }
 
 // RayTracingManager::Gather of the loaded scene for n points, on a fresh rt_ctx or an rt_multi as rth_trace_radiance; params may be null
 // (the library's defaults); out = n * 4 floats (mode 0) or n * 36 (mode 1).
 int rth_gather(void* hp, const int* devices, int n_contexts, const rt_ray* points, int n, const rt_gather_params* params, float* out)
 {
-    auto* h = static_cast<Handle*>(hp);
     if (n < 0 || (n > 0 && (!points || !out))) { g_err = "rth_gather: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_ray> r(points, points + n);
-        const std::vector<float> res = m ? mgr.Gather(m, r, params) : mgr.Gather(ctx, r, params);
-        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(float));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        copy_out(mgr.Gather(t, std::vector<rt_ray>(points, points + n), params), out);
+        return 0;
+    });
 }
 
 // RayTracingManager::Visibility of the loaded scene for n points, on a fresh rt_ctx or an rt_multi as rth_gather; params may be null (the
 // library's defaults); out = n * 4 floats (modes 0, 2) or n * 12 (mode 1).
 int rth_visibility(void* hp, const int* devices, int n_contexts, const rt_ray* points, int n, const rt_visibility_params* params, float* out)
 {
-    auto* h = static_cast<Handle*>(hp);
     if (n < 0 || (n > 0 && (!points || !out))) { g_err = "rth_visibility: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_ray> r(points, points + n);
-        const std::vector<float> res = m ? mgr.Visibility(m, r, params) : mgr.Visibility(ctx, r, params);
-        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(float));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        copy_out(mgr.Visibility(t, std::vector<rt_ray>(points, points + n), params), out);
+        return 0;
+    });
 }
 
 // RayTracingManager::ClosestPoints of the loaded scene for n points, on a fresh rt_ctx or an rt_multi as rth_gather; out = n rt_closest.
 int rth_closest_points(void* hp, const int* devices, int n_contexts, const rt_ray* points, int n, rt_closest* out)
 {
-    auto* h = static_cast<Handle*>(hp);
     if (n < 0 || (n > 0 && (!points || !out))) { g_err = "rth_closest_points: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_ray> r(points, points + n);
-        const std::vector<rt_closest> res = m ? mgr.ClosestPoints(m, r) : mgr.ClosestPoints(ctx, r);
-        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(rt_closest));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        copy_out(mgr.ClosestPoints(t, std::vector<rt_ray>(points, points + n)), out);
+        return 0;
+    });
 }
 
 // RayTracingManager::RaycastAll of the loaded scene for one ray, on a fresh rt_ctx or an rt_multi as rth_gather; out holds max_hits
@@ -177,23 +156,10 @@ int rth_closest_points(void* hp, const int* devices, int n_contexts, const rt_ra
 int rth_raycast_all(void* hp, const int* devices, int n_contexts, const float* origin, const float* direction, float max_distance, int max_hits,
                     int both_sides, rt_multihit* out)
 {
-    auto* h = static_cast<Handle*>(hp);
-    if (!h || !origin || !direction || !out || max_hits < 1 || max_hits > RT_HITS_MAX) { g_err = "rth_raycast_all: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_multihit> res = m ? mgr.RaycastAll(m, origin, direction, max_distance, max_hits, both_sides != 0)
-                                               : mgr.RaycastAll(ctx, origin, direction, max_distance, max_hits, both_sides != 0);
-        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(rt_multihit));
-        rc = (int)res.size();
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    if (!hp || !origin || !direction || !out || max_hits < 1 || max_hits > RT_HITS_MAX) { g_err = "rth_raycast_all: bad arguments"; return -1; }
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        return copy_out(mgr.RaycastAll(t, origin, direction, max_distance, max_hits, both_sides != 0), out);
+    });
 }
 
 // RayTracingManager::OverlapSphere of the loaded scene for one point, on a fresh rt_ctx or an rt_multi as rth_gather; out holds
@@ -201,22 +167,10 @@ int rth_raycast_all(void* hp, const int* devices, int n_contexts, const float* o
 // written (0 .. max_results), -1 on an error.
 int rth_overlap_sphere(void* hp, const int* devices, int n_contexts, const float* center, float radius, int max_results, rt_closest* out, int* total)
 {
-    auto* h = static_cast<Handle*>(hp);
-    if (!h || !center || !out || max_results < 1 || max_results > RT_HITS_MAX) { g_err = "rth_overlap_sphere: bad arguments"; return -1; }
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();                                 // (a copy of the handle's manager: nothing uploaded to this context yet)
-        const std::vector<rt_closest> res = m ? mgr.OverlapSphere(m, center, radius, max_results, total) : mgr.OverlapSphere(ctx, center, radius, max_results, total);
-        if (!res.empty()) std::memcpy(out, res.data(), res.size() * sizeof(rt_closest));
-        rc = (int)res.size();
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+    if (!hp || !center || !out || max_results < 1 || max_results > RT_HITS_MAX) { g_err = "rth_overlap_sphere: bad arguments"; return -1; }
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target t) {
+        return copy_out(mgr.OverlapSphere(t, center, radius, max_results, total), out);
+    });
 }
 
 // Animated scene through the compiled manager: `steps` times { every mesh is turned by the quaternion q4 (x, y, z, w: rotation = q * rotation)
@@ -226,14 +180,7 @@ int rth_overlap_sphere(void* hp, const int* devices, int n_contexts, const float
 int rth_render_animated(void* hp, const int* devices, int n_contexts, int device_geometry, int steps, int frames_per_step, const float* q4,
                         const float* shift3, float* rgba)
 {
-    auto* h = static_cast<Handle*>(hp);
-    rt_ctx* ctx = nullptr; rt_multi* m = nullptr;
-    if (n_contexts > 0) { m = rt_multi_create(devices, n_contexts); if (!m) { g_err = rt_multi_last_error(nullptr); return -1; } }
-    else { ctx = rt_create(devices ? devices[0] : 0); if (!ctx) { g_err = rt_last_error(nullptr); return -1; } }
-    int rc = 0;
-    try {
-        rthost::RayTracingManager mgr = h->mgr;
-        mgr.OnDisable();
+    return on_fresh_target(hp, n_contexts > 0, devices, n_contexts, [&](rthost::RayTracingManager& mgr, rthost::Target target) {
         mgr.deviceGeometry = device_geometry != 0;
         std::vector<float> out;
         for (int s = 0; s < steps; ++s) {
@@ -245,14 +192,12 @@ int rth_render_animated(void* hp, const int* devices, int n_contexts, int device
                 const float k = (float)(i + 1);
                 mgr.meshes[i].transform.position.x += shift3[0] * k; mgr.meshes[i].transform.position.y += shift3[1] * k; mgr.meshes[i].transform.position.z += shift3[2] * k;
             }
-            if (m) { mgr.Start(m); mgr.OnRenderImage(m, frames_per_step, &out); }
-            else { mgr.Start(ctx); mgr.OnRenderImage(ctx, frames_per_step, &out); }
+            mgr.Start(target);
+            mgr.OnRenderImage(target, frames_per_step, &out);
         }
         std::memcpy(rgba, out.data(), out.size() * sizeof(float));
-    } catch (const std::exception& e) { g_err = e.what(); rc = -1; }
-    if (m) rt_multi_destroy(m);
-    if (ctx) rt_destroy(ctx);
-    return rc;
+        return 0;
+    });
 }
 
 // ---- MeshSplitter / RayTracedMesh.GetSubMeshes through plain arrays (tests) --------------------------------------------

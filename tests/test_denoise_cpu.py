@@ -190,7 +190,7 @@ def test_csharp_and_cpp_hosts_carry_the_denoiser():
                                      ("double", "lastKernelMs"), ("double", "totalKernelMs")]
     hpp = open(os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp", "rt_host.hpp")).read()
     cpp = open(os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp", "rt_host.cpp")).read()
-    assert re.search(r"\bDenoise\s*\(", hpp) and "rt_denoise(" in cpp and "rt_multi_denoise(" in cpp
+    assert re.search(r"\bDenoise\s*\(", hpp) and re.search(r"\brt_denoise\b", cpp) and re.search(r"\brt_multi_denoise\b", cpp)
 
 
 def test_denoise_kernels_are_built_without_scratch_or_spilled_vgprs():

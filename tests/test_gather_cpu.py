@@ -353,8 +353,8 @@ def test_csharp_backend_and_compiled_host_reach_the_entry_points():
     for name in ("rt_gather_params", "rt_gather_info"):
         assert '"' + name + '"' in native, name                               # VerifyLayout
     host = os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp")
-    assert "Gather(rt_ctx*" in open(os.path.join(host, "rt_host.hpp")).read()
-    assert "Gather(rt_multi*" in open(os.path.join(host, "rt_host.hpp")).read()
+    hpp = open(os.path.join(host, "rt_host.hpp")).read()                      # one declaration, for either handle kind
+    assert "Gather(Target " in hpp and "Target(rt_ctx* " in hpp and "Target(rt_multi* " in hpp
     assert "rth_gather" in open(os.path.join(host, "rt_host_c.cpp")).read()
 
 

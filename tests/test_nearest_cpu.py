@@ -53,8 +53,8 @@ def test_the_surface_is_unchanged(rtx):
     # the compiled host: RayTracingManager::OverlapSphere and its C entry, which refuses bad arguments before it touches a device.  (The
     # Python window CppScene gets no method: its public surface is a recorded one, tests/golden/cabi_surface.json)
     host = os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp")
-    assert "OverlapSphere(rt_ctx*" in open(os.path.join(host, "rt_host.hpp")).read()
-    assert "OverlapSphere(rt_multi*" in open(os.path.join(host, "rt_host.hpp")).read()
+    hpp = open(os.path.join(host, "rt_host.hpp")).read()                      # one declaration, for either handle kind
+    assert "OverlapSphere(Target " in hpp and "Target(rt_ctx* " in hpp and "Target(rt_multi* " in hpp
     L = rtx.host_cpp_binding.load_host_library()
     import ctypes
     assert L.rth_overlap_sphere(None, None, 0, None, ctypes.c_float(1.0), 0, None, None) == -1 and b"rth_overlap_sphere" in L.rth_last_error()

@@ -395,7 +395,7 @@ def test_csharp_and_cpp_hosts_carry_the_step():
                                       ("double", "lastKernelMs"), ("double", "totalKernelMs")]
     hpp = open(os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp", "rt_host.hpp")).read()
     cpp = open(os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp", "rt_host.cpp")).read()
-    assert re.search(r"\bTemporal\s*\(", hpp) and "rt_temporal(" in cpp and "rt_multi_temporal(" in cpp
+    assert re.search(r"\bTemporal\s*\(", hpp) and re.search(r"\brt_temporal\b", cpp) and re.search(r"\brt_multi_temporal\b", cpp)
 
 
 def test_temporal_kernel_is_built_without_scratch_or_spilled_vgprs():

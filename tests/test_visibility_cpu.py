@@ -303,8 +303,8 @@ def test_csharp_backend_and_compiled_host_reach_the_entry_points():
     for name in ("rt_visibility_params", "rt_visibility_info"):
         assert '"' + name + '"' in native, name                               # VerifyLayout
     host = os.path.join(ROOT, "ray-tracing-extended_amd", "host_cpp")
-    assert "Visibility(rt_ctx*" in open(os.path.join(host, "rt_host.hpp")).read()
-    assert "Visibility(rt_multi*" in open(os.path.join(host, "rt_host.hpp")).read()
+    hpp = open(os.path.join(host, "rt_host.hpp")).read()                      # one declaration, for either handle kind
+    assert "Visibility(Target " in hpp and "Target(rt_ctx* " in hpp and "Target(rt_multi* " in hpp
     assert "rth_visibility" in open(os.path.join(host, "rt_host_c.cpp")).read()
 
 

@@ -1,11 +1,15 @@
 #!/bin/bash
 # AddressSanitizer + UBSan over the CPU-side code (GPU sanitizers are not available on the pool): the compiled host's scene loader
-# and marshal (on the six scenes re-written by save_unity_scene, and on 120 mutated copies), the BVH builder (with and without
+# and marshal (on the six scenes re-written by save_unity_scene, and on 120 mutated copies), every manager method and C-window entry
+# for both handle kinds against the recording stub (tests/host_transcript.cpp, tests/host_stub.c), the BVH builder (with and without
 # insertion-based optimisation), and the oracle's loop and search tree (fuzz scenes + the 100k-triangle scene).
 set -eo pipefail
 R=$(cd "$(dirname "$0")/.." && pwd); W=/tmp/rtx_sanitize; mkdir -p $W; cd "$R/tools/sanitize"
 SAN="-O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer"
-g++ $SAN -std=c++17 -ffp-contract=off host_harness.cpp ../../ray-tracing-extended_amd/host_cpp/rt_host.cpp ../../ray-tracing-extended_amd/host_cpp/unity_loader.cpp -x c device_stub.c -o $W/host_harness 2>/dev/null
+H=../../ray-tracing-extended_amd/host_cpp
+gcc $SAN -std=c11 -c ../../tests/host_stub.c -o $W/host_stub.o
+g++ $SAN -std=c++17 -ffp-contract=off host_harness.cpp $H/rt_host.cpp $H/unity_loader.cpp $W/host_stub.o -o $W/host_harness
+g++ $SAN -std=c++17 -ffp-contract=off ../../tests/host_transcript.cpp $H/rt_host.cpp $H/unity_loader.cpp $H/rt_host_c.cpp $W/host_stub.o -o $W/host_transcript
 g++ $SAN -std=c++17 bvh_harness.cpp ../../ray-tracing-extended_amd/csrc/bvh.cpp -o $W/bvh_harness
 gcc $SAN -std=c11 -ffp-contract=off -fopenmp oracle_harness.c ../../oracle/rt_oracle.c -lm -o $W/oracle_harness
 cd "$R"; python3 - <<'PY'
@@ -40,6 +44,7 @@ PY
 export ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1
 $W/host_harness $W/Chess.unity $W/Knight.unity $W/Suzanne.unity $W/Thumbnail.unity $W/Balls_Outdoors.unity $W/Reflective_Balls.unity
 $W/host_harness $W/mut*.unity | grep -c exception | sed 's/^/mutated scenes rejected with an exception: /'
+$W/host_transcript $W/Suzanne.unity | grep -c "^== " | sed 's/^/host transcript sections (both handle kinds, every failing call, leak check on): /'
 for t in 0 4 16 21 33 99; do $W/bvh_harness $W/pos$t.bin 0; $W/bvh_harness $W/pos$t.bin 2; $W/bvh_harness $W/pos$t.bin 2 1 4; $W/bvh_harness $W/pos$t.bin 0 1 1; $W/bvh_harness $W/pos$t.bin 2 2 4; done
 $W/oracle_harness 0 4 16 21 33 99
 echo "sanitize_cpu: clean"
